@@ -5,6 +5,7 @@
                                                         # under "kernels" in the same JSON line
     python bench.py --kernel bsw|chain|phmm|poa         # one kernel only, same JSON shape
     python bench.py --mode local                        # every rank generates its own shard (no scatter / gather)
+    python bench.py --dump-outputs DIR                  # + what the last timed step computed, as DIR/<kernel>_<name>.npy
 
 A step = one pass of the kernel's hot path (every launch of the *_device entry point) over this rank's shard of the
 synthetic dataset, inputs resident in HBM.  Work units are independent (pairs / calls / batches / windows), so
@@ -73,6 +74,51 @@ def _host_timed(fn, reps=4):
     return ms, res
 
 
+# --dump-outputs DIR: what the timed path returned in its last step, as DIR/<kind>_<name>.npy.  Integer outputs are written
+# as float64 (exact for every int32 / int64 these kernels return), float outputs in their own precision.  A run writes at
+# most DUMP_BYTES (under the 64 MB a dump may take); a kind whose outputs are larger keeps a seeded sample of its units
+# (pairs / anchors / windows / reads), so two runs with the same arguments write the same units.
+DUMP_BYTES = 60 << 20
+DUMP_SHARE = {"bsw": 0.4, "chain": 0.12, "phmm": 0.12, "poa": 0.12, "abea": 0.12, "fmi": 0.12}
+DUMP_SEED = 7
+
+
+def _dump_sample(values_per_unit, budget):
+    """Sorted indices of the units to write: all of them when their values (8 bytes each) fit `budget` bytes, else the
+    longest prefix of a seeded permutation that does (at least one unit)."""
+    cost = 8 * np.asarray(values_per_unit, dtype=np.int64)
+    if cost.sum() <= budget:
+        return np.arange(len(cost))
+    perm = np.random.default_rng(DUMP_SEED).permutation(len(cost))
+    k = int(np.searchsorted(np.cumsum(cost[perm]), budget, side="right"))
+    return np.sort(perm[:max(k, 1)])
+
+
+def _ragged_take(pieces, idx, to_rows):
+    """pieces: per gathered part (records, start, count) of its units in order; idx: sorted unit indices over all parts ->
+    (record counts of those units, their records concatenated as rows by to_rows)."""
+    first = np.cumsum([0] + [len(p[2]) for p in pieces])
+    counts, rows = [], []
+    for u in idx:
+        p = int(np.searchsorted(first, u, side="right")) - 1
+        rec, start, count = pieces[p]
+        j = int(u - first[p])
+        counts.append(int(count[j]))
+        rows.append(to_rows(rec[int(start[j]):int(start[j]) + int(count[j])]))
+    return np.array(counts, dtype=np.int64), np.concatenate(rows) if rows else np.zeros((0, 0))
+
+
+def _write_dump(path, kind, arrays):
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+        np.save(os.path.join(path, "%s_%s.npy" % (kind, name)), a)
+        total += a.nbytes
+    return total
+
+
 class BswWork:
     metric, unit, dtype = "bsw_large_gcups", "GCUPS", "int32"
 
@@ -118,6 +164,12 @@ class BswWork:
                 bad += int(not np.array_equal(got[:m].cpu().numpy(), want))
                 checked += m
         return "%d pairs (front of every shard) vs oracle, all 6 fields: %s" % (checked, "identical" if not bad else "DIFFER")
+
+    def dump_arrays(self, parts, hosts, budget):
+        """pair: indices of the pairs written; result: their score, tle, gtle, qle, gscore, max_off."""
+        out = np.concatenate([p.numpy() for p in parts])
+        idx = _dump_sample(np.full(len(out), 7), budget)
+        return {"pair": idx, "result": out[idx]}
 
     def run(self, stream):
         self.d.run(self.params, stream)
@@ -335,6 +387,12 @@ class ChainWork:
         return ("%d anchors (front of every shard) vs oracle, score/parent/target/peak: %s"
                 % (checked, "identical" if not bad else "DIFFER"))
 
+    def dump_arrays(self, parts, hosts, budget):
+        """anchor: indices of the anchors written; result: their score, parent, target, peak."""
+        out = np.concatenate([p.numpy() for p in parts])
+        idx = _dump_sample(np.full(len(out), 5), budget)
+        return {"anchor": idx, "result": out[idx]}
+
     def run(self, stream):
         self.d.run(stream)
 
@@ -500,6 +558,12 @@ class PhmmWork:
         return ("%d pairs (front of every shard) vs oracle: max rel err %.2e (bound 1e-5): %s"
                 % (checked, worst, "within tolerance" if ok and worst <= 1e-5 else "DIFFER"))
 
+    def dump_arrays(self, parts, hosts, budget):
+        """pair: indices of the (read, haplotype) pairs written; log10_likelihood: their results."""
+        out = np.concatenate([p.numpy() for p in parts])
+        idx = _dump_sample(np.full(len(out), 2), budget)
+        return {"pair": idx, "log10_likelihood": out[idx]}
+
     def run(self, stream):
         self.d.run(stream)
 
@@ -596,6 +660,17 @@ class PoaWork:
                 bad += int(self.decode(got[:m]) != want)
                 checked += m
         return "%d windows (front of every shard) vs oracle, consensus strings: %s" % (checked, "identical" if not bad else "DIFFER")
+
+    def dump_arrays(self, parts, hosts, budget):
+        """window: indices of the windows written; status, consensus_len: theirs; consensus: their consensus strings' bytes,
+        one after the other."""
+        rec = np.concatenate([p.numpy() for p in parts])
+        head = np.ascontiguousarray(rec[:, :8]).view(np.int32)
+        lens = np.clip(head[:, 1], 0, rec.shape[1] - 8)
+        idx = _dump_sample(3 + lens, budget)
+        cons = [rec[w, 8:8 + lens[w]] for w in idx]
+        return {"window": idx, "status": head[idx, 0], "consensus_len": head[idx, 1],
+                "consensus": np.concatenate(cons) if cons else np.zeros(0)}
 
     def run(self, stream):
         self.d.run(self.params, stream)
@@ -699,6 +774,20 @@ class AbeaWork:
                 bad += int(not ok)
                 checked += m
         return "%d reads (front of every shard) vs oracle, aligned pairs and QC verdicts: %s" % (checked, "identical" if not bad else "DIFFER")
+
+    def dump_arrays(self, parts, hosts, budget):
+        """read: indices of the reads written; n_pairs: theirs; pairs: their aligned (ref_pos, read_pos) pairs, one read
+        after the other."""
+        pieces = []
+        for (host, lo, hi), g in zip(hosts, parts):
+            ev = host.event_off[lo:hi + 1] - host.event_off[lo]
+            g = g.numpy()
+            n_flat = 4 * max(int(ev[-1]), 1)                # the pair array holds 2 x events pairs (gbx.h), then the counts
+            pieces.append((g[:n_flat].reshape(-1, 2), 2 * ev[:-1], g[n_flat:n_flat + hi - lo]))
+        counts = np.concatenate([c for _, _, c in pieces])
+        idx = _dump_sample(2 + 2 * counts.astype(np.int64), budget)
+        n, pairs = _ragged_take(pieces, idx, lambda r: r)
+        return {"read": idx, "n_pairs": n, "pairs": pairs}
 
     def roofline_bytes(self, kernel):
         # per band (100 cells): 64 B of back-pointers written and read once more by the traceback, + 1 B of move records
@@ -847,6 +936,20 @@ class FmiWork:
             bad += 1
         return "%d reads (front of every shard) vs oracle, every field of every SMEM: %s" % (checked, "identical" if not bad else "DIFFER")
 
+    def dump_arrays(self, parts, hosts, budget):
+        """read: indices of the reads written; n_smems: theirs; smems: their SMEMs' rid, m, n, k, l, s, one read after the
+        other."""
+        from genomicsbench_amd.fmi import SMEM_DTYPE
+        pieces = []
+        for (host, lo, hi), g in zip(hosts, parts):
+            g = g.numpy()
+            off = g[8:8 + 8 * (hi - lo + 1)].view(np.int64)
+            pieces.append((g[8 + 8 * (hi - lo + 1):].view(SMEM_DTYPE), off[:-1], np.diff(off)))
+        counts = np.concatenate([c for _, _, c in pieces])
+        idx = _dump_sample(2 + 6 * counts, budget)
+        n, smems = _ragged_take(pieces, idx, lambda r: np.stack([r[f].astype(np.int64) for f in ("rid", "m", "n", "k", "l", "s")], axis=1))
+        return {"read": idx, "n_smems": n, "smems": smems}
+
     def roofline_bytes(self, kernel):
         # a backwardExt reads two checkpoints of 64 bytes (rows k and k + s; often the same line late in a match, counted
         # twice here as the reference's GET_OCC pair does); a read's bases once; 40 bytes per SMEM written
@@ -943,8 +1046,9 @@ def _valu_roof(kind, kernel_name):
     return r["roof_lane_ops_per_s"], r["mean_cycles_per_valu"]
 
 
-def run_kernel(kind, args, ctx, steps, warmup, per_gpu_units=None, label=None):
-    """One kernel's whole protocol on all ranks; returns the JSON object on rank 0 (None elsewhere)."""
+def run_kernel(kind, args, ctx, steps, warmup, per_gpu_units=None, label=None, dump=None):
+    """One kernel's whole protocol on all ranks; returns the JSON object on rank 0 (None elsewhere).  dump: a directory that
+    receives rank 0's gathered outputs of the last timed step (--dump-outputs)."""
     import torch
     from genomicsbench_amd import _native as N
     rank, world, dev, dist = ctx["rank"], ctx["world"], ctx["dev"], ctx["dist"]
@@ -1026,6 +1130,10 @@ def run_kernel(kind, args, ctx, steps, warmup, per_gpu_units=None, label=None):
     gather_ms = (time.perf_counter() - t0) * 1e3
     if rank != 0:
         return None
+    if dump:
+        hosts = [(full, lo, hi) for lo, hi in ranges] if ranges is not None else [(mine_host, 0, work.n_units(mine_host))]
+        nbytes = _write_dump(dump, kind, work.dump_arrays(parts, hosts, int(DUMP_SHARE[kind] * DUMP_BYTES)))
+        print("bench.py: %s outputs of the last timed step -> %s (%.1f MB)" % (kind, dump, nbytes / 1e6), file=sys.stderr, flush=True)
 
     # ---- rank 0: the line
     # the dominant kernel = the longest-running launch among those that had a real share of the work (a launch whose class is empty
@@ -1307,9 +1415,16 @@ def main():
                          "prints one JSON line (tests/test_bench_launch.py); --launch-echo-fail R makes rank R exit 7")
     ap.add_argument("--launch-echo-fail", type=int, default=-1)
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port of the self-launched ranks (0 = a free one)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what every kernel of the line returned in its last step as DIR/<kernel>_<name>.npy "
+                         "(float64 / float32, under 64 MB in all: a seeded sample of the units of a larger output)")
     args = ap.parse_args()
     if args.pairs:
         args.size = args.pairs
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.predict_shards:
+        raise SystemExit("bench.py: --dump-outputs writes the outputs of a line's timed steps; --predict-shards has no such line")
 
     # ---- self-launch: `python bench.py --gpus N` with no rank environment starts its own N ranks.  This happens BEFORE
     # torch.cuda / libgbx are imported and before any GPU call: the parent never touches the GPU, the ranks are child
@@ -1389,15 +1504,15 @@ def main():
         line = {"metric": WORKLOADS[args.kernel].metric + "_predicted_%dgpu" % args.predict_shards, "n_gpus": 1, "scaling": "strong",
                 "config4_predicted": predict_shards(args.kernel, args, ctx, args.predict_shards, args.steps, args.warmup)}
     elif args.kernel:
-        line = run_kernel(args.kernel, args, ctx, args.steps, args.warmup)
+        line = run_kernel(args.kernel, args, ctx, args.steps, args.warmup, dump=args.dump_outputs)
     else:
-        line = run_kernel("bsw", args, ctx, args.steps, args.warmup)
+        line = run_kernel("bsw", args, ctx, args.steps, args.warmup, dump=args.dump_outputs)
         others = {}
         for kind in ("chain", "phmm", "poa", "abea", "fmi"):
             torch.cuda.empty_cache()
             sub = argparse.Namespace(**vars(args))
             sub.size, sub.cpu_units = 0, 0                   # --size / --cpu-units speak about the headline kernel
-            others[kind] = run_kernel(kind, sub, ctx, min(args.steps, args.other_steps), min(args.warmup, 2))
+            others[kind] = run_kernel(kind, sub, ctx, min(args.steps, args.other_steps), min(args.warmup, 2), dump=args.dump_outputs)
         # BASELINE config 4 as written: ONE 'large' poa job (6000 windows) sharded over the N GPUs (strong)
         if world > 1 and args.mode != "local":
             torch.cuda.empty_cache()
