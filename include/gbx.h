@@ -174,6 +174,68 @@ int gbx_bsw_extend_device(const gbx_bsw_params *p, int64_t n,
                           const int32_t *d_h0, gbx_bsw_result *d_out,
                           void *d_work, size_t work_bytes, void *stream);
 
+/* ------------------------------------------------------------ bsw: seeds
+ * Whole-seed extension: bwa-mem2's extension caller (mem_chain2aln: the left extension on the reversed
+ * prefixes, then the right one with the left score as its h0, each redone with a doubled band while
+ * MAX_BAND_TRY allows, then the local-vs-to-end choice per side).  Every ksw step is the per-pair
+ * semantics above (scalarBandedSWA), bit-exact.  For one seed, with a = mat[0] and ksw(Q, T, h0, w, bonus):
+ *
+ *   score = truesc = -1; aw0 = aw1 = w
+ *   if qbeg > 0:      Q = reverse(read[0:qbeg]), T = reverse(win[0:rbeg]), h0 = len*a, bonus = pen_clip5
+ *                     try i = 0..max_band_try-1 with band aw0 = w << i; stop when the score did not change or
+ *                     max_off < aw0/2 + aw0/4;  local (qb = qbeg-qle, rb = rbeg-tle, truesc = score) unless
+ *                     gscore > 0 and gscore > score - pen_clip5: to-end (qb = 0, rb = rbeg-gtle, truesc = gscore)
+ *   else:             score = truesc = len*a, qb = 0, rb = rbeg
+ *   sc0 = score
+ *   if qbeg+len < lq: Q = read[qbeg+len:lq], T = win[rbeg+len:rlen], h0 = sc0, bonus = pen_clip3, tries as above
+ *                     (the first try's "previous score" is sc0); local qe = q0+qle, re = r0+tle, truesc += score-sc0,
+ *                     or to-end qe = lq, re = r0+gtle, truesc += gscore-sc0
+ *   else:             qe = lq, re = rbeg+len
+ *   w_out = max(aw0, aw1)
+ *
+ * Coordinates are half-open; rb/re are relative to the seed's window (bwa adds rmax[0]).  Chaining, seedcov
+ * and the choice of seeds stay with the caller.
+ */
+typedef struct gbx_bsw_seed_params {
+    gbx_bsw_params bsw;              /* scoring, zdrop, w; bsw.end_bonus is not read                       */
+    int32_t pen_clip5, pen_clip3;    /* end bonus of the left / right extension (bwa: 5 / 5)               */
+    int32_t max_band_try;            /* 1..4; bwa's MAX_BAND_TRY is 2                                      */
+    int32_t pad_;
+} gbx_bsw_seed_params;
+
+/* gbx_bsw_default_params with pen_clip5 = pen_clip3 = 5, max_band_try = 2 (bwa mem's defaults). */
+void gbx_bsw_seed_default_params(gbx_bsw_seed_params *p);
+
+/* One seed: the read is qer[qoff .. qoff+lq), its reference window ref[roff .. roff+rlen), and the exact
+ * match read[qbeg, qbeg+len) ~ win[rbeg, rbeg+len) (not checked).  Rules: 0 <= qbeg, 1 <= len,
+ * qbeg+len <= lq, 0 <= rbeg, rbeg+len <= rlen, both ranges inside their arenas; the left side (qbeg x rbeg)
+ * and the right side (lq-qbeg-len x rlen-rbeg-len) within GBX_BSW_MAX_QLEN x GBX_BSW_MAX_TLEN. */
+typedef struct gbx_bsw_seed {        /* 40 bytes */
+    int64_t qoff, roff;
+    int32_t lq, rlen, qbeg, rbeg, len, pad_;
+} gbx_bsw_seed;
+
+typedef struct gbx_bsw_seed_result { /* 32 bytes */
+    int32_t score, truesc, qb, qe, rb, re, w;
+    int32_t sc0;                     /* the h0 handed to the right extension */
+} gbx_bsw_seed_result;
+
+/* Host buffers in and out.  All seeds and parameters are checked before any device is touched: a bad seed
+ * gives GBX_ERR_ARG (GBX_ERR_UNSUPPORTED past the length limits) naming the lowest such seed. */
+int gbx_bsw_extend_seeds_host(const gbx_bsw_seed_params *p, int64_t n,
+                              const uint8_t *ref, int64_t ref_bytes, const uint8_t *qer, int64_t qer_bytes,
+                              const gbx_bsw_seed *seeds, gbx_bsw_seed_result *out);
+
+/* Device entry: all pointers are device pointers, the arenas readable for 16 bytes past their end (hipMalloc
+ * slack is enough); work = scratch of gbx_bsw_seeds_workspace_bytes(n, ref_bytes, qer_bytes) bytes.
+ * Asynchronous on `stream`: no host synchronisation between the phases.  The seeds are on the device and are
+ * not checked on the host; a seed that breaks the rules gets a result of all -1 and is not extended. */
+size_t gbx_bsw_seeds_workspace_bytes(int64_t n, int64_t ref_bytes, int64_t qer_bytes);
+int gbx_bsw_extend_seeds_device(const gbx_bsw_seed_params *p, int64_t n,
+                                const uint8_t *d_ref, int64_t ref_bytes, const uint8_t *d_qer, int64_t qer_bytes,
+                                const gbx_bsw_seed *d_seeds, gbx_bsw_seed_result *d_out,
+                                void *d_work, size_t work_bytes, void *stream);
+
 /* ------------------------------------------------------------------- chain
  * minimap2 anchor chaining DP.
  * Replaces  host_chain_kernel(std::vector<call_t>&, std::vector<return_t>&, int)
