@@ -135,6 +135,15 @@ def _declare(L):
         L.gbx_fmi_smem_device.argtypes = [vp, vp, vp, i64, C.c_int32, vp, vp, vp, vp, i64, vp, vp, vp, sz, vp]
         L.gbx_fmi_extensions.argtypes = [vp, C.POINTER(C.c_int64), vp]
         L.gbx_fmi_overflow.argtypes = [vp, C.POINTER(C.c_int64), vp]
+    if hasattr(L, "gbx_fmi_sal_host"):
+        L.gbx_fmi_sa_bytes.argtypes = [i64, i64]
+        L.gbx_fmi_sa_bytes.restype = sz
+        L.gbx_fmi_sa_build.argtypes = [vp, i64, vp, sz, vp]
+        L.gbx_fmi_sal_workspace_bytes.argtypes = [i64, i64]
+        L.gbx_fmi_sal_workspace_bytes.restype = sz
+        L.gbx_fmi_sal_host.argtypes = [vp, vp, vp, i64, C.c_int32, vp, i64, vp, C.POINTER(C.c_int64)]
+        L.gbx_fmi_sal_device.argtypes = [vp, vp, vp, vp, vp, vp, i64, C.c_int32, vp, i64, vp, vp, vp, sz, vp]
+        L.gbx_fmi_sal_steps.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]
     if hasattr(L, "gbx_chain_host"):
         L.gbx_chain_job_stats.argtypes = [vp, i64, i64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]
         L.gbx_chain_workspace_bytes.argtypes = [i64, i64]

@@ -98,45 +98,16 @@ uint64_t fmi_fingerprint(const gbx_fmi_index *idx)
 }
 struct FmiUse {                       // holds a cache entry for the duration of a call
     void *d_index = nullptr;
-    ~FmiUse()
-    {
-        if (!d_index) return;
-        std::lock_guard<std::mutex> lk(g_fmi_mu);
-        for (FmiCached &c : g_fmi_cache) if (c.d_index == d_index && c.users > 0) { --c.users; break; }
-    }
+    ~FmiUse() { fmi_index_unuse(d_index); }
 };
 }
 
-// One device (the calling thread's current one).  `base` = index of read 0 in the caller's job (error texts only).
-static int fmi_host_one(const gbx_fmi_index *idx, const gbx_fmi_params *p, int64_t n_reads, const uint8_t *enc, int64_t enc_bytes,
-                        const int64_t *read_off, const int32_t *read_len, gbx_fmi_smem *out, int64_t out_cap,
-                        int64_t *smem_off, int64_t *n_out, int64_t base = 0)
+}  // extern "C"
+
+// The device index of a host call (one device: `dev`, the calling thread's current one): cached, or uploaded in the
+// reference's layout and re-laid on the device.  The entry is held until fmi_index_unuse.
+int gbx::fmi_index_acquire(const gbx_fmi_index *idx, int dev, hipStream_t s, void **out)
 {
-    RoctxRange range_("gbx_fmi_smem_host");
-    int rc = fmi_check(idx, p, "gbx_fmi_smem_host");
-    if (rc) return rc;
-    if (n_reads < 0 || out_cap < 0 || enc_bytes < 0) { set_error("gbx_fmi_smem_host: bad argument"); return GBX_ERR_ARG; }
-    if (!idx->cp_occ || !n_out || (n_reads > 0 && (!enc || !read_off || !read_len)) || (out_cap > 0 && !out)) {
-        set_error("gbx_fmi_smem_host: null pointer");
-        return GBX_ERR_ARG;
-    }
-    int32_t max_len = 0;
-    for (int64_t r = 0; r < n_reads; ++r) {
-        if (read_len[r] < 0 || read_off[r] < 0 || read_off[r] + read_len[r] > enc_bytes) {
-            set_error("gbx_fmi_smem_host: read %lld lies outside the base buffer", (long long)(base + r));
-            return GBX_ERR_ARG;
-        }
-        if (read_len[r] > max_len) max_len = read_len[r];
-    }
-    if ((rc = require_device())) return rc;
-    int dev = 0;
-    GBX_HIP(hipGetDevice(&dev));
-    HostLane lane;
-    if ((rc = lane.acquire())) return rc;
-    Lane *L = lane.l;
-    hipStream_t s = L->compute;
-    // the device index: cached, or uploaded in the reference's layout and re-laid on the device
-    FmiUse use;
     void *d_index = nullptr;
     {
         const uint64_t fp = fmi_fingerprint(idx);
@@ -203,8 +174,53 @@ static int fmi_host_one(const gbx_fmi_index *idx, const gbx_fmi_params *p, int64
             g_fmi_cv.notify_all();
             if (brc) return brc;
         }
-        use.d_index = d_index;
     }
+    *out = d_index;
+    return GBX_OK;
+}
+
+void gbx::fmi_index_unuse(void *d_index)
+{
+    if (!d_index) return;
+    std::lock_guard<std::mutex> lk(g_fmi_mu);
+    for (FmiCached &c : g_fmi_cache) if (c.d_index == d_index && c.users > 0) { --c.users; break; }
+}
+
+extern "C" {
+
+// One device (the calling thread's current one).  `base` = index of read 0 in the caller's job (error texts only).
+static int fmi_host_one(const gbx_fmi_index *idx, const gbx_fmi_params *p, int64_t n_reads, const uint8_t *enc, int64_t enc_bytes,
+                        const int64_t *read_off, const int32_t *read_len, gbx_fmi_smem *out, int64_t out_cap,
+                        int64_t *smem_off, int64_t *n_out, int64_t base = 0)
+{
+    RoctxRange range_("gbx_fmi_smem_host");
+    int rc = fmi_check(idx, p, "gbx_fmi_smem_host");
+    if (rc) return rc;
+    if (n_reads < 0 || out_cap < 0 || enc_bytes < 0) { set_error("gbx_fmi_smem_host: bad argument"); return GBX_ERR_ARG; }
+    if (!idx->cp_occ || !n_out || (n_reads > 0 && (!enc || !read_off || !read_len)) || (out_cap > 0 && !out)) {
+        set_error("gbx_fmi_smem_host: null pointer");
+        return GBX_ERR_ARG;
+    }
+    int32_t max_len = 0;
+    for (int64_t r = 0; r < n_reads; ++r) {
+        if (read_len[r] < 0 || read_off[r] < 0 || read_off[r] + read_len[r] > enc_bytes) {
+            set_error("gbx_fmi_smem_host: read %lld lies outside the base buffer", (long long)(base + r));
+            return GBX_ERR_ARG;
+        }
+        if (read_len[r] > max_len) max_len = read_len[r];
+    }
+    if ((rc = require_device())) return rc;
+    int dev = 0;
+    GBX_HIP(hipGetDevice(&dev));
+    HostLane lane;
+    if ((rc = lane.acquire())) return rc;
+    Lane *L = lane.l;
+    hipStream_t s = L->compute;
+    // the device index: cached, or uploaded in the reference's layout and re-laid on the device
+    FmiUse use;
+    void *d_index = nullptr;
+    if ((rc = fmi_index_acquire(idx, dev, s, &d_index))) return rc;
+    use.d_index = d_index;
     DevBuf denc(L), doff(L), dlen(L), dout(L), dso(L), dn(L), dw(L);
     const char *cap_env = getenv("GBX_FMI_RAW_CAP");          /* test aid: records per read slot of the first pass */
     const int cap0 = cap_env && atoi(cap_env) > 0 ? atoi(cap_env) : 0;
@@ -359,6 +375,7 @@ int gbx_fmi_host_release(void)
     }
     if (cur >= 0) (void)hipSetDevice(cur);
     (void)hipGetLastError();
+    fmi_sa_cache_release();
     return GBX_OK;
 }
 

@@ -7,7 +7,10 @@
 // batch_size is accepted and ignored: the three seeding rounds only combine SMEMs of one read and batches are contiguous
 // rid ranges, so the sorted output does not depend on it - all reads go to the GPU in one call.  n_threads = ingest
 // threads.  --print (the reference needs a PRINT_OUTPUT rebuild): the SMEMs in the format of fmi.cpp:312-343.
-// --parse-only stops after the ingest and prints counts and a checksum (no GPU needed).
+// --parse-only stops after the ingest and prints counts and a checksum (no GPU needed).  --print-sa [max_occ] (after the five
+// arguments; needs a bwa-mem2 index with real suffix-array samples): as --print, with the text positions of every SMEM's hits
+// (gbx_fmi_sal_host; bwa-mem's mem_chain sampling with max_occ, every row when it is absent or <= 0) - the reference's print
+// block with its #if 0 part on (fmi.cpp:330-340): "[m,n+1] [p,p,...,]".
 #include "driver_common.h"
 #include <algorithm>
 
@@ -75,13 +78,53 @@ static bool read_index(const char *ref_file, gbx_fmi_index &idx, std::vector<gbx
     return true;
 }
 
-static void help() { fprintf(stderr, "Need five arguments : ref_file query_set batch_size minSeedLen n_threads [--print] [--parse-only]\n"); }
+// The suffix-array samples of a bwa-mem2 file (--print-sa): the int8 upper bytes, then the uint32 lower words, behind the
+// checkpoints; n_sa from the file length.  All-zero samples (a file written without a suffix array) are refused: a real sample of
+// row 0 is SA[0] = reference_seq_len - 1.
+static bool read_sa(const char *ref_file, const gbx_fmi_index &idx, gbx_fmi_sa &sa, std::vector<int8_t> &ms, std::vector<uint32_t> &ls)
+{
+    const std::string pref = std::string(ref_file) + ".bwt.2bit.64";
+    std::string path = pref;
+    FILE *f = fopen(pref.c_str(), "rb");
+    if (!f) { path = ref_file; f = fopen(ref_file, "rb"); }
+    if (!f) { fprintf(stderr, "cannot open %s or %s\n", pref.c_str(), ref_file); return false; }
+    char magic[8];
+    if (fread(magic, 1, 8, f) != 8 || !memcmp(magic, "GBXFMI01", 8)) {
+        fprintf(stderr, "%s: --print-sa needs a bwa-mem2 index (.bwt.2bit.64) with suffix-array samples; this file has none\n", path.c_str());
+        fclose(f);
+        return false;
+    }
+    const int64_t n = idx.ref_seq_len, at = 48 + ((n >> 6) + 1) * (int64_t)sizeof(gbx_fmi_cp_occ);
+    fseek(f, 0, SEEK_END);
+    const int64_t size = (int64_t)ftell(f), rest = size - at - 8;
+    const int64_t n_sa = rest + 8 == 5 * n ? n : rest / 5;            // (the trailerless layout: one sample per row, no sentinel_index)
+    sa.sa_compx = n_sa == n ? 0 : 3;
+    sa.n_sa = n_sa;
+    if (n_sa != n && n_sa != (n >> 3) + 1) { fprintf(stderr, "%s: no suffix-array samples of a known layout\n", path.c_str()); fclose(f); return false; }
+    ms.resize((size_t)n_sa);
+    ls.resize((size_t)n_sa);
+    fseek(f, (long)at, SEEK_SET);
+    const bool ok = fread(ms.data(), 1, (size_t)n_sa, f) == (size_t)n_sa && fread(ls.data(), 4, (size_t)n_sa, f) == (size_t)n_sa;
+    fclose(f);
+    if (!ok) { fprintf(stderr, "%s: truncated\n", path.c_str()); return false; }
+    if ((((int64_t)(uint8_t)ms[0] << 32) | ls[0]) != n - 1) {
+        fprintf(stderr, "%s: the suffix-array samples are not real (the sample of row 0 must be %lld): the index was written without them\n",
+                path.c_str(), (long long)(n - 1));
+        return false;
+    }
+    sa.ms_byte = ms.data();
+    sa.ls_word = ls.data();
+    return true;
+}
+
+static void help() { fprintf(stderr, "Need five arguments : ref_file query_set batch_size minSeedLen n_threads [--print] [--parse-only] [--print-sa [max_occ]]\n"); }
 
 int main(int argc, char **argv)
 {
     const int gpus = take_gpus_flag(argc, argv);
     std::vector<const char *> pos;
-    bool print = false, parse_only = false;
+    bool print = false, parse_only = false, print_sa = false;
+    int32_t max_occ = 0;                                         // --print-sa: every row of an SMEM, as the reference's print block
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--index-info") && i + 1 < argc) {      // fmi --index-info <ref_file>: the tables' scalars and a checksum, no GPU
             gbx_fmi_index ix;
@@ -94,6 +137,15 @@ int main(int argc, char **argv)
         }
         if (!strcmp(argv[i], "--print")) print = true;
         else if (!strcmp(argv[i], "--parse-only")) parse_only = true;
+        else if (!strcmp(argv[i], "--print-sa")) {
+            // the optional max_occ (bwa-mem's mem_chain sampling; <= 0: every row) is taken when it follows the five arguments
+            print_sa = true;
+            char *end = nullptr;
+            if (i + 1 < argc && pos.size() == 5) {
+                const long v = strtol(argv[i + 1], &end, 10);
+                if (end && *end == 0 && end != argv[i + 1]) { max_occ = (int32_t)v; ++i; }
+            }
+        }
         else pos.push_back(argv[i]);
     }
     if (pos.size() != 5) { help(); return 1; }
@@ -154,6 +206,10 @@ int main(int argc, char **argv)
     std::vector<gbx_fmi_cp_occ> cp;
     if (!read_index(pos[0], idx, cp)) return EXIT_FAILURE;
     idx.cp_occ = cp.data();
+    gbx_fmi_sa sa{};
+    std::vector<int8_t> sa_ms;
+    std::vector<uint32_t> sa_ls;
+    if (print_sa && !read_sa(pos[0], idx, sa, sa_ms, sa_ls)) return EXIT_FAILURE;      // only loaded when asked for
     printf("reference seq len = %lld\n", (long long)idx.ref_seq_len);
     for (int c = 0; c < 5; ++c) printf("count[%d] = %lld\n", c, (long long)idx.count[c]);
 
@@ -175,14 +231,33 @@ int main(int argc, char **argv)
     const double dt = now_s() - t1;
     printf("Consumed: %0.4lf sec\n", dt);                        // the reference prints cycles too (rdtsc)
     printf("totalSmems = %lld\n", (long long)total);
-    if (print) {                                                 // fmi.cpp:312-343
+    // --print-sa: the positions of every SMEM's hits (gbx_fmi_sal_host), printed as the reference's print block does under #if 0
+    std::vector<int64_t> hit, hit_off;
+    if (print_sa) {
+        int64_t n_hit = 0;
+        hit_off.resize((size_t)total + 1);
+        rc = gbx_fmi_sal_host(&idx, &sa, smem.data(), total, max_occ, nullptr, 0, hit_off.data(), &n_hit);
+        if (rc == GBX_ERR_ARG && n_hit > 0) {
+            hit.resize((size_t)n_hit);
+            rc = gbx_fmi_sal_host(&idx, &sa, smem.data(), total, max_occ, hit.data(), n_hit, hit_off.data(), &n_hit);
+        }
+        die_on(rc, "gbx_fmi_sal_host");
+        printf("totalHits = %lld\n", (long long)n_hit);
+    }
+    if (print || print_sa) {                                     // fmi.cpp:312-343
         int64_t prev_rid = -1;
         for (int64_t i = 0; i < total; ++i) {
             const gbx_fmi_smem &s = smem[(size_t)i];
             if ((int64_t)s.rid != prev_rid)
                 for (int64_t j = prev_rid + 1; j <= (int64_t)s.rid; ++j) printf("%u:\n", (unsigned)j);
             prev_rid = s.rid;
-            printf("[%u,%u]\n", s.m, s.n + 1);
+            printf("[%u,%u]", s.m, s.n + 1);
+            if (print_sa) {
+                printf(" [");
+                for (int64_t u = hit_off[(size_t)i]; u < hit_off[(size_t)i + 1]; ++u) printf("%lld,", (long long)hit[(size_t)u]);
+                printf("]");
+            }
+            printf("\n");
         }
     }
     return 0;

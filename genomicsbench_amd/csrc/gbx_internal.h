@@ -172,6 +172,21 @@ int fmi_launch(const gbx_fmi_index *idx, const void *d_index, const gbx_fmi_para
                int64_t *d_smem_off, int64_t *d_n_out, void *d_work, size_t work_bytes, hipStream_t s, int raw_cap = 0);
 int fmi_read_extensions(const void *d_work, int64_t *ext, hipStream_t s);
 int fmi_read_overflow(const void *d_work, int64_t *worst, hipStream_t s);
+// the host entries' content-keyed cache of device indexes (capi_fmi.hip): a found or freshly built entry is held until
+// fmi_index_unuse; the suffix-array samples have a sibling cache (capi_fmi_sal.hip) that gbx_fmi_host_release empties too
+int fmi_index_acquire(const gbx_fmi_index *idx, int dev, hipStream_t s, void **d_index);
+void fmi_index_unuse(void *d_index);
+void fmi_sa_cache_release();
+
+// ---- fmi suffix-array lookup (fmi_sal_kernels.hip)
+bool fmi_sa_wide(int64_t ref_seq_len);           // 64-bit samples and kernel: ref_seq_len >= 2^32, or GBX_FMI_WIDE=1
+size_t fmi_sa_bytes(int64_t n_sa, int64_t ref_seq_len);
+int fmi_sa_build(const gbx_fmi_sa *sa, int64_t ref_seq_len, void *d_sa, size_t sa_bytes, hipStream_t s);
+size_t fmi_sal_workspace_bytes(int64_t smem_cap, int64_t pos_cap);
+int fmi_sal_launch(const gbx_fmi_index *idx, const void *d_index, const gbx_fmi_sa *sa, const void *d_sa, const gbx_fmi_smem *d_smems,
+                   const int64_t *d_n_smem, int64_t smem_cap, int32_t max_occ, int64_t *d_pos, int64_t pos_cap, int64_t *d_pos_off,
+                   int64_t *d_n_pos, void *d_work, size_t work_bytes, hipStream_t s);
+int fmi_sal_read_steps(const void *d_work, int64_t *steps, int64_t *max_steps, hipStream_t s);
 
 // ---- phmm (phmm_kernels.hip)
 size_t phmm_workspace_bytes(int64_t n_pairs, int64_t n_reads, int max_hap_len, int64_t stream_syms = -1);

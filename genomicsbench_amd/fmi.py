@@ -5,7 +5,9 @@ three seeding rounds per batch of reads).
 sentinel row) for reference + reverse complement - the job of `bwa-mem2 index`, which is outside the benchmark's
 timed region; tensor arithmetic only (suffix array by prefix doubling over torch.sort), so it runs on the GPU for the
 bench-sized genome and on the CPU in the tests.  ``smem_host`` / ``DeviceFmi`` call libgbx.so; all seeding
-arithmetic happens there on the GPU.
+arithmetic happens there on the GPU.  ``sal_host`` / ``DeviceFmi.sal`` turn SMEMs into text positions (the suffix-array
+lookup, gbx_fmi_sal_*) from the index's suffix-array samples (``FmiSa``: ``build_index(..., sa_compx=3)`` or
+``load_bwa_mem2_index(..., with_sa=True)``).
 """
 import ctypes as C
 
@@ -97,10 +99,11 @@ class FmiIndex:
                         torch.from_numpy(self.cp_occ.view(np.uint8).reshape(-1)).to(device))
 
 
-def build_index(ref, device=None):
+def build_index(ref, device=None, sa_compx=None):
     """ref: base codes 0..3 of the genome (one strand).  The index is over ref + reverse complement + sentinel, as
     bwa-mem2 builds it.  Returns an FmiIndex whose cp_occ lives on `device` (a torch uint8 tensor), or as a numpy
-    array when device is None / cpu."""
+    array when device is None / cpu.  With sa_compx (3 or 0) the suffix-array samples are kept too and the result is
+    (FmiIndex, FmiSa), the samples on the same side as the checkpoints."""
     import torch
     dev = torch.device(device) if device is not None else torch.device("cpu")
     f = (ref if isinstance(ref, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(ref, dtype=np.uint8))).to(dev)
@@ -115,7 +118,11 @@ def build_index(ref, device=None):
     prev[sent] = 0
     bwt[:n1] = text[prev]
     bwt[sent] = 4
-    del prev, sa
+    del prev
+    samples = None
+    if sa_compx is not None:
+        samples = FmiSa.from_sa(sa, sa_compx)
+    del sa
     cp = torch.zeros((ncp, 8), dtype=torch.int64, device=dev)
     blk = bwt.view(ncp, 64)
     weights = (torch.ones(64, dtype=torch.int64, device=dev) << torch.arange(63, -1, -1, device=dev))   # bit 63 - j for symbol j
@@ -128,7 +135,83 @@ def build_index(ref, device=None):
         count.append(count[-1] + int(per.sum().item()))
     raw = cp.view(torch.uint8).reshape(-1)
     idx = FmiIndex(n1, count, sent, raw)
+    if samples is not None:
+        return (idx.host(), samples.host()) if dev.type == "cpu" else (idx, samples)
     return idx.host() if dev.type == "cpu" else idx
+
+
+class FmiSaStruct(C.Structure):          # gbx_fmi_sa
+    _fields_ = [("sa_compx", C.c_int32), ("n_sa", C.c_int64), ("ms_byte", C.c_void_p), ("ls_word", C.c_void_p)]
+
+
+class FmiSa:
+    """Suffix-array samples as a .bwt.2bit.64 file stores them: ms[i] << 32 | ls[i] = SA[i << sa_compx], n_sa of them
+    ((ref_seq_len >> 3) + 1 for sa_compx 3, ref_seq_len for 0).  ms: int8, ls: uint32 - numpy arrays (host) or torch tensors
+    (device)."""
+
+    def __init__(self, sa_compx, ms, ls):
+        self.sa_compx, self.ms, self.ls = int(sa_compx), ms, ls
+        if self.sa_compx not in (0, 3):
+            raise ValueError("sa_compx must be 3 or 0, not %d" % self.sa_compx)
+
+    @staticmethod
+    def n_sa_for(ref_seq_len, sa_compx):
+        return (int(ref_seq_len) >> 3) + 1 if sa_compx else int(ref_seq_len)
+
+    @classmethod
+    def from_sa(cls, sa, sa_compx):
+        """Samples of a full suffix array (numpy or torch int64, ref_seq_len entries); rows past the end: 0."""
+        import torch
+        n = int(sa.shape[0])
+        n_sa = cls.n_sa_for(n, sa_compx)
+        if isinstance(sa, torch.Tensor):
+            smp = torch.zeros(n_sa, dtype=torch.int64, device=sa.device)
+            got = sa[::1 << sa_compx].to(torch.int64)
+            smp[:got.numel()] = got[:n_sa]
+            lo = (smp & 0xffffffff) - (((smp >> 31) & 1) << 32)             # the low word's bits as an int32 value
+            return cls(sa_compx, (smp >> 32).to(torch.uint8), lo.to(torch.int32))
+        smp = np.zeros(n_sa, dtype=np.int64)
+        got = np.asarray(sa, dtype=np.int64)[::1 << sa_compx][:n_sa]
+        smp[:len(got)] = got
+        return cls(sa_compx, (smp >> 32).astype(np.uint8).view(np.int8), (smp & 0xffffffff).astype(np.uint32))
+
+    @property
+    def n_sa(self):
+        return int(self.ms.shape[0])
+
+    def values(self):
+        """The 40-bit samples as int64 (host)."""
+        h = self.host()
+        return (h.ms.view(np.uint8).astype(np.int64) << 32) | h.ls.astype(np.int64)
+
+    def struct(self, ms_ptr, ls_ptr):
+        return FmiSaStruct(self.sa_compx, self.n_sa, ms_ptr, ls_ptr)
+
+    def ptrs(self):
+        if isinstance(self.ms, np.ndarray):
+            return self.ms.ctypes.data, self.ls.ctypes.data
+        return self.ms.data_ptr(), self.ls.data_ptr()
+
+    def host(self):
+        if isinstance(self.ms, np.ndarray):
+            return self
+        return FmiSa(self.sa_compx, np.ascontiguousarray(self.ms.cpu().numpy().view(np.int8)),
+                     np.ascontiguousarray(self.ls.cpu().numpy().view(np.uint32)))
+
+    def to(self, device):
+        import torch
+        h = self.host()
+        return FmiSa(self.sa_compx, torch.from_numpy(h.ms.view(np.uint8)).to(device),
+                     torch.from_numpy(h.ls.view(np.int32)).to(device))
+
+
+def depos(pos, n):
+    """bwa's bns_depos for text = genome + reverse complement of n = 2 L symbols: (is_rev, forward_pos) of raw text positions;
+    a position on the reverse strand maps to the forward coordinate of its last base, 2 L - 1 - pos."""
+    pos = np.asarray(pos, dtype=np.int64)
+    L = int(n) // 2
+    is_rev = pos >= L
+    return is_rev, np.where(is_rev, 2 * L - 1 - pos, pos)
 
 
 def save_index(index, path):
@@ -159,32 +242,43 @@ def load_index(path):
 #     int8    sa_ms_byte[n_sa]; uint32 sa_ls_word[n_sa]   suffix-array samples: n_sa = (reference_seq_len >> 3) + 1 with
 #                                                    SA_COMPRESSION (SA_COMPX 3, v2.1 on), = reference_seq_len before
 #     int64   sentinel_index
-# The SMEM search reads neither array of SA samples; a reader takes their size from the file length.
+# The SMEM search reads neither array of SA samples; a reader takes their size from the file length.  The suffix-array lookup
+# (sal_host, DeviceFmi.sal) reads both.
 def save_bwa_mem2_index(index, prefix, sa=None, sa_compx=3):
-    """Writes <prefix>.bwt.2bit.64.  sa: the full suffix array (int64[ref_seq_len]) to sample from, or None - the samples are
-    then written as zeros: such a file serves the seeding benchmark (and this repo's drivers), not `bwa-mem2 mem`."""
+    """Writes <prefix>.bwt.2bit.64.  sa: the full suffix array (int64[ref_seq_len]) to sample from, an FmiSa (written as it is,
+    its sa_compx wins), or None - the samples are then written as zeros: such a file serves the seeding benchmark (and this
+    repo's drivers), not `bwa-mem2 mem` nor the suffix-array lookup."""
     idx = index.host()
     n = int(idx.ref_seq_len)
+    if isinstance(sa, FmiSa):
+        sa_compx = sa.sa_compx
     n_sa = (n >> sa_compx) + 1 if sa_compx else n
     path = "%s.bwt.2bit.64" % prefix
     with open(path, "wb") as f:
         f.write(np.array([n] + [int(c) - 1 for c in idx.count], dtype="<i8").tobytes())
         f.write(idx.cp_occ.view(np.uint8).tobytes())
-        if sa is None:
+        if isinstance(sa, FmiSa):
+            h = sa.host()
+            assert h.n_sa == n_sa, "samples of another index"
+            f.write(h.ms.view(np.int8).tobytes())
+            f.write(h.ls.astype("<u4").tobytes())
+        elif sa is None:
             f.write(np.zeros(n_sa, dtype=np.int8).tobytes())
             f.write(np.zeros(n_sa, dtype="<u4").tobytes())
         else:
             smp = np.asarray(sa, dtype=np.int64)[::(1 << sa_compx) if sa_compx else 1][:n_sa]
             smp = np.concatenate([smp, np.zeros(n_sa - len(smp), dtype=np.int64)])
-            f.write((smp >> 32).astype(np.int8).tobytes())
+            f.write((smp >> 32).astype(np.uint8).tobytes())
             f.write((smp & 0xffffffff).astype("<u4").tobytes())
         f.write(np.array([idx.sentinel_index], dtype="<i8").tobytes())
     return path
 
 
-def load_bwa_mem2_index(prefix):
+def load_bwa_mem2_index(prefix, with_sa=False):
     """FMI_search::load_index as far as the SMEM search needs it: reads <prefix>.bwt.2bit.64 (or the file itself when
-    `prefix` already names one).  The SA samples are skipped, whichever of the two published sizes they have."""
+    `prefix` already names one).  The SA samples are skipped, whichever of the two published sizes they have - unless
+    with_sa, which returns (FmiIndex, FmiSa) and rejects samples that cannot be real (the all-zero ones save_bwa_mem2_index
+    writes without a suffix array: the sample of row 0 is SA[0] = ref_seq_len - 1)."""
     import os
     path = prefix if os.path.exists(prefix) and not os.path.exists("%s.bwt.2bit.64" % prefix) else "%s.bwt.2bit.64" % prefix
     size = os.path.getsize(path)
@@ -196,9 +290,19 @@ def load_bwa_mem2_index(prefix):
         rest = size - 48 - ncp * 64 - 8
         if len(cp) != ncp or rest < 0 or rest % 5 or rest // 5 not in (n, (n >> 3) + 1):
             raise ValueError("%s: not a bwa-mem2 .bwt.2bit.64 file (reference_seq_len %d, %d bytes)" % (path, n, size))
+        samples = None
+        if with_sa:
+            n_sa = rest // 5
+            ms = np.frombuffer(f.read(n_sa), dtype=np.int8).copy()
+            ls = np.frombuffer(f.read(4 * n_sa), dtype="<u4").astype(np.uint32)
+            samples = FmiSa(0 if n_sa == n else 3, ms, ls)
+            if n_sa == 0 or int(samples.values()[0]) != n - 1:
+                raise ValueError("%s: the suffix-array samples are not real (the sample of row 0 must be %d): the file was written "
+                                 "without a suffix array" % (path, n - 1))
         f.seek(size - 8)
         sentinel = int(np.frombuffer(f.read(8), dtype="<i8")[0])
-    return FmiIndex(n, [int(c) + 1 for c in head[1:6]], sentinel, cp)
+    idx = FmiIndex(n, [int(c) + 1 for c in head[1:6]], sentinel, cp)
+    return (idx, samples) if with_sa else idx
 
 
 def write_reads(path, reads, fastq=True, wrap=0):
@@ -273,6 +377,28 @@ def smem_host(index, reads, params=None, out_cap=None):
             continue
         N.check(rc)
         return out[:n_out.value], off
+
+
+def sal_host(index, sa, smems, max_occ=500, pos_cap=None):
+    """gbx_fmi_sal_host -> (pos int64[hits], pos_off int64[n_smem + 1]): the text positions of every SMEM's hits (bwa-mem's
+    mem_chain sampling with max_occ; <= 0: every row), SMEM j's in pos[pos_off[j]:pos_off[j + 1]]."""
+    idx, smp = index.host(), sa.host()
+    smems = np.ascontiguousarray(smems, dtype=SMEM_DTYPE)
+    n = len(smems)
+    off = np.zeros(n + 1, dtype=np.int64)
+    n_pos = C.c_int64(0)
+    st = idx.struct(idx.cp_occ.ctypes.data)
+    sst = smp.struct(*smp.ptrs())
+    cap = int(pos_cap) if pos_cap is not None else 0
+    while True:
+        pos = np.empty(max(cap, 1), dtype=np.int64)
+        rc = N.lib().gbx_fmi_sal_host(C.byref(st), C.byref(sst), N.ptr(smems) if n else None, n, int(max_occ), N.ptr(pos), cap,
+                                      N.ptr(off), C.byref(n_pos))
+        if rc == -1 and pos_cap is None and n_pos.value > cap:
+            cap = int(n_pos.value)
+            continue
+        N.check(rc)
+        return pos[:n_pos.value], off
 
 
 class DeviceFmi:
@@ -351,3 +477,53 @@ class DeviceFmi:
         v = C.c_int64(0)
         N.check(N.lib().gbx_fmi_extensions(self.work.data_ptr(), C.byref(v), stream))
         return v.value
+
+    def set_sa(self, sa):
+        """The index's suffix-array samples, re-laid for the device once (gbx_fmi_sa_build)."""
+        import torch
+        dev = self.dindex.device
+        self.sa = sa
+        src = sa.to(dev)
+        self.sa_st = src.struct(*src.ptrs())
+        L = N.lib()
+        self.dsa = torch.empty(max(1, L.gbx_fmi_sa_bytes(src.n_sa, self.index.ref_seq_len)), dtype=torch.uint8, device=dev)
+        N.check(L.gbx_fmi_sa_build(C.byref(self.sa_st), self.index.ref_seq_len, self.dsa.data_ptr(), self.dsa.numel(), None))
+        torch.cuda.synchronize()
+        del src
+
+    def sal(self, max_occ=500, pos_cap=None, stream=None, sa=None):
+        """gbx_fmi_sal_device on the SMEMs this object holds on the device (the output of the last run(), counted on the device:
+        no host round trip in between).  Results: sal_results()."""
+        import torch
+        if sa is not None:
+            self.set_sa(sa)
+        dev = self.dindex.device
+        cap = int(pos_cap if pos_cap is not None else max(64, 16 * self.out_cap))
+        if getattr(self, "pos_cap", None) != cap:
+            self.pos_cap = cap
+            self.pos = torch.empty(cap, dtype=torch.int64, device=dev)
+        if getattr(self, "pos_off", None) is None or self.pos_off.numel() != self.out_cap + 1:
+            self.pos_off = torch.zeros(self.out_cap + 1, dtype=torch.int64, device=dev)
+            self.n_pos = torch.zeros(1, dtype=torch.int64, device=dev)
+        wb = N.lib().gbx_fmi_sal_workspace_bytes(self.out_cap, self.pos_cap)
+        if getattr(self, "sal_work_bytes", None) != wb:
+            self.sal_work_bytes = wb
+            self.sal_work = torch.empty(wb, dtype=torch.uint8, device=dev)
+        N.check(N.lib().gbx_fmi_sal_device(C.byref(self.st), self.dindex.data_ptr(), C.byref(self.sa_st), self.dsa.data_ptr(),
+                                           self.out.data_ptr(), self.n_out.data_ptr(), self.out_cap, int(max_occ), self.pos.data_ptr(),
+                                           self.pos_cap, self.pos_off.data_ptr(), self.n_pos.data_ptr(), self.sal_work.data_ptr(),
+                                           self.sal_work_bytes, stream))
+
+    def sal_results(self):
+        """(pos, pos_off) of the last sal() call; raises when the hits did not fit."""
+        n = int(self.n_pos.item())
+        if n > self.pos_cap:
+            raise RuntimeError("fmi sal: %d hits do not fit the position capacity %d" % (n, self.pos_cap))
+        m = min(int(self.n_out.item()), self.out_cap)
+        return self.pos[:n].cpu().numpy(), self.pos_off[:m + 1].cpu().numpy()
+
+    def sal_steps(self, stream=None):
+        """(LF steps, longest walk of one hit) of the last sal() call."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        N.check(N.lib().gbx_fmi_sal_steps(self.sal_work.data_ptr(), C.byref(a), C.byref(b), stream))
+        return a.value, b.value

@@ -494,8 +494,51 @@ int gbx_fmi_overflow(const void *d_work, int64_t *worst, void *stream);
 int gbx_fmi_extensions(const void *d_work, int64_t *ext, void *stream);
 /* gbx_fmi_smem_host keeps the device copy of an index between calls (a caller hands over the same tables for every batch
  * of reads, fmi.cpp:218), found again by content - the index scalars and a fingerprint of 256 checkpoints - not by address;
- * at most four idle copies per device; this frees the ones no call is using. */
+ * at most four idle copies per device; this frees the ones no call is using (and the suffix-array samples gbx_fmi_sal_host
+ * keeps alike). */
 int gbx_fmi_host_release(void);
+
+/* ---- suffix-array lookup of SMEM hits (bwa-mem2's FMI_search::get_sa_entry, the step between seeding and extension)
+ * text = genome + reverse complement, n = 2 L, ref_seq_len = n + 1; SA row 0 is the sentinel suffix (SA[0] = n) and the
+ * BWT symbol at sentinel_index is the sentinel.  Samples as a .bwt.2bit.64 file stores them: the 40-bit value
+ * ms_byte[i] << 32 | ls_word[i] is SA[i << sa_compx]; sa_compx 3 (n_sa = (ref_seq_len >> 3) + 1) or 0 (n_sa = ref_seq_len).
+ * SA[r] of any row: while r is not sampled, step r <- LF(r) = count[b] + occ_b(r) (b the BWT symbol at r) and add 1 to an
+ * offset t; a walk that reaches the sentinel row gives t, one that reaches a sampled row r' gives sample(r') + t.
+ * Hits of an SMEM [k, k + s) follow bwa-mem's mem_chain sampling with max_occ (bwa's default 500): step = s > max_occ ?
+ * s / max_occ : 1, rows k + i step for i = 0, 1, ... while i step < s and i < max_occ - min(s, max_occ) hits; max_occ <= 0:
+ * every row.  SMEM j's hits go to pos[pos_off[j] .. pos_off[j + 1]) in increasing row order (pos_off: n_smem + 1 entries),
+ * as raw text coordinates in [0, n] (the strand split, bwa's bns_depos, is the caller's); the output does not depend on
+ * the scheduling.  An SMEM is bad unless k >= 0, s >= 1 and k + s <= ref_seq_len. */
+typedef struct gbx_fmi_sa {
+    int32_t sa_compx;                /* 3 or 0 */
+    int64_t n_sa;                    /* (ref_seq_len >> 3) + 1, or ref_seq_len */
+    const int8_t *ms_byte;           /* n_sa upper bytes; host pointers for *_host, device pointers for gbx_fmi_sa_build */
+    const uint32_t *ls_word;         /* n_sa lower words */
+} gbx_fmi_sa;
+
+/* Host-buffer entry.  Every SMEM is checked before the device is touched: a bad one gives GBX_ERR_ARG naming the lowest.
+ * *n_pos = the hit count; more than pos_cap gives GBX_ERR_ARG with the needed count in gbx_last_error().  pos_off
+ * (n_smem + 1, nullable).  The device copies of the index and of the samples are kept between calls, found by content
+ * (gbx_fmi_host_release frees them).  Safe under concurrent host threads. */
+int gbx_fmi_sal_host(const gbx_fmi_index *idx, const gbx_fmi_sa *sa, const gbx_fmi_smem *smems, int64_t n_smem, int32_t max_occ,
+                     int64_t *pos, int64_t pos_cap, int64_t *pos_off, int64_t *n_pos);
+
+/* Device path.  The samples are re-laid for the device once per index (gbx_fmi_sa_bytes / gbx_fmi_sa_build: 32 bits per
+ * sample when ref_seq_len < 2^32, 64 otherwise - or always with GBX_FMI_WIDE=1, which also selects the 64-bit kernel; the
+ * variable must be the same for the build and the lookups).  The SMEM count is read on the device (*d_n_smem, e.g. the
+ * d_n_out of gbx_fmi_smem_device on the same stream; at most smem_cap SMEMs are looked up), so the two calls chain without a
+ * host round trip.  d_pos_off holds smem_cap + 1 entries (those past the SMEM count repeat the total); *d_n_pos = the hit
+ * count, greater than pos_cap when the output did not fit (nothing past pos_cap is written).  A bad SMEM is not walked:
+ * its hits (as many as for min(s, ref_seq_len)) are -1. */
+size_t gbx_fmi_sa_bytes(int64_t n_sa, int64_t ref_seq_len);
+int gbx_fmi_sa_build(const gbx_fmi_sa *sa_with_device_arrays, int64_t ref_seq_len, void *d_sa, size_t sa_bytes, void *stream);
+size_t gbx_fmi_sal_workspace_bytes(int64_t smem_cap, int64_t pos_cap);
+int gbx_fmi_sal_device(const gbx_fmi_index *idx, const void *d_index, const gbx_fmi_sa *sa, const void *d_sa,
+                       const gbx_fmi_smem *d_smems, const int64_t *d_n_smem, int64_t smem_cap, int32_t max_occ,
+                       int64_t *d_pos, int64_t pos_cap, int64_t *d_pos_off, int64_t *d_n_pos, void *d_work, size_t work_bytes,
+                       void *stream);
+/* LF steps of the last gbx_fmi_sal_device call on this workspace: their total and the longest walk of one hit. */
+int gbx_fmi_sal_steps(const void *d_work, int64_t *steps, int64_t *max_steps, void *stream);
 
 #ifdef __cplusplus
 }

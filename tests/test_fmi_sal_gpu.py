@@ -1,0 +1,291 @@
+"""GPU tests of the suffix-array lookup (gbx_fmi_sal_host / gbx_fmi_sal_device): every hit's position equals the full suffix
+array, bit-exact, and the positions of tests/sal_ref.py's restated walk."""
+import os
+import subprocess
+import threading
+
+import numpy as np
+import pytest
+
+from genomicsbench_amd import _native as N
+from genomicsbench_amd import fmi as FM
+from genomicsbench_amd.datagen import gen_fmi_genome, gen_fmi_reads
+import sal_ref as R
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def full_sa(g):
+    return FM.suffix_array(np.concatenate([g, 3 - g[::-1]])).numpy()
+
+
+def want_pos(sa, smems, max_occ):
+    rows, off = R.hit_rows(smems["k"], smems["s"], max_occ)
+    return sa[rows], off
+
+
+def check(got, want):
+    (gp, go), (wp, wo) = got, want
+    assert np.array_equal(go, wo), "pos_off differs"
+    assert len(gp) == len(wp)
+    if not np.array_equal(gp, wp):
+        k = int(np.nonzero(gp != wp)[0][0])
+        raise AssertionError("%d of %d positions differ; first hit %d: got %d want %d" % (int((gp != wp).sum()), len(wp), k, gp[k], wp[k]))
+
+
+@pytest.fixture(scope="module")
+def small():
+    g = gen_fmi_genome(300_000, 6001)
+    idx, smp = FM.build_index(g, sa_compx=3)
+    _, smp0 = FM.build_index(g, sa_compx=0)
+    rs = gen_fmi_reads(g, 2000, 6002)
+    smems, _ = FM.smem_host(idx, rs)
+    return g, idx, smp, smp0, rs, smems, full_sa(g)
+
+
+def device_run(idx, smp, rs, max_occ, pos_cap=None):
+    import torch
+    d = FM.DeviceFmi(idx, rs, torch.device("cuda:0"))
+    d.run()
+    d.set_sa(smp)
+    d.sal(max_occ, pos_cap=pos_cap)
+    torch.cuda.synchronize()
+    return d
+
+
+@pytest.mark.parametrize("wide", ["0", "1"])
+@pytest.mark.parametrize("cx", [3, 0])
+def test_reads_of_the_generator(small, monkeypatch, wide, cx):
+    g, idx, smp3, smp0, rs, smems, sa = small
+    smp = smp3 if cx == 3 else smp0
+    monkeypatch.setenv("GBX_FMI_WIDE", wide)
+    assert len(smems) > 1000
+    want = want_pos(sa, smems, 500)
+    check(FM.sal_host(idx, smp, smems, 500), want)
+    d = device_run(idx, smp, rs, 500)
+    check(d.sal_results(), want)
+    steps, longest = d.sal_steps()
+    rows, _ = R.hit_rows(smems["k"], smems["s"], 500)
+    _, t = R.sa_walk(idx, smp, rows, return_steps=True)
+    assert steps == int(t.sum()) and longest == int(t.max())
+
+
+def repetitive():
+    rng = np.random.default_rng(5)
+    elem = rng.integers(0, 4, 700).astype(np.uint8)
+    parts = []
+    for _ in range(60):
+        c = elem.copy()
+        hit = rng.random(700) < 0.02
+        c[hit] = (c[hit] + 1) % 4
+        parts += [c, rng.integers(0, 4, int(rng.integers(5, 60))).astype(np.uint8)]
+    g = np.concatenate(parts)
+    reads = []
+    for _ in range(600):
+        p = int(rng.integers(0, len(g) - 151))
+        r = g[p:p + 151].copy()
+        if rng.random() < 0.5:
+            r = 3 - r[::-1]
+        hit = rng.random(151) < 0.015
+        r[hit] = (r[hit] + 1) % 4
+        reads.append(r)
+    return g, FM.FmiReadSet.fixed(np.array(reads))
+
+
+@pytest.mark.parametrize("wide", ["0", "1"])
+def test_repetitive_genome_many_hits_per_smem(monkeypatch, wide):
+    monkeypatch.setenv("GBX_FMI_WIDE", wide)
+    g, rs = repetitive()
+    idx, smp = FM.build_index(g, sa_compx=3)
+    sa = full_sa(g)
+    smems, _ = FM.smem_host(idx, rs)
+    assert int(smems["s"].max()) >= 20
+    # beside the reads' SMEMs, intervals of hundreds to thousands of rows: every base's interval and random ones
+    rng = np.random.default_rng(6)
+    wide_iv = np.zeros(24, dtype=FM.SMEM_DTYPE)
+    wide_iv["k"][:4] = idx.count[:4]
+    wide_iv["s"][:4] = np.diff(idx.count)
+    wide_iv["s"][4:] = rng.integers(100, 3000, 20)
+    wide_iv["k"][4:] = rng.integers(0, idx.ref_seq_len - wide_iv["s"][4:])
+    wide_iv["s"][5], wide_iv["s"][6] = 999, 1000                        # 2 max_occ - 1 and 2 max_occ for max_occ 500
+    allsm = np.concatenate([smems, wide_iv])
+    assert int(allsm["s"].max()) >= 500
+    for mo in (1, 5, 500, 0, -1):
+        want = want_pos(sa, allsm, mo)
+        check(FM.sal_host(idx, smp, allsm, mo), want)
+        d = device_run(idx, smp, rs, mo)
+        check(d.sal_results(), want_pos(sa, smems, mo))
+        check(device_on(d, allsm, mo), want)
+
+
+def device_on(d, smems, max_occ):
+    """gbx_fmi_sal_device on SMEMs of the caller's, written into the object's SMEM buffer."""
+    import torch
+    assert len(smems) <= d.out_cap
+    d.out[:len(smems) * FM.SMEM_DTYPE.itemsize] = torch.from_numpy(np.ascontiguousarray(smems).view(np.uint8)).to(d.out.device)
+    d.n_out.fill_(len(smems))
+    d.sal(max_occ)
+    torch.cuda.synchronize()
+    return d.sal_results()
+
+
+@pytest.mark.parametrize("wide", ["0", "1"])
+def test_frozen_fixture(monkeypatch, wide):
+    from util import load_fmi_golden
+    monkeypatch.setenv("GBX_FMI_WIDE", wide)
+    g, rs, _ = load_fmi_golden()
+    sa = full_sa(g)
+    for cx in (3, 0):
+        idx, smp = FM.build_index(g, sa_compx=cx)
+        smems, _ = FM.smem_host(idx, rs)
+        for mo in (500, 0):
+            check(FM.sal_host(idx, smp, smems, mo), want_pos(sa, smems, mo))
+
+
+def test_wide_instance_uses_the_upper_byte(small, monkeypatch):
+    """Samples shifted by c 2^32 (c = 1, 200): a walk that ends at a sampled row gives the shifted value, one that ends at the
+    sentinel row does not - exactly what the restatement gives."""
+    g, idx, smp, _, rs, smems, sa = small
+    monkeypatch.setenv("GBX_FMI_WIDE", "1")
+    for c in (1, 200):
+        v = smp.values() + (c << 32)
+        sh = FM.FmiSa(3, (v >> 32).astype(np.uint8).view(np.int8), (v & 0xffffffff).astype(np.uint32))
+        want = R.smem_positions(idx, sh, smems["k"], smems["s"], 500)
+        assert want[0].max() >= (c << 32)
+        check(FM.sal_host(idx, sh, smems, 500), want)
+        d = device_run(idx, sh, rs, 500)
+        check(d.sal_results(), want)
+
+
+def test_chained_on_one_stream_without_a_host_sync(small):
+    import torch
+    g, idx, smp, _, rs, smems, sa = small
+    d = FM.DeviceFmi(idx, rs, torch.device("cuda:0"))
+    d.set_sa(smp)
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        d.run(s.cuda_stream)
+        d.sal(500, stream=s.cuda_stream)
+    s.synchronize()
+    got_sm, _ = d.results()
+    assert np.array_equal(got_sm, smems)
+    check(d.sal_results(), FM.sal_host(idx, smp, smems, 500))
+    first = d.sal_results()
+    d.sal(500)                                                           # the same workspace again
+    torch.cuda.synchronize()
+    check(d.sal_results(), first)
+
+
+def test_capacity_overflow_is_reported(small):
+    import torch
+    g, idx, smp, _, rs, smems, sa = small
+    with pytest.raises(N.GbxError, match="do not fit"):
+        FM.sal_host(idx, smp, smems, 500, pos_cap=10)
+    d = device_run(idx, smp, rs, 500, pos_cap=100)
+    total = int(d.n_pos.item())
+    assert total == len(want_pos(sa, smems, 500)[0]) > 100
+    with pytest.raises(RuntimeError, match="do not fit"):
+        d.sal_results()
+    assert np.array_equal(d.pos[:100].cpu().numpy(), want_pos(sa, smems, 500)[0][:100])   # what fits is right
+    # nothing past pos_cap is written
+    guard = torch.full((200,), -7, dtype=torch.int64, device="cuda:0")
+    d.pos = guard
+    d.pos_cap = 100
+    d.sal(500, pos_cap=100)
+    torch.cuda.synchronize()
+    assert np.all(guard[100:].cpu().numpy() == -7)
+
+
+def test_bad_smems(small):
+    import torch
+    g, idx, smp, _, rs, smems, sa = small
+    bad = smems[:50].copy()
+    bad["k"][7] = idx.ref_seq_len - 1
+    bad["s"][7] = 3                                                      # past the last row
+    bad["k"][20] = -4
+    with pytest.raises(N.GbxError, match="SMEM 7 "):
+        FM.sal_host(idx, smp, bad, 500)
+    # on the device: hits of -1, the others untouched
+    d = FM.DeviceFmi(idx, rs, torch.device("cuda:0"))
+    d.set_sa(smp)
+    pos, off = device_on(d, bad, 500)
+    cnt = np.minimum(np.minimum(bad["s"], idx.ref_seq_len), 500)
+    assert np.array_equal(np.diff(off), cnt)
+    good = np.ones(len(bad), bool)
+    good[[7, 20]] = False
+    for j in range(len(bad)):
+        seg = pos[off[j]:off[j + 1]]
+        if good[j]:
+            assert np.array_equal(seg, want_pos(sa, bad[j:j + 1], 500)[0])
+        else:
+            assert np.all(seg == -1)
+
+
+def test_zero_smems(small):
+    import torch
+    g, idx, smp, _, rs, smems, sa = small
+    pos, off = FM.sal_host(idx, smp, smems[:0], 500)
+    assert len(pos) == 0 and off.tolist() == [0]
+    d = FM.DeviceFmi(idx, rs, torch.device("cuda:0"))
+    d.set_sa(smp)
+    d.n_out.zero_()
+    d.sal(500)
+    torch.cuda.synchronize()
+    pos, off = d.sal_results()
+    assert len(pos) == 0 and off.tolist() == [0]
+
+
+def test_four_host_threads(small):
+    g, idx, smp, smp0, rs, smems, sa = small
+    N.check(N.lib().gbx_fmi_host_release())
+    jobs = [(smp, 500), (smp0, 500), (smp, 0), (smp0, 7)]
+    want = [want_pos(sa, smems, mo) for _, mo in jobs]
+    got, err = [None] * 4, []
+
+    def work(k):
+        try:
+            got[k] = FM.sal_host(idx, jobs[k][0], smems, jobs[k][1])
+        except Exception as e:                                           # noqa: BLE001
+            err.append((k, repr(e)))
+
+    th = [threading.Thread(target=work, args=(k,)) for k in range(4)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join()
+    assert not err, err
+    for k in range(4):
+        check(got[k], want[k])
+    N.check(N.lib().gbx_fmi_host_release())
+
+
+def test_driver_print_sa(tmp_path):
+    g = gen_fmi_genome(30_000, 4101)
+    idx, smp = FM.build_index(g, sa_compx=3)
+    p = FM.save_bwa_mem2_index(idx, str(tmp_path / "g"), sa=smp)
+    rs = gen_fmi_reads(g, 60, 4102)
+    FM.write_reads(str(tmp_path / "r.fq"), rs)
+    smems, _ = FM.smem_host(idx, FM.FmiReadSet.fixed(np.array([np.concatenate([rs.enc[rs.read_off[r]:rs.read_off[r] + rs.read_len[r]],
+                                                                                np.full(rs.max_len - rs.read_len[r], 4, np.uint8)])
+                                                               for r in range(rs.n_reads)])))
+    exe = os.path.join(ROOT, "genomicsbench_amd", "bin", "fmi")
+    for mo in (None, 3):
+        args = [exe, str(tmp_path / "g"), str(tmp_path / "r.fq"), "512", "19", "2", "--print-sa"] + ([str(mo)] if mo else [])
+        r = subprocess.run(args, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr
+        pos, off = R.smem_positions(idx, smp, smems["k"], smems["s"], mo or 0)
+        want = []
+        for line in FM.smems_text(smems):
+            want.append(line)
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("[") or ln.endswith(":")]
+        j = 0
+        exp = []
+        for line in want:
+            if line.endswith(":"):
+                exp.append(line)
+            else:
+                exp.append("%s [%s]" % (line, "".join("%d," % v for v in pos[off[j]:off[j + 1]])))
+                j += 1
+        assert lines == exp
+    assert os.path.exists(p)
