@@ -34,14 +34,7 @@ static int fmi_check(const gbx_fmi_index *idx, const gbx_fmi_params *p, const ch
 {
     if (!idx || !p) { set_error("%s: null pointer", who); return GBX_ERR_ARG; }
     if (p->min_seed_len < 1 || p->split_width < 0 || p->max_mem_intv < 0) { set_error("%s: bad parameters", who); return GBX_ERR_ARG; }
-    if (idx->ref_seq_len < 2 || idx->count[0] != 1 || idx->count[4] != idx->ref_seq_len || idx->sentinel_index < 0 ||
-        idx->sentinel_index >= idx->ref_seq_len) {
-        set_error("%s: inconsistent index (count[0] must be 1, count[4] the reference length incl. the sentinel)", who);
-        return GBX_ERR_ARG;
-    }
-    for (int c = 0; c < 4; ++c)
-        if (idx->count[c] > idx->count[c + 1]) { set_error("%s: count[] not monotone", who); return GBX_ERR_ARG; }
-    return GBX_OK;
+    return fmi_index_check(idx, INT64_MAX, who);
 }
 
 int gbx_fmi_smem_device(const gbx_fmi_index *idx, const void *d_index, const gbx_fmi_params *p, int64_t n_reads,
@@ -73,117 +66,49 @@ int gbx_fmi_extensions(const void *d_work, int64_t *ext, void *stream)
     return fmi_read_extensions(d_work, ext, (hipStream_t)stream);
 }
 
-// The host entry keeps the device copy of an index between calls (a reference-side caller hands over the same
-// FMI_search tables for every batch of reads, fmi.cpp:218), one per device.  An entry is found by the index's CONTENT -
-// its scalars and a fingerprint of 256 checkpoints spread over the table - not by the caller's address: a buffer that
-// was freed and reused for another index of the same length is a different index.  Entries are reference-counted while a
-// call uses them (gbx_fmi_host_release leaves those alone) and at most four idle ones are kept per device.
-namespace {
-struct FmiCached { int dev; int64_t len, sentinel, count[5]; uint64_t fp; void *d_index; size_t bytes; int users; uint64_t last_use; bool building; };
-std::mutex g_fmi_mu;
-std::condition_variable g_fmi_cv;          // an entry under construction (building) has been finished or given up
-std::vector<FmiCached> g_fmi_cache;
-uint64_t g_fmi_clock = 0;
-
-uint64_t fmi_fingerprint(const gbx_fmi_index *idx)
-{
-    const int64_t ncp = (idx->ref_seq_len >> 6) + 1;
-    uint64_t h = 1469598103934665603ull;
-    auto mix = [&](const void *p, size_t n) { const unsigned char *b = (const unsigned char *)p; for (size_t k = 0; k < n; ++k) { h ^= b[k]; h *= 1099511628211ull; } };
-    // one checkpoint in every 4096 (at least 256): a table edited in place between two calls is caught unless the edit misses
-    // every sampled line - mutating an index that has been handed to the library is not supported (gbx_fmi_host_release forgets it)
-    const int64_t samples = ncp < 256 ? ncp : std::max<int64_t>(256, ncp >> 12);
-    for (int64_t k = 0; k < samples; ++k) mix(&idx->cp_occ[(size_t)(k * (ncp - 1) / (samples > 1 ? samples - 1 : 1))], sizeof(gbx_fmi_cp_occ));
-    return h;
-}
-struct FmiUse {                       // holds a cache entry for the duration of a call
-    void *d_index = nullptr;
-    ~FmiUse() { fmi_index_unuse(d_index); }
-};
-}
-
 }  // extern "C"
 
-// The device index of a host call (one device: `dev`, the calling thread's current one): cached, or uploaded in the
-// reference's layout and re-laid on the device.  The entry is held until fmi_index_unuse.
-int gbx::fmi_index_acquire(const gbx_fmi_index *idx, int dev, hipStream_t s, void **out)
+int gbx::fmi_index_check(const gbx_fmi_index *idx, int64_t max_len, const char *who)
 {
-    void *d_index = nullptr;
-    {
-        const uint64_t fp = fmi_fingerprint(idx);
-        auto same = [&](const FmiCached &c) {
-            return c.dev == dev && c.len == idx->ref_seq_len && c.sentinel == idx->sentinel_index && c.fp == fp && !memcmp(c.count, idx->count, sizeof(c.count));
-        };
-        bool build = false;
-        {
-            std::unique_lock<std::mutex> lk(g_fmi_mu);
-            for (;;) {
-                FmiCached *hit = nullptr;
-                for (FmiCached &c : g_fmi_cache) if (same(c)) hit = &c;
-                if (hit && hit->building) { g_fmi_cv.wait(lk); continue; }        // another caller is uploading this very index: wait for it
-                if (hit) { d_index = hit->d_index; ++hit->users; hit->last_use = ++g_fmi_clock; }
-                break;
-            }
-            if (!d_index) {
-                // at most four idle entries per device: the least recently used goes first
-                for (;;) {
-                    int idle = 0, victim = -1;
-                    for (size_t k = 0; k < g_fmi_cache.size(); ++k)
-                        if (g_fmi_cache[k].dev == dev && g_fmi_cache[k].users == 0 && !g_fmi_cache[k].building) {
-                            ++idle;
-                            if (victim < 0 || g_fmi_cache[k].last_use < g_fmi_cache[(size_t)victim].last_use) victim = (int)k;
-                        }
-                    if (idle < 4) break;
-                    (void)hipFree(g_fmi_cache[(size_t)victim].d_index);
-                    g_fmi_cache.erase(g_fmi_cache.begin() + victim);
-                }
-                // a place-holder under the lock; the upload and the re-layout (up to a gigabyte over PCIe) run outside it, so that
-                // the shards of a multi-device call build their copies side by side and gbx_fmi_host_release never waits for one
-                FmiCached c{dev, idx->ref_seq_len, idx->sentinel_index, {0, 0, 0, 0, 0}, fp, nullptr, 0, 1, ++g_fmi_clock, true};
-                memcpy(c.count, idx->count, sizeof(c.count));
-                g_fmi_cache.push_back(c);
-                build = true;
-            }
-        }
-        if (build) {
-            const size_t bytes = fmi_index_bytes(idx->ref_seq_len);
-            void *d_src = nullptr;
-            hipError_t e = hipMalloc(&d_index, bytes);
-            if (e != hipSuccess) d_index = nullptr;
-            if (e == hipSuccess) e = hipMalloc(&d_src, bytes);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_src, idx->cp_occ, bytes, hipMemcpyHostToDevice, s);
-            int brc = e == hipSuccess ? GBX_OK : hip_fail(e, "fmi index upload");
-            if (!brc) {
-                gbx_fmi_index di = *idx;
-                di.cp_occ = (const gbx_fmi_cp_occ *)d_src;
-                brc = fmi_index_build(&di, d_index, bytes, s);
-                const hipError_t e2 = hipStreamSynchronize(s);
-                if (!brc && e2 != hipSuccess) brc = hip_fail(e2, "fmi index build");
-            }
-            if (d_src) (void)hipFree(d_src);
-            if (brc && d_index) { (void)hipFree(d_index); d_index = nullptr; }
-            {
-                std::lock_guard<std::mutex> lk(g_fmi_mu);
-                for (size_t k = 0; k < g_fmi_cache.size(); ++k)
-                    if (g_fmi_cache[k].building && same(g_fmi_cache[k])) {
-                        if (brc) g_fmi_cache.erase(g_fmi_cache.begin() + (long)k);
-                        else { g_fmi_cache[k].d_index = d_index; g_fmi_cache[k].bytes = bytes; g_fmi_cache[k].building = false; }
-                        break;
-                    }
-            }
-            g_fmi_cv.notify_all();
-            if (brc) return brc;
-        }
+    if (idx->ref_seq_len < 2 || idx->ref_seq_len > max_len || idx->count[0] != 1 || idx->count[4] != idx->ref_seq_len ||
+        idx->sentinel_index < 0 || idx->sentinel_index >= idx->ref_seq_len) {
+        set_error("%s: inconsistent index (count[0] must be 1, count[4] the reference length incl. the sentinel)", who);
+        return GBX_ERR_ARG;
     }
-    *out = d_index;
+    for (int c = 0; c < 4; ++c)
+        if (idx->count[c] > idx->count[c + 1]) { set_error("%s: count[] not monotone", who); return GBX_ERR_ARG; }
     return GBX_OK;
 }
 
-void gbx::fmi_index_unuse(void *d_index)
+// The host entry keeps the device copy of an index between calls (a reference-side caller hands over the same FMI_search
+// tables for every batch of reads, fmi.cpp:218), one per device, keyed by the index's scalars and a fingerprint of its
+// checkpoints.
+HostCache gbx::fmi_index_cache;
+
+// The device index of a host call: cached, or uploaded in the reference's layout and re-laid on the device.
+int gbx::fmi_index_acquire(const gbx_fmi_index *idx, int dev, hipStream_t s, void **out)
 {
-    if (!d_index) return;
-    std::lock_guard<std::mutex> lk(g_fmi_mu);
-    for (FmiCached &c : g_fmi_cache) if (c.d_index == d_index && c.users > 0) { --c.users; break; }
+    const HostCacheKey key{dev, {idx->ref_seq_len, idx->sentinel_index, idx->count[0], idx->count[1], idx->count[2], idx->count[3], idx->count[4]},
+                           sampled_fingerprint((idx->ref_seq_len >> 6) + 1, [&](auto &mix, size_t i) { mix(&idx->cp_occ[i], sizeof(gbx_fmi_cp_occ)); })};
+    return fmi_index_cache.acquire(key, [&](void **d_index) {
+        const size_t bytes = fmi_index_bytes(idx->ref_seq_len);
+        void *d_src = nullptr;
+        hipError_t e = hipMalloc(d_index, bytes);
+        if (e != hipSuccess) *d_index = nullptr;
+        if (e == hipSuccess) e = hipMalloc(&d_src, bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_src, idx->cp_occ, bytes, hipMemcpyHostToDevice, s);
+        int rc = e == hipSuccess ? GBX_OK : hip_fail(e, "fmi index upload");
+        if (!rc) {
+            gbx_fmi_index di = *idx;
+            di.cp_occ = (const gbx_fmi_cp_occ *)d_src;
+            rc = fmi_index_build(&di, *d_index, bytes, s);
+            const hipError_t e2 = hipStreamSynchronize(s);
+            if (!rc && e2 != hipSuccess) rc = hip_fail(e2, "fmi index build");
+        }
+        if (d_src) (void)hipFree(d_src);
+        if (rc && *d_index) { (void)hipFree(*d_index); *d_index = nullptr; }
+        return rc;
+    }, out);
 }
 
 extern "C" {
@@ -216,11 +141,9 @@ static int fmi_host_one(const gbx_fmi_index *idx, const gbx_fmi_params *p, int64
     if ((rc = lane.acquire())) return rc;
     Lane *L = lane.l;
     hipStream_t s = L->compute;
-    // the device index: cached, or uploaded in the reference's layout and re-laid on the device
-    FmiUse use;
-    void *d_index = nullptr;
-    if ((rc = fmi_index_acquire(idx, dev, s, &d_index))) return rc;
-    use.d_index = d_index;
+    HostCache::Use index(fmi_index_cache);
+    if ((rc = fmi_index_acquire(idx, dev, s, &index.p))) return rc;
+    const void *d_index = index.p;
     DevBuf denc(L), doff(L), dlen(L), dout(L), dso(L), dn(L), dw(L);
     const char *cap_env = getenv("GBX_FMI_RAW_CAP");          /* test aid: records per read slot of the first pass */
     const int cap0 = cap_env && atoi(cap_env) > 0 ? atoi(cap_env) : 0;
@@ -361,21 +284,11 @@ int gbx_fmi_smem_host(const gbx_fmi_index *idx, const gbx_fmi_params *p, int64_t
     return GBX_OK;
 }
 
-// frees the device copies of the indexes gbx_fmi_smem_host keeps between calls
+// frees the device copies of the indexes and samples gbx_fmi_smem_host and gbx_fmi_sal_host keep between calls
 int gbx_fmi_host_release(void)
 {
-    std::lock_guard<std::mutex> lk(g_fmi_mu);
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    for (size_t k = 0; k < g_fmi_cache.size();) {
-        if (g_fmi_cache[k].users > 0) { ++k; continue; }        // a call is using it: it goes at the next release
-        (void)hipSetDevice(g_fmi_cache[k].dev);
-        (void)hipFree(g_fmi_cache[k].d_index);
-        g_fmi_cache.erase(g_fmi_cache.begin() + (long)k);
-    }
-    if (cur >= 0) (void)hipSetDevice(cur);
-    (void)hipGetLastError();
-    fmi_sa_cache_release();
+    fmi_index_cache.release_idle();
+    fmi_sa_cache.release_idle();
     return GBX_OK;
 }
 

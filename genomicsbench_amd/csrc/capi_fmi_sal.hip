@@ -1,5 +1,4 @@
 // capi_fmi_sal.hip — suffix-array lookup entries of the C-ABI (include/gbx.h): SMEM hits -> text positions.
-#include <condition_variable>
 #include "capi_common.h"
 
 using namespace gbx;
@@ -8,13 +7,8 @@ namespace {
 int sal_index_check(const gbx_fmi_index *idx, const gbx_fmi_sa *sa, const char *who)
 {
     if (!idx || !sa) { set_error("%s: null pointer", who); return GBX_ERR_ARG; }
-    if (idx->ref_seq_len < 2 || idx->ref_seq_len >= (1ll << 40) || idx->count[0] != 1 || idx->count[4] != idx->ref_seq_len ||
-        idx->sentinel_index < 0 || idx->sentinel_index >= idx->ref_seq_len) {
-        set_error("%s: inconsistent index (count[0] must be 1, count[4] the reference length incl. the sentinel)", who);
-        return GBX_ERR_ARG;
-    }
-    for (int c = 0; c < 4; ++c)
-        if (idx->count[c] > idx->count[c + 1]) { set_error("%s: count[] not monotone", who); return GBX_ERR_ARG; }
+    int rc = fmi_index_check(idx, (1ll << 40) - 1, who);
+    if (rc) return rc;
     if (sa->sa_compx != 0 && sa->sa_compx != 3) { set_error("%s: sa_compx must be 3 or 0", who); return GBX_ERR_ARG; }
     const int64_t want = sa->sa_compx ? (idx->ref_seq_len >> 3) + 1 : idx->ref_seq_len;
     if (sa->n_sa != want) {
@@ -24,122 +18,40 @@ int sal_index_check(const gbx_fmi_index *idx, const gbx_fmi_sa *sa, const char *
     return GBX_OK;
 }
 
-// The device copies of the samples gbx_fmi_sal_host keeps between calls: the sibling of the index cache in capi_fmi.hip and
-// found the same way, by content (length, layout width, a fingerprint of 256 samples spread over the arrays), one per device,
-// at most four idle ones per device.
-struct SaCached { int dev; int64_t len, n_sa; int compx; bool wide; uint64_t fp; void *d_sa; int users; uint64_t last_use; bool building; };
-std::mutex g_sa_mu;
-std::condition_variable g_sa_cv;
-std::vector<SaCached> g_sa_cache;
-uint64_t g_sa_clock = 0;
-
-uint64_t sa_fingerprint(const gbx_fmi_sa *sa)
-{
-    const int64_t n = sa->n_sa;
-    uint64_t h = 1469598103934665603ull;
-    auto mix = [&](const void *p, size_t m) { const unsigned char *b = (const unsigned char *)p; for (size_t k = 0; k < m; ++k) { h ^= b[k]; h *= 1099511628211ull; } };
-    const int64_t samples = n < 256 ? n : std::max<int64_t>(256, n >> 12);
-    for (int64_t k = 0; k < samples; ++k) {
-        const size_t i = (size_t)(k * (n - 1) / (samples > 1 ? samples - 1 : 1));
-        mix(&sa->ms_byte[i], 1);
-        mix(&sa->ls_word[i], 4);
-    }
-    return h;
-}
-
+// The device copies of the samples gbx_fmi_sal_host keeps between calls, one per device, keyed like the indexes by their
+// scalars and a fingerprint of their content.  The layout width is part of the key: GBX_FMI_WIDE=1 switches it at the same
+// length.
 int sa_acquire(const gbx_fmi_sa *sa, int64_t len, int dev, hipStream_t s, void **out)
 {
-    const uint64_t fp = sa_fingerprint(sa);
-    const bool wide = fmi_sa_wide(len);
-    auto same = [&](const SaCached &c) {
-        return c.dev == dev && c.len == len && c.n_sa == sa->n_sa && c.compx == sa->sa_compx && c.wide == wide && c.fp == fp;
-    };
-    void *d_sa = nullptr;
-    {
-        std::unique_lock<std::mutex> lk(g_sa_mu);
-        for (;;) {
-            SaCached *hit = nullptr;
-            for (SaCached &c : g_sa_cache) if (same(c)) hit = &c;
-            if (hit && hit->building) { g_sa_cv.wait(lk); continue; }        // another caller is uploading these very samples
-            if (hit) { ++hit->users; hit->last_use = ++g_sa_clock; *out = hit->d_sa; return GBX_OK; }
-            break;
+    const HostCacheKey key{dev, {len, sa->n_sa, sa->sa_compx, fmi_sa_wide(len)},
+                           sampled_fingerprint(sa->n_sa, [&](auto &mix, size_t i) { mix(&sa->ms_byte[i], 1); mix(&sa->ls_word[i], 4); })};
+    return fmi_sa_cache.acquire(key, [&](void **d_sa) {
+        const size_t bytes = fmi_sa_bytes(sa->n_sa, len), n = (size_t)sa->n_sa;
+        void *d_ms = nullptr, *d_ls = nullptr;
+        hipError_t e = hipMalloc(d_sa, bytes);
+        if (e != hipSuccess) *d_sa = nullptr;
+        if (e == hipSuccess) e = hipMalloc(&d_ms, n);
+        if (e == hipSuccess) e = hipMalloc(&d_ls, n * 4);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_ms, sa->ms_byte, n, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_ls, sa->ls_word, n * 4, hipMemcpyHostToDevice, s);
+        int rc = e == hipSuccess ? GBX_OK : hip_fail(e, "fmi sample upload");
+        if (!rc) {
+            gbx_fmi_sa dsa = *sa;
+            dsa.ms_byte = (const int8_t *)d_ms;
+            dsa.ls_word = (const uint32_t *)d_ls;
+            rc = fmi_sa_build(&dsa, len, *d_sa, bytes, s);
+            const hipError_t e2 = hipStreamSynchronize(s);
+            if (!rc && e2 != hipSuccess) rc = hip_fail(e2, "fmi sample build");
         }
-        for (;;) {
-            int idle = 0, victim = -1;
-            for (size_t k = 0; k < g_sa_cache.size(); ++k)
-                if (g_sa_cache[k].dev == dev && g_sa_cache[k].users == 0 && !g_sa_cache[k].building) {
-                    ++idle;
-                    if (victim < 0 || g_sa_cache[k].last_use < g_sa_cache[(size_t)victim].last_use) victim = (int)k;
-                }
-            if (idle < 4) break;
-            (void)hipFree(g_sa_cache[(size_t)victim].d_sa);
-            g_sa_cache.erase(g_sa_cache.begin() + victim);
-        }
-        g_sa_cache.push_back(SaCached{dev, len, sa->n_sa, sa->sa_compx, wide, fp, nullptr, 1, ++g_sa_clock, true});
-    }
-    // the upload and the re-layout run outside the lock behind the place-holder entry
-    const size_t bytes = fmi_sa_bytes(sa->n_sa, len), n = (size_t)sa->n_sa;
-    void *d_ms = nullptr, *d_ls = nullptr;
-    hipError_t e = hipMalloc(&d_sa, bytes);
-    if (e != hipSuccess) d_sa = nullptr;
-    if (e == hipSuccess) e = hipMalloc(&d_ms, n);
-    if (e == hipSuccess) e = hipMalloc(&d_ls, n * 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_ms, sa->ms_byte, n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_ls, sa->ls_word, n * 4, hipMemcpyHostToDevice, s);
-    int rc = e == hipSuccess ? GBX_OK : hip_fail(e, "fmi sample upload");
-    if (!rc) {
-        gbx_fmi_sa dsa = *sa;
-        dsa.ms_byte = (const int8_t *)d_ms;
-        dsa.ls_word = (const uint32_t *)d_ls;
-        rc = fmi_sa_build(&dsa, len, d_sa, bytes, s);
-        const hipError_t e2 = hipStreamSynchronize(s);
-        if (!rc && e2 != hipSuccess) rc = hip_fail(e2, "fmi sample build");
-    }
-    if (d_ms) (void)hipFree(d_ms);
-    if (d_ls) (void)hipFree(d_ls);
-    if (rc && d_sa) { (void)hipFree(d_sa); d_sa = nullptr; }
-    {
-        std::lock_guard<std::mutex> lk(g_sa_mu);
-        for (size_t k = 0; k < g_sa_cache.size(); ++k)
-            if (g_sa_cache[k].building && same(g_sa_cache[k])) {
-                if (rc) g_sa_cache.erase(g_sa_cache.begin() + (long)k);
-                else { g_sa_cache[k].d_sa = d_sa; g_sa_cache[k].building = false; }
-                break;
-            }
-    }
-    g_sa_cv.notify_all();
-    if (rc) return rc;
-    *out = d_sa;
-    return GBX_OK;
+        if (d_ms) (void)hipFree(d_ms);
+        if (d_ls) (void)hipFree(d_ls);
+        if (rc && *d_sa) { (void)hipFree(*d_sa); *d_sa = nullptr; }
+        return rc;
+    }, out);
 }
-
-void sa_unuse(void *d_sa)
-{
-    if (!d_sa) return;
-    std::lock_guard<std::mutex> lk(g_sa_mu);
-    for (SaCached &c : g_sa_cache) if (c.d_sa == d_sa && c.users > 0) { --c.users; break; }
-}
-
-struct SalUse {                       // holds both cache entries for the duration of a call
-    void *d_index = nullptr, *d_sa = nullptr;
-    ~SalUse() { fmi_index_unuse(d_index); sa_unuse(d_sa); }
-};
 }  // namespace
 
-void gbx::fmi_sa_cache_release()
-{
-    std::lock_guard<std::mutex> lk(g_sa_mu);
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    for (size_t k = 0; k < g_sa_cache.size();) {
-        if (g_sa_cache[k].users > 0 || g_sa_cache[k].building) { ++k; continue; }
-        (void)hipSetDevice(g_sa_cache[k].dev);
-        (void)hipFree(g_sa_cache[k].d_sa);
-        g_sa_cache.erase(g_sa_cache.begin() + (long)k);
-    }
-    if (cur >= 0) (void)hipSetDevice(cur);
-    (void)hipGetLastError();
-}
+HostCache gbx::fmi_sa_cache;
 
 extern "C" {
 
@@ -217,9 +129,9 @@ int gbx_fmi_sal_host(const gbx_fmi_index *idx, const gbx_fmi_sa *sa, const gbx_f
     if ((rc = lane.acquire())) return rc;
     Lane *L = lane.l;
     hipStream_t st = L->compute;
-    SalUse use;
-    if ((rc = fmi_index_acquire(idx, dev, st, &use.d_index))) return rc;
-    if ((rc = sa_acquire(sa, len, dev, st, &use.d_sa))) return rc;
+    HostCache::Use index(fmi_index_cache), samples(fmi_sa_cache);
+    if ((rc = fmi_index_acquire(idx, dev, st, &index.p))) return rc;
+    if ((rc = sa_acquire(sa, len, dev, st, &samples.p))) return rc;
     DevBuf dsm(L), dn(L), dpos(L), doff(L), dnp(L), dw(L);
     const size_t wb = fmi_sal_workspace_bytes(n_smem, total);
     if ((rc = dsm.alloc((size_t)n_smem * sizeof(gbx_fmi_smem))) || (rc = dn.alloc(8)) || (rc = dpos.alloc((size_t)total * 8)) ||
@@ -227,7 +139,7 @@ int gbx_fmi_sal_host(const gbx_fmi_index *idx, const gbx_fmi_sa *sa, const gbx_f
         return rc;
     GBX_HIP(hipMemcpyAsync(dsm.p, smems, (size_t)n_smem * sizeof(gbx_fmi_smem), hipMemcpyHostToDevice, st));
     GBX_HIP(hipMemcpyAsync(dn.p, &n_smem, 8, hipMemcpyHostToDevice, st));
-    if ((rc = fmi_sal_launch(idx, use.d_index, sa, use.d_sa, dsm.as<gbx_fmi_smem>(), dn.as<int64_t>(), n_smem, max_occ, dpos.as<int64_t>(),
+    if ((rc = fmi_sal_launch(idx, index.p, sa, samples.p, dsm.as<gbx_fmi_smem>(), dn.as<int64_t>(), n_smem, max_occ, dpos.as<int64_t>(),
                              total, doff.as<int64_t>(), dnp.as<int64_t>(), dw.p, wb, st)))
         return rc;
     int64_t got = -1;

@@ -172,11 +172,13 @@ int fmi_launch(const gbx_fmi_index *idx, const void *d_index, const gbx_fmi_para
                int64_t *d_smem_off, int64_t *d_n_out, void *d_work, size_t work_bytes, hipStream_t s, int raw_cap = 0);
 int fmi_read_extensions(const void *d_work, int64_t *ext, hipStream_t s);
 int fmi_read_overflow(const void *d_work, int64_t *worst, hipStream_t s);
-// the host entries' content-keyed cache of device indexes (capi_fmi.hip): a found or freshly built entry is held until
-// fmi_index_unuse; the suffix-array samples have a sibling cache (capi_fmi_sal.hip) that gbx_fmi_host_release empties too
+// the index scalars are consistent and ref_seq_len <= max_len (the caller has checked idx for null); else GBX_ERR_ARG
+int fmi_index_check(const gbx_fmi_index *idx, int64_t max_len, const char *who);
+// the device indexes and suffix-array samples the host entries keep between calls (host_cache.h; capi_fmi.hip, capi_fmi_sal.hip)
+struct HostCache;
+extern HostCache fmi_index_cache, fmi_sa_cache;
+// the device index of idx on device dev (the current one) from fmi_index_cache, held until fmi_index_cache.unuse(*d_index)
 int fmi_index_acquire(const gbx_fmi_index *idx, int dev, hipStream_t s, void **d_index);
-void fmi_index_unuse(void *d_index);
-void fmi_sa_cache_release();
 
 // ---- fmi suffix-array lookup (fmi_sal_kernels.hip)
 bool fmi_sa_wide(int64_t ref_seq_len);           // 64-bit samples and kernel: ref_seq_len >= 2^32, or GBX_FMI_WIDE=1

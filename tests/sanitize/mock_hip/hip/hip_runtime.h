@@ -3,7 +3,8 @@
 // TEST INFRASTRUCTURE ONLY - never built into libgbx.so.  Semantics kept: a stream is an in-order queue served by its
 // own thread (so a hipMemcpyAsync really is asynchronous to its caller), an event completes when the stream reaches its
 // record, hipStreamWaitEvent stalls the waiting stream, "device memory" is host memory.  mock_launch() queues a host
-// function as a kernel; mock_fail_after(n) makes the n-th following hipMemcpyAsync fail (error paths).
+// function as a kernel; mock_fail_after(n) makes the n-th following hipMemcpyAsync fail (error paths); mock_track(p)
+// follows a block until hipFree.
 #pragma once
 #include <atomic>
 #include <condition_variable>
@@ -13,6 +14,7 @@
 #include <deque>
 #include <functional>
 #include <mutex>
+#include <set>
 #include <thread>
 #include <vector>
 
@@ -66,7 +68,17 @@ inline hipError_t hipSetDevice(int d) { return d == 0 ? hipSuccess : hipErrorInv
 inline hipError_t hipGetLastError() { return hipSuccess; }
 inline const char *hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : "mock HIP error"; }
 inline hipError_t hipMalloc(void **p, size_t n) { *p = malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
-inline hipError_t hipFree(void *p) { free(p); return hipSuccess; }
+// blocks a test follows (mock_track): hipFree takes them out of the set again, so the test sees which are still allocated
+inline std::mutex &mock_tracked_mu() { static std::mutex m; return m; }
+inline std::set<void *> &mock_tracked() { static std::set<void *> s; return s; }
+inline void mock_track(void *p) { std::lock_guard<std::mutex> lk(mock_tracked_mu()); mock_tracked().insert(p); }
+inline bool mock_is_tracked(void *p) { std::lock_guard<std::mutex> lk(mock_tracked_mu()); return mock_tracked().count(p) > 0; }
+inline hipError_t hipFree(void *p)
+{
+    { std::lock_guard<std::mutex> lk(mock_tracked_mu()); mock_tracked().erase(p); }
+    free(p);
+    return hipSuccess;
+}
 inline hipError_t hipHostMalloc(void **p, size_t n, unsigned) { *p = malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
 inline hipError_t hipHostFree(void *p) { free(p); return hipSuccess; }
 inline hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned)

@@ -11,6 +11,7 @@
 #include <cstring>
 #include <mutex>
 #include <random>
+#include <set>
 #include <thread>
 #include <vector>
 #include "gbx_internal.h"
@@ -37,6 +38,8 @@ bool profile_active() { return false; }
 }
 // the call combiner of the host entries (csrc/host_combine.h, unmodified)
 #include "host_combine.h"
+// the device allocations the host entries keep between calls (csrc/host_cache.h, unmodified)
+#include "host_cache.h"
 
 using namespace gbx;
 
@@ -371,6 +374,120 @@ int main(int argc, char **argv)
         CHECK(combined_calls.load() > 0 && comb.largest.load() >= 2, "no call was ever combined (largest %llu)", (unsigned long long)comb.largest.load());
         printf("pipe_tsan: combiner %llu calls in %llu device calls, %llu shared, largest %llu\n", (unsigned long long)comb.n_calls.load(),
                (unsigned long long)comb.n_batches.load(), (unsigned long long)comb.n_shared.load(), (unsigned long long)comb.largest.load());
+    }
+    // (f) the host entries' device cache (host_cache.h): caller threads acquire a handful of keys on the mock device; a build
+    //     takes a while, writes its key into its block and now and then fails; another thread releases the idle entries
+    //     meanwhile.  Every block holds its own key, a key is built by one caller at a time, held entries survive the releases;
+    //     then a failed build with callers waiting for it, and the least-recently-used rule
+    {
+        HostCache cache;
+        constexpr int K = 16;
+        std::atomic<int> building[K], builds{0}, failed{0}, acquires{0};
+        for (auto &b : building) b = 0;
+        struct Block { int key; char pad[60]; };
+        auto key_of = [](int k) { return HostCacheKey{0, {k % 3, 7}, (uint64_t)(k / 3)}; };      // keys 0 and 3 differ in the fingerprint only
+        auto build_of = [&](int k, bool fail, int sleep_us) {
+            return [&, k, fail, sleep_us](void **d) {
+                CHECK(building[k].fetch_add(1) == 0, "two builds of key %d at once", k);
+                ++builds;
+                void *p = nullptr;
+                (void)hipMalloc(&p, sizeof(Block));
+                std::this_thread::sleep_for(std::chrono::microseconds(sleep_us));
+                --building[k];
+                if (fail) { (void)hipFree(p); ++failed; return GBX_ERR_HIP; }
+                ((Block *)p)->key = k;
+                mock_track(p);
+                *d = p;
+                return GBX_OK;
+            };
+        };
+        auto live_keys = [] {
+            std::lock_guard<std::mutex> lk(mock_tracked_mu());
+            std::set<int> s;
+            for (void *p : mock_tracked()) s.insert(((Block *)p)->key);
+            return s;
+        };
+        std::atomic<bool> stop{false};
+        std::thread releaser([&] { while (!stop) { cache.release_idle(); std::this_thread::sleep_for(std::chrono::microseconds(300)); } });
+        std::vector<std::thread> ct;
+        for (int t = 0; t < 2 * threads; ++t)
+            ct.emplace_back([&, t] {
+                std::mt19937_64 rng(9000u + (uint64_t)t);
+                for (int it = 0; it < 50 * rounds; ++it) {
+                    const int k = (int)(rng() % 6);
+                    HostCache::Use use(cache);
+                    const int rc = cache.acquire(key_of(k), build_of(k, rng() % 8 == 0, 100 + (int)(rng() % 400)), &use.p);
+                    ++acquires;
+                    if (rc) { CHECK(rc == GBX_ERR_HIP && !use.p, "a failed acquire of key %d: rc %d", k, rc); continue; }
+                    CHECK(use.p && ((Block *)use.p)->key == k, "key %d acquired another key's block", k);
+                    std::this_thread::sleep_for(std::chrono::microseconds(rng() % 300));
+                    CHECK(use.p && mock_is_tracked(use.p) && ((Block *)use.p)->key == k, "a held entry of key %d was freed", k);
+                }
+            });
+        for (auto &x : ct) x.join();
+        stop = true;
+        releaser.join();
+        // every block a build made is freed or still cached: a block that is left is what its key finds, without a build
+        {
+            const int b0 = builds.load();
+            std::vector<std::pair<int, void *>> left;
+            {
+                std::lock_guard<std::mutex> lk(mock_tracked_mu());
+                for (void *p : mock_tracked()) left.emplace_back(((Block *)p)->key, p);
+            }
+            for (auto &kp : left) {
+                HostCache::Use use(cache);
+                CHECK(cache.acquire(key_of(kp.first), build_of(kp.first, false, 0), &use.p) == GBX_OK && use.p == kp.second,
+                      "a block of key %d is neither freed nor cached", kp.first);
+            }
+            CHECK(builds.load() == b0, "a cached key was built again");
+            cache.release_idle();
+            CHECK(live_keys().empty(), "%zu blocks outlive a release with nothing held", live_keys().size());
+        }
+        // a failed build with callers waiting for it (a key of its own): it leaves no entry, one waiter builds in its place and
+        // the others take that
+        {
+            const int b0 = builds.load();
+            std::atomic<bool> started{false};
+            std::thread first([&] {
+                HostCache::Use use(cache);
+                auto b = build_of(12, true, 30000);
+                const int rc = cache.acquire(key_of(12), [&](void **d) { started = true; return b(d); }, &use.p);
+                CHECK(rc == GBX_ERR_HIP && !use.p, "the caller of a failed build: rc %d", rc);
+            });
+            while (!started) std::this_thread::yield();
+            std::vector<std::thread> waiters;
+            for (int w = 0; w < 3; ++w)
+                waiters.emplace_back([&] {
+                    HostCache::Use use(cache);
+                    const int rc = cache.acquire(key_of(12), build_of(12, false, 1000), &use.p);
+                    CHECK(rc == GBX_OK && use.p && ((Block *)use.p)->key == 12, "a waiter of a failed build: rc %d", rc);
+                });
+            first.join();
+            for (auto &x : waiters) x.join();
+            CHECK(builds.load() - b0 == 2, "a failed build with three waiters: %d builds, want 2", builds.load() - b0);
+            cache.release_idle();
+        }
+        // at most four idle entries per device stay after a miss, the least recently used going first; another device's do not count
+        {
+            auto get = [&](int k, int dev) {
+                HostCacheKey key = key_of(k);
+                key.dev = dev;
+                HostCache::Use use(cache);
+                CHECK(cache.acquire(key, build_of(k, false, 0), &use.p) == GBX_OK, "key %d", k);
+            };
+            get(15, 1);
+            for (int k = 0; k < 10; ++k) get(k, 0);
+            CHECK(live_keys() == std::set<int>({6, 7, 8, 9, 15}), "idle entries after ten misses");
+            const int b0 = builds.load();
+            get(6, 0);
+            CHECK(builds.load() == b0, "a cached key was built again");
+            get(10, 0);
+            CHECK(live_keys() == std::set<int>({6, 8, 9, 10, 15}), "the least recently used idle entry did not go first");
+            cache.release_idle();
+            CHECK(live_keys().empty(), "blocks outlive a release with nothing held");
+        }
+        printf("pipe_tsan: cache %d acquires, %d builds, %d failed\n", acquires.load(), builds.load(), failed.load());
     }
     if (g_fail.load()) { fprintf(stderr, "pipe_tsan: %d check(s) failed\n", g_fail.load()); return 1; }
     printf("pipe_tsan: ok (%d caller threads x %d rounds)\n", threads, rounds);

@@ -260,6 +260,27 @@ def test_four_host_threads(small):
     N.check(N.lib().gbx_fmi_host_release())
 
 
+def test_host_sample_cache_is_keyed_by_content_not_by_address():
+    """gbx_fmi_sal_host keeps the device copy of the samples between calls.  A caller that rewrites the same host buffers in
+    place with another genome's samples of the same length must get that genome's positions, not the cached ones; then more
+    sample sets than the cache keeps idle, and a release."""
+    ga, gb = gen_fmi_genome(120_000, 6401), gen_fmi_genome(120_000, 6402)
+    (ia, sa_a), (ib, sa_b) = FM.build_index(ga, sa_compx=3), FM.build_index(gb, sa_compx=3)
+    assert ia.ref_seq_len == ib.ref_seq_len and sa_a.n_sa == sa_b.n_sa
+    sma, _ = FM.smem_host(ia, gen_fmi_reads(ga, 500, 6403))
+    smb, _ = FM.smem_host(ib, gen_fmi_reads(gb, 500, 6404))
+    check(FM.sal_host(ia, sa_a, sma, 500), want_pos(full_sa(ga), sma, 500))
+    shared = FM.FmiSa(3, sa_a.ms, sa_a.ls)                                # A's buffers ...
+    shared.ms[:], shared.ls[:] = sa_b.ms, sa_b.ls                         # ... now hold B's samples: same addresses
+    check(FM.sal_host(ib, shared, smb, 500), want_pos(full_sa(gb), smb, 500))
+    for seed in range(6):                                                # more sample sets than the cache keeps idle
+        g = gen_fmi_genome(40_000 + 1000 * seed, 6500 + seed)
+        ix, sx = FM.build_index(g, sa_compx=3)
+        sm, _ = FM.smem_host(ix, gen_fmi_reads(g, 100, 6600 + seed))
+        check(FM.sal_host(ix, sx, sm, 500), want_pos(full_sa(g), sm, 500))
+    N.check(N.lib().gbx_fmi_host_release())
+
+
 def test_driver_print_sa(tmp_path):
     g = gen_fmi_genome(30_000, 4101)
     idx, smp = FM.build_index(g, sa_compx=3)

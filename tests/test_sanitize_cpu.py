@@ -86,11 +86,16 @@ def test_host_pipeline_under_thread_sanitizer(san_build):
     overlapped chunks with packed bases, strided-field upload + scattered download, a call abandoned after start(), a
     transfer failing mid-call: no data race, no hang, right results; and the call combiner (csrc/host_combine.h, unmodified):
     twelve callers submitting small requests of two classes, two leaders in flight, failing requests redone one by one, every
-    caller its own results and status.  The harness is checked to see a race when there is one."""
+    caller its own results and status; and the device cache of the fmi host entries (csrc/host_cache.h, unmodified): eight
+    callers acquiring six keys whose builds take a while and fail now and then, beside a thread that releases idle entries -
+    every block holds its own key, one build of a key at a time, held entries survive the releases, a failed build leaves no
+    entry and a waiter builds in its place, at most four idle entries per device stay after a miss (least recently used first),
+    and every block is freed or still cached.  The harness is checked to see a race when there is one."""
     exe = os.path.join(SAN, "_build", "pipe_tsan")
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=0:second_deadlock_stack=1")
     r = subprocess.run([exe, "--selftest-race"], capture_output=True, text=True, timeout=120, env=env)
     assert "ThreadSanitizer: data race" in r.stderr, "the TSan build does not report a deliberate race"
     r = subprocess.run([exe, "4", "1"], capture_output=True, text=True, timeout=900, env=env)
-    assert r.returncode == 0 and "ThreadSanitizer" not in r.stderr and "pipe_tsan: ok" in r.stdout and "pipe_tsan: combiner" in r.stdout, \
+    assert r.returncode == 0 and "ThreadSanitizer" not in r.stderr and "pipe_tsan: ok" in r.stdout and "pipe_tsan: combiner" in r.stdout \
+        and "pipe_tsan: cache" in r.stdout, \
         r.stdout[-1500:] + r.stderr[-4000:]
