@@ -193,27 +193,14 @@ int gbx_abea_align_host(int64_t n_reads, const int64_t *seq_off, const int32_t *
         if (seq_off[r] < 0 || seq_len[r] < 0 || seq_off[r] + seq_len[r] > seq_bytes || event_off[r + 1] < event_off[r] || event_off[r] < 0 ||
             event_off[r + 1] - event_off[r] < 1 || seq_len[r] < GBX_ABEA_KMER)
             return one();
-    int map[MAX_HOST_DEVICES];
-    const int n_dev = host_device_set(map);
-    if (n_dev < 0) return n_dev;
-    const int parts = shard_parts(n_dev, n_reads, 128);
-    if (parts == 1) {
-        DeviceGuard g;
-        int rc = g.set(map[host_next_small_call_device(n_dev)]);
-        return rc ? rc : one();
-    }
-    const std::vector<int64_t> cuts = split_by_cost(n_reads, parts, [&](int64_t r) {
-        return (double)((event_off[r + 1] - event_off[r] + 1) + ((int64_t)seq_len[r] - GBX_ABEA_KMER + 2)); });
-    return run_on_devices(parts, map, "gbx_abea_align_host", [&](int k) -> int {
-        const int64_t lo = cuts[(size_t)k], hi = cuts[(size_t)k + 1], m = hi - lo;
-        if (m == 0) return GBX_OK;
-        int64_t a0 = seq_bytes, a1 = 0;
-        for (int64_t r = lo; r < hi; ++r) { a0 = seq_off[r] < a0 ? seq_off[r] : a0; a1 = seq_off[r] + seq_len[r] > a1 ? seq_off[r] + seq_len[r] : a1; }
-        std::vector<int64_t> so((size_t)m);
-        for (int64_t r = 0; r < m; ++r) so[(size_t)r] = seq_off[lo + r] - a0;
-        return abea_host_one(m, so.data(), seq_len + lo, seq_arena + a0, a1 - a0, event_off + lo, events, models, scale + lo, shift + lo, out,
-                             n_pairs + lo, lo);
-    });
+    return spread_over_devices("gbx_abea_align_host", n_reads, n_reads, 128,
+        [&](int64_t r) { return (double)((event_off[r + 1] - event_off[r] + 1) + ((int64_t)seq_len[r] - GBX_ABEA_KMER + 2)); }, one,
+        [&](int, int64_t lo, int64_t hi) {
+            const Span sp = span_of(seq_off, seq_len, lo, hi);
+            const std::vector<int64_t> so = rebased(seq_off, lo, hi, sp.a0);
+            return abea_host_one(hi - lo, so.data(), seq_len + lo, seq_arena + sp.a0, sp.a1 - sp.a0, event_off + lo, events, models, scale + lo,
+                                 shift + lo, out, n_pairs + lo, lo);
+        });
 }
 
 }  // extern "C"

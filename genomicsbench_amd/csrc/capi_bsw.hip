@@ -282,6 +282,19 @@ static int bsw_host_one(const gbx_bsw_params *p, int64_t n,
     return rc;
 }
 
+// Would bsw_host_one accept this call?  (It checks the same itself, interleaved with its pipeline; this is the question the
+// multi-device path and the call combiner ask first, so that a bad call takes the one-device path, whose error names the pair.)
+static bool bsw_call_ok(const gbx_bsw_params *p, int64_t n, const uint8_t *ref, int64_t ref_bytes, const uint8_t *qer, int64_t qer_bytes,
+                        const int64_t *idr, const int64_t *idq, const int32_t *len1, const int32_t *len2, const int32_t *h0,
+                        const gbx_bsw_result *out)
+{
+    if (!p || n <= 0 || !ref || !qer || !idr || !idq || !len1 || !len2 || !h0 || !out || ref_bytes < 0 || qer_bytes < 0) return false;
+    return !any_bad_unit(n, host_workers(BSW_HOST_WORKERS), [&](int64_t j) {
+        return idr[j] < 0 || idq[j] < 0 || len1[j] < 0 || len2[j] < 0 || idr[j] + len1[j] > ref_bytes || idq[j] + len2[j] > qer_bytes ||
+               len2[j] > GBX_BSW_MAX_QLEN || len1[j] > GBX_BSW_MAX_TLEN;
+    });
+}
+
 // The host entry: one device, or the pairs cut into contiguous ranges of equal nominal cells (len1 x len2, the reference's
 // own cell count, main_banded.cpp:183,323) over the devices of gbx_host_set_devices / GBX_GPUS - the reference's per-thread
 // slices (main_banded.cpp:279-291) as per-device slices.  Each shard's bases are the byte range of the arenas its pairs
@@ -293,44 +306,16 @@ static int bsw_host_entry(const gbx_bsw_params *p, int64_t n,
                           const int32_t *len1, const int32_t *len2,
                           const int32_t *h0, gbx_bsw_result *out)
 {
-    if (!host_multi_wanted() || !p || n <= 0 || !ref || !qer || !idr || !idq || !len1 || !len2 || !h0 || !out || ref_bytes < 0 || qer_bytes < 0)
-        return bsw_host_one(p, n, ref, ref_bytes, qer, qer_bytes, idr, idq, len1, len2, h0, out);
-    {   // argument errors come first and read as on one device: a job with a bad pair takes the one-device path, which names it
-        const int T = host_workers(BSW_HOST_WORKERS);
-        std::vector<char> bad((size_t)T, 0);
-        parallel_ranges(n, T, [&](int t, int64_t lo, int64_t hi) {
-            for (int64_t j = lo; j < hi; ++j)
-                if (idr[j] < 0 || idq[j] < 0 || len1[j] < 0 || len2[j] < 0 || idr[j] + len1[j] > ref_bytes || idq[j] + len2[j] > qer_bytes ||
-                    len2[j] > GBX_BSW_MAX_QLEN || len1[j] > GBX_BSW_MAX_TLEN) { bad[(size_t)t] = 1; return; }
+    auto one = [&] { return bsw_host_one(p, n, ref, ref_bytes, qer, qer_bytes, idr, idq, len1, len2, h0, out); };
+    if (!host_multi_wanted() || !bsw_call_ok(p, n, ref, ref_bytes, qer, qer_bytes, idr, idq, len1, len2, h0, out)) return one();
+    return spread_over_devices("gbx_bsw_extend_host", n, n, 131072,
+        [&](int64_t k) { return len1[k] > 0 && len2[k] > 0 ? (double)len1[k] * (double)len2[k] : 0.0; }, one,
+        [&](int, int64_t lo, int64_t hi) {
+            const Span r = span_of(idr, len1, lo, hi), q = span_of(idq, len2, lo, hi);
+            const std::vector<int64_t> r2 = rebased(idr, lo, hi, r.a0), q2 = rebased(idq, lo, hi, q.a0);
+            return bsw_host_one(p, hi - lo, ref + r.a0, r.a1 - r.a0, qer + q.a0, q.a1 - q.a0, r2.data(), q2.data(), len1 + lo, len2 + lo,
+                                h0 + lo, out + lo, lo);
         });
-        for (char b : bad) if (b) return bsw_host_one(p, n, ref, ref_bytes, qer, qer_bytes, idr, idq, len1, len2, h0, out);
-    }
-    int map[MAX_HOST_DEVICES];
-    const int n_dev = host_device_set(map);
-    if (n_dev < 0) return n_dev;
-    const int parts = shard_parts(n_dev, n, 131072);
-    if (parts == 1) {
-        DeviceGuard g;
-        int rc = g.set(map[host_next_small_call_device(n_dev)]);
-        return rc ? rc : bsw_host_one(p, n, ref, ref_bytes, qer, qer_bytes, idr, idq, len1, len2, h0, out);
-    }
-    const std::vector<int64_t> cuts = split_by_cost(n, parts, [&](int64_t k) {
-        return len1[k] > 0 && len2[k] > 0 ? (double)len1[k] * (double)len2[k] : 0.0; });
-    return run_on_devices(parts, map, "gbx_bsw_extend_host", [&](int k) -> int {
-        const int64_t lo = cuts[(size_t)k], hi = cuts[(size_t)k + 1], m = hi - lo;
-        if (m == 0) return GBX_OK;
-        // the byte range of each arena this shard's pairs span (offsets re-based to its start)
-        int64_t ar = ref_bytes, br = 0, aq = qer_bytes, bq = 0;
-        for (int64_t j = lo; j < hi; ++j) {
-            ar = idr[j] < ar ? idr[j] : ar; br = idr[j] + len1[j] > br ? idr[j] + len1[j] : br;
-            aq = idq[j] < aq ? idq[j] : aq; bq = idq[j] + len2[j] > bq ? idq[j] + len2[j] : bq;
-        }
-        if (br < ar) br = ar;
-        if (bq < aq) bq = aq;
-        std::vector<int64_t> r2((size_t)m), q2((size_t)m);
-        for (int64_t j = 0; j < m; ++j) { r2[(size_t)j] = idr[lo + j] - ar; q2[(size_t)j] = idq[lo + j] - aq; }
-        return bsw_host_one(p, m, ref + ar, br - ar, qer + aq, bq - aq, r2.data(), q2.data(), len1 + lo, len2 + lo, h0 + lo, out + lo, lo);
-    });
 }
 
 }  // extern "C"
@@ -340,65 +325,50 @@ static int bsw_host_entry(const gbx_bsw_params *p, int64_t n,
 // requests end to end, their bases gathered into two compact arenas (4-byte aligned per pair, as the SeqPair entry does for
 // the driver's strided slots) - and every caller gets its own slice of the results.
 namespace {
+constexpr int64_t BSW_COMBINE_MAX_CALL = 65536, BSW_COMBINE_MAX_JOB = (int64_t)1 << 20;
 struct BswReq : CombineReq {
     const gbx_bsw_params *p; int64_t n;
     const uint8_t *ref; int64_t ref_bytes; const uint8_t *qer; int64_t qer_bytes;
     const int64_t *idr, *idq; const int32_t *len1, *len2, *h0; gbx_bsw_result *out;
     int64_t cr, cq;                       // bytes of its pairs in the compact arenas
+    struct Scratch { gbx::Scratch<uint8_t> ref, qer; gbx::Scratch<int64_t> idr, idq; gbx::Scratch<int32_t> l1, l2, h0; gbx::Scratch<gbx_bsw_result> out; };
+
+    int run() const { return bsw_host_entry(p, n, ref, ref_bytes, qer, qer_bytes, idr, idq, len1, len2, h0, out); }
+    static bool same(const BswReq &a, const BswReq &b) { return memcmp(a.p, b.p, offsetof(gbx_bsw_params, pad_)) == 0; }
+    static int combined(const std::vector<BswReq *> &batch, Scratch &S)
+    {
+        const size_t nb = batch.size();
+        std::vector<int64_t> p0(nb + 1, 0), r0(nb + 1, 0), q0(nb + 1, 0);
+        for (size_t k = 0; k < nb; ++k) { p0[k + 1] = p0[k] + batch[k]->n; r0[k + 1] = r0[k] + batch[k]->cr; q0[k + 1] = q0[k] + batch[k]->cq; }
+        const int64_t N = p0[nb], R = r0[nb], Q = q0[nb];
+        uint8_t *mref = S.ref.get((size_t)R + 16), *mqer = S.qer.get((size_t)Q + 16);
+        int64_t *midr = S.idr.get((size_t)N), *midq = S.idq.get((size_t)N);
+        int32_t *ml1 = S.l1.get((size_t)N), *ml2 = S.l2.get((size_t)N), *mh0 = S.h0.get((size_t)N);
+        gbx_bsw_result *mout = S.out.get((size_t)N);
+        combine_parallel((int64_t)nb, host_workers(), [&](int64_t k) {
+            const BswReq *r = batch[(size_t)k];
+            int64_t pr = r0[(size_t)k], pq = q0[(size_t)k];
+            const int64_t a = p0[(size_t)k];
+            for (int64_t j = 0; j < r->n; ++j) {
+                memcpy(mref + pr, r->ref + r->idr[j], (size_t)r->len1[j]);
+                memcpy(mqer + pq, r->qer + r->idq[j], (size_t)r->len2[j]);
+                midr[a + j] = pr; midq[a + j] = pq;
+                pr += (r->len1[j] + 3) & ~3; pq += (r->len2[j] + 3) & ~3;
+            }
+            memcpy(ml1 + a, r->len1, (size_t)r->n * 4); memcpy(ml2 + a, r->len2, (size_t)r->n * 4); memcpy(mh0 + a, r->h0, (size_t)r->n * 4);
+        });
+        const int rc = bsw_host_entry(batch[0]->p, N, mref, R + 8, mqer, Q + 8, midr, midq, ml1, ml2, mh0, mout);
+        if (rc) return rc;
+        combine_parallel((int64_t)nb, nb >= 8 ? 4 : 1, [&](int64_t k) {
+            BswReq *r = batch[(size_t)k];
+            memcpy(r->out, mout + p0[(size_t)k], (size_t)r->n * sizeof(gbx_bsw_result));
+            r->rc = GBX_OK;
+        });
+        return GBX_OK;
+    }
 };
-struct BswScratch {
-    Scratch<uint8_t> ref, qer; Scratch<int64_t> idr, idq; Scratch<int32_t> l1, l2, h0; Scratch<gbx_bsw_result> out;
-};
-constexpr int64_t BSW_COMBINE_MAX_CALL = 65536, BSW_COMBINE_MAX_JOB = (int64_t)1 << 20;
 }
 namespace gbx { Combiner &combiner_bsw() { static Combiner *c = new Combiner(); return *c; } }
-
-static void bsw_run_alone(BswReq *r)
-{
-    r->rc = bsw_host_entry(r->p, r->n, r->ref, r->ref_bytes, r->qer, r->qer_bytes, r->idr, r->idq, r->len1, r->len2, r->h0, r->out);
-    if (r->rc) r->err = gbx_last_error();
-}
-
-static void bsw_run_combined(const std::vector<CombineReq *> &batch, int slot)
-{
-    if (batch.size() == 1) { bsw_run_alone((BswReq *)batch[0]); return; }
-    static BswScratch *slots = new BswScratch[Combiner::MAX_LEADERS];      // one per leader in flight (Combiner::submit)
-    BswScratch *S = slots + slot;
-    const size_t nb = batch.size();
-    std::vector<int64_t> p0(nb + 1, 0), r0(nb + 1, 0), q0(nb + 1, 0);
-    for (size_t k = 0; k < nb; ++k) {
-        const BswReq *r = (const BswReq *)batch[k];
-        p0[k + 1] = p0[k] + r->n; r0[k + 1] = r0[k] + r->cr; q0[k + 1] = q0[k] + r->cq;
-    }
-    const int64_t N = p0[nb], R = r0[nb], Q = q0[nb];
-    uint8_t *mref = S->ref.get((size_t)R + 16), *mqer = S->qer.get((size_t)Q + 16);
-    int64_t *midr = S->idr.get((size_t)N), *midq = S->idq.get((size_t)N);
-    int32_t *ml1 = S->l1.get((size_t)N), *ml2 = S->l2.get((size_t)N), *mh0 = S->h0.get((size_t)N);
-    gbx_bsw_result *mout = S->out.get((size_t)N);
-    combine_parallel((int64_t)nb, host_workers(), [&](int64_t k) {
-        const BswReq *r = (const BswReq *)batch[(size_t)k];
-        int64_t pr = r0[(size_t)k], pq = q0[(size_t)k];
-        const int64_t a = p0[(size_t)k];
-        for (int64_t j = 0; j < r->n; ++j) {
-            memcpy(mref + pr, r->ref + r->idr[j], (size_t)r->len1[j]);
-            memcpy(mqer + pq, r->qer + r->idq[j], (size_t)r->len2[j]);
-            midr[a + j] = pr; midq[a + j] = pq;
-            pr += (r->len1[j] + 3) & ~3; pq += (r->len2[j] + 3) & ~3;
-        }
-        memcpy(ml1 + a, r->len1, (size_t)r->n * 4); memcpy(ml2 + a, r->len2, (size_t)r->n * 4); memcpy(mh0 + a, r->h0, (size_t)r->n * 4);
-    });
-    const BswReq *lead = (const BswReq *)batch[0];
-    const int rc = bsw_host_entry(lead->p, N, mref, R + 8, mqer, Q + 8, midr, midq, ml1, ml2, mh0, mout);
-    if (rc) {                                       // redone one by one: every caller gets the status of its own call
-        for (CombineReq *q : batch) bsw_run_alone((BswReq *)q);
-        return;
-    }
-    combine_parallel((int64_t)nb, nb >= 8 ? 4 : 1, [&](int64_t k) {
-        BswReq *r = (BswReq *)batch[(size_t)k];
-        memcpy(r->out, mout + p0[(size_t)k], (size_t)r->n * sizeof(gbx_bsw_result));
-        r->rc = GBX_OK;
-    });
-}
 
 extern "C" {
 
@@ -409,23 +379,13 @@ int gbx_bsw_extend_host(const gbx_bsw_params *p, int64_t n,
                         const int32_t *len1, const int32_t *len2,
                         const int32_t *h0, gbx_bsw_result *out)
 {
-    auto plain = [&] { return bsw_host_entry(p, n, ref, ref_bytes, qer, qer_bytes, idr, idq, len1, len2, h0, out); };
-    if (!p || n <= 0 || n > BSW_COMBINE_MAX_CALL || !ref || !qer || !idr || !idq || !len1 || !len2 || !h0 || !out || ref_bytes < 0 || qer_bytes < 0 ||
-        !combine_enabled() || profile_active())
-        return plain();
     BswReq r;
     r.p = p; r.n = n; r.ref = ref; r.ref_bytes = ref_bytes; r.qer = qer; r.qer_bytes = qer_bytes;
     r.idr = idr; r.idq = idq; r.len1 = len1; r.len2 = len2; r.h0 = h0; r.out = out; r.units = n; r.cr = r.cq = 0;
-    for (int64_t k = 0; k < n; ++k) {               // a call with a bad pair goes its own way: its error names the pair
-        if (len1[k] < 0 || len2[k] < 0 || idr[k] < 0 || idq[k] < 0 || idr[k] + len1[k] > ref_bytes || idq[k] + len2[k] > qer_bytes ||
-            len2[k] > GBX_BSW_MAX_QLEN || len1[k] > GBX_BSW_MAX_TLEN)
-            return plain();
-        r.cr += (len1[k] + 3) & ~3; r.cq += (len2[k] + 3) & ~3;
-    }
-    if (hipGetDevice(&r.dev) != hipSuccess) { (void)hipGetLastError(); return plain(); }
-    return combiner_bsw().submit(&r, BSW_COMBINE_MAX_JOB, Combiner::max_leaders(1),
-        [](const CombineReq *a, const CombineReq *b) { return memcmp(((const BswReq *)a)->p, ((const BswReq *)b)->p, offsetof(gbx_bsw_params, pad_)) == 0; },
-        bsw_run_combined);
+    // a call with a bad pair goes its own way: its error names the pair
+    if (n > BSW_COMBINE_MAX_CALL || !bsw_call_ok(p, n, ref, ref_bytes, qer, qer_bytes, idr, idq, len1, len2, h0, out)) return r.run();
+    for (int64_t k = 0; k < n; ++k) { r.cr += (len1[k] + 3) & ~3; r.cq += (len2[k] + 3) & ~3; }
+    return combine_call(combiner_bsw(), r, BSW_COMBINE_MAX_JOB, 1);
 }
 
 int gbx_bsw_extend_seqpairs(const gbx_bsw_params *p, gbx_seqpair *pairs, int64_t n,

@@ -174,31 +174,19 @@ static int chain_host_one(int64_t n_calls, const int64_t *anchor_off, const uint
 int gbx_chain_host(int64_t n_calls, const int64_t *anchor_off, const uint64_t *ax, const uint64_t *ay,
                    const gbx_chain_call *hdr, int32_t *score, int32_t *parent, int32_t *target, int32_t *peak)
 {
-    if (!host_multi_wanted() || n_calls <= 0 || !anchor_off || !hdr || !score || !parent || anchor_off[0] != 0)
-        return chain_host_one(n_calls, anchor_off, ax, ay, hdr, score, parent, target, peak);
+    auto one = [&] { return chain_host_one(n_calls, anchor_off, ax, ay, hdr, score, parent, target, peak); };
+    if (!host_multi_wanted() || n_calls <= 0 || !anchor_off || !hdr || !score || !parent || anchor_off[0] != 0) return one();
     for (int64_t c = 0; c < n_calls; ++c)
-        if (anchor_off[c + 1] < anchor_off[c]) return chain_host_one(n_calls, anchor_off, ax, ay, hdr, score, parent, target, peak);   // names the call
-    if (anchor_off[n_calls] > 0 && (!ax || !ay)) return chain_host_one(n_calls, anchor_off, ax, ay, hdr, score, parent, target, peak);
-    int map[MAX_HOST_DEVICES];
-    const int n_dev = host_device_set(map);
-    if (n_dev < 0) return n_dev;
-    int parts = shard_parts(n_dev, anchor_off[n_calls], 1 << 20);      // a million anchors per shard at least
-    if (parts > n_calls) parts = (int)n_calls;
-    if (parts == 1) {
-        DeviceGuard g;
-        int rc = g.set(map[host_next_small_call_device(n_dev)]);
-        return rc ? rc : chain_host_one(n_calls, anchor_off, ax, ay, hdr, score, parent, target, peak);
-    }
-    const std::vector<int64_t> cuts = split_by_cost(n_calls, parts, [&](int64_t c) { return (double)(anchor_off[c + 1] - anchor_off[c]); });
-    return run_on_devices(parts, map, "gbx_chain_host", [&](int k) -> int {
-        const int64_t lo = cuts[(size_t)k], hi = cuts[(size_t)k + 1], m = hi - lo;
-        if (m == 0) return GBX_OK;
-        const int64_t a = anchor_off[lo];
-        std::vector<int64_t> off2((size_t)m + 1);
-        for (int64_t c = 0; c <= m; ++c) off2[(size_t)c] = anchor_off[lo + c] - a;
-        return chain_host_one(m, off2.data(), ax ? ax + a : ax, ay ? ay + a : ay, hdr + lo, score + a, parent + a, target ? target + a : nullptr,
-                              peak ? peak + a : nullptr, lo);
-    });
+        if (anchor_off[c + 1] < anchor_off[c]) return one();      // (names the call)
+    if (anchor_off[n_calls] > 0 && (!ax || !ay)) return one();
+    return spread_over_devices("gbx_chain_host", n_calls, anchor_off[n_calls], 1 << 20,      // a million anchors per shard at least
+        [&](int64_t c) { return (double)(anchor_off[c + 1] - anchor_off[c]); }, one,
+        [&](int, int64_t lo, int64_t hi) {
+            const int64_t a = anchor_off[lo];
+            const std::vector<int64_t> off2 = rebased(anchor_off, lo, hi + 1, a);
+            return chain_host_one(hi - lo, off2.data(), ax ? ax + a : ax, ay ? ay + a : ay, hdr + lo, score + a, parent + a,
+                                  target ? target + a : nullptr, peak ? peak + a : nullptr, lo);
+        });
 }
 
 int gbx_chain_evaluated_pairs(const void *d_work, int64_t *pairs, void *stream)

@@ -222,48 +222,38 @@ int gbx_fmi_smem_host(const gbx_fmi_index *idx, const gbx_fmi_params *p, int64_t
         return one();
     for (int64_t r = 0; r < n_reads; ++r)
         if (read_len[r] < 0 || read_off[r] < 0 || read_off[r] + read_len[r] > enc_bytes) return one();
-    int map[MAX_HOST_DEVICES];
-    const int n_dev = host_device_set(map);
-    if (n_dev < 0) return n_dev;
-    const int parts = shard_parts(n_dev, n_reads, 131072);
-    if (parts == 1) {
-        DeviceGuard g;
-        int rc = g.set(map[host_next_small_call_device(n_dev)]);
-        return rc ? rc : one();
-    }
-    const std::vector<int64_t> cuts = split_by_cost(n_reads, parts, [&](int64_t r) { return (double)read_len[r] + 1.0; });
     // (uninitialised: a vector's resize() would value-initialise 40 bytes per record slot on the shard's thread)
     struct RawBuf { gbx_fmi_smem *p = nullptr; ~RawBuf() { free(p); } gbx_fmi_smem *data() { return p; }
                     bool resize(size_t n) { free(p); p = (gbx_fmi_smem *)malloc((n ? n : 1) * sizeof(gbx_fmi_smem)); return p != nullptr; } };
-    std::vector<RawBuf> bufs((size_t)parts);
-    std::vector<std::vector<int64_t>> offs((size_t)parts);
-    std::vector<int64_t> counts((size_t)parts, 0);
-    int rc = run_on_devices(parts, map, "gbx_fmi_smem_host", [&](int k) -> int {
-        const int64_t lo = cuts[(size_t)k], hi = cuts[(size_t)k + 1], m = hi - lo;
-        if (m == 0) return GBX_OK;
-        int64_t a0 = enc_bytes, a1 = 0;
-        for (int64_t r = lo; r < hi; ++r) { a0 = read_off[r] < a0 ? read_off[r] : a0; a1 = read_off[r] + read_len[r] > a1 ? read_off[r] + read_len[r] : a1; }
-        std::vector<int64_t> ro((size_t)m);
-        for (int64_t r = 0; r < m; ++r) ro[(size_t)r] = read_off[lo + r] - a0;
-        offs[(size_t)k].resize((size_t)m + 1);
+    RawBuf bufs[MAX_HOST_DEVICES];                       // per shard
+    std::vector<int64_t> offs[MAX_HOST_DEVICES], cuts;
+    int64_t counts[MAX_HOST_DEVICES] = {};
+    int rc = spread_over_devices("gbx_fmi_smem_host", n_reads, n_reads, 131072, [&](int64_t r) { return (double)read_len[r] + 1.0; }, one,
+                                 [&](int k, int64_t lo, int64_t hi) -> int {
+        const int64_t m = hi - lo;
+        const Span sp = span_of(read_off, read_len, lo, hi);
+        const std::vector<int64_t> ro = rebased(read_off, lo, hi, sp.a0);
+        offs[k].resize((size_t)m + 1);
         // twice the shard's share of out_cap (SMEMs per read are uneven: repeats concentrate; a shard that still does not fit runs
         // again with the exact size, which doubles that device's time - the margin is there to make it rare)
         int64_t cap = (int64_t)((double)out_cap * (double)m / (double)n_reads * 2.0) + 4096;
         if (cap > out_cap) cap = out_cap;
         for (int attempt = 0;; ++attempt) {
-            if (!bufs[(size_t)k].resize((size_t)cap)) { set_error("gbx_fmi_smem_host: out of host memory"); return GBX_ERR_NOMEM; }
+            if (!bufs[k].resize((size_t)cap)) { set_error("gbx_fmi_smem_host: out of host memory"); return GBX_ERR_NOMEM; }
             int64_t got = 0;
-            const int rc1 = fmi_host_one(idx, p, m, enc + a0, a1 - a0, ro.data(), read_len + lo, bufs[(size_t)k].data(), cap, offs[(size_t)k].data(), &got, lo);
-            counts[(size_t)k] = got;
+            const int rc1 = fmi_host_one(idx, p, m, enc + sp.a0, sp.a1 - sp.a0, ro.data(), read_len + lo, bufs[k].data(), cap,
+                                         offs[k].data(), &got, lo);
+            counts[k] = got;
             if (rc1 == GBX_ERR_ARG && got > cap && attempt == 0 && got <= out_cap) { cap = got; continue; }   // did not fit: once more, exactly
             if (rc1 == GBX_ERR_ARG && got > cap) return GBX_OK;      // more than the whole job's out_cap: reported below with the job's total
             return rc1;
         }
-    });
-    if (rc) return rc;
+    }, &cuts);
+    if (rc || cuts.empty()) return rc;                  // (cuts.empty(): the call ran whole on one device)
+    const int parts = (int)cuts.size() - 1;
     int64_t total = 0;
     std::vector<int64_t> first((size_t)parts + 1, 0);
-    for (int k = 0; k < parts; ++k) { first[(size_t)k] = total; total += counts[(size_t)k]; }
+    for (int k = 0; k < parts; ++k) { first[(size_t)k] = total; total += counts[k]; }
     first[(size_t)parts] = total;
     *n_out = total;
     if (total > out_cap) {
@@ -273,9 +263,9 @@ int gbx_fmi_smem_host(const gbx_fmi_index *idx, const gbx_fmi_params *p, int64_t
     std::vector<Helper> th;
     auto merge = [&](int k) {
         const int64_t lo = cuts[(size_t)k], m = cuts[(size_t)k + 1] - lo, f = first[(size_t)k];
-        const gbx_fmi_smem *src = bufs[(size_t)k].data();
-        for (int64_t j = 0; j < counts[(size_t)k]; ++j) { gbx_fmi_smem rec = src[j]; rec.rid += (uint32_t)lo; out[f + j] = rec; }
-        if (smem_off && m > 0) for (int64_t r = 0; r < m; ++r) smem_off[lo + r] = offs[(size_t)k][(size_t)r] + f;
+        const gbx_fmi_smem *src = bufs[k].data();
+        for (int64_t j = 0; j < counts[k]; ++j) { gbx_fmi_smem rec = src[j]; rec.rid += (uint32_t)lo; out[f + j] = rec; }
+        if (smem_off && m > 0) for (int64_t r = 0; r < m; ++r) smem_off[lo + r] = offs[k][(size_t)r] + f;
     };
     for (int k = 1; k < parts; ++k) th.emplace_back([&, k] { merge(k); });
     merge(0);

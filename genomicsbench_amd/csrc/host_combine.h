@@ -155,4 +155,34 @@ template <class T> struct Scratch {
     T *get(size_t n) { if (v.size() < n) v.resize(n + n / 4 + 64); return v.data(); }
 };
 
+// A request performed on its own: its status, and its error text kept for its caller.
+template <class Req> static void combine_alone(Req *r)
+{
+    r->rc = r->run();
+    if (r->rc) r->err = gbx_last_error();
+}
+
+// The combine path of a kernel's public entry, for a call the one-device path accepts and the kernel's per-call cap admits.
+// Req (a CombineReq) brings what is the kernel's own:
+//   int run() const                        the call on its own (the kernel's host entry on the caller's arrays)
+//   struct Scratch                         the leader's arrays, one set per leader slot
+//   static bool same(a, b)                 may b ride in a's call (scoring parameters)
+//   static int combined(batch, Scratch &)  lays the batch end to end, makes ONE call and hands every request its results;
+//                                          a status other than GBX_OK: every request of the batch is redone on its own
+// A call that meets no other, a thread that is collecting kernel timings, GBX_COMBINE=0 or no current device: run() as is.
+template <class Req> static int combine_call(Combiner &cmb, Req &r, int64_t max_units, int dflt_leaders)
+{
+    if (!combine_enabled() || profile_active()) return r.run();
+    if (hipGetDevice(&r.dev) != hipSuccess) { (void)hipGetLastError(); return r.run(); }
+    static typename Req::Scratch *scratch = new typename Req::Scratch[Combiner::MAX_LEADERS];
+    return cmb.submit(&r, max_units, Combiner::max_leaders(dflt_leaders),
+        [](const CombineReq *a, const CombineReq *b) { return Req::same(*(const Req *)a, *(const Req *)b); },
+        [](const std::vector<CombineReq *> &batch, int slot) {
+            std::vector<Req *> reqs(batch.size());
+            for (size_t k = 0; k < batch.size(); ++k) reqs[k] = (Req *)batch[k];
+            if (reqs.size() == 1 || Req::combined(reqs, scratch[slot]))
+                for (Req *q : reqs) combine_alone(q);
+        });
+}
+
 }  // namespace gbx

@@ -138,4 +138,63 @@ template <class F> static int run_on_devices(int parts, const int *map, const ch
     return rcs[(size_t)first];
 }
 
+// An entry's multi-device path, after its own argument checks: n units (reads, pairs, calls, windows) over the devices of
+// host_device_set, in at most n shards of at least min_units of `units` each (chain counts anchors but cuts calls).  One
+// shard: one() on the next small-call device.  More: the units are cut by cost and shard(k, lo, hi) runs for every
+// non-empty range [lo, hi) on device k (run_on_devices); cuts_out, if given, receives the cuts of that case.
+template <class Cost, class One, class Shard>
+static int spread_over_devices(const char *who, int64_t n, int64_t units, int64_t min_units, Cost cost, One one, Shard shard,
+                               std::vector<int64_t> *cuts_out = nullptr)
+{
+    int map[MAX_HOST_DEVICES];
+    const int n_dev = host_device_set(map);
+    if (n_dev < 0) return n_dev;
+    int parts = shard_parts(n_dev, units, min_units);
+    if (parts > n) parts = n > 1 ? (int)n : 1;
+    if (parts == 1) {
+        DeviceGuard g;
+        const int rc = g.set(map[host_next_small_call_device(n_dev)]);
+        return rc ? rc : one();
+    }
+    std::vector<int64_t> cuts = split_by_cost(n, parts, cost);
+    const int rc = run_on_devices(parts, map, who, [&](int k) -> int {
+        const int64_t lo = cuts[(size_t)k], hi = cuts[(size_t)k + 1];
+        return lo < hi ? shard(k, lo, hi) : GBX_OK;
+    });
+    if (cuts_out) *cuts_out = std::move(cuts);
+    return rc;
+}
+
+// The bytes records [lo, hi) of an arena occupy, given their offsets and lengths: [a0, a1) from the lowest offset to the
+// furthest end, {0, 0} when the range holds no record.  rebased(): their offsets relative to a0, for the shard's own call.
+struct Span { int64_t a0, a1; };
+template <class Len> static Span span_of(const int64_t *off, const Len *len, int64_t lo, int64_t hi)
+{
+    if (lo >= hi) return {0, 0};
+    Span s = {off[lo], off[lo] + len[lo]};
+    for (int64_t j = lo + 1; j < hi; ++j) {
+        s.a0 = off[j] < s.a0 ? off[j] : s.a0;
+        s.a1 = off[j] + len[j] > s.a1 ? off[j] + len[j] : s.a1;
+    }
+    return s;
+}
+static std::vector<int64_t> rebased(const int64_t *off, int64_t lo, int64_t hi, int64_t a0)
+{
+    std::vector<int64_t> r((size_t)(hi - lo));
+    for (int64_t j = lo; j < hi; ++j) r[(size_t)(j - lo)] = off[j] - a0;
+    return r;
+}
+
+// bad(j) for some j in [0, n)?  A scan over parallel_ranges: each thread stops at its first bad unit.
+template <class Bad> static bool any_bad_unit(int64_t n, int threads, Bad bad)
+{
+    std::vector<char> hit((size_t)threads, 0);
+    parallel_ranges(n, threads, [&](int t, int64_t lo, int64_t hi) {
+        for (int64_t j = lo; j < hi; ++j)
+            if (bad(j)) { hit[(size_t)t] = 1; return; }
+    });
+    for (char h : hit) if (h) return true;
+    return false;
+}
+
 }  // namespace gbx

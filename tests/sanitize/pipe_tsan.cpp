@@ -26,8 +26,9 @@ RoctxRange::~RoctxRange() {}
 }  // namespace gbx
 
 #include "host_pipeline.h"
-// the multi-device layer of the host entries (csrc/host_multi.h, unmodified): the cut rule and the shard runner.  The
-// mock runtime has one device; the logical devices of a call all map onto it, as GBX_DEVICE_MAP=0,0,0 does on a GPU box.
+// the multi-device layer of the host entries (csrc/host_multi.h, unmodified): the cut rule, the shard runner, the spread
+// skeleton and the shard spans.  The mock runtime has one device; the logical devices of a call all map onto it, as
+// GBX_DEVICE_MAP=0,0,0 does on a GPU box.
 extern "C" const char *gbx_last_error(void) { return gbx::g_err; }
 #include "host_multi.h"
 namespace gbx {
@@ -261,89 +262,139 @@ int main(int argc, char **argv)
         std::thread b([] { CHECK(call_field_and_scatter(3000000, 4002) == GBX_OK, "large field / scatter call: %s", g_err); });
         a.join(); b.join();
     }
-    // (d) the multi-device shape of an entry (host_multi.h): a job cut by cost into three shards, every shard a staged call on
-    //     a lane of its own from a thread of its own, two such jobs in flight at once; then a job one of whose shards fails:
-    //     the lowest failing shard's status and text come back on the calling thread, the other shards finish
+    // (d) the multi-device shape of an entry (host_multi.h: spread_over_devices): a job cut by cost into three shards, every
+    //     shard a staged call on a lane of its own from a thread of its own, two such jobs in flight at once; then a job one of
+    //     whose shards fails: the lowest failing shard's status and text come back on the calling thread, the other shards
+    //     finish.  A job too small to cut runs whole, on the small-call devices in turn; shards that the cut leaves empty are
+    //     not run; a job of fewer units than devices gets one shard per unit; and the byte span of a shard's records, {0, 0}
+    //     for a shard that holds none
     {
-        auto multi_job = [](size_t units, uint64_t seed, int fail_shard) -> int {
+        std::atomic<int> small_calls{0};
+        auto multi_job = [&](size_t units, uint64_t seed, int fail_shard, std::vector<int64_t> *cuts_out = nullptr) -> int {
             std::vector<double> cost(units);
             std::mt19937_64 r(seed);
             for (auto &c : cost) c = (double)(r() % 1000);
-            const std::vector<int64_t> cuts = split_by_cost((int64_t)units, 3, [&](int64_t i) { return cost[(size_t)i]; });
-            CHECK(cuts[0] == 0 && cuts[3] == (int64_t)units && cuts[1] <= cuts[2], "cuts not monotone");
-            int map[MAX_HOST_DEVICES];
-            const int n = host_device_set(map);
-            return run_on_devices(n, map, "multi_job", [&](int k) -> int {
-                if (k == fail_shard) { set_error("shard %d was told to fail", k); return GBX_ERR_ARG; }
-                const size_t m = (size_t)(cuts[(size_t)k + 1] - cuts[(size_t)k]);
-                return m ? call_one_chunk(m * 64, seed + (uint64_t)k, true) : GBX_OK;
-            });
+            std::vector<int64_t> cuts;
+            const int rc = spread_over_devices("multi_job", (int64_t)units, (int64_t)units, 1000, [&](int64_t i) { return cost[(size_t)i]; },
+                [&] { ++small_calls; return call_one_chunk(units * 64, seed, true); },
+                [&](int k, int64_t lo, int64_t hi) -> int {
+                    CHECK(lo < hi && lo >= 0 && hi <= (int64_t)units, "shard %d got the range [%lld, %lld)", k, (long long)lo, (long long)hi);
+                    if (k == fail_shard) { set_error("shard %d was told to fail", k); return GBX_ERR_ARG; }
+                    return call_one_chunk((size_t)(hi - lo) * 64, seed + (uint64_t)k, true);
+                }, &cuts);
+            CHECK(cuts.empty() || (cuts.size() == 4 && cuts[0] == 0 && cuts[3] == (int64_t)units && cuts[1] <= cuts[2]), "cuts not monotone");
+            if (cuts_out) *cuts_out = cuts;
+            return rc;
         };
         std::thread a([&] { CHECK(multi_job(40000, 5001, -1) == GBX_OK, "multi-device job: %s", g_err); });
         std::thread b([&] { CHECK(multi_job(30000, 5002, -1) == GBX_OK, "multi-device job: %s", g_err); });
         a.join(); b.join();
-        const int rc = multi_job(20000, 5003, 1);
+        std::vector<int64_t> cuts;
+        const int rc = multi_job(20000, 5003, 1, &cuts);
         CHECK(rc == GBX_ERR_ARG && strstr(g_err, "shard 1 was told to fail") && strstr(g_err, "[shard 1 of 3"), "failing shard: rc %d, text '%s'", rc, g_err);
+        CHECK(cuts.size() == 4 && cuts[0] == 0 && cuts[3] == 20000 && cuts[1] <= cuts[2], "the cuts of a three-shard job");
         CHECK(call_one_chunk((size_t)1 << 20, 5004, true) == GBX_OK, "call after a failed multi-device job: %s", g_err);
+        CHECK(small_calls.load() == 0, "a job of three shards ran whole");
+        // too small to cut (fewer than 2 x 1000 units): one() once per job, on the next small-call device, and no cuts
+        const int rr0 = host_next_small_call_device(3);
+        for (int j = 0; j < 4; ++j) {
+            cuts.assign(1, -1);
+            CHECK(multi_job(1500, 5010 + (uint64_t)j, 0, &cuts) == GBX_OK, "a small job: %s", g_err);
+            CHECK(cuts.empty(), "a small job handed back cuts");
+        }
+        CHECK(small_calls.load() == 4 && host_next_small_call_device(3) == (rr0 + 5) % 3, "small jobs: %d whole calls, rotation", small_calls.load());
+        // all the cost in unit 0: the cut leaves shard 1 empty, shards 0 and 2 run
+        {
+            std::atomic<int> ran{0};
+            const int rc2 = spread_over_devices("skewed", 3000, 3000, 1000, [](int64_t i) { return i == 0 ? 1.0 : 0.0; }, [] { return GBX_ERR_ARG; },
+                [&](int k, int64_t lo, int64_t hi) { CHECK(k != 1 && lo < hi, "shard %d [%lld, %lld) ran", k, (long long)lo, (long long)hi); ++ran; return GBX_OK; },
+                &cuts);
+            CHECK(rc2 == GBX_OK && ran.load() == 2 && cuts == std::vector<int64_t>({0, 1, 1, 3000}), "a cut with an empty shard: rc %d, %d ran", rc2, ran.load());
+        }
+        // two units, three devices, enough "anchors" for more: one shard per unit
+        {
+            std::atomic<int> ran{0};
+            const int rc2 = spread_over_devices("few units", 2, 5000000, 1, [](int64_t) { return 1.0; }, [] { return GBX_ERR_ARG; },
+                [&](int, int64_t lo, int64_t hi) { CHECK(hi == lo + 1, "a shard of %lld units", (long long)(hi - lo)); ++ran; return GBX_OK; }, &cuts);
+            CHECK(rc2 == GBX_OK && ran.load() == 2 && cuts.size() == 3, "two units over three devices: rc %d, %d shards", rc2, ran.load());
+        }
+        // spans: records 0..5 at {10 +4, 2 +3, 30 +0, 7 +1, 0 +0, 50 +5}; windows as in poa, one of them without records
+        {
+            const int64_t off[6] = {10, 2, 30, 7, 0, 50};
+            const int32_t len[6] = {4, 3, 0, 1, 0, 5};
+            const Span s01 = span_of(off, len, 0, 2), s23 = span_of(off, len, 2, 4), s5 = span_of(off, len, 5, 6), s33 = span_of(off, len, 3, 3);
+            CHECK(s01.a0 == 2 && s01.a1 == 14 && s23.a0 == 7 && s23.a1 == 30 && s5.a0 == 50 && s5.a1 == 55, "spans of records");
+            CHECK(s33.a0 == 0 && s33.a1 == 0, "the span of no record is {%lld, %lld}", (long long)s33.a0, (long long)s33.a1);
+            CHECK(rebased(off, 0, 2, s01.a0) == std::vector<int64_t>({8, 0}) && rebased(off, 3, 3, 0).empty(), "rebased offsets");
+            const int64_t wfs[5] = {0, 2, 2, 2, 6};             // windows 1 and 2 hold no records
+            std::atomic<int> empty_spans{0};
+            const int rc2 = spread_over_devices("windows", 4, 4, 1, [](int64_t w) { return w == 1 ? 0.0 : 1.0; }, [] { return GBX_ERR_ARG; },
+                [&](int, int64_t lo, int64_t hi) {
+                    const Span sp = span_of(off, len, wfs[lo], wfs[hi]);
+                    if (wfs[lo] == wfs[hi]) { empty_spans += sp.a0 == 0 && sp.a1 == 0; return GBX_OK; }
+                    return sp.a0 <= sp.a1 ? GBX_OK : GBX_ERR_ARG;
+                }, &cuts);
+            CHECK(rc2 == GBX_OK && cuts == std::vector<int64_t>({0, 1, 3, 4}) && empty_spans.load() == 1, "a shard of windows without records: rc %d, cuts %zu",
+                  rc2, cuts.size());
+        }
+        CHECK(any_bad_unit(100000, 4, [](int64_t j) { return j == 99999; }) && !any_bad_unit(100000, 4, [](int64_t j) { return j < 0; }) &&
+              any_bad_unit(3, 4, [](int64_t j) { return j == 1; }), "any_bad_unit");
     }
-    // (e) the call combiner (host_combine.h): many caller threads submit small requests round after round; a leader lays a
-    //     batch's inputs end to end in its slot's scratch arrays (helper threads copy), runs ONE staged call for all of them and
-    //     hands every caller its slice; two leaders in flight, requests of two "scoring" classes that must not mix, one request
-    //     in twenty a bad one whose combined call fails and is redone request by request: every caller gets the result and the
-    //     status of its own call
+    // (e) the call combiner (host_combine.h: combine_call over a Combiner): many caller threads submit small requests round
+    //     after round; a leader lays a batch's inputs end to end in its slot's scratch arrays (helper threads copy), runs ONE
+    //     staged call for all of them and hands every caller its slice; two leaders in flight, requests of two "scoring"
+    //     classes that must not mix, one request in twenty a bad one whose combined call fails and is redone request by
+    //     request: every caller gets the result and the status of its own call.  A batch of one is never laid out.
     {
-        struct Req : CombineReq { int cls; std::vector<uint8_t> in, out; bool bad; };
-        struct Slot { Scratch<uint8_t> in, out; };
         static Combiner comb;
-        static Slot slots[Combiner::MAX_LEADERS];
-        static std::atomic<int> mixed{0}, combined_calls{0};
-        auto alone = [](Req *r) {
-            if (r->bad) { r->rc = GBX_ERR_ARG; r->err = "request was told to fail"; return; }
-            for (size_t i = 0; i < r->in.size(); ++i) r->out[i] = (uint8_t)(r->in[i] * 3 + r->cls);
-            r->rc = GBX_OK;
-        };
-        auto run = [&](const std::vector<CombineReq *> &batch, int slot) {
-            if (batch.size() == 1) { alone((Req *)batch[0]); return; }
-            ++combined_calls;
-            std::vector<size_t> off(batch.size() + 1, 0);
-            bool any_bad = false;
-            for (size_t k = 0; k < batch.size(); ++k) {
-                const Req *r = (const Req *)batch[k];
-                off[k + 1] = off[k] + r->in.size();
-                any_bad = any_bad || r->bad;
-                if (r->cls != ((const Req *)batch[0])->cls) ++mixed;
-            }
-            uint8_t *in = slots[slot].in.get(off.back() + 1), *out = slots[slot].out.get(off.back() + 1);
-            combine_parallel((int64_t)batch.size(), 4, [&](int64_t k) { const Req *r = (const Req *)batch[(size_t)k]; memcpy(in + off[(size_t)k], r->in.data(), r->in.size()); });
-            if (any_bad) { for (CombineReq *q : batch) alone((Req *)q); return; }      // the combined call failed: one by one
-            // the device call of the batch: a staged one-chunk upload / "kernel" / download through a lane (host_pipeline.h)
+        static std::atomic<int> mixed{0}, combined_calls{0}, single_batches{0};
+        struct Req : CombineReq {
+            int cls; bool bad; std::vector<uint8_t> in; uint8_t *out;
+            struct Scratch { gbx::Scratch<uint8_t> in, out; };
+            int run() const
             {
+                if (bad) { set_error("request was told to fail"); return GBX_ERR_ARG; }
+                for (size_t i = 0; i < in.size(); ++i) out[i] = (uint8_t)(in[i] * 3 + cls);
+                return GBX_OK;
+            }
+            static bool same(const Req &a, const Req &b) { return a.cls == b.cls; }
+            static int combined(const std::vector<Req *> &batch, Scratch &S)
+            {
+                if (batch.size() < 2) ++single_batches;
+                ++combined_calls;
+                std::vector<size_t> off(batch.size() + 1, 0);
+                bool any_bad = false;
+                for (size_t k = 0; k < batch.size(); ++k) {
+                    off[k + 1] = off[k] + batch[k]->in.size();
+                    any_bad = any_bad || batch[k]->bad;
+                    if (batch[k]->cls != batch[0]->cls) ++mixed;
+                }
+                uint8_t *in = S.in.get(off.back() + 1), *out = S.out.get(off.back() + 1);
+                combine_parallel((int64_t)batch.size(), 4, [&](int64_t k) { memcpy(in + off[(size_t)k], batch[(size_t)k]->in.data(), batch[(size_t)k]->in.size()); });
+                if (any_bad) { set_error("a combined call was told to fail"); return GBX_ERR_ARG; }      // redone one by one by combine_call
+                // the device call of the batch: a staged one-chunk upload / "kernel" / download through a lane (host_pipeline.h)
                 HostLane lane;
                 int rc = lane.acquire();
                 DevBuf din(lane.l), dout(lane.l);
                 if (!rc) rc = din.alloc(off.back() + 1);
                 if (!rc) rc = dout.alloc(off.back() + 1);
-                if (!rc) {
-                    HostPipe pipe(lane.l, off.back(), false);
-                    rc = pipe.prepare(1);
-                    if (!rc) {
-                        pipe.stage(0, din.p, in, off.back());
-                        pipe.start();
-                        rc = pipe.wait_stage(0);
-                        const int cls = ((const Req *)batch[0])->cls;
-                        const size_t total = off.back();
-                        uint8_t *a = din.as<uint8_t>(), *b = dout.as<uint8_t>();
-                        if (!rc) mock_launch(lane.l->compute, [=] { for (size_t i = 0; i < total; ++i) b[i] = (uint8_t)(a[i] * 3 + cls); });
-                        if (!rc) { pipe.fetch(0, out, dout.p, total); rc = pipe.chunk_launched(0); }
-                        rc = pipe.finish(rc);
-                    }
+                if (rc) return rc;
+                HostPipe pipe(lane.l, off.back(), false);
+                if ((rc = pipe.prepare(1))) return rc;
+                pipe.stage(0, din.p, in, off.back());
+                pipe.start();
+                rc = pipe.wait_stage(0);
+                const int cls = batch[0]->cls;
+                const size_t total = off.back();
+                uint8_t *a = din.as<uint8_t>(), *b = dout.as<uint8_t>();
+                if (!rc) mock_launch(lane.l->compute, [=] { for (size_t i = 0; i < total; ++i) b[i] = (uint8_t)(a[i] * 3 + cls); });
+                if (!rc) { pipe.fetch(0, out, dout.p, total); rc = pipe.chunk_launched(0); }
+                if ((rc = pipe.finish(rc))) return rc;
+                for (size_t k = 0; k < batch.size(); ++k) {
+                    memcpy(batch[k]->out, out + off[k], batch[k]->in.size());
+                    batch[k]->rc = GBX_OK;
                 }
-                if (rc) { for (CombineReq *q : batch) { q->rc = rc; q->err = g_err; } return; }
-            }
-            for (size_t k = 0; k < batch.size(); ++k) {
-                Req *r = (Req *)batch[k];
-                memcpy(r->out.data(), out + off[k], r->in.size());
-                r->rc = GBX_OK;
+                return GBX_OK;
             }
         };
         setenv("GBX_COMBINE_GATHER_US", "300", 1);
@@ -357,21 +408,34 @@ int main(int argc, char **argv)
                     r.cls = (t + it) & 1;
                     r.bad = rng() % 20 == 0;
                     r.in = random_bytes(200 + (size_t)(rng() % 30000), rng());
-                    r.out.assign(r.in.size(), 0);
+                    std::vector<uint8_t> out(r.in.size(), 0);
+                    r.out = out.data();
                     r.units = (int64_t)r.in.size();
-                    const int rc = comb.submit(&r, (int64_t)1 << 20, 2,
-                        [](const CombineReq *a, const CombineReq *b) { return ((const Req *)a)->cls == ((const Req *)b)->cls; }, run);
-                    if (r.bad) { CHECK(rc == GBX_ERR_ARG && strstr(g_err, "told to fail"), "a bad request's status: %d '%s'", rc, g_err); continue; }
+                    const int rc = combine_call(comb, r, (int64_t)1 << 20, 2);
+                    if (r.bad) { CHECK(rc == GBX_ERR_ARG && strstr(g_err, "request was told to fail"), "a bad request's status: %d '%s'", rc, g_err); continue; }
                     CHECK(rc == GBX_OK, "combined request: %s", g_err);
                     bool ok = true;
-                    for (size_t i = 0; i < r.in.size() && ok; ++i) ok = r.out[i] == (uint8_t)(r.in[i] * 3 + r.cls);
+                    for (size_t i = 0; i < r.in.size() && ok; ++i) ok = out[i] == (uint8_t)(r.in[i] * 3 + r.cls);
                     CHECK(ok, "a combined request came back with another request's results");
                 }
             });
         for (auto &x : ct) x.join();
         CHECK(mixed.load() == 0, "requests of different classes shared a call");
+        CHECK(single_batches.load() == 0, "a batch of one request was laid out as a combined call");
         CHECK(comb.n_calls.load() == (uint64_t)callers * 40u * (uint64_t)rounds, "combiner call count");
         CHECK(combined_calls.load() > 0 && comb.largest.load() >= 2, "no call was ever combined (largest %llu)", (unsigned long long)comb.largest.load());
+        // GBX_COMBINE=0: the request runs on its own, the combiner never sees it
+        {
+            setenv("GBX_COMBINE", "0", 1);
+            Req r;
+            r.cls = 1; r.bad = false; r.in = random_bytes(100, 1); r.units = 100;
+            std::vector<uint8_t> out(100, 0);
+            r.out = out.data();
+            const uint64_t calls0 = comb.n_calls.load();
+            CHECK(combine_call(comb, r, (int64_t)1 << 20, 2) == GBX_OK && out[7] == (uint8_t)(r.in[7] * 3 + 1) && comb.n_calls.load() == calls0,
+                  "GBX_COMBINE=0 still combined");
+            unsetenv("GBX_COMBINE");
+        }
         printf("pipe_tsan: combiner %llu calls in %llu device calls, %llu shared, largest %llu\n", (unsigned long long)comb.n_calls.load(),
                (unsigned long long)comb.n_batches.load(), (unsigned long long)comb.n_shared.load(), (unsigned long long)comb.largest.load());
     }
