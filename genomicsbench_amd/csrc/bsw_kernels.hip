@@ -1015,6 +1015,359 @@ __global__ void __launch_bounds__(64) bsw_lane_kernel(BswDev prm, BswPairs P, Bs
 #undef LTAB
 }
 
+// ---- compact lane classes with the cells in registers ----------------------------------------------------------
+// bsw_lane_kernel<SYM, COMPACT> for the long compact classes keeps a wavefront's cells in LDS, 20+ KB of it: six or seven
+// wavefronts per CU, too few to hide the LDS round trips.  Here a lane holds its pair's cells in VGPRs instead, cell[p] = the
+// dword of column pair p ({e(2p), h(2p), e(2p+1), h(2p+1)}, as in LDS), and the query codes as v_perm_b32 selectors, two
+// column pairs a dword.  Registers take compile-time indices only, so the columns run in lock-step as the rows already do:
+// every lane steps through the same absolute column pair, in blocks of four pairs, and a block is entered when some lane's
+// window [beg, end] touches it (a scalar bit test of a wave-wide OR).  A block every running lane covers whole runs the
+// hand-scheduled step; the others run the masked form (reg_pair_masked).  Lanes whose pair is done stay in the loop with an
+// empty window, so the wave-wide reductions see 64 defined lanes.  Used for the 80..99 class (149 VGPRs, no scratch): the
+// 100..135 class needs 68 cell and 34 selector registers and spilled at 168 VGPRs, and measured slower.
+
+// lane_pair_step on register operands: sa = the row's scores of two column pairs (v_perm_b32 of the selectors, bytes 0, 1 for
+// the even pair, 2, 3 for the odd one: HI picks), PA = the position of column 2p within its block of eight (key = h << 18 | pos)
+#define GBX_REG_STEP_HEAD(SEL0, SEL1)                                                                                                   \
+    "v_cmp_ne_u32_sdwa vcc, %[w], %[zero] src0_sel:BYTE_1 src1_sel:DWORD\n"                                                            \
+    "v_subrev_u32 %[fd], %[eins], %[f]\n"                                                                                               \
+    "v_add_u32_sdwa %[ta], sext(%[sa]), %[w] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:" SEL0 " src1_sel:BYTE_1\n"                  \
+    "v_cndmask_b32 %[ma], 0, %[ta], vcc\n"                                                                                              \
+    "v_cmp_ne_u32_sdwa vcc, %[w], %[zero] src0_sel:BYTE_3 src1_sel:DWORD\n"                                                            \
+    "v_max_i32_sdwa %[x], %[ma], %[w] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0\n"                            \
+    "v_add_u32_sdwa %[tb], sext(%[sa]), %[w] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:" SEL1 " src1_sel:BYTE_3\n"                  \
+    "v_max_i32 %[ha], %[x], %[f]\n"
+#define GBX_REG_STEP_SYM(SEL0, SEL1)                                                                                                    \
+    GBX_REG_STEP_HEAD(SEL0, SEL1)                                                                                                       \
+    "v_subrev_u32 %[td], %[oed], %[ma]\n"                                                                                               \
+    "v_cndmask_b32 %[mb], 0, %[tb], vcc\n"                                                                                              \
+    "v_sub_u32_sdwa %[ed], %[w], %[edel] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:DWORD\n"                         \
+    "v_max3_i32 %[f], %[fd], %[td], 0\n"                                                                                                \
+    "v_max3_i32 %[ena], %[ed], %[td], 0\n"                                                                                              \
+    "v_max_i32_sdwa %[x], %[mb], %[w] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2\n"                            \
+    "v_lshl_or_b32 %[ka], %[ha], 18, %[pa]\n"                                                                                           \
+    "v_max_i32 %[hb], %[x], %[f]\n"                                                                                                     \
+    "v_subrev_u32 %[td], %[oed], %[mb]\n"                                                                                               \
+    "v_subrev_u32 %[fd], %[eins], %[f]\n"                                                                                               \
+    "v_sub_u32_sdwa %[ed], %[w], %[edel] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_2 src1_sel:DWORD\n"                         \
+    "v_max3_i32 %[f], %[fd], %[td], 0\n"                                                                                                \
+    "v_max3_i32 %[enb], %[ed], %[td], 0\n"                                                                                              \
+    "v_lshl_or_b32 %[kb], %[hb], 18, %[pa1]\n"                                                                                          \
+    "v_lshl_or_b32 %[u], %[left], 8, %[ena]\n"                                                                                          \
+    "v_lshl_or_b32 %[v], %[ha], 8, %[enb]\n"                                                                                            \
+    "v_max3_u32 %[key], %[kin], %[ka], %[kb]\n"                                                                                         \
+    "v_lshl_or_b32 %[wn], %[v], 16, %[u]\n"
+#define GBX_REG_STEP_ASYM(SEL0, SEL1)                                                                                                   \
+    GBX_REG_STEP_HEAD(SEL0, SEL1)                                                                                                       \
+    "v_subrev_u32 %[td], %[oed], %[ma]\n"                                                                                               \
+    "v_subrev_u32 %[ti], %[oei], %[ma]\n"                                                                                               \
+    "v_cndmask_b32 %[mb], 0, %[tb], vcc\n"                                                                                              \
+    "v_sub_u32_sdwa %[ed], %[w], %[edel] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:DWORD\n"                         \
+    "v_max3_i32 %[f], %[fd], %[ti], 0\n"                                                                                                \
+    "v_max3_i32 %[ena], %[ed], %[td], 0\n"                                                                                              \
+    "v_max_i32_sdwa %[x], %[mb], %[w] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2\n"                            \
+    "v_lshl_or_b32 %[ka], %[ha], 18, %[pa]\n"                                                                                           \
+    "v_max_i32 %[hb], %[x], %[f]\n"                                                                                                     \
+    "v_subrev_u32 %[td], %[oed], %[mb]\n"                                                                                               \
+    "v_subrev_u32 %[ti], %[oei], %[mb]\n"                                                                                               \
+    "v_subrev_u32 %[fd], %[eins], %[f]\n"                                                                                               \
+    "v_sub_u32_sdwa %[ed], %[w], %[edel] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_2 src1_sel:DWORD\n"                         \
+    "v_max3_i32 %[f], %[fd], %[ti], 0\n"                                                                                                \
+    "v_max3_i32 %[enb], %[ed], %[td], 0\n"                                                                                              \
+    "v_lshl_or_b32 %[kb], %[hb], 18, %[pa1]\n"                                                                                          \
+    "v_lshl_or_b32 %[u], %[left], 8, %[ena]\n"                                                                                          \
+    "v_lshl_or_b32 %[v], %[ha], 8, %[enb]\n"                                                                                            \
+    "v_max3_u32 %[key], %[kin], %[ka], %[kb]\n"                                                                                         \
+    "v_lshl_or_b32 %[wn], %[v], 16, %[u]\n"
+template <bool SYM, bool HI, int PA>
+__device__ __forceinline__ uint32_t reg_pair_step(uint32_t w, uint32_t sa, int &f, int &left, uint32_t &key, int zero, int oe_del, int oe_ins,
+                                                  int e_del, int e_ins)
+{
+    uint32_t wn, kout;
+    int hb, ta, tb, ma, mb, x, ha, td, ti, ed, ena, enb, fd, ka, kb, u, v;
+#define GBX_REG_STEP_OPS                                                                                                                \
+    : [ta] "=&v"(ta), [tb] "=&v"(tb), [ma] "=&v"(ma), [mb] "=&v"(mb), [x] "=&v"(x), [ha] "=&v"(ha), [hb] "=&v"(hb), [td] "=&v"(td),   \
+      [ti] "=&v"(ti), [ed] "=&v"(ed), [ena] "=&v"(ena), [enb] "=&v"(enb), [fd] "=&v"(fd), [ka] "=&v"(ka), [kb] "=&v"(kb), [u] "=&v"(u), \
+      [v] "=&v"(v), [wn] "=&v"(wn), [f] "+v"(f), [key] "=v"(kout)                                                                       \
+    : [w] "v"(w), [sa] "v"(sa), [left] "v"(left), [kin] "v"(key), [pa] "i"(PA), [pa1] "i"(PA + 1), [zero] "v"(zero), [oed] "s"(oe_del), \
+      [oei] "s"(oe_ins), [edel] "s"(e_del), [eins] "s"(e_ins)                                                                           \
+    : "vcc"
+    if (SYM && !HI) asm volatile(GBX_REG_STEP_SYM("BYTE_0", "BYTE_1") GBX_REG_STEP_OPS);
+    if (SYM && HI) asm volatile(GBX_REG_STEP_SYM("BYTE_2", "BYTE_3") GBX_REG_STEP_OPS);
+    if (!SYM && !HI) asm volatile(GBX_REG_STEP_ASYM("BYTE_0", "BYTE_1") GBX_REG_STEP_OPS);
+    if (!SYM && HI) asm volatile(GBX_REG_STEP_ASYM("BYTE_2", "BYTE_3") GBX_REG_STEP_OPS);
+#undef GBX_REG_STEP_OPS
+    (void)ti;
+    left = hb;
+    key = kout;
+    return wn;
+}
+#undef GBX_REG_STEP_SYM
+#undef GBX_REG_STEP_ASYM
+#undef GBX_REG_STEP_HEAD
+
+// wave-wide OR / AND (every lane defined; lane 63 ends with the total)
+template <bool AND>
+__device__ inline uint32_t wave_bits(uint32_t x)
+{
+    auto op = [](uint32_t a, uint32_t b) { return AND ? a & b : a | b; };
+    int y = (int)x;
+    y = (int)op(y, dpp<0x111>(y, y));
+    y = (int)op(y, dpp<0x112>(y, y));
+    y = (int)op(y, dpp<0x114>(y, y));
+    y = (int)op(y, dpp<0x118>(y, y));
+    y = (int)op(y, dpp<0x142, 0xa>(y, y));
+    y = (int)op(y, dpp<0x143, 0xc>(y, y));
+    return (uint32_t)__builtin_amdgcn_readlane(y, 63);
+}
+// bits lo..31 of a word (all for lo <= 0, none for lo >= 32)
+__device__ inline uint32_t bits_from(int lo)
+{
+    return lo <= 0 ? ~0u : lo >= 32 ? 0u : ~0u << lo;
+}
+// bits lo..hi of a word (none when lo > hi; 0 <= lo, hi <= 31)
+__device__ inline uint32_t bit_span(int lo, int hi)
+{
+    return lo > hi ? 0u : (hi >= 31 ? ~0u : (2u << hi) - 1u) & ~((1u << lo) - 1u);
+}
+
+// A column pair of a block that some lane covers only in part: per lane, the pair is inside [beg, end) (the step; a column
+// before beg gets a zero input cell, as in bsw_lane_kernel), holds end in its high half (the low column alone, then eh[end] =
+// {h, 0}), holds end in its low half (eh[end] = {left, 0}, the high half kept), or lies outside (the cell kept: stale cells past
+// end are what bwa reads when end grows).  The row maximum sees the window only; left is H(i, end - 1) after the pair holding end.
+// (beg, end relative to the block; PA = the pair's first column within it)
+template <bool SYM, bool HI, int PA>
+__device__ __forceinline__ void reg_pair_masked(uint32_t &cell, uint32_t sa, int beg, int end, int &f, int &left, uint32_t &key,
+                                                int zero, int oe_del, int oe_ins, int e_del, int e_ins)
+{
+    constexpr int c0 = PA;
+    if (c0 + 1 < end && c0 + 1 >= beg) {
+        const uint32_t win = c0 < beg ? cell & 0xffff0000u : cell;
+        cell = reg_pair_step<SYM, HI, PA>(win, sa, f, left, key, zero, oe_del, oe_ins, e_del, e_ins);
+    } else if (c0 + 1 == end) {
+        if (c0 >= beg) {                               // :187-212 for column c0 alone
+            const int sc = (int)(int8_t)(sa >> (HI ? 16 : 0));
+            const int diag = (int)((cell >> 8) & 0xffu), e = (int)(cell & 0xffu);
+            const int m = diag ? diag + sc : 0;
+            const int h = imax3(m, e, f);
+            key = max(key, ((uint32_t)h << 18) | (uint32_t)PA);
+            const int en = imax3(e - e_del, m - oe_del, 0);
+            cell = ((uint32_t)h << 24) | ((uint32_t)left << 8) | (uint32_t)en;
+            left = h;
+        } else {
+            cell = (cell & 0xffffu) | ((uint32_t)left << 24);
+        }
+    } else if (c0 == end) {
+        cell = (cell & 0xffff0000u) | ((uint32_t)left << 8);
+    }
+}
+
+// QHI: the class's longest query.  One pair per lane, the same sorted lists, chunk cursor and result as bsw_lane_kernel.
+template <bool SYM, int QHI>
+__global__ void __launch_bounds__(64, 3) bsw_lane_reg_kernel(BswDev prm, BswPairs P, BswWork W, int rlo, int rhi, int slot)
+{
+    constexpr int NCP = QHI / 2 + 1;                   // column pairs: columns 0..QHI (end <= qlen <= QHI)
+    constexpr int NB = (NCP + 3) / 4;                  // blocks of four pairs (eight columns)
+    constexpr int NQ = (NCP + 1) / 2;                  // selector dwords, two pairs each
+    constexpr int NW = (2 * NCP + 31) / 32;            // words of a one-bit-per-column mask
+    static_assert(NB <= 31, "block masks are 32-bit");
+    constexpr int OUT = 1 << 12;                       // beg = end of a lane whose pair is done: past every block
+    __shared__ uint2 s_tab[5];                         // the scoring matrix by target base: {bytes against A C G T, byte against N}
+    const int lane = threadIdx.x;
+    if (lane < 5) s_tab[lane] = make_uint2(prm.row0[lane], prm.row1[lane]);
+    __syncthreads();
+    const int first = W.lbase[rlo << 8], count = W.lbase[(rhi + 1) << 8] - first;
+    const int nchunks = (count + 63) >> 6;
+    const int32_t *order = W.lorder + first;
+    const int e_ins = prm.e_ins, e_del = prm.e_del, oe_ins = prm.oe_ins, oe_del = prm.oe_del;
+    for (;;) {
+        int c = 0;
+        if (lane == 0) c = atomicAdd(&W.lchunk[slot], 1);
+        c = __builtin_amdgcn_readfirstlane(c);
+        if (c >= nchunks) break;
+        const int hi_ = count - (c << 6), idx = hi_ - 64 + lane;
+        const bool have = idx >= 0;                    // the ragged last chunk's spare lanes repeat entry 0
+        const int pair = order[have ? idx : 0];
+        const int qlen = P.len2[pair], tlen = P.len1[pair], h0 = P.h0[pair];
+        const uint8_t *q = P.qer + P.idq[pair];
+        const uint8_t *t = P.ref + P.idr[pair];
+
+        // query codes min(code, 4) as selector bytes, four columns a dword (the arenas are readable 16 bytes past their last base;
+        // the codes of columns at and past qlen are never those of a live cell: what they hold does not matter)
+        uint32_t qs[NQ];
+#pragma unroll
+        for (int k = 0; k < (4 * NQ + 15) / 16; ++k) {
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (16 * k <= qlen) __builtin_memcpy(&v, q + 16 * k, 16);
+            const uint32_t vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int m = 0; m < 4 && 4 * k + m < NQ; ++m) {
+                const uint32_t x = vv[m];
+                const uint32_t ge5 = ((((x | 0x80808080u) - 0x05050505u) | x) & 0x80808080u) >> 7;     // 1 in the bytes >= 5
+                const uint32_t msk = ge5 * 0xffu;
+                qs[4 * k + m] = (x & ~msk) | (0x04040404u & msk);
+            }
+        }
+        // first row, :155-157: eh[j].h = h0 - oe_ins - (j - 1) e_ins clipped at 0 (h0 at j = 0), up to column qlen; zero past it
+        uint32_t cell[NCP];
+        {
+            int hr = h0 - oe_ins, rem = qlen;              // hr = the formula's value at column j + 1, rem = qlen - j
+#pragma unroll
+            for (int p = 0; p < NCP; ++p) {
+                const int hv0 = p == 0 ? h0 : max(hr + e_ins, 0), hv1 = max(hr, 0);
+                cell[p] = (rem >= 0 ? (uint32_t)hv0 << 8 : 0u) | (rem >= 1 ? (uint32_t)hv1 << 24 : 0u);
+                hr -= 2 * e_ins;
+                rem -= 2;
+            }
+        }
+        const int w = band_width(prm, qlen);
+        int best = h0, best_i = -1, best_j = -1, g_i = -1, g_score = -1, off = 0;
+        int beg = 0, end = qlen;
+        bool running = true;
+        // the matrix row of the target base two rows ahead of its use, as in bsw_lane_kernel
+        uint2 mrow = s_tab[min((int)t[0], 4)], mnext = s_tab[min((int)t[1], 4)];
+        int tb2 = t[2];
+        const uint8_t *tp = t + 3;
+        int hrow = h0 - prm.o_del - e_del;             // h0 - (o_del + e_del * (i + 1))
+        int imw = -w, ipw = w + 1;                     // i - w, i + w + 1
+        for (int i = 0;; ++i) {
+            if (!__any(running)) break;
+            const uint32_t rw = mrow.x, rwn = mrow.y;
+            mrow = mnext;
+            mnext = s_tab[min(tb2, 4)];
+            tb2 = running ? (int)*tp : 0;              // a finished pair's target is not read on
+            tp += running ? 1 : 0;
+            beg = max(beg, imw);                       // :179-181
+            end = min(min(end, ipw), qlen);
+            ++imw; ++ipw;
+            int left = beg == 0 ? max(hrow, 0) : 0;    // :183-186
+            hrow -= e_del;
+            const int bb = running ? beg : OUT, ee = running ? end : OUT;
+            // blocks the lane's window [beg, end] touches / covers whole, and the blocks of the cells its next window is decided on
+            const int sp0 = bb >> 1, sq = max((ee >> 1) - 1, 0);
+            const uint32_t touch = running ? bit_span(bb >> 3, min(ee >> 3, NB - 1)) : 0u;
+            const uint32_t whole = running ? bit_span((bb + 7) >> 3, min((ee >> 3) - 1, NB - 1)) : ~0u;
+            auto blk = [](int pp) { return pp < 4 * NB ? 1u << (pp >> 2) : 0u; };      // the block of column pair pp, none past the last
+            const uint32_t probe = running ? blk(sp0) | blk(sp0 + 1) | blk(sq) | blk(sq + 1) : 0u;
+            const uint32_t touch_w = wave_bits<false>(touch), whole_w = wave_bits<true>(whole), probe_w = wave_bits<false>(probe);
+            int vzero = 0;
+            asm volatile("" : "+v"(vzero));              // a zero in a vector register (SDWA compare operand)
+            int f = 0;
+            uint32_t key = 0;                            // (row maximum << 18) | column of its last arg-max
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                if (!((touch_w >> b) & 1u)) continue;
+                const uint32_t sa0 = __builtin_amdgcn_perm(rwn, rw, qs[2 * b]);
+                const uint32_t sa1 = 2 * b + 1 < NQ ? __builtin_amdgcn_perm(rwn, rw, qs[2 * b + 1]) : 0u;
+                uint32_t kt = (uint32_t)vzero;           // the block's maximum, positions within the block
+                if ((whole_w >> b) & 1u) {
+                    cell[4 * b] = reg_pair_step<SYM, false, 0>(cell[4 * b], sa0, f, left, kt, vzero, oe_del, oe_ins, e_del, e_ins);
+                    if (4 * b + 1 < NCP) cell[4 * b + 1] = reg_pair_step<SYM, true, 2>(cell[4 * b + 1], sa0, f, left, kt, vzero, oe_del, oe_ins, e_del, e_ins);
+                    if (4 * b + 2 < NCP) cell[4 * b + 2] = reg_pair_step<SYM, false, 4>(cell[4 * b + 2], sa1, f, left, kt, vzero, oe_del, oe_ins, e_del, e_ins);
+                    if (4 * b + 3 < NCP) cell[4 * b + 3] = reg_pair_step<SYM, true, 6>(cell[4 * b + 3], sa1, f, left, kt, vzero, oe_del, oe_ins, e_del, e_ins);
+                } else {
+                    // the window relative to the block, made here (opaque to the compiler, which would otherwise hoist every
+                    // block's lane compares to the row's head and hold them in scalar registers)
+                    int lb = bb - 8 * b, le = ee - 8 * b;
+                    asm volatile("" : "+v"(lb), "+v"(le));
+                    reg_pair_masked<SYM, false, 0>(cell[4 * b], sa0, lb, le, f, left, kt, vzero, oe_del, oe_ins, e_del, e_ins);
+                    if (4 * b + 1 < NCP) reg_pair_masked<SYM, true, 2>(cell[4 * b + 1], sa0, lb, le, f, left, kt, vzero, oe_del, oe_ins, e_del, e_ins);
+                    if (4 * b + 2 < NCP) reg_pair_masked<SYM, false, 4>(cell[4 * b + 2], sa1, lb, le, f, left, kt, vzero, oe_del, oe_ins, e_del, e_ins);
+                    if (4 * b + 3 < NCP) reg_pair_masked<SYM, true, 6>(cell[4 * b + 3], sa1, lb, le, f, left, kt, vzero, oe_del, oe_ins, e_del, e_ins);
+                }
+                key = max(key, kt + (uint32_t)(8 * b));
+            }
+            // the cells that decide the next window (:230-233): the four from beg's pair on, the four from end's pair - 1 on
+            uint32_t sb0 = 0, sb1 = 0, se0 = 0, se1 = 0;
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                if (!((probe_w >> b) & 1u)) continue;
+                int db = sp0 - 4 * b, de = sq - 4 * b;
+                asm volatile("" : "+v"(db), "+v"(de));
+#pragma unroll
+                for (int m = 0; m < 4 && 4 * b + m < NCP; ++m) {
+                    const uint32_t cv = cell[4 * b + m];
+                    sb0 = db == m ? cv : sb0;
+                    sb1 = db == m - 1 ? cv : sb1;
+                    se0 = de == m ? cv : se0;
+                    se1 = de == m - 1 ? cv : se1;
+                }
+            }
+            if (running) {
+                const int jfin = beg < end ? end : beg;
+                if (jfin == qlen) {                      // :214-217
+                    if (!(g_score > left)) g_i = i;
+                    g_score = max(g_score, left);
+                }
+                const int row_best = (int)(key >> 18), row_arg = (int)(key & 0x3ffffu);
+                bool stop = row_best == 0;               // :218
+                if (!stop) {
+                    if (row_best > best) {               // :219-221
+                        best = row_best; best_i = i; best_j = row_arg;
+                        off = max(off, abs(row_arg - i));
+                    } else if (prm.zdrop > 0) {          // :222-228
+                        const int di = i - best_i, dj = row_arg - best_j;
+                        stop = di > dj ? best - row_best - (di - dj) * e_del > prm.zdrop : best - row_best - (dj - di) * e_ins > prm.zdrop;
+                    }
+                }
+                if (!stop) {
+                    // next window, :230-233, as bsw_lane_kernel decides it from the same eight cells
+                    int k = (sb1 >> 16) ? 3 : 4;
+                    k = (sb1 & 0xffffu) ? 2 : k;
+                    k = (sb0 >> 16) ? 1 : k;
+                    k = (sb0 & 0xffffu) && !(beg & 1) ? 0 : k;
+                    int j = 2 * sp0 + k;
+                    const int khi = end - 2 * sq;
+                    int ke = (se0 & 0xffffu) ? 0 : -1;
+                    ke = (se0 >> 16) && khi >= 1 ? 1 : ke;
+                    ke = (se1 & 0xffffu) && khi >= 2 ? 2 : ke;
+                    ke = (se1 >> 16) && khi >= 3 ? 3 : ke;
+                    // rare (four zero cells in a row at either end): a bit mask of the non-zero columns, one bit per column
+                    uint32_t nz[NW];
+                    if (k == 4 || ke < 0) {
+#pragma unroll
+                        for (int u = 0; u < NW; ++u) nz[u] = 0u;
+#pragma unroll
+                        for (int p = 0; p < NCP; ++p) {
+                            const uint32_t two = ((cell[p] & 0xffffu) ? 1u : 0u) | ((cell[p] >> 16) ? 2u : 0u);
+                            nz[p >> 4] |= two << ((2 * p) & 31);
+                        }
+                    }
+                    if (k == 4) {                        // the first non-zero column from j on, below end; end if none
+                        int jn = end;
+#pragma unroll
+                        for (int u = NW - 1; u >= 0; --u) {
+                            const uint32_t m = nz[u] & bits_from(j - 32 * u) & ~bits_from(end - 32 * u);
+                            jn = m ? 32 * u + __builtin_ctz(m) : jn;
+                        }
+                        j = jn;
+                    }
+                    j = min(j, end);
+                    const int nbeg = beg < end ? j : beg;
+                    j = 2 * sq + ke;
+                    if (ke < 0 && 2 * sq > nbeg) {       // the last non-zero column from nbeg on, up to j; nbeg - 1 if none
+                        int jl = nbeg - 1;
+#pragma unroll
+                        for (int u = 0; u < NW; ++u) {
+                            const uint32_t m = nz[u] & bits_from(nbeg - 32 * u) & ~bits_from(j + 1 - 32 * u);
+                            jl = m ? 32 * u + 31 - __builtin_clz(m) : jl;
+                        }
+                        j = jl;
+                    }
+                    j = max(j, nbeg - 1);
+                    j = nbeg > end ? end : j;
+                    beg = nbeg;
+                    end = min(j + 2, qlen);
+                }
+                running = !stop && i + 1 < tlen;
+            }
+        }
+        gbx_bsw_result r;
+        r.score = best; r.tle = best_i + 1; r.gtle = g_i + 1; r.qle = best_j + 1; r.gscore = g_score; r.max_off = off;
+        if (have) P.out[pair] = r;
+    }
+}
+
 // ---- kernel shapes ----------------------------------------------------------
 // class c (query length) -> (lanes per pair, columns per lane).  Short queries use narrow groups:
 // the per-row fixed cost (scan, reductions, epilogue) is paid once per wavefront row, so 16 pairs per
@@ -1216,6 +1569,9 @@ int bsw_launch_direct(const gbx_bsw_params *p, int64_t n, int max_qlen,
     GBX_HIP(hipGetLastError());
     return GBX_OK;
 }
+
+// launches of bsw_lane_reg_kernel so far (gbx_debug_bsw_lane_reg_launches: the tests check that it ran)
+static std::atomic<long long> g_lane_reg_launches{0};
 
 // lane path: large jobs only (a wavefront holds 64 pairs: the chip wants a few thousand wavefronts), GBX_BSW_LANE=0/1 overrides
 static bool lane_wanted(int64_t n)
@@ -1431,6 +1787,27 @@ int bsw_launch(const gbx_bsw_params *p, int64_t n,
                 if (blocks > want) blocks = want;
                 const int rlo = fmt * (LANE_QMAX + 1) + qlo, rhi = fmt * (LANE_QMAX + 1) + qhi, slot = fmt * LANE_NRANGE + r;
                 Stage st(names[fmt][r], sc);
+                // the compact 80..99 class of unpacked bases with its cells in registers (bsw_lane_reg_kernel), as many wavefronts
+                // as its registers allow; GBX_BSW_LANE_REG=0 keeps it on bsw_lane_kernel
+                const char *rege = getenv("GBX_BSW_LANE_REG");           /* read per call: the tests vary it */
+                if (fmt == 0 && !P.packed && qhi == 99 && !(rege && atoi(rege) == 0)) {
+                    static_assert(LANE_RANGE_HI[0][2] == 99, "bsw_lane_reg_kernel instance");
+                    typedef void (*LaneRegFn)(BswDev, BswPairs, BswWork, int, int, int);
+                    static const LaneRegFn reg_fn[2] = {bsw_lane_reg_kernel<false, 99>, bsw_lane_reg_kernel<true, 99>};
+                    static std::atomic<int> reg_bpc[2];                    // resident blocks per CU, cached
+                    const LaneRegFn fn = reg_fn[sym];
+                    std::atomic<int> &bc = reg_bpc[sym];
+                    int bpc = bc.load(std::memory_order_relaxed);
+                    if (!bpc) {
+                        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, (const void *)fn, 64, 0) != hipSuccess || bpc < 1) { (void)hipGetLastError(); bpc = 8; }
+                        bc.store(bpc, std::memory_order_relaxed);
+                    }
+                    int64_t rblocks = (int64_t)cus * bpc;
+                    if (rblocks > want) rblocks = want;
+                    hipLaunchKernelGGL(fn, dim3((unsigned)rblocks), dim3(64), 0, sc, dev, P, W, rlo, rhi, slot);
+                    g_lane_reg_launches.fetch_add(1, std::memory_order_relaxed);
+                    continue;
+                }
                 auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64), lds, sc, dev, P, W, rlo, rhi, cols, slot); };
                 if (P.packed) {
                     if (fmt == 0 && code4) { if (sym) go(bsw_lane_kernel<true, true, true, true>); else go(bsw_lane_kernel<false, true, true, true>); }
@@ -1477,6 +1854,11 @@ int bsw_launch(const gbx_bsw_params *p, int64_t n,
 }
 
 }  // namespace gbx
+
+extern "C" long long gbx_debug_bsw_lane_reg_launches(void)
+{
+    return gbx::g_lane_reg_launches.load(std::memory_order_relaxed);
+}
 
 #ifdef GBX_BSW_LANE_STATS
 extern "C" int gbx_debug_bsw_lane_stats(unsigned long long *out, int reset)
