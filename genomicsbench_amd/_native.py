@@ -144,6 +144,11 @@ def _declare(L):
         L.gbx_fmi_sal_host.argtypes = [vp, vp, vp, i64, C.c_int32, vp, i64, vp, C.POINTER(C.c_int64)]
         L.gbx_fmi_sal_device.argtypes = [vp, vp, vp, vp, vp, vp, i64, C.c_int32, vp, i64, vp, vp, vp, sz, vp]
         L.gbx_fmi_sal_steps.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]
+    if hasattr(L, "gbx_kmer_count_host"):
+        L.gbx_kmer_workspace_bytes.argtypes = [C.c_int32, i64, C.c_int32]
+        L.gbx_kmer_workspace_bytes.restype = sz
+        L.gbx_kmer_count_host.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64]
+        L.gbx_kmer_count_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp, sz, vp]
     if hasattr(L, "gbx_chain_host"):
         L.gbx_chain_job_stats.argtypes = [vp, i64, i64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]
         L.gbx_chain_workspace_bytes.argtypes = [i64, i64]

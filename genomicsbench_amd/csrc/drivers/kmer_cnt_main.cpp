@@ -1,0 +1,294 @@
+// kmer_cnt_main.cpp — the kmer-cnt benchmark driver (R/benchmarks/kmer-cnt/kmer_cnt.cpp) over gbx_kmer_count_host.
+//
+// CLI as the reference: --reads a,b,... --config path [--kmer k] [--min-read n] [--min-ovlp n] [--threads n] [--debug]
+// [--log file].  k is --kmer, else kmer_size of the config file (Flye's key=value lines, '#' comments, %include relative to
+// the file, config.h:36-72); only the count path (use_minimizers = 0) is built.  Reads longer than max(--min-read,
+// --min-ovlp) are kept (kmer_cnt.cpp:189, sequence_container.cpp:102), duplicated IDs among them are refused
+// (sequence_container.cpp:62-69), and a character outside ACGTacgt turns itself and the rest of its 32-base chunk into T, as
+// the reference's DnaSequence packing does on LP64 (see genomicsbench_amd/kmer.py: encode).
+// Printed as the reference: "Hash size: H" and "Total k-mers N" (with --debug) and "Kernel time: X sec" (stderr).
+// Not reference flags: --hist FILE (f<TAB>n lines, 1 <= f < 255, the last bin "count >= 255"), --solid MIN FILE (k-mers with
+// count >= MIN as ACGT...<TAB>count, ascending code), --parse-only (reads, bases and a checksum; no GPU), --gpus N.
+// Unlike the reference, gzip-compressed inputs are refused (no zlib).
+#include <omp.h>
+#include <map>
+#include <set>
+#include "driver_common.h"
+
+namespace {
+
+struct Options {
+    std::vector<std::string> reads;
+    std::string config, log, hist, solid;
+    int kmer = -1, min_read = 0, min_ovlp = 5000, threads = 1;
+    long solid_min = 0;
+    bool debug = false, parse_only = false;
+};
+
+void usage()
+{
+    fprintf(stderr, "Usage: kmer-cnt --reads path1[,path2,...] --config path [--kmer size] [--min-read length] [--min-ovlp size]\n"
+                    "\t\t[--threads num] [--debug] [--log path] [--hist path] [--solid min path] [--parse-only] [--gpus n]\n");
+}
+
+std::string trim(const std::string &s)
+{
+    size_t a = 0, b = s.size();
+    while (a < b && isspace((unsigned char)s[a])) ++a;
+    while (b > a && isspace((unsigned char)s[b - 1])) --b;
+    return s.substr(a, b - a);
+}
+
+// config.h:36-72; false with a message on an unreadable file or a malformed line
+bool load_config(const std::string &path, std::map<std::string, double> &kv, int depth = 0)
+{
+    FILE *f = fopen(path.c_str(), "r");
+    if (!f) { fprintf(stderr, "Can't open config file: %s\n", path.c_str()); return false; }
+    if (depth > 16) { fclose(f); fprintf(stderr, "Config %%include nested too deep: %s\n", path.c_str()); return false; }
+    const size_t slash = path.find_last_of("/\\");
+    const std::string dir = slash == std::string::npos ? "" : path.substr(0, slash + 1);
+    char buf[4096];
+    bool ok = true;
+    while (ok && fgets(buf, sizeof buf, f)) {
+        std::string line(buf);
+        while (!line.empty() && (line.back() == '\n' || line.back() == '\r')) line.pop_back();
+        if (line.empty() || line[0] == '#') continue;
+        if (line.compare(0, 8, "%include") == 0) {
+            const std::string rest = trim(line.substr(8));
+            ok = load_config(dir + rest, kv, depth + 1);
+            continue;
+        }
+        const size_t eq = line.find('=');
+        if (eq == std::string::npos || line.find('=', eq + 1) != std::string::npos) {
+            fprintf(stderr, "Error parsing config file %s: %s\n", path.c_str(), line.c_str());
+            ok = false;
+            break;
+        }
+        kv[trim(line.substr(0, eq))] = atof(trim(line.substr(eq + 1)).c_str());
+    }
+    fclose(f);
+    return ok;
+}
+
+// sequence_container.cpp:23-48: the file type by its suffix, ".gz" ignored
+int file_kind(const std::string &name)
+{
+    std::string s = name;
+    if (s.size() > 3 && s.compare(s.size() - 3, 3, ".gz") == 0) s = s.substr(0, s.size() - 3);
+    const size_t dot = s.rfind('.');
+    const std::string suf = dot == std::string::npos ? "" : s.substr(dot + 1);
+    if (suf == "fasta" || suf == "fa") return 0;
+    if (suf == "fastq" || suf == "fq") return 1;
+    return -1;
+}
+
+struct Record {
+    std::string name;
+    std::vector<std::pair<const char *, int>> parts;      // the sequence's lines
+    int64_t len = 0;
+};
+
+// records of one file's text (kept alive by the caller); false with a message on a format error
+bool parse_file(const std::vector<char> &text, bool fastq, int threads, std::vector<Record> &out, const std::string &path)
+{
+    std::vector<const char *> line;
+    std::vector<int> llen;
+    split_lines(text.data(), text.size() - 1, threads, line, llen);
+    auto header = [](const char *p, int n) {
+        int e = 1;
+        while (e < n && !isspace((unsigned char)p[e])) ++e;
+        return std::string(p + 1, (size_t)(e - 1));
+    };
+    if (!fastq) {
+        Record cur;
+        bool have = false;
+        for (size_t k = 0; k < line.size(); ++k) {
+            int n = llen[k];
+            if (n > 0 && line[k][n - 1] == '\r') --n;
+            if (n == 0) continue;
+            if (line[k][0] == '>') {
+                if (have) {
+                    if (cur.len == 0) { fprintf(stderr, "parse error in %s: empty sequence\n", path.c_str()); return false; }
+                    out.push_back(std::move(cur));
+                    cur = Record();
+                }
+                cur.name = header(line[k], n);
+                if (cur.name.empty()) { fprintf(stderr, "parse error in %s: empty header\n", path.c_str()); return false; }
+                have = true;
+            } else {
+                cur.parts.emplace_back(line[k], n);
+                cur.len += n;
+            }
+        }
+        if (!have || cur.len == 0) { fprintf(stderr, "parse error in %s: Fasta format error\n", path.c_str()); return false; }
+        out.push_back(std::move(cur));
+        return true;
+    }
+    int state = 0;
+    std::string name;
+    for (size_t k = 0; k < line.size(); ++k) {
+        int n = llen[k];
+        if (n > 0 && line[k][n - 1] == '\r') --n;
+        if (n == 0) { state = (state + 1) % 4; continue; }
+        if (state == 0) {
+            if (line[k][0] != '@') { fprintf(stderr, "parse error in %s: Fastq format error\n", path.c_str()); return false; }
+            name = header(line[k], n);
+            if (name.empty()) { fprintf(stderr, "parse error in %s: empty header\n", path.c_str()); return false; }
+        } else if (state == 1) {
+            Record r;
+            r.name = name;
+            r.parts.emplace_back(line[k], n);
+            r.len = n;
+            out.push_back(std::move(r));
+        } else if (state == 2 && line[k][0] != '+') {
+            fprintf(stderr, "parse error in %s: Fastq format error\n", path.c_str());
+            return false;
+        }
+        state = (state + 1) % 4;
+    }
+    return true;
+}
+
+}  // namespace
+
+int main(int argc, char **argv)
+{
+    const int gpus = take_gpus_flag(argc, argv);
+    Options o;
+    for (int i = 1; i < argc; ++i) {
+        const std::string a = argv[i];
+        auto need = [&](int n) { if (i + n >= argc) { usage(); exit(EXIT_FAILURE); } };
+        if (a == "--reads") { need(1); std::string s = argv[++i]; size_t p = 0; while (true) { size_t q = s.find(',', p); o.reads.push_back(s.substr(p, q - p)); if (q == std::string::npos) break; p = q + 1; } }
+        else if (a == "--config") { need(1); o.config = argv[++i]; }
+        else if (a == "--kmer") { need(1); o.kmer = atoi(argv[++i]); }
+        else if (a == "--min-read") { need(1); o.min_read = atoi(argv[++i]); }
+        else if (a == "--min-ovlp") { need(1); o.min_ovlp = atoi(argv[++i]); }
+        else if (a == "--threads") { need(1); o.threads = std::max(1, atoi(argv[++i])); }
+        else if (a == "--log") { need(1); o.log = argv[++i]; }
+        else if (a == "--debug") o.debug = true;
+        else if (a == "--hist") { need(1); o.hist = argv[++i]; }
+        else if (a == "--solid") { need(2); o.solid_min = atol(argv[++i]); o.solid = argv[++i]; }
+        else if (a == "--parse-only") o.parse_only = true;
+        else if (a == "-h" || a == "--help") { usage(); return 0; }
+        else { fprintf(stderr, "unknown option %s\n", argv[i]); usage(); return EXIT_FAILURE; }
+    }
+    if (o.reads.empty() || o.config.empty()) { usage(); return EXIT_FAILURE; }
+    if (!o.log.empty() && !freopen(o.log.c_str(), "a", stderr)) { fprintf(stdout, "Can't open log file %s\n", o.log.c_str()); return EXIT_FAILURE; }
+    std::map<std::string, double> cfg;
+    if (!load_config(o.config, cfg)) return EXIT_FAILURE;
+    if (o.kmer == -1) {
+        if (!cfg.count("kmer_size")) { fprintf(stderr, "No such parameter: kmer_size (and no --kmer)\n"); return EXIT_FAILURE; }
+        o.kmer = (int)cfg["kmer_size"];
+    }
+    if (cfg.count("use_minimizers") && cfg["use_minimizers"] != 0) {
+        fprintf(stderr, "use_minimizers = %g: the minimizer index (buildIndexMinimizers) is not built; only the k-mer count path (use_minimizers=0) is\n",
+                cfg["use_minimizers"]);
+        return EXIT_FAILURE;
+    }
+    if (o.kmer < 1 || o.kmer > GBX_KMER_MAX_K) { fprintf(stderr, "Can't use flat counter for k-mer size %d (1..%d)\n", o.kmer, GBX_KMER_MAX_K); return EXIT_FAILURE; }
+    if (o.debug) fprintf(stderr, "Running with k-mer size: %d\n", o.kmer);
+
+    // ---- ingest: every file whole, lines split with threads, records in file order, then the kept reads encoded in parallel
+    const int64_t min_len = std::max(o.min_read, o.min_ovlp);
+    const double t0 = now_s();
+    std::vector<std::vector<char>> texts(o.reads.size());
+    std::vector<Record> kept;
+    for (size_t f = 0; f < o.reads.size(); ++f) {
+        const int kind = file_kind(o.reads[f]);
+        if (kind < 0) { fprintf(stderr, "Can't identify input file type: %s\n", o.reads[f].c_str()); return EXIT_FAILURE; }
+        std::vector<char> &text = texts[f];
+        if (!slurp(o.reads[f].c_str(), text)) { fprintf(stderr, "Can't open reads file %s\n", o.reads[f].c_str()); return EXIT_FAILURE; }
+        if (text.size() > 2 && (unsigned char)text[0] == 0x1f && (unsigned char)text[1] == 0x8b) {    // the reference reads gzip (zlib); not linked here
+            fprintf(stderr, "%s is gzip-compressed: decompress it first\n", o.reads[f].c_str());
+            return EXIT_FAILURE;
+        }
+        if (text.size() > 1 && text[text.size() - 2] != '\n') { text[text.size() - 1] = '\n'; text.push_back(0); }
+        std::vector<Record> recs;
+        if (!parse_file(text, kind == 1, o.threads, recs, o.reads[f])) return EXIT_FAILURE;
+        for (Record &r : recs)
+            if (r.len > min_len) kept.push_back(std::move(r));
+    }
+    {
+        std::set<std::string> seen;
+        for (const Record &r : kept)
+            if (!seen.insert(r.name).second) {
+                fprintf(stderr, "The input contain reads with duplicated IDs. Make sure all reads have unique IDs and restart. "
+                                "The first problematic ID was: %s\n", r.name.c_str());
+                return EXIT_FAILURE;
+            }
+    }
+    const int64_t n_reads = (int64_t)kept.size();
+    std::vector<int64_t> off((size_t)n_reads);
+    std::vector<int32_t> len((size_t)n_reads);
+    int64_t total = 0;
+    for (int64_t r = 0; r < n_reads; ++r) {
+        if (kept[(size_t)r].len > INT32_MAX) { fprintf(stderr, "read %s is longer than 2^31 - 1 bases\n", kept[(size_t)r].name.c_str()); return EXIT_FAILURE; }
+        off[(size_t)r] = total;
+        len[(size_t)r] = (int32_t)kept[(size_t)r].len;
+        total += kept[(size_t)r].len;
+    }
+    std::vector<uint8_t> enc((size_t)total);
+    static uint8_t lut[256];
+    for (int c = 0; c < 256; ++c) lut[c] = 255;
+    lut['A'] = lut['a'] = 0; lut['C'] = lut['c'] = 1; lut['G'] = lut['g'] = 2; lut['T'] = lut['t'] = 3;
+#pragma omp parallel for num_threads(o.threads) schedule(dynamic, 64)
+    for (int64_t r = 0; r < n_reads; ++r) {
+        uint8_t *q = enc.data() + off[(size_t)r];
+        int64_t i = 0;
+        bool spill = false;                      // an invalid character earlier in this 32-base chunk: T up to its end
+        for (const auto &pt : kept[(size_t)r].parts)
+            for (int c = 0; c < pt.second; ++c, ++i) {
+                if ((i & 31) == 0) spill = false;
+                const uint8_t v = lut[(unsigned char)pt.first[c]];
+                spill = spill || v == 255;
+                q[i] = spill ? 3 : v;
+            }
+    }
+    fprintf(stderr, "ingest: %lld reads, %lld bases, %.3f s with %d threads\n", (long long)n_reads, (long long)total, now_s() - t0, o.threads);
+    if (o.debug) fprintf(stderr, "Total sequence: %lld bp\n", (long long)total);
+    if (o.parse_only) {
+        uint64_t h = fnv1a(len.data(), len.size() * sizeof(int32_t));
+        h = fnv1a(enc.data(), enc.size(), h);
+        printf("{\"reads\": %lld, \"bases\": %lld, \"fnv1a\": \"%016llx\"}\n", (long long)n_reads, (long long)total, (unsigned long long)h);
+        return 0;
+    }
+
+    print_device_banner(gpus);
+    gbx_kmer_params p{o.kmer, 256, o.solid.empty() ? 0u : (uint32_t)std::max(1l, o.solid_min), 0u};
+    gbx_kmer_stats st{};
+    std::vector<int64_t> hist(256);
+    std::vector<uint64_t> sel_kmer;
+    std::vector<uint32_t> sel_count;
+    const double t1 = now_s();
+    int rc = gbx_kmer_count_host(&p, n_reads, enc.data(), (int64_t)enc.size(), off.data(), len.data(), &st, hist.data(), nullptr, nullptr, 0);
+    if (rc == GBX_ERR_ARG && st.n_selected > 0) {            // the selection's size is known now: run again with room for it
+        sel_kmer.resize((size_t)st.n_selected);
+        sel_count.resize((size_t)st.n_selected);
+        rc = gbx_kmer_count_host(&p, n_reads, enc.data(), (int64_t)enc.size(), off.data(), len.data(), &st, hist.data(), sel_kmer.data(),
+                                 sel_count.data(), (int64_t)sel_kmer.size());
+    }
+    die_on(rc, "gbx_kmer_count_host");
+    const double dt = now_s() - t1;
+    if (o.debug) {
+        fprintf(stderr, "Hash size: %lld\n", (long long)st.n_ge16);
+        fprintf(stderr, "Total k-mers %lld\n", (long long)st.n_distinct);
+    }
+    fprintf(stderr, "Kernel time: %.3f sec\n", dt);
+    if (!o.hist.empty()) {
+        FILE *f = fopen(o.hist.c_str(), "w");
+        if (!f) { fprintf(stderr, "Can't open %s\n", o.hist.c_str()); return EXIT_FAILURE; }
+        for (size_t b = 1; b < hist.size(); ++b) fprintf(f, "%zu\t%lld\n", b, (long long)hist[b]);
+        fclose(f);
+    }
+    if (!o.solid.empty()) {
+        FILE *f = fopen(o.solid.c_str(), "w");
+        if (!f) { fprintf(stderr, "Can't open %s\n", o.solid.c_str()); return EXIT_FAILURE; }
+        std::string s((size_t)o.kmer, 'A');
+        for (size_t j = 0; j < sel_kmer.size(); ++j) {
+            for (int b = 0; b < o.kmer; ++b) s[(size_t)b] = "ACGT"[(sel_kmer[j] >> (2 * (o.kmer - 1 - b))) & 3];
+            fprintf(f, "%s\t%u\n", s.c_str(), sel_count[j]);
+        }
+        fclose(f);
+    }
+    return 0;
+}

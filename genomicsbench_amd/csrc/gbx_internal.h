@@ -190,6 +190,12 @@ int fmi_sal_launch(const gbx_fmi_index *idx, const void *d_index, const gbx_fmi_
                    int64_t *d_n_pos, void *d_work, size_t work_bytes, hipStream_t s);
 int fmi_sal_read_steps(const void *d_work, int64_t *steps, int64_t *max_steps, hipStream_t s);
 
+// ---- kmer (kmer_kernels.hip)
+size_t kmer_workspace_bytes(int32_t k, int64_t n_reads);
+int kmer_launch(const gbx_kmer_params *p, int64_t n_reads, const uint8_t *d_enc, const int64_t *d_read_off, const int32_t *d_read_len,
+                gbx_kmer_stats *d_stats, int64_t *d_hist, uint64_t *d_sel_kmer, uint32_t *d_sel_count, int64_t sel_cap, void *d_work,
+                size_t work_bytes, hipStream_t s);
+
 // ---- phmm (phmm_kernels.hip)
 size_t phmm_workspace_bytes(int64_t n_pairs, int64_t n_reads, int max_hap_len, int64_t stream_syms = -1);
 int phmm_init_tables();

@@ -176,3 +176,82 @@ def gen_fmi_reads(ref, n_reads, seed, first=0, read_len=151):
     enc = np.zeros((int(n_reads), int(read_len)), dtype=np.uint8)
     L.gbx_gen_fmi_reads(seed, first, int(n_reads), _p(ref), len(ref), int(read_len), _p(enc))
     return FmiReadSet.fixed(enc)
+
+
+KMER_PRESETS = {
+    # the reference's inputs: Loman_E.coli_MAP006-1_2D_50x.fasta ('large', ~230 Mbp) and its first 1000 reads ('small')
+    "small": dict(genome_len=4_600_000, coverage=None, n_reads=1000, seed=7001),
+    "large": dict(genome_len=4_600_000, coverage=50.0, n_reads=None, seed=7002),
+}
+
+
+def gen_kmer_reads(genome_len, coverage, seed, n_reads=None, mean_len=9000, sub=0.06, ins=0.03, dele=0.03, repeat_copies=8,
+                   repeat_len=3000, n_runs=4, short_frac=0.05):
+    """Long noisy reads in the shape of kmer-cnt's nanopore input, deterministic in `seed`.  Returns [(name, ASCII bytes)].
+    The genome carries `repeat_copies` copies of one `repeat_len` segment (k-mers seen hundreds of times) and a 200 bp
+    homopolymer run.  Read lengths are log-normal around mean_len, clipped to 1..40 kbp, with `short_frac` of the reads
+    drawn from 1..5000 bp (the reference's filter drops them); each read comes from either strand with about
+    sub + ins + dele errors per base; `n_runs` reads carry a run of N or IUPAC codes.  n_reads, when given, overrides
+    coverage."""
+    rng = np.random.default_rng(seed)
+    g = rng.integers(0, 4, genome_len, dtype=np.uint8)
+    if repeat_copies > 0 and repeat_len * (repeat_copies + 1) < genome_len:
+        rep = g[:repeat_len].copy()
+        for s in rng.choice(np.arange(1, genome_len // repeat_len - 1), repeat_copies, replace=False):
+            g[s * repeat_len:(s + 1) * repeat_len] = rep
+    if genome_len > 1000:
+        h = int(rng.integers(0, genome_len - 200))
+        g[h:h + 200] = 0
+    if n_reads is None:
+        n_reads = max(1, int(genome_len * coverage / mean_len))
+    sigma = 0.6
+    lens = np.exp(rng.normal(np.log(mean_len) - sigma * sigma / 2, sigma, n_reads)).astype(np.int64)
+    short = rng.random(n_reads) < short_frac
+    lens[short] = rng.integers(1, 5001, int(short.sum()))
+    lens = np.clip(lens, 1, min(40000, genome_len))
+    runs = set(rng.choice(n_reads, min(n_runs, n_reads), replace=False).tolist())
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    out = []
+    for r in range(n_reads):
+        L = int(lens[r])
+        st = int(rng.integers(0, genome_len - L + 1))
+        s = g[st:st + L]
+        if rng.random() < 0.5:
+            s = 3 - s[::-1]
+        u = rng.random(L)
+        keep = u >= dele                                             # deletions
+        sb = (u >= dele) & (u < dele + sub)
+        s = np.where(sb, (s + rng.integers(1, 4, L, dtype=np.uint8)) % 4, s).astype(np.uint8)
+        insr = (u >= dele + sub) & (u < dele + sub + ins)
+        s = s[keep]
+        insr = insr[keep]
+        if insr.any():
+            at = np.flatnonzero(insr) + 1
+            s = np.insert(s, at, rng.integers(0, 4, at.size, dtype=np.uint8))
+        txt = acgt[s]
+        if r in runs and txt.size > 20:
+            a = int(rng.integers(0, txt.size - 10))
+            txt = txt.copy()
+            txt[a:a + 10] = np.frombuffer(b"NNNNRYKMSW"[:10], dtype=np.uint8)
+        out.append(("read_%d" % r, txt.tobytes()))
+    return out
+
+
+def gen_kmer_preset(name):
+    p = KMER_PRESETS[name]
+    return gen_kmer_reads(p["genome_len"], p["coverage"], p["seed"], n_reads=p["n_reads"])
+
+
+def write_fasta(path, records, wrap=0, fastq=False):
+    """records: [(name, ASCII bytes)].  wrap > 0 breaks FASTA sequence lines every `wrap` characters; fastq writes
+    4-line records with constant qualities."""
+    with open(path, "wb") as f:
+        for name, seq in records:
+            if fastq:
+                f.write(b"@%s\n%s\n+\n%s\n" % (name.encode(), seq, b"5" * len(seq)))
+            elif wrap > 0:
+                f.write(b">%s\n" % name.encode())
+                for i in range(0, len(seq), wrap):
+                    f.write(seq[i:i + wrap] + b"\n")
+            else:
+                f.write(b">%s\n%s\n" % (name.encode(), seq))

@@ -1,5 +1,6 @@
 /* gbx.h — C-ABI of libgbx.so: MI355X (gfx950) kernels for GenomicsBench's
- * dynamic-programming hot path (bsw, chain, phmm, poa).
+ * dynamic-programming hot path (bsw, chain, phmm, poa) and its neighbours
+ * (abea, fmi, kmer).
  *
  * This is the drop-in boundary.  Every entry point is `extern "C"`, takes
  * plain pointers and sizes, returns an int status (0 = GBX_OK, <0 = error;
@@ -539,6 +540,67 @@ int gbx_fmi_sal_device(const gbx_fmi_index *idx, const void *d_index, const gbx_
                        void *stream);
 /* LF steps of the last gbx_fmi_sal_device call on this workspace: their total and the longest walk of one hit. */
 int gbx_fmi_sal_steps(const void *d_work, int64_t *steps, int64_t *max_steps, void *stream);
+
+/* -------------------------------------------------------------------- kmer
+ * Canonical k-mer counting of long reads: Flye's KmerCounter::count as the kmer-cnt benchmark times it
+ * (R/benchmarks/kmer-cnt/kmer_cnt.cpp:224-237, vertex_index.cpp:513-612).
+ *   R/kmer.h:185-197             IterKmers: a read of len bases gives the k-mers at positions 0 .. len - k - 1, that is
+ *                                max(0, len - k) of them (the window ending at the last base is not counted)
+ *   R/kmer.h:39-63               code = 2 bits per base, A C G T = 0 1 2 3, first base most significant; the canonical form
+ *                                is min(code, revcomp(code)), the complement of base b being 3 - b
+ *   R/vertex_index.cpp:537       each read once, on its forward strand
+ *   R/vertex_index.cpp:540-577   the flat 4-bit counter saturates at 15 and spills into the cuckoo map, so a k-mer's count
+ *                                is 15 + its map value: "Total k-mers" = n_distinct, "Hash size" = n_ge16 below
+ *   R/vertex_index.cpp:518-521   k > 17 is refused
+ * The reads' filter (length > max(--min-read, --min-ovlp), R/sequence_container.cpp:102) and the treatment of non-ACGT
+ * characters (on LP64 the reference's DnaSequence packing turns such a base and the rest of its 32-base chunk into T; see
+ * DESIGN 3.7) belong to the parser, not to these entries: every read given is counted.
+ * Reads are base codes 0..3, one per byte, read r = enc[read_off[r] ..+ read_len[r]), as gbx_fmi_smem_host takes them.  The
+ * CONTRACT is codes 0..3: larger values are not checked (the kernels use their low two bits).
+ * Results (exact, independent of the scheduling):
+ *   st->n_positions  sum of max(0, len - k); at or above 2^32 the host entry returns GBX_ERR_UNSUPPORTED (32-bit counters)
+ *                    and the device entry counts nothing and sets the four fields below to -1
+ *   st->n_distinct   distinct canonical k-mers;  st->n_ge16 those counted at least 16 times;  st->max_count the largest count
+ *   hist[n_hist]     hist[f] = canonical k-mers counted f times for 1 <= f < n_hist - 1, hist[n_hist - 1] = those counted at
+ *                    least n_hist - 1 times, hist[0] = 0 (Flye's _kmerDistribution, vertex_index.cpp:586-602);
+ *                    n_hist = 0: no histogram (hist may be NULL), else 2..GBX_KMER_MAX_HIST
+ *   selection        the canonical k-mers with min_freq <= count <= max_freq (max_freq 0: no upper bound; min_freq 0:
+ *                    nothing is selected) as (sel_kmer, sel_count) pairs in ascending canonical code; st->n_selected is
+ *                    their number and may exceed sel_cap, when only the first sel_cap were written
+ * The count is a direct-address table of 32-bit counters over the 4^k codes, in slices of 2^30 counters: one pass over
+ * the reads for k <= 15, 4 for k = 16, 16 for k = 17; the workspace is about 4^min(k, 15) x 4 bytes (4 GB from k = 15). */
+#define GBX_KMER_MAX_K    17
+#define GBX_KMER_MAX_HIST 4096
+typedef struct gbx_kmer_params {
+    int32_t k;           /* 1..17 (the reference's flat-counter limit) */
+    int32_t n_hist;      /* hist[f] for 1 <= f < n_hist-1; hist[n_hist-1] = count >= n_hist-1; hist[0] = 0 */
+    uint32_t min_freq;   /* selection: canonical k-mers with min_freq <= count <= max_freq ... */
+    uint32_t max_freq;   /* ... 0 = no upper bound; min_freq 0 = select nothing */
+} gbx_kmer_params;
+typedef struct gbx_kmer_stats {
+    int64_t n_positions; /* k-mers counted: sum of max(0, len - k) */
+    int64_t n_distinct;  /* the reference's "Total k-mers" */
+    int64_t n_ge16;      /* the reference's "Hash size" */
+    int64_t max_count;
+    int64_t n_selected;  /* may exceed sel_cap: then the output did not fit */
+} gbx_kmer_stats;
+
+/* Host-buffer entry.  Every read is checked (inside enc_bytes) and the positions counted before the device is touched.
+ * A selection larger than sel_cap gives GBX_ERR_ARG with the needed count in st->n_selected and in gbx_last_error(); st and
+ * hist are filled then too.  Safe under concurrent host threads; calls are serialised (a call's table is up to 4 GB of
+ * device memory, kept between calls like the other host entries' buffers, gbx_host_release frees it).  It runs on the
+ * calling thread's current device also when gbx_host_set_devices(n > 1) is in force: the key-space slices would spread
+ * over devices naturally, but that is not built. */
+int gbx_kmer_count_host(const gbx_kmer_params *p, int64_t n_reads, const uint8_t *enc, int64_t enc_bytes,
+                        const int64_t *read_off, const int32_t *read_len, gbx_kmer_stats *st, int64_t *hist,
+                        uint64_t *sel_kmer, uint32_t *sel_count, int64_t sel_cap);
+/* Device path: every pointer is device memory, the work is queued on `stream` and nothing is synchronised.  *d_stats,
+ * d_hist and the selection are written on the device (nothing past sel_cap).  The workspace (gbx_kmer_workspace_bytes)
+ * holds the units of the reads and the counter table of one slice. */
+size_t gbx_kmer_workspace_bytes(int32_t k, int64_t n_reads, int32_t n_hist);
+int gbx_kmer_count_device(const gbx_kmer_params *p, int64_t n_reads, const uint8_t *d_enc, const int64_t *d_read_off,
+                          const int32_t *d_read_len, gbx_kmer_stats *d_stats, int64_t *d_hist, uint64_t *d_sel_kmer,
+                          uint32_t *d_sel_count, int64_t sel_cap, void *d_work, size_t work_bytes, void *stream);
 
 #ifdef __cplusplus
 }

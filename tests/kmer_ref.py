@@ -1,0 +1,34 @@
+"""Restatement of kmer-cnt's count (include/gbx.h, gbx_kmer_*) in numpy: the k-mers at positions 0 .. len - k - 1 of every
+read, each as min(code, revcomp(code)) with the first base most significant, counted by np.unique."""
+import numpy as np
+
+
+def canonical_codes(reads, k):
+    """Canonical codes (uint64) of every counted position of every read of a KmerReadSet, read by read."""
+    out = []
+    for o, n in zip(reads.read_off.tolist(), reads.read_len.tolist()):
+        npos = n - k
+        if npos <= 0:
+            continue
+        b = reads.enc[o:o + n].astype(np.uint64)
+        fwd = np.zeros(npos, dtype=np.uint64)
+        rev = np.zeros(npos, dtype=np.uint64)
+        for j in range(k):
+            fwd = (fwd << np.uint64(2)) | b[j:j + npos]
+            rev = rev | ((np.uint64(3) - b[j:j + npos]) << np.uint64(2 * j))
+        out.append(np.minimum(fwd, rev))
+    return np.concatenate(out) if out else np.zeros(0, dtype=np.uint64)
+
+
+def count_ref(reads, k, n_hist=256, min_freq=0, max_freq=0):
+    """-> (stats dict, hist, kmers, counts) as genomicsbench_amd.kmer.count_host returns them (the whole selection)."""
+    codes = canonical_codes(reads, k)
+    kmers, counts = np.unique(codes, return_counts=True)
+    hist = np.zeros(n_hist, dtype=np.int64)
+    if n_hist:
+        np.add.at(hist, np.minimum(counts, n_hist - 1), 1)
+        hist[0] = 0
+    sel = np.zeros(len(counts), dtype=bool) if min_freq == 0 else (counts >= min_freq) & ((max_freq == 0) | (counts <= max_freq))
+    stats = dict(n_positions=int(codes.size), n_distinct=int(kmers.size), n_ge16=int((counts >= 16).sum()),
+                 max_count=int(counts.max()) if counts.size else 0, n_selected=int(sel.sum()))
+    return stats, hist, kmers[sel].astype(np.uint64), counts[sel].astype(np.uint32)
