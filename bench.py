@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark: bsw 'large' GCUPS on N MI355X (BASELINE.json), one JSON line on rank 0.
 
-    python bench.py [--gpus N --steps K --warmup W]     # bsw large = the headline; chain, phmm and poa 'large' follow
-                                                        # under "kernels" in the same JSON line
-    python bench.py --kernel bsw|chain|phmm|poa         # one kernel only, same JSON shape
+    python bench.py [--gpus N --steps K --warmup W]     # bsw large = the headline; chain, phmm, poa, abea and fmi 'large'
+                                                        # follow under "kernels" in the same JSON line
+    python bench.py --full                              # + the oracle checks, host entries, drivers end to end, CPU baselines
+                                                        # and poa's BASELINE config 4 legs (work of their own, after the steps)
+    python bench.py --kernel bsw|chain|phmm|poa|abea|fmi  # one kernel only, same JSON shape
     python bench.py --mode local                        # every rank generates its own shard (no scatter / gather)
     python bench.py --dump-outputs DIR                  # + what the last timed step computed, as DIR/<kernel>_<name>.npy
 
@@ -14,8 +16,8 @@ the job shards over ranks with no data-path collective ("weak": the dataset is N
   mode "scatter" (default): rank 0 owns the whole dataset, cuts it into N cost-balanced contiguous shards
   (genomicsbench_amd/shard.py), ships each shard as one packed message over RCCL point-to-point (scatter_ms),
   every rank runs the timed steps on its HBM-resident shard, rank 0 gathers the fixed-stride outputs (gather_ms)
-  and checks units from every rank's shard against the CPU oracle.  With N = 1 the scatter is the H2D copy and the
-  gather the D2H copy.
+  and, with --full, checks units from every rank's shard against the CPU oracle.  With N = 1 the scatter is the H2D
+  copy and the gather the D2H copy.
 
 value = units of ALL ranks per second of the slowest rank over the K timed steps (barrier + synchronize on both
 sides).  Per-kernel durations come from HIP events recorded around every launch on the launch stream inside the
@@ -1221,10 +1223,12 @@ def run_kernel(kind, args, ctx, steps, warmup, per_gpu_units=None, label=None, d
             rf["achieved_source"] = "line requests (no counter table for these sources): an upper bound on HBM bytes"
     if args.mode != "local":
         line["dataset_gen_s"] = gen_s
-        line["gather_verified"] = work.check_gathered(full, ranges, parts, args.verify_units or
-                                                      {"bsw": 20000, "chain": 40, "phmm": 20, "poa": 8, "abea": 8, "fmi": 20000}[kind])
+        if args.full:
+            line["gather_verified"] = work.check_gathered(full, ranges, parts, args.verify_units or
+                                                          {"bsw": 20000, "chain": 40, "phmm": 20, "poa": 8, "abea": 8, "fmi": 20000}[kind])
         line["shard_units"] = [hi - lo for lo, hi in ranges]
-    if not args.no_cpu and world == 1:                      # the CPU baseline is an N=1 figure (rank 0's host cores)
+    # ---- --full only: the oracle check above and everything below runs work of its own (host entries, drivers, CPU baselines)
+    if args.full and not args.no_cpu and world == 1:        # the CPU baseline is an N=1 figure (rank 0's host cores)
         # the host-buffer entry first, on quiet host cores (the CPU baseline runs OpenMP teams on all of them)
         if hasattr(work, "host_entry"):
             line["host_entry"] = work.host_entry()
@@ -1398,16 +1402,21 @@ def main():
     ap.add_argument("--mode", choices=["scatter", "local"], default="scatter")
     ap.add_argument("--size", type=int, default=0, help="units per GPU (pairs / calls / batches / windows / reads); 0 = 'large'")
     ap.add_argument("--pairs", type=int, default=0, help="alias of --size for bsw")
-    ap.add_argument("--cpu-units", type=int, default=0, help="units in the CPU-baseline sample (0 = kernel default)")
-    ap.add_argument("--verify-units", type=int, default=0, help="units per shard checked against the oracle after the gather")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes work of its own beyond the timed steps: the oracle check of the gathered outputs, the host "
+                         "entries, the drivers end to end, chain's realistic and longest-call legs, the CPU baselines and poa's BASELINE "
+                         "config 4 legs (default: set-up, warm-up, timed steps, --dump-outputs and the line only)")
+    ap.add_argument("--cpu-units", type=int, default=0, help="units in the CPU-baseline sample (0 = kernel default; --full)")
+    ap.add_argument("--verify-units", type=int, default=0,
+                    help="units per shard checked against the oracle after the gather (--full) or per shard of --predict-shards")
     ap.add_argument("--other-steps", type=int, default=5, help="timed steps of chain / phmm / poa / abea in the all-kernel run")
     ap.add_argument("--full-kernels", action="store_true", help="the other kernels' records in full inside the line (default: short form in the line, "
                     "full records on stderr)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no host entries, drivers, extra legs or CPU baselines")
     ap.add_argument("--predict-shards", type=int, default=0,
                     help="N=1 only, with --kernel K: cut ONE 'large' job into this many shards as the N-GPU strong-scaling leg does, run "
                          "every shard alone, print per-shard ms and the predicted N-GPU step (BASELINE config 4 is poa over 8)")
-    ap.add_argument("--no-predict", action="store_true", help="skip poa's config4_predicted leg of the all-kernel run")
+    ap.add_argument("--no-predict", action="store_true", help="skip poa's config4_predicted leg of the all-kernel --full run")
     ap.add_argument("--launch-dry-run", action="store_true",
                     help="print the argv / environment of the ranks `--gpus N` would start, start nothing")
     ap.add_argument("--launch-echo", action="store_true",
@@ -1514,7 +1523,7 @@ def main():
             sub.size, sub.cpu_units = 0, 0                   # --size / --cpu-units speak about the headline kernel
             others[kind] = run_kernel(kind, sub, ctx, min(args.steps, args.other_steps), min(args.warmup, 2), dump=args.dump_outputs)
         # BASELINE config 4 as written: ONE 'large' poa job (6000 windows) sharded over the N GPUs (strong)
-        if world > 1 and args.mode != "local":
+        if args.full and world > 1 and args.mode != "local":
             torch.cuda.empty_cache()
             sub = argparse.Namespace(**vars(args))
             sub.size, sub.cpu_units, sub.no_cpu = 0, 0, True
@@ -1526,7 +1535,7 @@ def main():
                 st["scaling"] = "strong"
                 others["poa"]["config4_strong"] = st
         # ... and at N = 1 its prediction: the eight shards of that cut, each alone on this GPU (the slowest one is the 8-GPU step)
-        if world == 1 and args.mode != "local" and not args.size and not args.no_predict:
+        if args.full and world == 1 and args.mode != "local" and not args.size and not args.no_predict:
             torch.cuda.empty_cache()
             others["poa"]["config4_predicted"] = predict_shards("poa", args, ctx, 8, 2, 1, whole_ms=others["poa"]["ms_per_step"])
         if line is not None:

@@ -6,7 +6,7 @@ out=gpurun_out/${tag}_ab_env.txt; : > $out
 for rep in $(seq $reps); do for v in "$@"; do
   echo "== $k [$v]" | tee -a $out
   if [ "$v" = "-" ]; then v="GBX_NOOP=1"; fi
-  env $v timeout 300 python3 bench.py --kernel $k --steps 3 --warmup 1 --no-cpu 2>/dev/null | python3 -c '
+  env $v timeout 300 python3 bench.py --kernel $k --steps 3 --warmup 1 --full --no-cpu 2>/dev/null | python3 -c '
 import json,sys
 for ln in sys.stdin:
     if ln.startswith("{"):

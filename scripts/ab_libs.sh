@@ -12,7 +12,7 @@ for ln in sys.stdin:
 for rep in $(seq $reps); do
   for lib in "$@"; do
     echo "== $k $lib" | tee -a $out
-    if [ "$lib" = intree ]; then timeout 300 python3 bench.py --kernel $k --steps 3 --warmup 1 --no-cpu 2>/dev/null | line | tee -a $out
-    else GBX_LIB=$PWD/$lib timeout 300 python3 bench.py --kernel $k --steps 3 --warmup 1 --no-cpu 2>/dev/null | line | tee -a $out; fi
+    if [ "$lib" = intree ]; then timeout 300 python3 bench.py --kernel $k --steps 3 --warmup 1 --full --no-cpu 2>/dev/null | line | tee -a $out
+    else GBX_LIB=$PWD/$lib timeout 300 python3 bench.py --kernel $k --steps 3 --warmup 1 --full --no-cpu 2>/dev/null | line | tee -a $out; fi
   done
 done

@@ -9,7 +9,7 @@ for ln in sys.stdin:
 '; }
 for rep in 1 2 3; do
   echo "== poa in-tree" | tee -a $out
-  timeout 300 python3 bench.py --kernel poa --steps 3 --warmup 1 --no-cpu 2>/dev/null | line | tee -a $out
+  timeout 300 python3 bench.py --kernel poa --steps 3 --warmup 1 --full --no-cpu 2>/dev/null | line | tee -a $out
   echo "== poa $other" | tee -a $out
-  GBX_LIB=$PWD/$other timeout 300 python3 bench.py --kernel poa --steps 3 --warmup 1 --no-cpu 2>/dev/null | line | tee -a $out
+  GBX_LIB=$PWD/$other timeout 300 python3 bench.py --kernel poa --steps 3 --warmup 1 --full --no-cpu 2>/dev/null | line | tee -a $out
 done

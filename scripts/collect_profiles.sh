@@ -8,7 +8,7 @@ mkdir -p $out
 timeout 900 python -m pytest tests -m gpu -x -q > $out/${tag}_pytest_gpu.log 2>&1; tail -2 $out/${tag}_pytest_gpu.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $out/${tag}_smoke.log 2>&1; tail -1 $out/${tag}_smoke.log
 for k in bsw chain phmm poa; do
-  timeout 900 python bench.py --kernel $k > $out/${tag}_${k}_bench.log 2>&1
+  timeout 900 python bench.py --kernel $k --full > $out/${tag}_${k}_bench.log 2>&1
   tail -1 $out/${tag}_${k}_bench.log > $out/${tag}_${k}_large_bench.json
   cut -c1-160 $out/${tag}_${k}_large_bench.json
 done

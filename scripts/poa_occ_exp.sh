@@ -7,7 +7,7 @@ for ln in sys.stdin:
     if ln.startswith("{"):
         d=json.loads(ln); print(json.dumps({"ms_per_step": round(d["ms_per_step"],2), "gcups": round(d["value"],1), "verified": (d.get("gather_verified") or "")[-10:], "slots": d["config"].get("slots"), "kernels_ms": {k: round(v,2) for k,v in d["kernels_ms"].items()}}))
 '; }
-run() { echo "== $*" | tee -a $out; env "$@" timeout 400 python3 bench.py --kernel poa --steps 3 --warmup 1 --no-cpu 2>/dev/null | line | tee -a $out; }
+run() { echo "== $*" | tee -a $out; env "$@" timeout 400 python3 bench.py --kernel poa --steps 3 --warmup 1 --full --no-cpu 2>/dev/null | line | tee -a $out; }
 for rep in 1 2; do
 run GBX_POA_OCC=3
 run GBX_POA_NODE_FACTOR=4

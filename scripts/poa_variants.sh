@@ -5,7 +5,7 @@ tag=${1:-r04}
 out=gpurun_out/${tag}_poa_variants.txt; : > $out
 run() {
     echo "== $*" | tee -a $out
-    env "$@" timeout 600 python3 bench.py --kernel poa --steps 3 --warmup 1 --no-cpu 2>/dev/null | python3 -c '
+    env "$@" timeout 600 python3 bench.py --kernel poa --steps 3 --warmup 1 --full --no-cpu 2>/dev/null | python3 -c '
 import json,sys
 for ln in sys.stdin:
     if ln.startswith("{"):

@@ -42,7 +42,9 @@ def main():
     peak = {"vram": 0, "rss": 0, "vram_idle": vram_used()}
     t0 = time.time()
     with open(base + "_bench.json", "w") as fo, open(base + "_stderr.log", "w") as fe:
-        child = subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n)] + sys.argv[3:], env=env, stdout=fo, stderr=fe, cwd=ROOT)
+        # --full: the gather check of every shard and poa's config4_strong leg are what the rehearsal reads
+        child = subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--full"] + sys.argv[3:], env=env, stdout=fo,
+                                 stderr=fe, cwd=ROOT)
         stop = threading.Event()
 
         def poll():
