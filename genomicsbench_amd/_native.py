@@ -149,6 +149,13 @@ def _declare(L):
         L.gbx_kmer_workspace_bytes.restype = sz
         L.gbx_kmer_count_host.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64]
         L.gbx_kmer_count_device.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp, sz, vp]
+    if hasattr(L, "gbx_pileup_layout_host"):
+        L.gbx_pileup_workspace_bytes.argtypes = [vp, i64, i64]
+        L.gbx_pileup_workspace_bytes.restype = sz
+        L.gbx_pileup_layout_host.argtypes = [vp, vp, vp, vp]
+        L.gbx_pileup_count_host.argtypes = [vp, vp, vp, i64, i64, vp, vp, vp]
+        L.gbx_pileup_layout_device.argtypes = [vp, vp, vp, vp, vp, sz, vp]
+        L.gbx_pileup_count_device.argtypes = [vp, vp, vp, i64, i64, vp, vp, vp, vp, sz, vp]
     if hasattr(L, "gbx_chain_host"):
         L.gbx_chain_job_stats.argtypes = [vp, i64, i64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]
         L.gbx_chain_workspace_bytes.argtypes = [i64, i64]

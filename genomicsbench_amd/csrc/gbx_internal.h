@@ -50,7 +50,7 @@ struct Stage {
 //   GBX_GUARD_TRIP(var, kernel, loop, unit) true when the bound is exhausted (constant false in the product build)
 //   GBX_GUARD_CHECK(what)                   in a launch function, after its launches: hipDeviceSynchronize() (the whole device, other
 //                                           callers' streams included: the guard build is diagnostic only and its timings mean nothing), then a record becomes an error
-enum { GBX_GK_BSW = 1, GBX_GK_CHAIN = 2, GBX_GK_PHMM = 3, GBX_GK_POA = 4, GBX_GK_ABEA = 5, GBX_GK_FMI = 6 };
+enum { GBX_GK_BSW = 1, GBX_GK_CHAIN = 2, GBX_GK_PHMM = 3, GBX_GK_POA = 4, GBX_GK_ABEA = 5, GBX_GK_FMI = 6, GBX_GK_PILEUP = 8 };
 #ifdef GBX_LOOP_GUARD
 namespace { __device__ unsigned long long gbx_guard_word; }      // one per translation unit
 __device__ inline bool gbx_guard_report(int kernel, int loop, long long unit)
@@ -195,6 +195,15 @@ size_t kmer_workspace_bytes(int32_t k, int64_t n_reads);
 int kmer_launch(const gbx_kmer_params *p, int64_t n_reads, const uint8_t *d_enc, const int64_t *d_read_off, const int32_t *d_read_len,
                 gbx_kmer_stats *d_stats, int64_t *d_hist, uint64_t *d_sel_kmer, uint32_t *d_sel_count, int64_t sel_cap, void *d_work,
                 size_t work_bytes, hipStream_t s);
+
+// ---- pileup (pileup_kernels.hip)
+size_t pileup_workspace_bytes(int64_t n_reads, int64_t n_cigar, int64_t n_pos);
+int pileup_layout_launch(const gbx_pileup_params *p, const gbx_pileup_reads *d, int64_t *d_pos_col, gbx_pileup_layout_stats *d_stats,
+                         void *d_work, size_t work_bytes, hipStream_t s);
+int pileup_count_launch(const gbx_pileup_params *p, const gbx_pileup_reads *d, const int64_t *d_pos_col, int64_t p0, int64_t p1,
+                        int32_t *d_major, int32_t *d_minor, uint32_t *d_counts, void *d_work, size_t work_bytes, hipStream_t s);
+// after a count launch: the lowest read whose entries it skipped for want of a dtype, or -1 (synchronises s)
+int pileup_read_bad(const gbx_pileup_params *p, const gbx_pileup_reads *d, const void *d_work, int64_t *bad, hipStream_t s);
 
 // ---- phmm (phmm_kernels.hip)
 size_t phmm_workspace_bytes(int64_t n_pairs, int64_t n_reads, int max_hap_len, int64_t stream_syms = -1);

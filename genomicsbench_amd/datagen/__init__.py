@@ -255,3 +255,174 @@ def write_fasta(path, records, wrap=0, fastq=False):
                     f.write(seq[i:i + wrap] + b"\n")
             else:
                 f.write(b">%s\n%s\n" % (name.encode(), seq))
+
+
+# ------------------------------------------------------------------------------------------------------------- pileup
+PILEUP_PRESETS = {
+    # the shape of the reference's S. aureus input (R/README: a ~2.8 Mb genome of ONT reads), scaled to 1.5 Mb at 40x
+    "small": dict(contig_len=1_500_000, coverage=40, mean_len=8000, seed=81),
+    # a scaled-down chr20: 12 Mb at 50x, 12 kb mean reads
+    "large": dict(contig_len=12_000_000, coverage=50, mean_len=12000, seed=82),
+}
+PILEUP_DTYPES = ("r941", "r10")
+
+
+def _homopolymer_runs(ref):
+    """run length of the homopolymer each reference base belongs to"""
+    change = np.flatnonzero(np.diff(ref.astype(np.int16)) != 0) + 1
+    starts = np.concatenate(([0], change))
+    lens = np.diff(np.concatenate((starts, [ref.size])))
+    return np.repeat(lens, lens)
+
+
+def _sim_read(rng, ref, hp, start, span):
+    """One ONT-like read over ref[start:start+span]: substitutions, IUPAC N, deletions and insertions (both three times
+    as likely inside homopolymers; an insertion there repeats the homopolymer's base) -> (cigar [(op, len)], nt16 codes)."""
+    seg, h = ref[start:start + span], hp[start:start + span] > 1
+    boost = np.where(h, 3.0, 1.0)
+    dele = rng.random(span) < 0.02 * boost
+    ins = np.where(rng.random(span) < 0.015 * boost, rng.geometric(0.5, span), 0)
+    ins[-1] = 0
+    dele[0] = dele[-1] = False
+    base = seg.copy()
+    sub = rng.random(span) < 0.03
+    base[sub] = (base[sub] + rng.integers(1, 4, int(sub.sum()))) % 4
+    base[rng.random(span) < 0.001] = 4                          # N
+    slots = 1 + ins
+    first = np.concatenate(([0], np.cumsum(slots)[:-1]))
+    total = int(slots.sum())
+    ops = np.full(total, 1, dtype=np.int8)                      # I
+    ops[first] = np.where(dele, 2, 0)                           # D / M
+    idx = np.repeat(np.arange(span), slots)                     # the reference base each slot follows
+    ins_base = np.where(h[idx], seg[idx], rng.integers(0, 4, total))
+    qb = np.where(ops == 0, base[idx], ins_base)
+    keep = ops != 2
+    codes = np.array([1, 2, 4, 8, 15], dtype=np.uint8)[qb[keep]]
+    change = np.flatnonzero(np.diff(ops) != 0) + 1
+    st = np.concatenate(([0], change))
+    ln = np.diff(np.concatenate((st, [total])))
+    cigar = list(zip(ops[st].tolist(), ln.tolist()))
+    return cigar, codes
+
+
+def _quals(rng, n):
+    """qualities spread over the homopolymer strata 1..5 and a little above"""
+    return np.minimum(1 + rng.geometric(0.35, n), 60).astype(np.uint8)
+
+
+def _pileup_chunk(args):
+    from .. import pileup as P
+    seed, c0, ref, hp, starts, lens, dts = args
+    rng = np.random.default_rng([seed, c0])
+    nt = np.array([1, 2, 4, 8], dtype=np.uint8)
+    filt = (0x4, 0x100, 0x200, 0x400, 0x800)
+    out = []
+    for i in range(starts.size):
+        r = c0 + i
+        span = int(min(lens[i], ref.size - starts[i]))
+        rev = int(rng.random() < 0.5)
+        cigar, codes = _sim_read(rng, ref, hp, int(starts[i]), span)
+        lclip, rclip = (int(rng.integers(1, 200)) if rng.random() < 0.3 else 0), (int(rng.integers(1, 200)) if rng.random() < 0.3 else 0)
+        if lclip:
+            cigar = [(4, lclip)] + cigar
+            codes = np.concatenate((nt[rng.integers(0, 4, lclip)], codes))
+        if rclip:
+            cigar = cigar + [(4, rclip)]
+            codes = np.concatenate((codes, nt[rng.integers(0, 4, rclip)]))
+        if rng.random() < 0.1:
+            cigar = [(5, int(rng.integers(1, 500)))] + cigar
+        if rng.random() < 0.1:
+            cigar = cigar + [(5, int(rng.integers(1, 500)))]
+        qual = np.full(codes.size, 0xFF, dtype=np.uint8) if rng.random() < 0.02 else _quals(rng, codes.size)
+        flag, mapq = 0x10 * rev, int(rng.integers(1, 61))
+        u = rng.random()
+        if u < 0.05:
+            flag |= filt[int(rng.integers(0, len(filt)))]
+        elif u < 0.06:
+            mapq = 0
+        passes = not (flag & P.FILTER_FLAGS) and mapq >= 1
+        dt = dts[int(rng.integers(0, len(dts)))]
+        out.append((int(starts[i]), passes, ("read_%d" % r, 0, int(starts[i]), mapq, flag, cigar, codes, qual, dt)))
+    return out
+
+
+def gen_pileup_reads(contig_len, coverage, seed, mean_len=8000, adversarial=False, n_dtypes=2, missing_dt=0, contig_name="ctg1",
+                     workers=1):
+    """A random contig (with homopolymer runs) and ONT-like reads on it, both strands, soft and hard clips, IUPAC N,
+    reads with missing qualities, filtered reads (every flag of the filter, mapq 0) and a few reads on a second contig,
+    as raw BAM records in coordinate order.  Each read carries DT:Z (one of PILEUP_DTYPES[:n_dtypes]) unless it is one of
+    the first `missing_dt` kept reads.  adversarial adds one read per CIGAR case of the contract.
+    -> (contigs [(name, length)], records [bytes])."""
+    from .. import pileup as P
+    rng = np.random.default_rng(seed)
+    ref = rng.integers(0, 4, contig_len, dtype=np.uint8)
+    for a in rng.integers(0, max(1, contig_len - 12), contig_len // 60):         # homopolymer runs of 3..8
+        ref[a:a + int(rng.integers(3, 9))] = ref[a]
+    hp = _homopolymer_runs(ref)
+    n_reads = max(1, int(contig_len * coverage / mean_len))
+    lens = np.clip(rng.gamma(2.0, mean_len / 2.0, n_reads).astype(np.int64), 200, max(201, contig_len - 2))
+    starts = np.sort(rng.integers(0, np.maximum(1, contig_len - lens)))
+    contigs = [(contig_name, contig_len), ("ctg2", 50000)]
+    dts = PILEUP_DTYPES[:max(1, n_dtypes)]
+    # reads in chunks of 256, each with a generator of its own: the same records whatever the number of workers
+    chunks = [(seed, c, ref, hp, starts[c:c + 256], lens[c:c + 256], dts) for c in range(0, n_reads, 256)]
+    if workers > 1 and len(chunks) > 1:
+        import multiprocessing as mp
+        with mp.get_context("fork").Pool(workers) as pool:
+            parts = pool.map(_pileup_chunk, chunks)
+    else:
+        parts = [_pileup_chunk(c) for c in chunks]
+    recs = []
+    kept = 0
+    for part in parts:
+        for pos, passes, rec_args in part:
+            name, tid, pos_, mapq, flag, cigar, codes, qual, dt = rec_args
+            tags = b"" if (passes and kept < missing_dt) else P.dt_tag(dt)
+            kept += passes
+            recs.append((pos, P.bam_record(name, tid, pos_, mapq, flag, cigar, codes, qual, tags)))
+    nt = np.array([1, 2, 4, 8], dtype=np.uint8)
+    if adversarial:
+        for k, (cigar, pos) in enumerate(_adversarial_cigars(contig_len)):
+            qlen = sum(ln for op, ln in cigar if op in (0, 1, 4, 7, 8))
+            codes = nt[rng.integers(0, 4, qlen)]
+            if k % 3 == 0 and qlen > 2:
+                codes[1] = 15
+            recs.append((pos, P.bam_record("adv_%d" % k, 0, pos, 30, 0x10 * (k & 1), cigar, codes, _quals(rng, qlen),
+                                           P.dt_tag(dts[k % len(dts)]))))
+    recs.sort(key=lambda x: x[0])
+    other = []
+    for r in range(20):                                    # the second contig: never in a pileup of the first
+        pos = int(rng.integers(0, 40000))
+        codes = nt[rng.integers(0, 4, 500)]
+        other.append((pos, P.bam_record("other_%d" % r, 1, pos, 30, 0, [(0, 500)], codes, _quals(rng, 500), P.dt_tag(dts[0]))))
+    other.sort(key=lambda x: x[0])
+    return contigs, [b for _, b in recs] + [b for _, b in other]
+
+
+def _adversarial_cigars(contig_len):
+    """(cigar, pos) of every CIGAR case of the contract, at fixed places near the contig's start"""
+    M, I, D, N, S, H, P, EQ, X = range(9)
+    base = min(1000, max(0, contig_len // 4))
+    cases = [
+        [(M, 10), (I, 3), (D, 2), (M, 10)],                    # I then D
+        [(M, 10), (D, 2), (I, 3), (M, 10)],                    # D then I: the D's last position carries +3
+        [(M, 8), (N, 20), (M, 8)],                             # refskip
+        [(M, 8), (N, 5), (I, 4), (M, 8)],                      # N then I
+        [(EQ, 5), (X, 1), (EQ, 5), (I, 2), (X, 3)],            # = and X
+        [(M, 6), (P, 2), (I, 3), (M, 6)],                      # P then I
+        [(M, 6), (I, 2), (P, 1), (I, 3), (M, 6)],              # I, P, I: the first I decides
+        [(M, 6), (P, 1), (I, 2), (P, 1), (I, 1), (M, 6)],      # P I P I: their sum
+        [(I, 4), (M, 12)],                                     # leading I: never reported
+        [(S, 5), (I, 3), (M, 12)],                             # leading S and I
+        [(H, 7), (S, 2), (M, 12), (I, 5)],                     # trailing I: reported
+        [(M, 12), (I, 2), (S, 4), (H, 3)],                     # trailing I then clips
+        [(M, 9), (D, 1), (D, 2), (M, 9)],                      # D after D: no indel for the first D
+        [(M, 3), (I, 40), (M, 3)],                             # a long insertion
+        [(M, 5), (D, 3), (N, 4), (M, 5)],                      # D then N
+    ]
+    return [(c, base + 7 * k) for k, c in enumerate(cases)]
+
+
+def gen_pileup_preset(name, adversarial=False, workers=1):
+    p = PILEUP_PRESETS[name]
+    return gen_pileup_reads(p["contig_len"], p["coverage"], p["seed"], p["mean_len"], adversarial=adversarial, workers=workers)

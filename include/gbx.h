@@ -1,6 +1,6 @@
 /* gbx.h — C-ABI of libgbx.so: MI355X (gfx950) kernels for GenomicsBench's
  * dynamic-programming hot path (bsw, chain, phmm, poa) and its neighbours
- * (abea, fmi, kmer).
+ * (abea, fmi, kmer, pileup).
  *
  * This is the drop-in boundary.  Every entry point is `extern "C"`, takes
  * plain pointers and sizes, returns an int status (0 = GBX_OK, <0 = error;
@@ -601,6 +601,91 @@ size_t gbx_kmer_workspace_bytes(int32_t k, int64_t n_reads, int32_t n_hist);
 int gbx_kmer_count_device(const gbx_kmer_params *p, int64_t n_reads, const uint8_t *d_enc, const int64_t *d_read_off,
                           const int32_t *d_read_len, gbx_kmer_stats *d_stats, int64_t *d_hist, uint64_t *d_sel_kmer,
                           uint32_t *d_sel_count, int64_t sel_cap, void *d_work, size_t work_bytes, void *stream);
+
+/* ------------------------------------------------------------------ pileup
+ * medaka's pileup feature counts over a region of aligned long reads: calculate_pileup as the pileup benchmark times it
+ * (R/benchmarks/pileup/medaka_counts.c:298-478).  Points marked UPSTREAM rest on htslib's pileup engine.
+ * Reads are given already filtered (the benchmark's read filter, medaka_bamiter.c: no UNMAP / SECONDARY / SUPPLEMENTARY /
+ * QCFAIL / DUP flag, mapq >= 1, on the region's contig), in BAM's own encodings, sorted by pos (non-decreasing, as a
+ * coordinate-sorted BAM holds them):
+ *   pos[r]                      0-based leftmost reference position (BAM pos)
+ *   cigar[cigar_off[r] ..+)     BAM CIGAR words len << 4 | op, op 0..8 = M I D N S H P = X; cigar_off has n_reads + 1 entries
+ *   seq_off[r] .. seq_off[r+1]  read r's bases: l_seq = seq_off[r+1] - seq_off[r], qualities qual[seq_off[r] ..+ l_seq)
+ *                               (0xFF = missing), nt16 codes packed two a byte, first base in the high nibble, from byte
+ *                               seq[seq_boff[r]] (BAM's (l_seq + 1) / 2 bytes)
+ *   rev[r]                      1: reverse strand (BAM flag 0x10);  dtype[r]: the index of the read's DT:Z value among the
+ *                               caller's dtypes, -1 when it has none (may be NULL when num_dtypes == 1)
+ * A read spans [pos, pos + its M D N = X lengths).  Every position p in [start, end) that some read spans has
+ * 1 + max_ins columns (major = p, minor = 0 .. max_ins), max_ins the largest positive indel among p's pileup entries
+ * (refskip entries included); positions no read spans have none.  pos_col[p - start] is the first column of p,
+ * pos_col[end - start] = n_cols.  Entries (UPSTREAM: htslib resolve_cigar2): an M = X position gives a base at its query
+ * position, D a deletion, N a refskip; at the last position of an op the next op gives indel: I +len, D after a non-D op
+ * -len, P then the sum of the I lengths up to the next op that consumes the reference.
+ * Counts: F = 10 * num_dtypes * num_homop uint32 per column, index (dtype * num_homop + stratum) * 10 + b with b in
+ * "acgtACGTdD".  A deletion adds 1 to d (reverse) or D (forward) at stratum 0; a base entry with indel i adds, for
+ * j = 0 .. max(i, 0), base seq[qpos + j] (IUPAC codes other than A C G T: nothing) to column j of the position at stratum
+ * max(0, min(qual[qpos + j], num_homop) - 1) (0 when num_homop == 1); refskip entries add nothing.  The counts are exact
+ * and do not depend on the scheduling, the slicing or the number of devices.
+ * Not modelled: htslib's cap of 8000 reads per start position, Weibull summation (GBX_ERR_UNSUPPORTED). */
+#define GBX_PILEUP_FEATLEN    10
+#define GBX_PILEUP_MAX_DTYPES 64
+#define GBX_PILEUP_MAX_HOMOP  64
+#define GBX_PILEUP_MAX_F      10240   /* 10 * num_dtypes * num_homop */
+typedef struct gbx_pileup_params {
+    int32_t num_dtypes;      /* 1..64 */
+    int32_t num_homop;       /* 1..64 quality strata; num_dtypes * num_homop <= 1024 */
+    int64_t start, end;      /* the region [start, end), 0-based, 0 <= start <= end < 2^31 */
+    int64_t slice_positions; /* host entries: at most this many positions per device slice; 0 = the default, 2^22 (a test
+                                aid: any value >= 1 gives the same results) */
+    int32_t weibull;         /* must be 0: Weibull summation is not built */
+    int32_t pad_;
+} gbx_pileup_params;
+typedef struct gbx_pileup_reads {
+    int64_t n_reads;
+    int64_t seq_bytes;       /* bytes of seq (host entries check every read against it) */
+    const int32_t *pos;
+    const int64_t *cigar_off;
+    const uint32_t *cigar;
+    const int64_t *seq_off;
+    const int64_t *seq_boff;
+    const uint8_t *seq;
+    const uint8_t *qual;
+    const uint8_t *rev;
+    const int8_t *dtype;
+} gbx_pileup_reads;
+typedef struct gbx_pileup_layout_stats {
+    int64_t n_cols;          /* pos_col[end - start] */
+    int64_t n_positions;     /* positions with columns */
+    int64_t max_ins;
+    int64_t max_depth;       /* reads spanning one position, at most */
+    int64_t aligned_bases;   /* M = X positions of the reads inside [start, end) */
+    int64_t bad_read;        /* num_dtypes > 1: the lowest read without a valid dtype that has a non-refskip entry in the
+                                region, else -1 */
+} gbx_pileup_layout_stats;
+
+/* Host-buffer entries.  Every read is checked (ops, l_seq against the query length of its CIGAR, offsets inside their
+ * arrays, pos sorted and below 2^31) before the device is touched.  The region is cut into slices, spread over the devices
+ * of gbx_host_set_devices / GBX_GPUS by their aligned bases.  A slice's device memory is about 40 bytes a position, 8 + 4 F
+ * a column and its reads: the layout's slices hold at most slice_positions positions; the count's, cut from pos_col, also at
+ * most 64 M counters (256 MB) of columns, unless one position alone has more.
+ * layout: pos_col[end - start + 1] and *st; a read without a valid dtype (st->bad_read >= 0) gives GBX_ERR_ARG, with pos_col
+ * and *st filled.
+ * count: the columns of positions [p0, p1) (start <= p0 <= p1 <= end) of the layout pos_col: c = pos_col[p1 - start] -
+ * pos_col[p0 - start] of them, major[c], minor[c] and counts[c * F]; a sub-range bounds the caller's memory. */
+int gbx_pileup_layout_host(const gbx_pileup_params *p, const gbx_pileup_reads *reads, int64_t *pos_col,
+                           gbx_pileup_layout_stats *st);
+int gbx_pileup_count_host(const gbx_pileup_params *p, const gbx_pileup_reads *reads, const int64_t *pos_col, int64_t p0,
+                          int64_t p1, int32_t *major, int32_t *minor, uint32_t *counts);
+/* Device path: `reads` is a host struct whose pointers are device memory; every other pointer is device memory, the work
+ * is queued on `stream` and nothing is synchronised; the whole region is one slice.  count takes the pos_col the layout
+ * wrote; entries of a read without a valid dtype are not counted there (the layout's bad_read reports them).  The
+ * workspace (gbx_pileup_workspace_bytes) serves both. */
+size_t gbx_pileup_workspace_bytes(const gbx_pileup_params *p, int64_t n_reads, int64_t n_cigar);
+int gbx_pileup_layout_device(const gbx_pileup_params *p, const gbx_pileup_reads *reads, int64_t *d_pos_col,
+                             gbx_pileup_layout_stats *d_stats, void *d_work, size_t work_bytes, void *stream);
+int gbx_pileup_count_device(const gbx_pileup_params *p, const gbx_pileup_reads *reads, const int64_t *d_pos_col, int64_t p0,
+                            int64_t p1, int32_t *d_major, int32_t *d_minor, uint32_t *d_counts, void *d_work,
+                            size_t work_bytes, void *stream);
 
 #ifdef __cplusplus
 }
