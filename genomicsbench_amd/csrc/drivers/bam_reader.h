@@ -270,4 +270,48 @@ inline bool region_reads(const File &f, const Region &reg, const std::vector<std
     return true;
 }
 
+// The dbg driver's reads: every record of [beg, end) on `contig` in file order, as htslib's region iterator returns them
+// (UPSTREAM: pos < end and bam_endpos > beg, bam_endpos = pos + reference length, or pos + 1 when unmapped or of length 0),
+// with no flag or mapq filter.  Per record: the BAM name, flag, pos, bam_endpos, CIGAR words, l_seq, packed bases and
+// qualities (pointers into f.data).
+struct Record {
+    const char *name; int l_name;
+    uint16_t flag; int32_t pos; int64_t endpos;
+    const uint8_t *cigar; int n_cigar;
+    const uint8_t *seq, *qual; int64_t l_seq;
+};
+inline bool region_records(const File &f, const Region &reg, std::vector<Record> &out, std::string *err)
+{
+    int tid = -1;
+    for (size_t k = 0; k < f.contigs.size(); ++k) if (f.contigs[k].name == reg.contig) { tid = (int)k; break; }
+    if (tid < 0) { *err = "contig '" + reg.contig + "' is not in the BAM header"; return false; }
+    const std::vector<uint8_t> &d = f.data;
+    char msg[160];
+    for (size_t at = f.first_record; at < d.size();) {
+        if (d.size() - at < 4) { snprintf(msg, sizeof msg, "truncated BAM record at byte %zu", at); *err = msg; return false; }
+        const int64_t bs = rd32(d.data() + at);
+        if (bs < 32 || (size_t)bs > d.size() - at - 4) { snprintf(msg, sizeof msg, "truncated or bad BAM record at byte %zu", at); *err = msg; return false; }
+        const uint8_t *p = d.data() + at + 4;
+        const int32_t rtid = rd32(p), pos = rd32(p + 4);
+        const int l_rn = p[8], n_cig = rd16(p + 12), flag = rd16(p + 14);
+        const int64_t l_seq = rd32(p + 16);
+        if (l_seq < 0 || l_rn < 1 || 32 + l_rn + 4ll * n_cig + (l_seq + 1) / 2 + l_seq > bs) {
+            snprintf(msg, sizeof msg, "bad BAM record at byte %zu", at);
+            *err = msg;
+            return false;
+        }
+        if (rtid == tid && pos >= 0 && pos < reg.end) {
+            const uint8_t *c = p + 32 + l_rn;
+            int64_t rlen = 0;
+            if (!(flag & 0x4))
+                for (int k = 0; k < n_cig; ++k) { const uint32_t w = rdu32(c + 4 * k); if (ref_op((int)(w & 15u))) rlen += w >> 4; }
+            const int64_t e = pos + (rlen > 0 ? rlen : 1);
+            if (e > reg.beg)
+                out.push_back(Record{(const char *)p + 32, l_rn - 1, (uint16_t)flag, pos, e, c, n_cig, c + 4 * n_cig, c + 4 * n_cig + (l_seq + 1) / 2, l_seq});
+        }
+        at += 4 + (size_t)bs;
+    }
+    return true;
+}
+
 }  // namespace bam

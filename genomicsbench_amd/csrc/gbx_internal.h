@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <mutex>
+#include <vector>
 #include "../../include/gbx.h"
 
 namespace gbx {
@@ -50,7 +51,7 @@ struct Stage {
 //   GBX_GUARD_TRIP(var, kernel, loop, unit) true when the bound is exhausted (constant false in the product build)
 //   GBX_GUARD_CHECK(what)                   in a launch function, after its launches: hipDeviceSynchronize() (the whole device, other
 //                                           callers' streams included: the guard build is diagnostic only and its timings mean nothing), then a record becomes an error
-enum { GBX_GK_BSW = 1, GBX_GK_CHAIN = 2, GBX_GK_PHMM = 3, GBX_GK_POA = 4, GBX_GK_ABEA = 5, GBX_GK_FMI = 6, GBX_GK_PILEUP = 8 };
+enum { GBX_GK_BSW = 1, GBX_GK_CHAIN = 2, GBX_GK_PHMM = 3, GBX_GK_POA = 4, GBX_GK_ABEA = 5, GBX_GK_FMI = 6, GBX_GK_PILEUP = 8, GBX_GK_DBG = 9 };
 #ifdef GBX_LOOP_GUARD
 namespace { __device__ unsigned long long gbx_guard_word; }      // one per translation unit
 __device__ inline bool gbx_guard_report(int kernel, int loop, long long unit)
@@ -204,6 +205,35 @@ int pileup_count_launch(const gbx_pileup_params *p, const gbx_pileup_reads *d, c
                         int32_t *d_major, int32_t *d_minor, uint32_t *d_counts, void *d_work, size_t work_bytes, hipStream_t s);
 // after a count launch: the lowest read whose entries it skipped for want of a dtype, or -1 (synchronises s)
 int pileup_read_bad(const gbx_pileup_params *p, const gbx_pileup_reads *d, const void *d_work, int64_t *bad, hipStream_t s);
+
+// ---- dbg (dbg_kernels.hip)
+// The device inputs of a call: reads and window references (device pointers), rcp[r] = the occurrence slots of reads before r
+// (max(0, l_seq - k - 1) each), ref_bytes: where the reads' byte addresses start in the kernels' one address space.
+struct DbgDev {
+    int32_t k, min_qual;
+    int64_t ref_bytes;
+    const uint8_t *ref, *seq, *qual;
+    const int64_t *seq_off, *rcp;
+    const uint16_t *flag;
+};
+// One window of a batch (dbg_plan): C occurrence slots from cand0 in the batch, nref_c of them the reference's; its tables at
+// base in the batch region, nc node slots and ec edge slots (powers of two); win its index in the call's outputs.
+struct DbgWinPlan {
+    int64_t cand0, C, nref_c, base, nc, ec, read_lo, read_hi, ref_off, ref_pos, win;
+};
+// gbx_dbg_graph_*: where the nodes and edges of the call's windows go (nodes == nullptr: stats only); src values are moved
+// by ref_shift / seq_shift (a shard's rebased arrays back to the caller's).
+struct DbgGraphOut {
+    gbx_dbg_node *nodes = nullptr;
+    gbx_dbg_edge *edges = nullptr;
+    const int64_t *node_off = nullptr, *edge_off = nullptr;
+    int64_t ref_shift = 0, seq_shift = 0;
+};
+size_t dbg_window_bytes(int64_t C);
+int dbg_plan(int64_t k, int64_t w0, int64_t w1, const int64_t *ref_off, const int64_t *ref_pos, const int64_t *read_lo, const int64_t *read_hi,
+             const int64_t *rcp, size_t table_bytes, std::vector<DbgWinPlan> &plan, std::vector<int64_t> &batches);
+int dbg_launch(const DbgDev &a, const std::vector<DbgWinPlan> &plan, const std::vector<int64_t> &batches, DbgWinPlan *d_plan, int *d_err,
+               char *d_region, gbx_dbg_stats *d_stats, const DbgGraphOut &g, hipStream_t s);
 
 // ---- phmm (phmm_kernels.hip)
 size_t phmm_workspace_bytes(int64_t n_pairs, int64_t n_reads, int max_hap_len, int64_t stream_syms = -1);

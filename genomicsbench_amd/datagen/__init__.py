@@ -426,3 +426,130 @@ def _adversarial_cigars(contig_len):
 def gen_pileup_preset(name, adversarial=False, workers=1):
     p = PILEUP_PRESETS[name]
     return gen_pileup_reads(p["contig_len"], p["coverage"], p["seed"], p["mean_len"], adversarial=adversarial, workers=workers)
+
+
+# ---------------------------------------------------------------------------------------------------------- dbg
+# contig lengths: 'small' is for the GPU tests (the plain-Python restatement checks every window of it); 'large' gives about
+# 0.75e9 edge occurrences inserted (1.01e9 slots, 16 000 windows) for scripts/time_dbg.py
+DBG_PRESETS = {
+    "small": dict(contig_len=20000, coverage=30, seed=91),
+    "large": dict(contig_len=12000000, coverage=40, seed=92),
+}
+_ASCII_NT16 = {c: i for i, c in enumerate("=ACMGRSVTWYHKDBN")}
+
+
+def _dbg_contig(rng, n, adversarial):
+    """ACGT with homopolymers and tandem repeats; adversarial: lowercase and N runs, and one k-mer followed by six different
+    bytes (a node with more than 4 successors in the reference alone)"""
+    ref = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, n)].copy()
+    for _ in range(max(1, n // 4000)):
+        at = int(rng.integers(0, max(1, n - 200)))
+        if rng.random() < 0.5:
+            ref[at:at + int(rng.integers(8, 40))] = ref[at]                                       # homopolymer
+        else:
+            unit = ref[at:at + int(rng.integers(2, 7))].copy()
+            reps = int(rng.integers(6, 20))
+            run = np.tile(unit, reps)[:max(0, min(len(unit) * reps, n - at))]
+            ref[at:at + run.size] = run                                                            # tandem repeat
+    if adversarial:
+        for _ in range(max(1, n // 5000)):
+            at = int(rng.integers(0, max(1, n - 300)))
+            ref[at:at + int(rng.integers(20, 200))] += 32                                         # lowercase run (ACGT -> acgt)
+            at = int(rng.integers(0, max(1, n - 100)))
+            ref[at:at + int(rng.integers(1, 30))] = ord("N")
+        at = n // 2                                                                # a homopolymer and a tandem repeat long
+        ref[at:at + 30] = ord("A")                                                 # enough for self-loops and cycles at k = 15
+        ref[at + 60:at + 60 + 48] = np.frombuffer(b"CAG" * 16, dtype=np.uint8)
+        key = b"GATTACAGATTACAG"
+        at = n // 3
+        for j, nxt in enumerate(b"ACGTaR"):
+            s = at + 40 * j
+            if s + 16 < n:
+                ref[s:s + 15] = np.frombuffer(key, dtype=np.uint8)
+                ref[s + 15] = nxt
+    return ref
+
+
+def _dbg_donor(rng, ref):
+    """the sampled haplotype: SNPs (1 in 1000) and short indels (1 in 5000), with a map donor index -> reference position"""
+    n = ref.size
+    snp = rng.random(n) < 0.001
+    alt = ref.copy()
+    alt[snp] = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, int(snp.sum()))]
+    ev = np.flatnonzero(rng.random(n) < 0.0002)
+    pieces, pmap, last = [], [], 0
+    for e in ev:
+        pieces.append(alt[last:e]); pmap.append(np.arange(last, e))
+        if rng.random() < 0.5:
+            ins = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, int(rng.integers(1, 6)))]
+            pieces.append(ins); pmap.append(np.full(ins.size, e))
+            last = e
+        else:
+            last = min(n, e + int(rng.integers(1, 6)))
+    pieces.append(alt[last:]); pmap.append(np.arange(last, n))
+    return np.concatenate(pieces), np.concatenate(pmap)
+
+
+def gen_dbg_reads(contig_len, coverage, seed, read_len=150, adversarial=False, contig_name="ctg1", deep=2000):
+    """Illumina-like reads of at most read_len bases at `coverage` over a contig with SNPs and indels ->
+    (contigs [(name, length)], BAM records in coordinate order (pileup.bam_record), the contig's FASTA bytes).
+    adversarial=True adds: lowercase and N runs in the reference, IUPAC and '=' bases in reads, homopolymers and tandem
+    repeats, a k-mer with six successors, qualities around 20, QC-fail records, unmapped records with a position, leading
+    soft clips at the contig start (the uint32 wrap), reads shorter than k + 2, a stretch of windows with no reads and one
+    window of `deep` extra reads (the capacity path)."""
+    from ..pileup import bam_record
+    rng = np.random.default_rng(seed)
+    ref = _dbg_contig(rng, contig_len, adversarial)
+    donor, dmap = _dbg_donor(rng, np.where(ref >= 97, ref - 32, ref).astype(np.uint8))
+    n_reads = int(contig_len * coverage / read_len)
+    starts = np.sort(rng.integers(0, max(1, donor.size - read_len), n_reads))
+    if adversarial:
+        gap0, gap1 = int(contig_len * 0.6), int(contig_len * 0.6) + 4000          # no reads start or end in here
+        starts = starts[(dmap[np.minimum(starts + read_len, donor.size - 1)] < gap0) | (dmap[starts] >= gap1)]
+        extra = np.full(deep, donor.size // 5)
+        starts = np.sort(np.concatenate((starts, extra, [0, 2, 4])))
+    enc = np.zeros(256, dtype=np.uint8)
+    for c, v in _ASCII_NT16.items():
+        enc[ord(c)] = v
+        enc[ord(c.lower())] = v
+    recs = []
+    for i, st in enumerate(starts.tolist()):
+        ln = read_len
+        if adversarial and rng.random() < 0.03:
+            ln = int(rng.integers(1, 18))                                         # shorter than k + 2
+        seg = donor[st:st + ln].copy()
+        ln = seg.size
+        if ln == 0:
+            continue
+        err = rng.random(ln) < 0.004
+        seg[err] = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, int(err.sum()))]
+        codes = enc[seg]
+        if adversarial:
+            iu = rng.random(ln) < 0.003
+            codes[iu] = rng.choice(np.array([0, 3, 5, 6, 7, 9, 10, 11, 12, 13, 14, 15], dtype=np.uint8), int(iu.sum()))
+        if adversarial and rng.random() < 0.5:
+            q = np.clip(rng.normal(23, 2, ln), 2, 41).astype(np.uint8)              # around min_qual
+        else:
+            q = np.clip(rng.normal(36, 3, ln) - np.linspace(0, 8, ln), 2, 41).astype(np.uint8)
+            q[rng.random(ln) < 0.02] = 8
+        pos = int(dmap[st])
+        cigar = [(0, ln)]
+        flag = 0x10 if rng.random() < 0.5 else 0
+        if adversarial:
+            u = rng.random()
+            if u < 0.02:
+                flag |= 0x200                                                      # QC fail
+            elif u < 0.04:
+                flag |= 0x4                                                        # unmapped, placed
+                cigar = []
+            if pos < 40 and ln > 12 and (pos < 8 or rng.random() < 0.7):
+                cigar = [(4, 10), (0, ln - 10)]                                    # leading clip at the contig start: pos - 10 wraps
+        recs.append((pos, bam_record("r%d" % i, 0, pos, 60, flag, cigar, codes, q)))
+    recs.sort(key=lambda x: x[0])
+    fasta = b">" + contig_name.encode() + b"\n" + b"\n".join(ref[i:i + 60].tobytes() for i in range(0, ref.size, 60)) + b"\n"
+    return [(contig_name, contig_len)], [r for _, r in recs], fasta
+
+
+def gen_dbg_preset(name, adversarial=False):
+    p = DBG_PRESETS[name]
+    return gen_dbg_reads(p["contig_len"], p["coverage"], p["seed"], adversarial=adversarial)

@@ -1,6 +1,6 @@
 /* gbx.h — C-ABI of libgbx.so: MI355X (gfx950) kernels for GenomicsBench's
  * dynamic-programming hot path (bsw, chain, phmm, poa) and its neighbours
- * (abea, fmi, kmer, pileup).
+ * (abea, fmi, kmer, pileup, dbg).
  *
  * This is the drop-in boundary.  Every entry point is `extern "C"`, takes
  * plain pointers and sizes, returns an int status (0 = GBX_OK, <0 = error;
@@ -686,6 +686,109 @@ int gbx_pileup_layout_device(const gbx_pileup_params *p, const gbx_pileup_reads 
 int gbx_pileup_count_device(const gbx_pileup_params *p, const gbx_pileup_reads *reads, const int64_t *d_pos_col, int64_t p0,
                             int64_t p1, int32_t *d_major, int32_t *d_minor, uint32_t *d_counts, void *d_work,
                             size_t work_bytes, void *stream);
+
+/* --------------------------------------------------------------------- dbg
+ * Platypus's de Bruijn graph assembly of a BAM region as the dbg benchmark times it: one graph per assembly window, built
+ * and destroyed (R/benchmarks/dbg/debruijn.cpp:1565-1589; cycle detection there is commented out).  Points marked UPSTREAM
+ * rest on htslib (the region iterator, bam_endpos, faidx) and are not confirmed by anything in the tree.
+ * Reads (gbx_dbg_reads), in the order the region iterator returns them (file order, no filter):
+ *   seq[seq_off[r] ..+ l_seq]    ASCII bases (BAM nt16 through "=ACMGRSVTWYHKDBN"), qual the raw qualities, flag the BAM flag
+ *   pos[r]                       BAM pos minus the length of a leading S op, as uint32 (wraps below 0)
+ *   end[r]                       bam_endpos (UPSTREAM: pos + reference length, or pos + 1 when unmapped or of length 0)
+ * Windows (gbx_dbg_windows): for a = beg, beg + shift, ... while a < end, shift = max(100, min(1000, region_size / 2)):
+ *   assem [a, min(a + region_size, end)), ref [max(0, a - region_size), assem_end + region_size) clamped to the contig by the
+ *   caller's FASTA fetch (UPSTREAM: faidx), bytes as stored.  Its reads: lo = bisect_left(pos, max(1, a - longest)) then lo
+ *   advances while end[lo] <= a, hi = bisect_left(pos, assem_end), reads [lo, min(hi, n)), every comparison unsigned (uint32),
+ *   longest = max over reads of (int32)(end - pos) and 0; lo > hi is the reference's fatal error.
+ * The graph of a window (k, min_qual): edge occurrences, in this order,
+ *   the reference's i = 0 .. ref_len - k - 2: k-mer i -> k-mer i + 1, weight 1, colour REF (1), positions ref_pos + i (+ 1);
+ *   then every read of the window without flag 0x200, i = 0 .. l_seq - k - 2: its k + 1 bases [i, i + k], skipped when one
+ *   of them is 'N' or their minimum quality is below min_qual; else weight = that minimum, colour READ (2), position -1.
+ * Each occurrence touches its start node, then its end node (identity: the k bytes, case-sensitive); a new node takes the
+ * occurrence's colour, position and weight, an existing one gets colours |= and weight +=.  The edge: the start node's edge
+ * to that end node grows by the weight, or is appended when the node has fewer than 4, or is dropped.  So a node's weight
+ * is the sum over its touches, its position comes from its first touch, the nodes are in first-touch order, and an edge
+ * is kept iff it is among the first 4 distinct successors of its start node by first appearance (its weight: all of its
+ * occurrences).  The graph is exact and does not depend on scheduling or device count.
+ * Digest: FNV-1a 64 (offset basis 0xcbf29ce484222325, prime 0x100000001b3) over every node in first-touch order:
+ *   its k bytes, colours (1 byte), position (int32 LE), weight (int64 LE), n_edges (1 byte), then for each kept edge in
+ *   order of first appearance the end node's index in first-touch order (int32 LE) and the edge weight (int64 LE). */
+#define GBX_DBG_MIN_K    3
+#define GBX_DBG_MAX_K    64
+#define GBX_DBG_REF      1
+#define GBX_DBG_READ     2
+typedef struct gbx_dbg_params {
+    int32_t k;               /* 3..64; 15 in the benchmark */
+    int32_t min_qual;        /* 0..255; 20 */
+    int32_t region_size;     /* >= 1; 1500 */
+    int32_t pad_;
+} gbx_dbg_params;
+void gbx_dbg_default_params(gbx_dbg_params *p);
+typedef struct gbx_dbg_reads {
+    int64_t n_reads;
+    int64_t seq_bytes;       /* bytes of seq and qual */
+    const int64_t *seq_off;  /* n_reads + 1, non-decreasing, seq_off[n_reads] <= seq_bytes */
+    const uint8_t *seq;
+    const uint8_t *qual;
+    const uint16_t *flag;
+    const uint32_t *pos;     /* gbx_dbg_windows only (may be NULL elsewhere) */
+    const uint32_t *end;     /* gbx_dbg_windows only */
+} gbx_dbg_reads;
+typedef struct gbx_dbg_wins {
+    int64_t n_win;
+    int64_t ref_bytes;       /* bytes of ref */
+    const int64_t *ref_off;  /* n_win + 1: window w's reference is ref[ref_off[w] .. ref_off[w + 1]) */
+    const uint8_t *ref;
+    const int64_t *ref_pos;  /* the reference position of its first byte (refStart) */
+    const int64_t *read_lo;  /* its reads [read_lo, read_hi) */
+    const int64_t *read_hi;
+} gbx_dbg_wins;
+typedef struct gbx_dbg_stats {
+    int64_t n_nodes;
+    int64_t n_edges;         /* kept */
+    int64_t n_dropped;       /* distinct successors past the 4th */
+    int64_t n_occ;           /* edge occurrences inserted */
+    int64_t weight_sum;      /* their weights */
+    int64_t n_ref, n_read, n_both;   /* nodes by colours: REF only, READ only, both */
+    uint64_t digest;
+} gbx_dbg_stats;
+typedef struct gbx_dbg_node {
+    int64_t weight;
+    int64_t src;             /* where its first touch read it: >= 0 a byte offset in ref, < 0: -1 - a byte offset in seq */
+    int64_t first_edge;      /* its edges are edges[first_edge ..+ n_edges] (indices into the call's edge array) */
+    int32_t position;
+    uint8_t colours;
+    uint8_t n_edges;
+    uint8_t pad_[2];
+} gbx_dbg_node;
+typedef struct gbx_dbg_edge {
+    int64_t weight;
+    int32_t end;             /* the end node's index in its window's first-touch order */
+    int32_t pad_;
+} gbx_dbg_edge;
+
+/* Host only (no device): the windows of [beg, end) (0 <= beg, end < 2^31) and their read ranges.  n_win receives their
+ * number; with cap >= it, assem_start / assem_end / ref_start / ref_end / read_lo / read_hi[0 .. n_win) are filled (any
+ * may be NULL).  lo > hi: GBX_ERR_ARG, *n_win = the failing window + 1 and its raw lo / hi written when cap allows. */
+int gbx_dbg_windows(const gbx_dbg_params *p, const gbx_dbg_reads *reads, int64_t beg, int64_t end, int64_t cap, int64_t *n_win,
+                    int64_t *assem_start, int64_t *assem_end, int64_t *ref_start, int64_t *ref_end, int64_t *read_lo, int64_t *read_hi);
+/* The benchmark step: every window's graph, stats[n_win].  Reads and windows are checked before the device is touched;
+ * windows are spread over the devices of gbx_host_set_devices / GBX_GPUS by their occurrences. */
+int gbx_dbg_build_host(const gbx_dbg_params *p, const gbx_dbg_reads *reads, const gbx_dbg_wins *wins, gbx_dbg_stats *stats);
+/* The graphs of windows [w0, w1): node_off / edge_off[w1 - w0 + 1] place window w0 + j's nodes at nodes[node_off[j] ..)
+ * and its kept edges at edges[edge_off[j] ..) (prefix sums of the stats' n_nodes and n_edges; the range bounds memory). */
+int gbx_dbg_graph_host(const gbx_dbg_params *p, const gbx_dbg_reads *reads, const gbx_dbg_wins *wins, int64_t w0, int64_t w1,
+                       const int64_t *node_off, const int64_t *edge_off, gbx_dbg_node *nodes, gbx_dbg_edge *edges);
+/* Device path: `reads` and `wins` are host structs whose pointers are device memory, as are every other pointer; the call
+ * reads the offsets and ranges back once to plan its passes (it synchronises `stream` there), then queues the rest.
+ * max_window_occ: the most occurrence slots of one window, max over w of max(0, ref_len - k - 1) + sum over its reads of
+ * max(0, l_seq - k - 1); the workspace holds at least that window. */
+size_t gbx_dbg_workspace_bytes(const gbx_dbg_params *p, int64_t n_win, int64_t n_reads, int64_t max_window_occ);
+int gbx_dbg_build_device(const gbx_dbg_params *p, const gbx_dbg_reads *reads, const gbx_dbg_wins *wins, gbx_dbg_stats *d_stats,
+                         void *d_work, size_t work_bytes, void *stream);
+int gbx_dbg_graph_device(const gbx_dbg_params *p, const gbx_dbg_reads *reads, const gbx_dbg_wins *wins, int64_t w0, int64_t w1,
+                         const int64_t *d_node_off, const int64_t *d_edge_off, gbx_dbg_node *d_nodes, gbx_dbg_edge *d_edges,
+                         void *d_work, size_t work_bytes, void *stream);
 
 #ifdef __cplusplus
 }
