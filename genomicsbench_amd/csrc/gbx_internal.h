@@ -263,7 +263,7 @@ constexpr int POA_PIPE_MAXLEN = 512;     // longest sequence of the pipelined DP
 size_t poa_slot_bytes(int ncap, int deg, int lmax, bool long_slot);
 size_t poa_workspace_bytes(const gbx_poa_plan *plan);
 int poa_waves_per_cu(int ncap);
-bool poa_lockstep_wanted(int64_t n_main, int64_t resident);      // the lock-step form (a slot per window) pays for this job
+int poa_cu_count();                   // CUs of the current device (256 when it cannot be asked)
 bool poa_scores_fit_int16(const gbx_poa_params *p, int64_t ncap, int lmax);
 // int32 cells (poa_wide_kernel): windows whose scores may leave the int16 range, or whose graph outgrew what int16 admits
 size_t poa_wide_slot_bytes(int ncap, int deg, int lmax);

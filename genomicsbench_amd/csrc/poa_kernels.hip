@@ -85,9 +85,14 @@ __host__ __device__ inline int poa_cap_stride(int lmax) { const int s = poa_row_
 struct SlotLayout {
     int64_t code, in_cnt, out_cnt, aln_cnt, out_slot, out_slot_x, mark, check, decoder, coder;
     int64_t in_src, in_wt, out_dst, in_src_x, in_wt_x, out_dst_x, aln, r2n, n2r, stack, score, pred, path_node, path_pos, mat, total;
-    int64_t hdr, st8save;      // lock-step form: the window's scalars and the sort's state bytes between launches
+    int64_t hdr, st8save;      // hdr: 64 reserved bytes (they keep every array behind them at the offset it has always had); st8save: the sort's state bytes while the DP's ring has its LDS
     int stk_cap, path_cap;
 };
+
+// wavefronts per SIMD the kernels' instances are compiled for
+constexpr int POA_LONG_WAVES = 1;          // the long-window instance of the one-wavefront kernel
+constexpr int POA_TEAM_WAVES = 3;          // the team kernel (a window per workgroup of four wavefronts): its main-list instance
+constexpr int POA_TEAM_LONG_WAVES = 1;     // ... and its long-window instance (column-block DP for sequences over 512 bases)
 
 __host__ __device__ inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 
@@ -108,33 +113,9 @@ __host__ __device__ inline SlotLayout make_layout(int ncap, int deg, int lmax, b
     L.r2n = take((int64_t)ncap * 4); L.n2r = take((int64_t)ncap * 4);
     L.stack = take((int64_t)L.stk_cap * 4); L.score = take((int64_t)ncap * 4); L.pred = take((int64_t)ncap * 4);
     L.path_node = take((int64_t)L.path_cap * 4); L.path_pos = take((int64_t)L.path_cap * 4);
-#ifndef GBX_POA_DP_WAVES
-#define GBX_POA_DP_WAVES 5          // wavefronts per SIMD of the lock-step DP kernel's default instance
-#endif
-#ifndef GBX_POA_SERIAL_WAVES
-#define GBX_POA_SERIAL_WAVES 3      // ... and the serial-phase kernel (its LDS admits twelve windows per CU)
-#endif
-#ifndef GBX_POA_LONG_WAVES
-#define GBX_POA_LONG_WAVES 1        // the long-window instance: wavefronts per SIMD it is compiled for,
-#endif
-#ifndef GBX_POA_LONG_RING
-#define GBX_POA_LONG_RING 1         // ... whether its pipelined DP (sequences up to 512 columns) uses the row ring,
-#endif
-#ifndef GBX_POA_LONG_INC
-#define GBX_POA_LONG_INC 1          // ... and whether its topological sort is the incremental one
-#endif
-#ifndef GBX_POA_TEAM_WAVES
-#define GBX_POA_TEAM_WAVES 3        // the team kernel (a window per workgroup of four wavefronts): wavefronts per SIMD of the main-list instance
-#endif
-#ifndef GBX_POA_TEAM_LONG_WAVES
-#define GBX_POA_TEAM_LONG_WAVES 1   // ... and of the long-window instance (column-block DP for sequences over 512 bases)
-#endif
-#ifndef GBX_POA_PLANES
-#define GBX_POA_PLANES 2
-#endif
     // pipelined DP (sequences up to 512 columns): the H plane + one plane of (H-F, H-O) byte pairs.  Only the slots of the
     // second launch (windows that hold a longer sequence: column-block DP) keep spoa's five int16 planes.
-    L.mat = take((int64_t)(ncap + 1) * (long_slot ? poa_cap_stride(lmax) : POA_PIPE_STRIDE) * (long_slot ? 5 : GBX_POA_PLANES) * (int64_t)cell_bytes + 64);
+    L.mat = take((int64_t)(ncap + 1) * (long_slot ? poa_cap_stride(lmax) : POA_PIPE_STRIDE) * (long_slot ? 5 : 2) * (int64_t)cell_bytes + 64);
     L.total = align_up(o, 256);
     return L;
 }
@@ -477,7 +458,7 @@ typedef __attribute__((address_space(3))) v8s lds_v8s;
 typedef __attribute__((address_space(3))) v4u lds_v4u;
 typedef __attribute__((address_space(3))) v2u lds_v2u;
 
-template <int POA_RING_ROWS, bool DESC_DONE = false>        // POA_RING_ROWS 0: no ring; DESC_DONE: the row descriptors are in place (poa_serial_call)
+template <int POA_RING_ROWS>                                // POA_RING_ROWS 0: no ring
 __device__ __attribute__((always_inline)) void poa_dp_pipelined(const PoaGraph &g, const PoaMatrices &M, const PoaArgs &A, const uint8_t *seq, int len,
                                  int &max_i, int &max_j, char *lds_ring = nullptr)
 {
@@ -507,7 +488,7 @@ __device__ __attribute__((always_inline)) void poa_dp_pipelined(const PoaGraph &
     int32_t *d_pred = g.score, *d_info = g.pred;
     const int32_t *d_pred1 = g.path_node, *d_pred2 = g.path_pos;
     int32_t *d_pred3 = g.stack;                                // RING: the 4th predecessor's row (the sort's order buffer is free during the DP)
-    if (!DESC_DONE) {
+    {
         PoaGraph &gm = const_cast<PoaGraph &>(g);
         for (int r = lane; r < n; r += 64) {
             poa_rowdesc_one(gm, r);
@@ -1239,10 +1220,7 @@ __device__ __attribute__((always_inline)) void poa_traceback_wave(PoaGraph &g, c
                     if (np > g.aln_path_cap) { g.err |= POA_ERR_NODES; break; }
                     continue;
                 }
-#ifndef GBX_POA_TB_BLOCK23
-#define GBX_POA_TB_BLOCK23 1          // 0: the block serves first in-edge sources only (round 5), for A/B builds
-#endif
-                if (LD == 1 && GBX_POA_TB_BLOCK23) {
+                if (LD == 1) {
                     const int icf = (d_info >> 8) & 0xff;
                     int took = -1, Lt = 0, ht = 0;
 #pragma unroll
@@ -1291,23 +1269,9 @@ __device__ __attribute__((always_inline)) void poa_traceback_wave(PoaGraph &g, c
             if (LD == 1) { n_p1 = (int)ldesc[ldn + pr]; n_p2 = (int)ldesc[2 * ldn + pr]; }
             if (j != 0) {
                 const int mc = (info & 0xff) == seq[j - 1] ? S.m : S.n;
-                int pfirst = 0;
-#ifndef GBX_POA_TB_BATCH
-#define GBX_POA_TB_BATCH 0            // measured (profiles/r05o_poa_team_tb_ab.txt): 56.8 against 55.3 ms for a lone window - most general steps end at the first predecessor; off
-#endif
-                if (LD == 1 && GBX_POA_TB_BATCH) {
-                    // the diagonal cells of the first four predecessors in ONE round trip: their rows come out of LDS, so the loads
-                    // do not depend on each other (through memory each row took two dependent loads first: the loop below)
-                    const int icc = ic ? ic : 1;
-                    int pis[4], hds[4];
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) { pis[p] = p && p < icc ? pred_row(i - 1, node, p) : p0; hds[p] = PG_AT(M.H, pis[p], j - 1); }
-#pragma unroll
-                    for (int p = 0; p < 4; ++p)
-                        if (!found && p < icc && Hij == hds[p] + mc) { prev_i = pis[p]; prev_j = j - 1; found = true; Hnext = hds[p]; hn_known = true; dn_first = p == 0 && p0 > 0; }
-                    pfirst = 4;
-                }
-                for (int p = pfirst; p < (ic ? ic : 1) && !found; ++p) {
+                // (asking for the diagonal cells of the first four predecessors in one round trip was measured, profiles/r05o_poa_team_tb_ab.txt:
+                // 56.8 against 55.3 ms for a lone window - most general steps end at the first predecessor)
+                for (int p = 0; p < (ic ? ic : 1) && !found; ++p) {
                     const int pi = p ? pred_row(i - 1, node, p) : p0;
                     const int hd = PG_AT(M.H, pi, j - 1);
                     if (Hij == hd + mc) { prev_i = pi; prev_j = j - 1; found = true; Hnext = hd; hn_known = true; dn_first = p == 0 && p0 > 0; }
@@ -2032,8 +1996,8 @@ __device__ __attribute__((always_inline)) inline void poa_bind_lds(PoaTopoLds &T
 // DP grew by a dozen instructions) takes `PoaGraph &` by reference: the graph's pointers then live in scratch memory,
 // lose their address space, and every access of the kernel becomes a FLAT instruction (993 of them, 397 instead of
 // 330 ms, found through SQ_INSTS_LDS dropping to nothing).
-// WAVES / RROWS: wavefronts per SIMD the instance is compiled for and rows of the DP's LDS ring (main launch only): <3, 6> is
-// the default (168 VGPRs with spills, twelve windows per CU), <2, 9> the variant without spills (GBX_POA_OCC=2)
+// WAVES / RROWS: wavefronts per SIMD the instance is compiled for and rows of the DP's LDS ring: <false, 3, 6> is the main launch
+// (168 VGPRs with spills, twelve windows per CU), <true, POA_LONG_WAVES, 6> the long one
 template <bool LONG, int WAVES = 3, int RROWS = POA_RING_DEFAULT>
 __global__ void __launch_bounds__(64, WAVES) poa_kernel(PoaArgs A, SlotLayout L)
 {
@@ -2083,14 +2047,12 @@ __global__ void __launch_bounds__(64, WAVES) poa_kernel(PoaArgs A, SlotLayout L)
                 // The serial phases (one useful lane) are latency chains that lose issue slots to the other wavefronts' DP rows;
                 // the DP is throughput work that does not mind waiting.  Priority 3 for the former: 300.8 -> 294.7 ms.
                 __builtin_amdgcn_s_setprio(0);
-                if (!LONG || len <= POA_PIPE_MAXLEN) poa_dp_pipelined<(LONG && !GBX_POA_LONG_RING) ? 0 : RROWS>(g, M, A, seq, len, mi, mj, lds_raw);
+                if (!LONG || len <= POA_PIPE_MAXLEN) poa_dp_pipelined<RROWS>(g, M, A, seq, len, mi, mj, lds_raw);      // (the long instance too: ring and incremental sort won there as well, profiles/r04l_ab_libs.txt)
                 else poa_dp<8>(g, M, A, seq, len, mi, mj);     // longer sequences run as several column blocks
                 PH_ACC(t_dp)
                 __builtin_amdgcn_s_setprio(3);
-#ifndef GBX_POA_TB_LDS3
-#define GBX_POA_TB_LDS3 1           // (round 5, measured: profiles/r05z_poa_tb_lds3_ab.txt, 200.2 against 201.9 ms) the one-wavefront kernel's traceback with p0 / info / node of every row in the ring's LDS
-#endif
-                const bool ld3 = GBX_POA_TB_LDS3 && T.use && (!LONG || len <= POA_PIPE_MAXLEN) && g.n_nodes * 6 <= 3 * T.cap;      // (the sort's per-node arrays: 3 bytes per node, free until add_alignment restores them)
+                // (round 5, measured: profiles/r05z_poa_tb_lds3_ab.txt, 200.2 against 201.9 ms) the traceback with p0 / info / node of every row in the ring's LDS
+                const bool ld3 = T.use && (!LONG || len <= POA_PIPE_MAXLEN) && g.n_nodes * 6 <= 3 * T.cap;      // (the sort's per-node arrays: 3 bytes per node, free until add_alignment restores them)
                 if (ld3) {
                     typedef __attribute__((address_space(3))) unsigned short lds_u16;
                     lds_u16 *const ldw = (lds_u16 *)((lds_u8 *)lds_raw + POA_LDS_FIXED);
@@ -2116,7 +2078,7 @@ __global__ void __launch_bounds__(64, WAVES) poa_kernel(PoaArgs A, SlotLayout L)
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                 }
-                if (g.err == 0) poa_add_alignment_wave<(!LONG || GBX_POA_LONG_INC)>(g, seq, len, T);
+                if (g.err == 0) poa_add_alignment_wave<true>(g, seq, len, T);
                 if (T.use && s + 1 < s1) {
                     uint8_t *save = (uint8_t *)(slot + L.st8save);
                     for (int i = threadIdx.x & 63; i < g.n_nodes; i += 64) save[i] = T.st8[i];
@@ -2261,10 +2223,7 @@ __global__ void __launch_bounds__(64 * POA_TEAM_NW, WAVES) poa_team_kernel(PoaAr
                 if (piped) poa_dp_team<NW, POA_TEAM_RR, POA_TEAM_K>(g, M, A, seq, len, n_nodes, lds_raw, sy, wave, mi, mj);
                 else poa_dp<8, NW>(g, M, A, seq, len, mi, mj, sy, wave, n_nodes);          // column blocks; the rows shared out like the team DP's
                 // the row descriptors into the ring's LDS for the traceback (the path it writes shares memory with two of them)
-#ifndef GBX_POA_TB_NOLDS
-#define GBX_POA_TB_NOLDS 0            // tuning aid: 1 = the team's traceback reads its descriptors from memory, as the one-wavefront kernel's
-#endif
-                const bool ld = piped && !GBX_POA_TB_NOLDS && n_nodes * 12 <= POA_TEAM_RING_BYTES;
+                const bool ld = piped && n_nodes * 12 <= POA_TEAM_RING_BYTES;
                 if (ld) {
                     typedef __attribute__((address_space(3))) unsigned short lds_u16;
                     lds_u16 *const ldw = (lds_u16 *)(lds_u8 *)lds_raw;
@@ -2324,396 +2283,34 @@ __global__ void __launch_bounds__(64 * POA_TEAM_NW, WAVES) poa_team_kernel(PoaAr
 #endif
 }
 
-
-// ---- the serial phases as ONE out-of-line function (round 5) -----------------------------------------------------------------------
-// poa_kernel and poa_team_kernel above are single functions: every phase is inlined, and the PoaGraph (25 pointers), the output
-// pointers and the sort's LDS arrays are live from a window's first sequence to its consensus - through the DP's row loop too, which
-// needs a dozen of them.  258-332 scalar registers spill; the allocator keeps some of the live-through values in registers and
-// reloads loop constants instead (the scan's matrices, one v_readlane per use): 34 reloads in the row loop.
-// Here the kernel's body is the DP and nothing else.  Traceback, add_alignment with the sort, the row descriptors of the next
-// alignment and the consensus are poa_serial_call: NOT inlined, it binds the graph by itself - from the launch's arguments, which it
-// reads out of the kernel-argument segment (scalar loads through the pointer the kernel passes; the workgroup id comes with the call), and the window's five words of
-// state, which travel as arguments and return value.  One call per sequence; inside it the allocator starts from nothing, and in the
-// kernel body nothing of the graph is live across the row loop.  (A first attempt at out-of-line phases, round 3, passed `PoaGraph &`:
-// the struct went to scratch memory and every access became FLAT.  Nothing is passed by reference here.)
-struct PoaKernArgs { PoaArgs A; SlotLayout L; };
-static_assert(sizeof(PoaKernArgs) % 4 == 0, "copied word by word out of the kernel-argument segment");
-struct PoaWinState { int n_nodes, n_codes, err, n_sorted, flags_ok; };
-constexpr int POA_SF_FIRST = 1, POA_SF_RAN_DP = 2, POA_SF_LAST = 4, POA_SF_LONGSEQ = 8, POA_SF_EMPTY = 16;
-
-__device__ inline int poa_uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ inline int64_t poa_uni64(int64_t v)
-{
-    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v & 0xffffffff)), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32));
-    return (int64_t)(((unsigned long long)hi << 32) | lo);
-}
-
-// WAVES: wavefronts per SIMD of the calling kernel (an instance per caller: the compiler hands the caller's register budget down
-// to a function all of whose callers agree on it).  LONG: the caller's slots have five planes, sequences over 512 bases may come.
-// DESC: also builds the row descriptors of the next alignment (the one-wavefront kernel; the team builds them with all its lanes).
-template <int WAVES, bool LONG, bool INC, bool DESC>
-__device__ __attribute__((noinline)) PoaWinState poa_serial_call(PoaWinState st, int64_t w, int64_t s, int mi, int mj, int flags, unsigned long long kernargs)
-{
-    // arguments arrive in vector registers: everything below must know that they are the same in every lane
-    st.n_nodes = poa_uni(st.n_nodes); st.n_codes = poa_uni(st.n_codes); st.err = poa_uni(st.err);
-    st.n_sorted = poa_uni(st.n_sorted); st.flags_ok = poa_uni(st.flags_ok);
-    w = poa_uni64(w); s = poa_uni64(s); mi = poa_uni(mi); mj = poa_uni(mj); flags = poa_uni(flags);
-    // (a struct cannot be copy-constructed out of the constant address space: its words are loaded and put together again; the
-    // loads are scalar - s_load - and only those of fields that are used survive)
-    typedef const __attribute__((address_space(4))) int kernarg_word_t;
-    // (the kernel hands its kernel-argument pointer down: asked for inside a callee, __builtin_amdgcn_kernarg_segment_ptr() faults on
-    // this toolchain - scripts/kernarg_probe.hip)
-    kernarg_word_t *const kw = (kernarg_word_t *)(unsigned long long)poa_uni64((int64_t)kernargs);
-    PoaKernArgs KK;
-    {
-        int words[sizeof(PoaKernArgs) / 4];
-#pragma unroll
-        for (unsigned k = 0; k < sizeof(PoaKernArgs) / 4; ++k) words[k] = kw[k];
-        __builtin_memcpy(&KK, words, sizeof(PoaKernArgs));
-    }
-    const PoaArgs &A = KK.A;
-    const SlotLayout &L = KK.L;
-    char *slot = A.work + (int64_t)blockIdx.x * A.slot_bytes;
-    PoaGraph g;
-    poa_bind_graph(g, slot, L, A);
-    extern __shared__ __attribute__((aligned(16))) char lds_raw[];
-    PoaTopoLds T;
-    poa_bind_lds(T, lds_raw, A);
-    g.n_nodes = st.n_nodes; g.n_codes = st.n_codes; g.err = st.err; g.n_path = 0; g.path_lo = g.path_hi = -1;
-    T.n_sorted = st.n_sorted; T.flags_ok = st.flags_ok;
-    if (st.n_sorted < 0) { T.use = 0; T.n_sorted = 0; }       // (the window has outgrown the sort's LDS arrays: see poa_add_alignment_wave)
-    const int lane = threadIdx.x & 63;
-    if (flags & POA_SF_FIRST) { poa_graph_reset(g); T.n_sorted = 0; T.flags_ok = 0; T.use = A.lds_marks; }
-    if (!(flags & POA_SF_EMPTY)) {
-        const uint8_t *seq = A.arena + A.seq_off[s];
-        const int len = A.seq_len[s];
-        poa_cell_t *mat = (poa_cell_t *)(slot + L.mat);
-        const bool ran_dp = (flags & POA_SF_RAN_DP) != 0;
-        if (ran_dp) {
-            const bool piped = !LONG || !(flags & POA_SF_LONGSEQ);
-            const int wp = piped ? POA_PIPE_STRIDE : poa_row_stride(len);
-            const int64_t plane = (int64_t)(g.n_nodes + 1) * wp;
-            PoaMatrices M = {mat, mat + plane, mat + 2 * plane, mat + 3 * plane, mat + 4 * plane, wp};
-#ifdef GBX_POA_PHASE_STATS
-            const unsigned long long t0_ = __builtin_readcyclecounter();
-#endif
-            if (piped) poa_traceback_wave(g, M, A.S, seq, len, mi, mj);
-            else if (LONG) { poa_dp<8>(g, M, A, seq, len, mi, mj); poa_traceback(g, M, A.S, seq, mi, mj); }
-#ifdef GBX_POA_PHASE_STATS
-            if (lane == 0) { atomicAdd(A.cells + 2, __builtin_readcyclecounter() - t0_); atomicAdd(A.cells + 13, (unsigned long long)g.n_path); }
-#endif
-        }
-#ifdef GBX_POA_PHASE_STATS
-        const unsigned long long t1_ = __builtin_readcyclecounter();
-#endif
-        if (T.use && ran_dp) {
-            // the DP's row ring has used the sort's LDS: state bytes back from the slot, previous ranks = n2r
-            const uint8_t *save = (const uint8_t *)(slot + L.st8save);
-            for (int i = lane; i < g.n_nodes; i += 64) { T.st8[i] = save[i]; T.old[i] = i < T.n_sorted ? (short)g.n2r[i] : (short)-1; }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
-        if (g.err == 0) poa_add_alignment_wave<INC>(g, seq, len, T);
-        if (T.use && !(flags & POA_SF_LAST)) {
-            uint8_t *save = (uint8_t *)(slot + L.st8save);
-            for (int i = lane; i < g.n_nodes; i += 64) save[i] = T.st8[i];
-        }
-        if (DESC && !(flags & POA_SF_LAST) && g.err == 0) {
-            // the row descriptors of the graph as it now is: what the next alignment's DP and traceback read (the path arrays and the
-            // sort's order buffer, which three of them share, are free again)
-            int32_t *d_pred3 = g.stack;
-            for (int r = lane; r < g.n_nodes; r += 64) {
-                poa_rowdesc_one(g, r);
-                const int node = g.r2n[r];
-                d_pred3[r] = g.in_cnt[node] > 3 ? g.n2r[PG_IN_SRC(g, node, 3)] + 1 : 0;
-            }
-        }
-#ifdef GBX_POA_PHASE_STATS
-        if (lane == 0) atomicAdd(A.cells + 3, __builtin_readcyclecounter() - t1_);
-#endif
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (flags & POA_SF_LAST) {
-#ifdef GBX_POA_PHASE_STATS
-        const unsigned long long t2_ = __builtin_readcyclecounter();
-#endif
-        int clen = 0;
-        if (g.err == 0) clen = poa_consensus(g, A.cons + w * A.cons_stride, (int)A.cons_stride);
-        if (lane == 0) { A.cons_len[w] = clen; A.status[w] = g.err; }
-#ifdef GBX_POA_PHASE_STATS
-        if (lane == 0) atomicAdd(A.cells + 4, __builtin_readcyclecounter() - t2_);
-#endif
-    }
-    PoaWinState out = {g.n_nodes, g.n_codes, g.err, A.lds_marks && !T.use ? -1 : T.n_sorted, T.flags_ok};
-    return out;
-}
-
-// the few graph arrays the DP itself reads (row descriptors; the in-edge lists for a fifth predecessor), bound for the DP alone
-__device__ __attribute__((always_inline)) inline void poa_bind_dp_graph(PoaGraph &g, char *slot, const SlotLayout &L, const PoaArgs &A, bool with_lists)
-{
-    g.ncap = A.ncap; g.deg = A.deg;
-    g.r2n = (int32_t *)(slot + L.r2n); g.n2r = (int32_t *)(slot + L.n2r);
-    g.in_src = (int32_t *)(slot + L.in_src); g.in_src_x = (int32_t *)(slot + L.in_src_x);
-    g.stack = (int32_t *)(slot + L.stack); g.score = (int32_t *)(slot + L.score); g.pred = (int32_t *)(slot + L.pred);
-    g.path_node = (int32_t *)(slot + L.path_node); g.path_pos = (int32_t *)(slot + L.path_pos);
-    if (with_lists) {                                          // (the team builds the descriptors itself: it needs what poa_rowdesc_one reads)
-        g.in_cnt = (uint8_t *)(slot + L.in_cnt); g.out_cnt = (uint8_t *)(slot + L.out_cnt);
-        g.code = (uint8_t *)(slot + L.code); g.decoder = (uint8_t *)(slot + L.decoder);
-    }
-}
-
-// the window kernel (one wavefront per window) with the serial phases out of line
-template <bool LONG, int WAVES = 3, int RROWS = POA_RING_DEFAULT>
-__global__ void __launch_bounds__(64, WAVES) poa_kernel2(PoaKernArgs K)
-{
-    const PoaArgs &A = K.A;
-    char *slot = A.work + (int64_t)blockIdx.x * A.slot_bytes;
-    extern __shared__ __attribute__((aligned(16))) char lds_raw[];
-    const int lane = threadIdx.x & 63;
-    if (LONG && lane == 0) atomicAdd(A.cells + POA_LONG_STARTED, 1ull);
-    unsigned long long cells = 0;
-#ifdef GBX_POA_PHASE_STATS
-    unsigned long long t_dp = 0, n_rows = 0;
-#endif
-    const unsigned nwork = (unsigned)A.cells[A.cnt_idx];
-    for (;;) {
-        unsigned long long wq = 0;
-        if (lane == 0) wq = atomicAdd(A.cells + A.cur_idx, 1ull);
-        const unsigned q32 = (unsigned)__builtin_amdgcn_readfirstlane((int)wq);
-        if (q32 >= nwork) break;
-        const int64_t w = (int64_t)A.wlist[q32];
-        PoaWinState st = {0, 0, 0, 0, 0};
-        const int64_t s0 = A.win_first_seq[w], s1 = A.win_first_seq[w + 1];
-        if (s0 == s1) st = poa_serial_call<WAVES, LONG, true, true>(st, w, s0, -1, -1, POA_SF_FIRST | POA_SF_LAST | POA_SF_EMPTY, (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr());
-        for (int64_t s = s0; s < s1; ++s) {
-            const int len = A.seq_len[s];
-            int mi = -1, mj = -1, flags = (s == s0 ? POA_SF_FIRST : 0) | (s + 1 == s1 ? POA_SF_LAST : 0);
-            if (st.n_nodes != 0 && len != 0 && st.err == 0) {
-                flags |= POA_SF_RAN_DP;
-                cells += (unsigned long long)st.n_nodes * (unsigned long long)len;
-                if (!LONG || len <= POA_PIPE_MAXLEN) {
-                    const uint8_t *seq = A.arena + A.seq_off[s];
-                    poa_cell_t *mat = (poa_cell_t *)(slot + K.L.mat);
-                    const int64_t plane = (int64_t)(st.n_nodes + 1) * POA_PIPE_STRIDE;
-                    PoaMatrices M = {mat, mat + plane, mat + 2 * plane, mat + 3 * plane, mat + 4 * plane, POA_PIPE_STRIDE};
-                    PoaGraph gd;
-                    poa_bind_dp_graph(gd, slot, K.L, A, false);
-                    gd.n_nodes = st.n_nodes;
-#ifdef GBX_POA_PHASE_STATS
-                    const unsigned long long t0_ = __builtin_readcyclecounter();
-#endif
-                    __builtin_amdgcn_s_setprio(0);
-                    poa_dp_pipelined<RROWS, true>(gd, M, A, seq, len, mi, mj, lds_raw);
-                    __builtin_amdgcn_s_setprio(3);
-#ifdef GBX_POA_PHASE_STATS
-                    t_dp += __builtin_readcyclecounter() - t0_; n_rows += (unsigned long long)st.n_nodes;
-#endif
-                } else flags |= POA_SF_LONGSEQ;
-            }
-            st = poa_serial_call<WAVES, LONG, true, true>(st, w, s, mi, mj, flags, (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr());
-            st.n_nodes = poa_uni(st.n_nodes); st.n_codes = poa_uni(st.n_codes); st.err = poa_uni(st.err);
-            st.n_sorted = poa_uni(st.n_sorted); st.flags_ok = poa_uni(st.flags_ok);
-        }
-    }
-    if (lane == 0) atomicAdd(A.cells, cells);
-#ifdef GBX_POA_PHASE_STATS
-    if (lane == 0) { atomicAdd(A.cells + 1, t_dp); atomicAdd(A.cells + 12, n_rows); }
-#endif
-}
-
-// the team kernel with the serial phases out of line
-template <bool LONG, int WAVES>
-__global__ void __launch_bounds__(64 * POA_TEAM_NW, WAVES) poa_team2_kernel(PoaKernArgs K, int sync_off)
-{
-    constexpr int NW = POA_TEAM_NW;
-    const PoaArgs &A = K.A;
-    char *slot = A.work + (int64_t)blockIdx.x * A.slot_bytes;
-    extern __shared__ __attribute__((aligned(16))) char lds_raw[];
-    lds_team *const sy = (lds_team *)((lds_u8 *)lds_raw + sync_off);
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int lane = threadIdx.x & 63;
-    if (LONG && threadIdx.x == 0) atomicAdd(A.cells + POA_LONG_STARTED, 1ull);
-
-    unsigned long long cells = 0;
-    const unsigned nwork = (unsigned)A.cells[A.cnt_idx];
-    for (;;) {
-        if (threadIdx.x == 0) {
-            const unsigned long long wq = atomicAdd(A.cells + A.cur_idx, 1ull);
-            *(volatile lds_i32 *)&sy->widx = (int)(wq < 0x7fffffffull ? wq : 0x7fffffffull);
-        }
-        __syncthreads();
-        const unsigned q32 = (unsigned)__builtin_amdgcn_readfirstlane(*(volatile lds_i32 *)&sy->widx);
-        if (q32 >= nwork) break;
-        const int64_t w = (int64_t)A.wlist[q32];
-        PoaWinState st = {0, 0, 0, 0, 0};
-        int n_nodes = 0, err = 0;
-        const int64_t s0 = A.win_first_seq[w], s1 = A.win_first_seq[w + 1];
-        if (s0 == s1 && wave == 0) st = poa_serial_call<WAVES, LONG, true, false>(st, w, s0, -1, -1, POA_SF_FIRST | POA_SF_LAST | POA_SF_EMPTY, (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr());
-        for (int64_t s = s0; s < s1; ++s) {
-            const int len = A.seq_len[s];
-            int mi = -1, mj = -1, flags = (s == s0 ? POA_SF_FIRST : 0) | (s + 1 == s1 ? POA_SF_LAST : 0);
-            if (n_nodes != 0 && len != 0 && err == 0) {
-                flags |= POA_SF_RAN_DP;
-                const bool piped = !LONG || len <= POA_PIPE_MAXLEN;
-                if (wave == 0) cells += (unsigned long long)n_nodes * (unsigned long long)len;
-                if (piped) {
-                    const uint8_t *seq = A.arena + A.seq_off[s];
-                    poa_cell_t *mat = (poa_cell_t *)(slot + K.L.mat);
-                    const int64_t plane = (int64_t)(n_nodes + 1) * POA_PIPE_STRIDE;
-                    PoaMatrices M = {mat, mat + plane, mat + 2 * plane, mat + 3 * plane, mat + 4 * plane, POA_PIPE_STRIDE};
-                    PoaGraph gd;
-                    poa_bind_dp_graph(gd, slot, K.L, A, true);
-#ifdef GBX_POA_PHASE_STATS
-                    const unsigned long long t0_ = __builtin_readcyclecounter();
-#endif
-                    __builtin_amdgcn_s_setprio(0);
-                    poa_dp_team<NW, POA_TEAM_RR, POA_TEAM_K>(gd, M, A, seq, len, n_nodes, lds_raw, sy, wave, mi, mj);
-                    __builtin_amdgcn_s_setprio(3);
-#ifdef GBX_POA_PHASE_STATS
-                    if (threadIdx.x == 0) { atomicAdd(A.cells + 1, __builtin_readcyclecounter() - t0_); atomicAdd(A.cells + 12, (unsigned long long)n_nodes); }
-#endif
-                } else flags |= POA_SF_LONGSEQ;                  // column blocks: DP and traceback inside the call
-            }
-            if (wave == 0) {
-                st = poa_serial_call<WAVES, LONG, true, false>(st, w, s, mi, mj, flags, (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr());
-                if (lane == 0) { *(volatile lds_i32 *)&sy->n_nodes = st.n_nodes; *(volatile lds_i32 *)&sy->err = st.err; }
-            }
-            __syncthreads();
-            n_nodes = __builtin_amdgcn_readfirstlane(*(volatile lds_i32 *)&sy->n_nodes);
-            err = __builtin_amdgcn_readfirstlane(*(volatile lds_i32 *)&sy->err);
-            if (wave == 0) { st.n_nodes = n_nodes; st.err = err; st.n_codes = poa_uni(st.n_codes); st.n_sorted = poa_uni(st.n_sorted); st.flags_ok = poa_uni(st.flags_ok); }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) atomicAdd(A.cells, cells);
-}
-
-
-// ---- the lock-step form (round 4): every window resident, one launch per phase and sequence index ----------------
-// poa_kernel keeps a window in one wavefront from its first sequence to its consensus: the DP (throughput work: packed
-// arithmetic and row traffic), the traceback (one dependent row fetch per step) and add_alignment / the sort (chains of
-// dependent LDS reads) share one register budget (168 VGPRs, 234 spilled SGPRs) and one occupancy (12 windows per CU),
-// and a CU's issue slots and memory queues are shared by whatever mix of phases its twelve windows happen to be in.
-// With a slot per window (288 GB of HBM: 'large' takes 55 GB) the phases become launches of their own over ALL windows:
-// for sequence index s = 1, 2, ...: poa_phase_kernel<DP> aligns sequence s of every window that has one against its graph,
-// poa_phase_kernel<serial> adds the alignments and re-sorts.  Each kernel holds only what its phase needs (the DP no sort
-// state and no LDS, the serial phases a third of the DP's registers), every wavefront of a launch is in the same phase,
-// and what a window carries from launch to launch - the graph's counters, the alignment's end point and path, the state
-// bytes of the incremental sort - sits in its slot (PoaSlotHdr, st8save; the previous ranks are n2r).  The windows with a
-// sequence over 512 bases keep the window kernel (second launch, side stream), small jobs too.
-// MEASURED (round 4, 6 000 windows, profiles/r04b_poa_variants.txt): 310 ms (traceback with the DP, 5 wavefronts per SIMD),
-// 334 (6 per SIMD: all windows in flight), 327 / 334 (traceback with the serial phases) against 233 ms of the window kernel.
-// The DP launches alone take 5.5 ms x 39: a chip doing nothing but DP rows moves 3.7 TB/s, which is what the window kernel
-// averages WITH its serial phases hidden behind it - the DP is bound by its HBM traffic (8.8 B per cell), not by registers,
-// occupancy or issue slots (300 VALU instructions per row: 45 % of the issue rate), and lock-step only takes away the
-// overlap.  What the measurement pointed to instead is the traffic itself: poa_dp_pipelined's row ring.
-struct PoaSlotHdr { int n_nodes, n_codes, n_path, err, path_lo, path_hi, mi, mj, n_sorted, flags_ok, dp_ran, pad_[5]; };
-static_assert(sizeof(PoaSlotHdr) == 64, "one 64-byte line per window");
-
-// WAVES = wavefronts per SIMD the instance is compiled for (DP alone: 87 VGPRs as the compiler likes it = 5, 80 VGPRs with two
-// spilled = 6, i.e. 24 windows per CU: all 6 000 of 'large' in flight at once)
-template <bool DO_DP, bool DO_TB, bool DO_ADD, int WAVES>
-__global__ void __launch_bounds__(64, WAVES) poa_phase_kernel(PoaArgs A, SlotLayout L, int s_idx)
-{
-    const int q = blockIdx.x;                                  // position in the work list = the window's slot
-    const int64_t w = (int64_t)A.wlist[q];
-    const int64_t s0 = A.win_first_seq[w], s1 = A.win_first_seq[w + 1];
-    const int nseq = (int)(s1 - s0);
-    if (s_idx >= nseq && !(DO_ADD && s_idx == 0)) return;      // (a window without sequences still gets its empty consensus)
-    char *slot = A.work + (int64_t)q * A.slot_bytes;
-    PoaSlotHdr *hdr = (PoaSlotHdr *)(slot + L.hdr);
-    PoaGraph g;
-    poa_bind_graph(g, slot, L, A);
-    const int lane = threadIdx.x & 63;
-    if (DO_ADD && s_idx == 0) {
-        poa_graph_reset(g);
-        g.path_lo = g.path_hi = -1;
-        if (nseq == 0) {
-            const int clen = poa_consensus(g, A.cons + w * A.cons_stride, (int)A.cons_stride);
-            if (lane == 0) { A.cons_len[w] = clen; A.status[w] = g.err; }
-            return;
-        }
-    } else {
-        g.n_nodes = hdr->n_nodes; g.n_codes = hdr->n_codes; g.n_path = hdr->n_path; g.err = hdr->err;
-        g.path_lo = hdr->path_lo; g.path_hi = hdr->path_hi;
-    }
-    const uint8_t *seq = A.arena + A.seq_off[s0 + s_idx];
-    const int len = A.seq_len[s0 + s_idx];
-    poa_cell_t *mat = (poa_cell_t *)(slot + L.mat);
-    const int wp = POA_PIPE_STRIDE;
-    const int64_t plane = (int64_t)(g.n_nodes + 1) * wp;
-    const PoaMatrices M = {mat, mat + plane, mat + 2 * plane, mat + 3 * plane, mat + 4 * plane, wp};
-    int mi = -1, mj = -1, dp_ran = 0;
-    if (DO_DP) {
-        g.n_path = 0;
-        if (g.n_nodes != 0 && len != 0 && g.err == 0) {
-            extern __shared__ __attribute__((aligned(16))) char lds_dp[];
-            poa_dp_pipelined<POA_RING_DEFAULT>(g, M, A, seq, len, mi, mj, lds_dp);     // the row ring: this kernel has no other use for LDS
-            dp_ran = 1;
-            if (lane == 0) atomicAdd(A.cells, (unsigned long long)g.n_nodes * (unsigned long long)len);
-        }
-        if (!DO_TB && lane == 0) { hdr->mi = mi; hdr->mj = mj; hdr->dp_ran = dp_ran; hdr->n_path = 0; }
-    } else if (DO_TB) {
-        mi = hdr->mi; mj = hdr->mj; dp_ran = hdr->dp_ran;
-        if (s_idx == 0) dp_ran = 0;
-    }
-    if (DO_TB) {
-        if (dp_ran) poa_traceback_wave(g, M, A.S, seq, len, mi, mj);
-        else g.n_path = 0;
-        if (!DO_ADD && lane == 0) { hdr->n_path = g.n_path; hdr->path_lo = g.path_lo; hdr->path_hi = g.path_hi; hdr->err = g.err; }
-    }
-    if (DO_ADD) {
-        extern __shared__ __attribute__((aligned(16))) char lds_raw[];
-        PoaTopoLds T;
-        poa_bind_lds(T, lds_raw, A);
-        uint8_t *const save = (uint8_t *)(slot + L.st8save);
-        if (s_idx != 0) {
-            T.n_sorted = hdr->n_sorted; T.flags_ok = hdr->flags_ok;
-            if (T.n_sorted < 0) { T.use = 0; T.n_sorted = 0; }       // (the window has outgrown the sort's LDS arrays)
-            if (T.use) {
-                // the sort's state as the previous launch left it: state bytes from the slot, previous ranks = n2r
-                for (int i = lane; i < g.n_nodes; i += 64) { T.st8[i] = save[i]; T.old[i] = i < T.n_sorted ? (short)g.n2r[i] : (short)-1; }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            }
-        }
-        if (g.err == 0) poa_add_alignment_wave<true>(g, seq, len, T);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (s_idx == nseq - 1) {
-            int clen = 0;
-            if (g.err == 0) clen = poa_consensus(g, A.cons + w * A.cons_stride, (int)A.cons_stride);
-            if (lane == 0) { A.cons_len[w] = clen; A.status[w] = g.err; }
-        } else {
-            if (T.use) for (int i = lane; i < g.n_nodes; i += 64) save[i] = T.st8[i];
-            if (lane == 0) {
-                hdr->n_nodes = g.n_nodes; hdr->n_codes = g.n_codes; hdr->n_path = 0; hdr->err = g.err; hdr->path_lo = -1; hdr->path_hi = -1;
-                hdr->n_sorted = A.lds_marks && !T.use ? -1 : T.n_sorted; hdr->flags_ok = T.flags_ok; hdr->dp_ran = 0;
-            }
-        }
-    }
-}
-
 }  // namespace
 
-// wavefronts (= windows in flight) one CU keeps resident for this node capacity: registers and the LDS of
-// the topological sort decide
+// CUs of the current device (256 when it cannot be asked)
+int poa_cu_count()
+{
+    int cus = 256, dev = 0;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    else (void)hipGetLastError();
+    return cus;
+}
+
+// windows one CU keeps in flight, at most.  Measured on MI355X (6000 windows, cursor schedule): 8 per CU 410 ms, 9: 393, 10: 378,
+// 11: 361, 12: 329 - twelve is what 168 VGPRs admit; poa_lds_plan sizes a window's share of the LDS so that twelve fit
+constexpr int POA_WINDOWS_PER_CU = 12;
+
 // LDS of the topological sort per window: state byte + previous rank per node, the block cache, and a DFS stack
-// sized so that as many windows as the registers allow (12 per CU at 168 VGPRs) fit the CU's 160 KB: the stack
+// sized so that as many windows as the registers allow (POA_WINDOWS_PER_CU at 168 VGPRs) fit the CU's 160 KB: the stack
 // takes what is left of a window's share, between 128 and POA_LDS_STACK16 entries (a deeper walk falls back to the
 // global-memory sort).  Returns the bytes, or 0 when the node capacity does not fit LDS at all.
 static size_t poa_lds_plan(int ncap, int *stack_entries, int *lds_ncap)
 {
     if (ncap >= 32768) return 0;
-    int max_waves = 12;
-    if (const char *e = getenv("GBX_POA_MAX_WAVES")) { const int v = atoi(e); if (v >= 8 && v <= 16) max_waves = v; }   // tuning aid
     // measured (node capacity 3364): twelve windows of 12304 B run together (336 ms); at 13024 B the twelfth is
     // resident only some of the time (362-386 ms), so the budget is 12 x 12544 B, not the nominal 160 KB.
     // Round 5: the per-node arrays hold what fits a window's share, not the graph's capacity: a window that outgrows them sorts in
     // global memory from then on (before, a job whose capacity did not fit lost windows per CU - or the LDS sort altogether - for all
     // its windows).
-    const size_t share = ((size_t)12 * 12544 / (size_t)max_waves) & ~(size_t)31;
+    const size_t share = ((size_t)12 * 12544 / (size_t)POA_WINDOWS_PER_CU) & ~(size_t)31;
     int fit = (int)((share - POA_LDS_FIXED) / 3) & ~15;
     const int ncp = (ncap + 15) & ~15;
     if (fit > ncp) fit = ncp;
@@ -2726,26 +2323,19 @@ static size_t poa_lds_plan(int ncap, int *stack_entries, int *lds_ncap)
     return (size_t)3 * (size_t)fit + POA_LDS_FIXED;
 }
 
+// wavefronts (= windows in flight) one CU keeps resident for this node capacity: registers and the LDS of
+// the topological sort decide
 int poa_waves_per_cu(int ncap)
 {
     int lds_stack = 0, lds_ncap = 0;
     const size_t lds_need = poa_lds_plan(ncap, &lds_stack, &lds_ncap);
-    const bool lds_marks = lds_need != 0;
     int q = 0;
-    const char *oe_ = getenv("GBX_POA_OCC");
-    const bool occ4 = oe_ && atoi(oe_) == 4;                 // tuning aid: the 128-VGPR / four-ring-row instance
-    const hipError_t qe = occ4 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, poa_kernel<false, 4, 4>, 64, std::max<size_t>(lds_marks ? lds_need : 0, (size_t)4 * POA_RING_SLOT))
-                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, poa_kernel<false>, 64, std::max<size_t>(lds_marks ? lds_need : 0, (size_t)POA_RING_BYTES));
-    if (qe != hipSuccess || q < 1) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, poa_kernel<false>, 64, std::max<size_t>(lds_need, (size_t)POA_RING_BYTES)) != hipSuccess || q < 1) {
         (void)hipGetLastError();
         q = 8;
     }
-    // measured on MI355X (6000 windows, cursor schedule): 8 per CU 410 ms, 9: 393, 10: 378, 11: 361, 12: 329 - twelve is what
-    // 168 VGPRs admit; poa_lds_plan sizes the LDS stack so that twelve fit
     const int hw = q;
-    int max_waves = 12;
-    if (const char *e = getenv("GBX_POA_MAX_WAVES")) { const int v = atoi(e); if (v >= 8 && v <= 16) max_waves = v; }
-    if (q > max_waves) q = max_waves;
+    if (q > POA_WINDOWS_PER_CU) q = POA_WINDOWS_PER_CU;
     if (const char *e = getenv("GBX_POA_WAVES_PER_CU")) {      // tuning aid: another number of windows in flight (up to what the hardware admits)
         const int v = atoi(e);
         if (v >= 1 && v <= hw) q = v;
@@ -2753,35 +2343,12 @@ int poa_waves_per_cu(int ncap)
     return q;
 }
 
-// The lock-step form needs a slot per window of the main list and pays for ~2 launches per sequence index.  It is built,
-// tested and selectable (GBX_POA_LOCKSTEP=1 when the plan is made and at the launch) but NOT the default: see the measurement
-// at poa_phase_kernel.
-bool poa_lockstep_wanted(int64_t n_main, int64_t resident)
-{
-    if (const char *e = getenv("GBX_POA_LOCKSTEP")) return atoi(e) != 0 && n_main > 0;
-    (void)resident;
-    return false;          // measured (MI355X, 'large'): 310-334 ms against the window kernel's 233 - see the note at poa_phase_kernel
-}
-namespace {
-bool poa_use_lockstep(const gbx_poa_plan *plan, int64_t n_main)
-{
-    if (n_main <= 0 || plan->n_slots < n_main) return false;
-    int cus = 256, dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    else (void)hipGetLastError();
-    return poa_lockstep_wanted(n_main, (int64_t)cus * poa_waves_per_cu(plan->node_cap));
-}
-}  // namespace
-
 // windows of a main list up to which the team kernel takes it: what the chip keeps resident as team workgroups (three per CU at
 // 168 VGPRs; beyond that the workgroups queue and one wavefront per window, twelve per CU, is the better use of the SIMDs)
 static int64_t poa_team_max_windows()
 {
     if (const char *e = getenv("GBX_POA_TEAM_MAX")) return atoll(e);          // tuning aid
-    int cus = 256, dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    else (void)hipGetLastError();
-    return (int64_t)cus * (GBX_POA_TEAM_WAVES + 1);          // (measured: 1 024 windows 85 against 91 ms, 1 500 windows 120 against 96)
+    return (int64_t)poa_cu_count() * (POA_TEAM_WAVES + 1);          // (measured: 1 024 windows 85 against 91 ms, 1 500 windows 120 against 96)
 }
 
 // workspace = main slots | counter block | main work list | long-window list | long slots
@@ -2813,11 +2380,37 @@ int poa_read_cells(const void *d_work, size_t slots_bytes, int64_t *cells, hipSt
     return GBX_OK;
 }
 
-bool poa_scores_fit_int16(const gbx_poa_params *p, int64_t ncap, int lmax)
+// The scores as the kernels take them.  spoa's createAlignmentEngine: g >= e is the LINEAR subtype (one gap cost g:
+// msa_spoa_omp.cpp:170-196 lets -o / -e produce it; poa_graph.h: PoaScore), g <= q or e >= c the affine one (convex with both
+// pieces equal), else convex
+static PoaScore poa_score_of(const gbx_poa_params *p)
 {
     PoaScore S = {p->m, p->n, p->g, p->e, p->q, p->c, 0};
-    if (S.g >= S.e) { S.e = S.q = S.c = S.g; S.linear = 1; }           // the linear subtype (poa_graph.h: PoaScore)
+    if (S.g >= S.e) { S.e = S.q = S.c = S.g; S.linear = 1; }
     else if (S.g <= S.q || S.e >= S.c) { S.q = S.g; S.c = S.e; }
+    return S;
+}
+
+// what the int16 and the int32 launch pass alike; the work area (work, slot_bytes, wlist, the counters' indices) and the sort's LDS plan are the caller's
+static PoaArgs poa_common_args(int64_t n_windows, const int64_t *d_win_first_seq, const int64_t *d_seq_off, const int32_t *d_seq_len, const uint8_t *d_arena,
+                               uint8_t *d_cons, int32_t *d_cons_len, int32_t *d_status, int64_t cons_stride, unsigned long long *d_cells,
+                               int ncap, int deg, int lmax, const PoaScore &S)
+{
+    PoaArgs A;
+    A.n_windows = n_windows; A.win_first_seq = d_win_first_seq; A.seq_off = d_seq_off; A.seq_len = d_seq_len;
+    A.arena = d_arena; A.cons = d_cons; A.cons_len = d_cons_len; A.status = d_status; A.cons_stride = cons_stride;
+    A.cells = d_cells; A.ncap = ncap; A.deg = deg; A.lmax = lmax; A.S = S;
+    const Mat2 T = {S.e, S.g, S.q, S.c};
+    for (int v = 0; v < 2; ++v) {
+        A.Tc[v][0] = mp_pow(T, v == 0 ? 8 : 16);
+        for (int k = 1; k < 4; ++k) A.Tc[v][k] = mp_mul(A.Tc[v][k - 1], A.Tc[v][k - 1]);
+    }
+    return A;
+}
+
+bool poa_scores_fit_int16(const gbx_poa_params *p, int64_t ncap, int lmax)
+{
+    const PoaScore S = poa_score_of(p);
     const int64_t worst = -(int64_t)(S.q < S.g ? -S.q : -S.g) * 2 - (int64_t)(S.c > S.e ? -S.c : -S.e) * (ncap + lmax);
     const int64_t worst_mis = (int64_t)S.n * lmax, hi = (int64_t)S.m * lmax;
     // the pipelined DP keeps H - F and H - O in one byte each (PoaPredIn): H - F <= smax - max(g,q) - g, H - O likewise with q
@@ -2834,27 +2427,15 @@ int poa_launch(const gbx_poa_params *p, const gbx_poa_plan *plan, int64_t n_wind
     if (n_windows == 0) return GBX_OK;
     if (n_windows != plan->n_windows) { set_error("poa: the plan was made for %lld windows, the call has %lld", (long long)plan->n_windows, (long long)n_windows); return GBX_ERR_ARG; }
     const int lmax = plan->max_seq_len, deg = plan->max_seqs_per_window, ncap = plan->node_cap;
-    PoaScore S = {p->m, p->n, p->g, p->e, p->q, p->c, 0};
-    if (S.g > 0 || S.q > 0 || S.e > 0 || S.c > 0) { set_error("poa: gap penalties must be non-positive"); return GBX_ERR_ARG; }
-    // spoa's createAlignmentEngine: g >= e is the LINEAR subtype (one gap cost g: msa_spoa_omp.cpp:170-196 lets -o / -e produce it),
-    // g <= q or e >= c the affine one (convex with both pieces equal), else convex
-    if (S.g >= S.e) { S.e = S.q = S.c = S.g; S.linear = 1; }
-    else if (S.g <= S.q || S.e >= S.c) { S.q = S.g; S.c = S.e; }
+    if (p->g > 0 || p->q > 0 || p->e > 0 || p->c > 0) { set_error("poa: gap penalties must be non-positive"); return GBX_ERR_ARG; }
+    const PoaScore S = poa_score_of(p);
     const PoaWs ws = poa_ws(plan);
     if (work_bytes < ws.total) { set_error("poa: workspace too small"); return GBX_ERR_ARG; }
     if (n_windows >= ((int64_t)1 << 31)) { set_error("poa: more than 2^31 windows in one call"); return GBX_ERR_UNSUPPORTED; }
     char *wb = (char *)d_work;
     unsigned long long *d_cells = (unsigned long long *)(wb + ws.counters);
     GBX_HIP(hipMemsetAsync(d_cells, 0, POA_NCOUNTERS * 8, s));
-    const Mat2 T = {S.e, S.g, S.q, S.c};
-    PoaArgs A;
-    A.n_windows = n_windows; A.win_first_seq = d_win_first_seq; A.seq_off = d_seq_off; A.seq_len = d_seq_len;
-    A.arena = d_arena; A.cons = d_cons; A.cons_len = d_cons_len; A.status = d_status; A.cons_stride = cons_stride;
-    A.cells = d_cells; A.ncap = ncap; A.deg = deg; A.lmax = lmax; A.S = S;
-    for (int v = 0; v < 2; ++v) {
-        A.Tc[v][0] = mp_pow(T, v == 0 ? 8 : 16);
-        for (int k = 1; k < 4; ++k) A.Tc[v][k] = mp_mul(A.Tc[v][k - 1], A.Tc[v][k - 1]);
-    }
+    PoaArgs A = poa_common_args(n_windows, d_win_first_seq, d_seq_off, d_seq_len, d_arena, d_cons, d_cons_len, d_status, cons_stride, d_cells, ncap, deg, lmax, S);
     // int16 cells: every real score must stay above -30000 (poa_graph.h); worst case = one long gap
     if (!poa_scores_fit_int16(p, ncap, lmax)) {
         set_error("poa: scores may leave the int16 range for these capacities (nodes %d, length %d)", ncap, lmax);
@@ -2882,108 +2463,43 @@ int poa_launch(const gbx_poa_params *p, const gbx_poa_plan *plan, int64_t n_wind
     // the team kernel (a window per workgroup of four wavefronts): for the windows of the long launch, and for a main list with
     // fewer windows than the chip keeps team workgroups resident (a job as long as its slowest window: see poa_team_kernel)
     const bool team_on = !(getenv("GBX_POA_TEAM") && atoi(getenv("GBX_POA_TEAM")) == 0);
-    const int serial_form = getenv("GBX_POA_SERIAL_FORM") ? atoi(getenv("GBX_POA_SERIAL_FORM")) : 1;      // 2: poa_kernel2 (serial phases out of line)
-    const int team_form = getenv("GBX_POA_TEAM_FORM") ? atoi(getenv("GBX_POA_TEAM_FORM")) : 1;      // 2: the serial phases out of line (poa_serial_call)
-    const size_t team_ring = std::max<size_t>(A.lds_marks ? lds_need : 0, (size_t)POA_TEAM_RING_BYTES);
+    const size_t team_ring = std::max<size_t>(lds_need, (size_t)POA_TEAM_RING_BYTES);
     const int team_sync_off = (int)((team_ring + 15) & ~(size_t)15);
     const size_t team_lds = (size_t)team_sync_off + sizeof(PoaTeamSync);
     // (the team form of the long launch takes a whole CU per window - 512 VGPRs per wavefront - which a job of many windows would
     // rather give to its main launch: there the long windows, a wavefront each, end well before it anyway: 165 against 215 ms on
     // 'large'; measured with the team form: 81 ms for them, 226-231 for the job)
     const bool team_long = team_on && n_windows - plan->n_long_windows <= 4 * poa_team_max_windows();
-    if (has_long && team_long) {
+    const size_t wave_lds = std::max<size_t>(lds_need, (size_t)POA_RING_BYTES);      // one-wavefront kernel: the sort's arrays and the DP's ring share it
+    if (has_long) {
         const SlotLayout LL = make_layout(ncap, deg, lmax, true);
         PoaArgs B = A;
         B.work = wb + ws.lslots; B.slot_bytes = LL.total; B.wlist = d_llist; B.cnt_idx = POA_CNT_LONG; B.cur_idx = POA_CUR_LONG;
         hipStream_t sl = ss ? ss->side[0] : s;
         Stage st("poa_window_long", sl);
-        if (team_form == 2) {
-            PoaKernArgs KB; KB.A = B; KB.L = LL;
-            hipLaunchKernelGGL((poa_team2_kernel<true, GBX_POA_TEAM_LONG_WAVES>), dim3(plan->long_slots), dim3(64 * POA_TEAM_NW), team_lds, sl, KB, team_sync_off);
-        } else
-        hipLaunchKernelGGL((poa_team_kernel<true, GBX_POA_TEAM_LONG_WAVES>), dim3(plan->long_slots), dim3(64 * POA_TEAM_NW), team_lds, sl, B, LL, team_sync_off);
-    } else if (has_long) {
-        const SlotLayout LL = make_layout(ncap, deg, lmax, true);
-        PoaArgs B = A;
-        B.work = wb + ws.lslots; B.slot_bytes = LL.total; B.wlist = d_llist; B.cnt_idx = POA_CNT_LONG; B.cur_idx = POA_CUR_LONG;
-        hipStream_t sl = ss ? ss->side[0] : s;
-        Stage st("poa_window_long", sl);
-        // (compiled for one wavefront per SIMD: the handful of long windows of a job run a wavefront per CU at most, and with
-        // all 512 VGPRs the instance - column-block DP, ring, both sorts - has no spills; at 168 it spilled 222)
-        if (serial_form == 2) {
-            PoaKernArgs KB; KB.A = B; KB.L = LL;
-            hipLaunchKernelGGL((poa_kernel2<true, GBX_POA_LONG_WAVES>), dim3(plan->long_slots), dim3(64), std::max<size_t>(A.lds_marks ? lds_need : 0, (size_t)POA_RING_BYTES), sl, KB);
-        } else
-        hipLaunchKernelGGL((poa_kernel<true, GBX_POA_LONG_WAVES>), dim3(plan->long_slots), dim3(64), std::max<size_t>(A.lds_marks ? lds_need : 0, (size_t)POA_RING_BYTES), sl, B, LL);
+        if (team_long)
+            hipLaunchKernelGGL((poa_team_kernel<true, POA_TEAM_LONG_WAVES>), dim3(plan->long_slots), dim3(64 * POA_TEAM_NW), team_lds, sl, B, LL, team_sync_off);
+        else
+            // (compiled for one wavefront per SIMD: the handful of long windows of a job run a wavefront per CU at most, and with
+            // all 512 VGPRs the instance - column-block DP, ring, both sorts - has no spills; at 168 it spilled 222)
+            hipLaunchKernelGGL((poa_kernel<true, POA_LONG_WAVES>), dim3(plan->long_slots), dim3(64), wave_lds, sl, B, LL);
     }
-    const int64_t n_main = n_windows - plan->n_long_windows;
-    if (has_main && poa_use_lockstep(plan, n_main)) {
-        // lock-step form: a slot per window, per sequence index one DP (+ traceback) launch and one launch of the serial phases
-        // over all windows of the list (heaviest class first; a window without a sequence s leaves at once)
+    if (has_main) {
         const SlotLayout L = make_layout(ncap, deg, lmax, false);
         A.slot_bytes = L.total;
-        const dim3 grid((unsigned)n_main), tb(64);
-        const size_t lds = A.lds_marks ? lds_need : 0;
-        // tuning aids, read per call: GBX_POA_TB_SERIAL=1 moves the traceback from the DP launch to the serial one,
-        // GBX_POA_DP_OCC=5|6 picks the DP instance
-        const bool tb_with_dp = !(getenv("GBX_POA_TB_SERIAL") && atoi(getenv("GBX_POA_TB_SERIAL")) != 0);
-        const int occ = getenv("GBX_POA_DP_OCC") ? atoi(getenv("GBX_POA_DP_OCC")) : GBX_POA_DP_WAVES;
-        for (int sidx = 0; sidx < plan->max_seqs_per_window; ++sidx) {
-            if (sidx > 0) {
-                Stage st("poa_dp", s);
-                if (tb_with_dp && occ >= 6) hipLaunchKernelGGL((poa_phase_kernel<true, true, false, 6>), grid, tb, (size_t)POA_RING_BYTES, s, A, L, sidx);
-                else if (tb_with_dp) hipLaunchKernelGGL((poa_phase_kernel<true, true, false, 5>), grid, tb, (size_t)POA_RING_BYTES, s, A, L, sidx);
-                else if (occ >= 6) hipLaunchKernelGGL((poa_phase_kernel<true, false, false, 6>), grid, tb, (size_t)POA_RING_BYTES, s, A, L, sidx);
-                else hipLaunchKernelGGL((poa_phase_kernel<true, false, false, 5>), grid, tb, (size_t)POA_RING_BYTES, s, A, L, sidx);
-            }
-            Stage st("poa_serial", s);
-            if (tb_with_dp) hipLaunchKernelGGL((poa_phase_kernel<false, false, true, GBX_POA_SERIAL_WAVES>), grid, tb, lds, s, A, L, sidx);
-            else hipLaunchKernelGGL((poa_phase_kernel<false, true, true, GBX_POA_SERIAL_WAVES>), grid, tb, lds, s, A, L, sidx);
-        }
-    } else if (has_main && team_on && n_main <= poa_team_max_windows()) {
-        const SlotLayout L = make_layout(ncap, deg, lmax, false);
-        A.slot_bytes = L.total;
-        const int grid = (int)std::min<int64_t>(n_main, plan->n_slots);
-        if (has_long && !(getenv("GBX_POA_GATE") && atoi(getenv("GBX_POA_GATE")) == 0)) {
-            int cus = 256, dev = 0;
-            if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-            hipLaunchKernelGGL(poa_gate_kernel, dim3(1), dim3(64), 0, s, (const unsigned long long *)(A.cells + POA_LONG_STARTED),
-                               (unsigned)std::min<int64_t>(plan->long_slots, cus));
-        }
-        Stage st("poa_window_team", s);
-        if (team_form == 2) {
-            PoaKernArgs KA; KA.A = A; KA.L = L;
-            hipLaunchKernelGGL((poa_team2_kernel<false, GBX_POA_TEAM_WAVES>), dim3(grid), dim3(64 * POA_TEAM_NW), team_lds, s, KA, team_sync_off);
-        } else
-        hipLaunchKernelGGL((poa_team_kernel<false, GBX_POA_TEAM_WAVES>), dim3(grid), dim3(64 * POA_TEAM_NW), team_lds, s, A, L, team_sync_off);
-    } else if (has_main) {
-        const SlotLayout L = make_layout(ncap, deg, lmax, false);
-        A.slot_bytes = L.total;
-        // (the long launch was queued first and its wavefronts need their place on the chip: a full main grid would keep them
-        // out until its first wavefronts retire, i.e. turn the long windows into a tail)
+        const int64_t n_main = n_windows - plan->n_long_windows;
+        const bool team_main = team_on && n_main <= poa_team_max_windows();
+        // (one wavefront per window: the long launch was queued first and its wavefronts need their place on the chip: a full main
+        // grid would keep them out until its first wavefronts retire, i.e. turn the long windows into a tail)
         int64_t resident = plan->n_slots;
-        if (has_long && resident > 2 * (int64_t)plan->long_slots) resident -= plan->long_slots;
-        const int grid = (int)std::min<int64_t>(n_windows - plan->n_long_windows, resident);
-        if (has_long && !(getenv("GBX_POA_GATE") && atoi(getenv("GBX_POA_GATE")) == 0)) {
-            int cus = 256, dev = 0;
-            if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        if (!team_main && has_long && resident > 2 * (int64_t)plan->long_slots) resident -= plan->long_slots;
+        const int grid = (int)std::min<int64_t>(n_main, resident);
+        if (has_long && !(getenv("GBX_POA_GATE") && atoi(getenv("GBX_POA_GATE")) == 0))
             hipLaunchKernelGGL(poa_gate_kernel, dim3(1), dim3(64), 0, s, (const unsigned long long *)(A.cells + POA_LONG_STARTED),
-                               (unsigned)std::min<int64_t>(plan->long_slots, cus));
-        }
-        Stage st("poa_window", s);
-        const char *oe = getenv("GBX_POA_OCC");             // tuning aid: 2 = the instance compiled for two wavefronts per SIMD (no spills, nine ring rows)
-        if (oe && atoi(oe) == 4 && serial_form == 2) {      // sixteen windows per CU with the serial phases out of line (128 VGPRs without the spills)
-            PoaKernArgs KA; KA.A = A; KA.L = L;
-            hipLaunchKernelGGL((poa_kernel2<false, 4, 4>), dim3(grid), dim3(64), std::max<size_t>(A.lds_marks ? lds_need : 0, (size_t)4 * POA_RING_SLOT), s, KA);
-        } else if (oe && atoi(oe) == 4)   // with GBX_POA_MAX_WAVES=16: sixteen windows per CU (128 VGPRs, four ring rows; the sort's LDS arrays hold 2 352 nodes)
-            hipLaunchKernelGGL((poa_kernel<false, 4, 4>), dim3(grid), dim3(64), std::max<size_t>(A.lds_marks ? lds_need : 0, (size_t)4 * POA_RING_SLOT), s, A, L);
-        else if (oe && atoi(oe) == 2)
-            hipLaunchKernelGGL((poa_kernel<false, 2, 9>), dim3(grid), dim3(64), std::max<size_t>(A.lds_marks ? lds_need : 0, (size_t)9 * POA_RING_SLOT), s, A, L);
-        else if (serial_form == 2) {
-            PoaKernArgs KA; KA.A = A; KA.L = L;
-            hipLaunchKernelGGL((poa_kernel2<false>), dim3(grid), dim3(64), std::max<size_t>(A.lds_marks ? lds_need : 0, (size_t)POA_RING_BYTES), s, KA);
-        } else
-            hipLaunchKernelGGL((poa_kernel<false>), dim3(grid), dim3(64), std::max<size_t>(A.lds_marks ? lds_need : 0, (size_t)POA_RING_BYTES), s, A, L);
+                               (unsigned)std::min<int64_t>(plan->long_slots, poa_cu_count()));
+        Stage st(team_main ? "poa_window_team" : "poa_window", s);
+        if (team_main) hipLaunchKernelGGL((poa_team_kernel<false, POA_TEAM_WAVES>), dim3(grid), dim3(64 * POA_TEAM_NW), team_lds, s, A, L, team_sync_off);
+        else hipLaunchKernelGGL((poa_kernel<false>), dim3(grid), dim3(64), wave_lds, s, A, L);
     }
     if (ss && (rc = ss->join(s))) return rc;
     GBX_HIP(hipGetLastError());
@@ -3006,24 +2522,14 @@ int poa_launch_wide(const gbx_poa_params *p, int64_t n_windows, const int64_t *d
     if (n_windows == 0) return GBX_OK;
     if (n_slots < 1 || work_bytes < poa_wide_workspace_bytes(ncap, deg, lmax, n_slots)) { set_error("poa: wide workspace too small"); return GBX_ERR_ARG; }
     if (n_windows >= ((int64_t)1 << 31)) { set_error("poa: more than 2^31 windows in one call"); return GBX_ERR_UNSUPPORTED; }
-    PoaScore S = {p->m, p->n, p->g, p->e, p->q, p->c, 0};
-    if (S.g > 0 || S.q > 0 || S.e > 0 || S.c > 0) { set_error("poa: gap penalties must be non-positive"); return GBX_ERR_ARG; }
-    if (S.g >= S.e) { S.e = S.q = S.c = S.g; S.linear = 1; }
-    else if (S.g <= S.q || S.e >= S.c) { S.q = S.g; S.c = S.e; }
+    if (p->g > 0 || p->q > 0 || p->e > 0 || p->c > 0) { set_error("poa: gap penalties must be non-positive"); return GBX_ERR_ARG; }
+    const PoaScore S = poa_score_of(p);
     // int32 cells with -2^29 as -infinity: real scores stay far above it (|score| <= 128 x (nodes + length))
     if (((int64_t)ncap + lmax) * 130 > ((int64_t)1 << 28)) { set_error("poa: window too large even for 32-bit cells (%d nodes, length %d)", ncap, lmax); return GBX_ERR_UNSUPPORTED; }
     char *wb = (char *)d_work;
     unsigned long long *d_cells = (unsigned long long *)wb;
     GBX_HIP(hipMemsetAsync(d_cells, 0, POA_NCOUNTERS * 8, s));
-    const Mat2 T = {S.e, S.g, S.q, S.c};
-    PoaArgs A;
-    A.n_windows = n_windows; A.win_first_seq = d_win_first_seq; A.seq_off = d_seq_off; A.seq_len = d_seq_len;
-    A.arena = d_arena; A.cons = d_cons; A.cons_len = d_cons_len; A.status = d_status; A.cons_stride = cons_stride;
-    A.cells = d_cells; A.ncap = ncap; A.deg = deg; A.lmax = lmax; A.S = S;
-    for (int v = 0; v < 2; ++v) {
-        A.Tc[v][0] = mp_pow(T, v == 0 ? 8 : 16);
-        for (int k = 1; k < 4; ++k) A.Tc[v][k] = mp_mul(A.Tc[v][k - 1], A.Tc[v][k - 1]);
-    }
+    PoaArgs A = poa_common_args(n_windows, d_win_first_seq, d_seq_off, d_seq_len, d_arena, d_cons, d_cons_len, d_status, cons_stride, d_cells, ncap, deg, lmax, S);
     A.lds_marks = 0; A.lds_stack = 0; A.lds_ncap = 0;
     const SlotLayout L = make_layout(ncap, deg, lmax, true, 4);
     A.work = wb + (size_t)POA_NCOUNTERS * 8 + 256; A.slot_bytes = L.total; A.wlist = nullptr; A.cnt_idx = POA_CNT_MAIN; A.cur_idx = POA_CUR_MAIN;

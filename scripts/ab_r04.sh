@@ -13,9 +13,3 @@ for prio in "0,0,0" "-1,-1,0" "-1,0,1" "-1,-1,-1"; do
   GBX_SIDE_PRIO=$prio timeout 300 python3 bench.py --kernel bsw --steps 20 --warmup 5 --no-cpu 2>/dev/null | line | tee -a $out
 done
 done
-for occ in 3 2 3 2; do
-  echo "== poa GBX_POA_OCC=$occ" | tee -a $out
-  GBX_POA_OCC=$occ timeout 300 python3 bench.py --kernel poa --steps 3 --warmup 1 --no-cpu 2>/dev/null | line | tee -a $out
-done
-echo "== poa GBX_POA_OCC=2 GBX_POA_WAVES_PER_CU=8" | tee -a $out
-GBX_POA_OCC=2 GBX_POA_WAVES_PER_CU=8 timeout 300 python3 bench.py --kernel poa --steps 3 --warmup 1 --no-cpu 2>/dev/null | line | tee -a $out

@@ -1,7 +1,7 @@
 // kernarg_probe.hip - development aid (round 5): how a NON-INLINED device function can read the kernel's arguments with scalar loads.
 // -DUSE_KERNARG: the callee reads them through a pointer to the kernel-argument segment that the KERNEL passes down (works);
 // asking for that pointer inside the callee (__builtin_amdgcn_kernarg_segment_ptr() there) faults on this toolchain (ROCm 7.2, gfx950).
-// -DUSE_BID / -DUSE_LDS: blockIdx and dynamic LDS inside the callee (both work).  genomicsbench_amd/csrc/poa_kernels.hip: poa_serial_call.
+// -DUSE_BID / -DUSE_LDS: blockIdx and dynamic LDS inside the callee (both work).  Made for poa's out-of-line serial phases (since removed).
 //   hipcc -O3 --offload-arch=gfx950 -DUSE_KERNARG -DUSE_BID -DUSE_LDS scripts/kernarg_probe.hip -o build_tmp/kernarg_probe && build_tmp/kernarg_probe
 #include <hip/hip_runtime.h>
 #include <cstdio>

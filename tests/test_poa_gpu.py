@@ -213,11 +213,7 @@ def test_windows_with_long_sequences_take_the_second_launch():
 # shared LDS ring).  Jobs of up to four windows per CU take it by themselves, i.e. every small job of this file; here the three
 # ways a job can be split over the kernels are forced and compared: team everywhere (default), no team at all
 # (GBX_POA_TEAM=0: one wavefront per window, the kernel of 'large'), and team for the long windows only (GBX_POA_TEAM_MAX=0).
-# GBX_POA_SERIAL_FORM / GBX_POA_TEAM_FORM = 2: the same kernels with traceback, add_alignment, the sort and the consensus in one
-# out-of-line function (poa_serial_call) - measured no faster (profiles/r05m_poa_serial_out_of_line_ab.txt), kept selectable.
-@pytest.mark.parametrize("env", [{}, {"GBX_POA_TEAM": "0"}, {"GBX_POA_TEAM_MAX": "0"}, {"GBX_POA_TEAM_MAX": "5"},
-                                 {"GBX_POA_TEAM_FORM": "2", "GBX_POA_SERIAL_FORM": "2"}, {"GBX_POA_TEAM": "0", "GBX_POA_SERIAL_FORM": "2"},
-                                 {"GBX_POA_TEAM_MAX": "5", "GBX_POA_TEAM_FORM": "2", "GBX_POA_SERIAL_FORM": "2"}])
+@pytest.mark.parametrize("env", [{}, {"GBX_POA_TEAM": "0"}, {"GBX_POA_TEAM_MAX": "0"}, {"GBX_POA_TEAM_MAX": "5"}])
 def test_team_kernel_equals_the_window_kernel(monkeypatch, env):
     p = make_params()
     rng = np.random.default_rng(5)
@@ -235,14 +231,11 @@ def test_team_kernel_equals_the_window_kernel(monkeypatch, env):
 
 
 @pytest.mark.parametrize("env", [{"GBX_POA_LDS_NCAP": "640"}, {"GBX_POA_LDS_NCAP": "640", "GBX_POA_TEAM": "0"},
-                                 {"GBX_POA_LDS_NCAP": "1200", "GBX_POA_TEAM": "0", "GBX_POA_SERIAL_FORM": "2"},
-                                 {"GBX_POA_LDS_NCAP": "640", "GBX_POA_LOCKSTEP": "1"},
-                                 {"GBX_POA_OCC": "4", "GBX_POA_MAX_WAVES": "16", "GBX_POA_TEAM": "0"}])
+                                 {"GBX_POA_LDS_NCAP": "1200", "GBX_POA_TEAM": "0"}])
 def test_windows_that_outgrow_the_sorts_lds_arrays(monkeypatch, env):
     """The topological sort's per-node LDS arrays hold what fits a window's share of the CU (PoaArgs::lds_ncap), not the graph's
     capacity: a window that may outgrow them switches to the global-memory sort for the rest of its life, the others keep the LDS
-    sort.  GBX_POA_LDS_NCAP (test aid) makes that happen early and in the middle of windows; the last case is the sixteen-windows-
-    per-CU instance, whose arrays hold 2 352 nodes."""
+    sort.  GBX_POA_LDS_NCAP (test aid) makes that happen early and in the middle of windows."""
     p = make_params()
     sets = [gen_poa(24, 4001), random_windows(27, 16, 520, 9),
             PoaWindowSet.from_lists([["ACGTACGTAC"] * 3, ["A", "C", "A"], ["GATTACA", "GATTACA", "GATTTACA", "GATTACA"]])]
@@ -253,30 +246,9 @@ def test_windows_that_outgrow_the_sorts_lds_arrays(monkeypatch, env):
         diff(consensus_host(p, ws), w)
 
 
-# ---- the lock-step form (poa_kernels.hip: a slot per window, one launch per phase and sequence index).  Jobs with more
-# windows than the chip holds wavefronts take it by themselves ('large': tests/test_fullsize_gpu.py); GBX_POA_LOCKSTEP=1
-# forces it on the small jobs here.
-@pytest.mark.parametrize("tb_serial,occ", [("0", "5"), ("0", "6"), ("1", "5"), ("1", "6")])
-def test_lockstep_form_equals_the_window_kernel(monkeypatch, tb_serial, occ):
-    p = make_params()
-    sets = [gen_poa(48, 4001), random_windows(7, 24, 300, 7), random_windows(8, 30, 500, 9),
-            PoaWindowSet.from_lists([["ACGTACGTAC"] * 3, ["A", "C", "A"], ["ACGT"], ["GATTACA", "GATTACA", "GATTTACA", "GATTACA"]])]
-    want = [O.poa_oracle(p, ws, 8) for ws in sets]
-    mono = [consensus_host(p, ws) for ws in sets]
-    monkeypatch.setenv("GBX_POA_LOCKSTEP", "1")
-    monkeypatch.setenv("GBX_POA_TB_SERIAL", tb_serial)
-    monkeypatch.setenv("GBX_POA_DP_OCC", occ)
-    for ws, w, m in zip(sets, want, mono):
-        got = consensus_host(p, ws)
-        diff(got, w)
-        assert got == m
-
-
-def test_lockstep_form_edge_paths(monkeypatch):
-    """Under the lock-step form: the sort's fallback to global memory (state must survive the launches without root flags),
-    windows with long sequences beside it (second launch keeps the window kernel), the node-capacity redo of the host entry,
-    windows of one sequence and ragged sequence counts (a window leaves the launches when it runs out of sequences)."""
-    monkeypatch.setenv("GBX_POA_LOCKSTEP", "1")
+def test_edge_paths_and_a_second_run_on_the_same_workspace():
+    """The sort's fallback to global memory, windows with long sequences beside short ones (second launch), the node-capacity
+    redo of the host entry, windows of one sequence and ragged sequence counts; then the device entry twice on one workspace."""
     p = make_params()
     rng = np.random.default_rng(11)
     base = "".join(rng.choice(list("ACGT"), 300))
@@ -289,11 +261,9 @@ def test_lockstep_form_edge_paths(monkeypatch):
     b2 = "".join(rng.choice(list("ACGT"), 180))
     ws = PoaWindowSet.from_lists([[b2] * 4, deep, [b2[:170], b2, b2[5:]]])
     diff(consensus_host(p, ws), O.poa_oracle(p, ws, 4))
-    for tb in ("0", "1"):
-        monkeypatch.setenv("GBX_POA_TB_SERIAL", tb)
-        ws = random_windows(21, 40, 700, 6)                                     # some windows over 512 columns: second launch
-        diff(consensus_host(p, ws), O.poa_oracle(p, ws, 4))
-    # the device entry re-run on the same workspace (slots hold the previous run's headers and state bytes)
+    ws = random_windows(21, 40, 700, 6)                                         # some windows over 512 columns: second launch
+    diff(consensus_host(p, ws), O.poa_oracle(p, ws, 4))
+    # the device entry re-run on the same workspace (slots hold the previous run's state bytes)
     import torch
     ws = gen_poa(32, 77)
     d = DevicePoaWindowSet(ws, torch.device("cuda:0"))
