@@ -123,6 +123,11 @@ def _declare(L):
         L.gbx_abea_align_host.argtypes = [i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
         L.gbx_abea_align_device.argtypes = [i64] + [vp] * 11 + [i64, i64, vp, vp, vp, sz, vp]
         L.gbx_abea_cells.argtypes = [vp, C.POINTER(C.c_int64), vp]
+    if hasattr(L, "gbx_abea_signal_align_host"):
+        L.gbx_abea_events_device.argtypes = [i32, i64] + [vp] * 9 + [i64, vp, vp]
+        L.gbx_abea_scalings_device.argtypes = [i64] + [vp] * 9
+        L.gbx_abea_events_host.argtypes = [i64] + [vp] * 8 + [i64, vp, vp]
+        L.gbx_abea_signal_align_host.argtypes = [i64] + [vp] * 8 + [i64, vp, vp, vp, i64] + [vp] * 6
     if hasattr(L, "gbx_fmi_smem_host"):
         L.gbx_fmi_default_params.argtypes = [vp, C.c_int32]
         L.gbx_fmi_default_params.restype = None

@@ -258,6 +258,13 @@ int abea_launch(int64_t n_reads, const int64_t *d_seq_off, const int32_t *d_seq_
                 const double *d_lp, int64_t n_kmers_total, int64_t n_bands_total,
                 gbx_abea_pair *d_out, int32_t *d_n_pairs, void *d_work, size_t work_bytes, hipStream_t s);
 
+// ---- abea from raw signal (abea_events_kernels.hip)
+int abea_events_launch(int pass, int64_t n_reads, const int16_t *d_raw, const int64_t *d_raw_off, const float *d_range,
+                       const float *d_digitisation, const float *d_offset, int64_t *d_n_events, int64_t *d_event_off,
+                       gbx_abea_event *d_events, float *d_event_mean, int64_t event_cap, int32_t *d_status, hipStream_t s);
+int abea_scalings_launch(int64_t n_reads, const int64_t *d_seq_off, const int32_t *d_seq_len, const char *d_seq, const int64_t *d_event_off,
+                         const float *d_event_mean, const gbx_abea_model *d_models, float *d_scale, float *d_shift, hipStream_t s);
+
 // ---- poa (poa_kernels.hip)
 constexpr int POA_PIPE_MAXLEN = 512;     // longest sequence of the pipelined DP (two-plane slots)
 size_t poa_slot_bytes(int ncap, int deg, int lmax, bool long_slot);

@@ -39,6 +39,9 @@ def _L():
         _lib.gbx_gen_abea_model.argtypes = [u64, vp, vp]
         _lib.gbx_gen_abea_counts_many.argtypes = [u64, i64, i64, vp, vp]
         _lib.gbx_gen_abea_fill_many.argtypes = [u64, i64, i64] + [vp] * 8
+        _lib.gbx_gen_abea_raw_counts_many.argtypes = [u64, i64, i64] + [vp] * 4
+        _lib.gbx_gen_abea_raw_fill_many.argtypes = [u64, i64, i64] + [vp] * 12
+        _lib.gbx_gen_abea_raw_counts_many.restype = _lib.gbx_gen_abea_raw_fill_many.restype = None
         _lib.gbx_gen_fmi_genome.argtypes = [u64, i64, vp]
         _lib.gbx_gen_fmi_reads.argtypes = [u64, i64, i64, vp, i64, C.c_int32, vp]
         for f in ("abea_model", "abea_counts_many", "abea_fill_many", "fmi_genome", "fmi_reads"):
@@ -159,6 +162,26 @@ def gen_abea(n_reads, seed, first=0):
     scale, shift = np.zeros(n_reads, np.float32), np.zeros(n_reads, np.float32)
     L.gbx_gen_abea_fill_many(seed, first, n_reads, _p(lm), _p(ls), _p(seq_off), _p(event_off), _p(seq), _p(ev), _p(scale), _p(shift))
     return AbeaReadSet(seq_off[:-1].copy(), seq_len, seq, event_off, ev[:int(event_off[-1])], scale, shift, make_model(lm, ls))
+
+
+def gen_abea_raw(n_reads, seed, first=0):
+    """Raw signal for the reads of gen_abea(n_reads, seed, first): an AbeaSignalSet (int16 ADC counts, range / digitisation /
+    offset, the reads' bases and the pore model) with the generator's true scalings in .true_scale / .true_shift.  Some reads
+    fail the exactness predicate of the event kernels and some have no events (datagen.c)."""
+    from ..abea_signal import AbeaSignalSet
+    rs = gen_abea(n_reads, seed, first)
+    L = _L()
+    lm, ls = np.ascontiguousarray(rs.model["level_mean"]), np.ascontiguousarray(rs.model["level_stdv"])
+    ns = np.zeros(n_reads, dtype=np.int64)
+    L.gbx_gen_abea_raw_counts_many(seed, first, n_reads, _p(rs.seq_off), _p(rs.seq_len), _p(rs.seq_arena), _p(ns))
+    raw_off = np.zeros(n_reads + 1, dtype=np.int64); np.cumsum(ns, out=raw_off[1:])
+    raw = np.zeros(int(raw_off[-1]) + 8, dtype=np.int16)
+    rg, dg, of = (np.zeros(n_reads, np.float32) for _ in range(3))
+    L.gbx_gen_abea_raw_fill_many(seed, first, n_reads, _p(rs.seq_off), _p(rs.seq_len), _p(rs.seq_arena), _p(lm), _p(ls), _p(rs.scale),
+                                 _p(rs.shift), _p(raw_off), _p(raw), _p(rg), _p(dg), _p(of))
+    ss = AbeaSignalSet(raw[:int(raw_off[-1])], raw_off, rg, dg, of, rs.seq_off, rs.seq_len, rs.seq_arena, rs.model)
+    ss.true_scale, ss.true_shift = rs.scale, rs.shift
+    return ss
 
 
 def gen_fmi_genome(length, seed):

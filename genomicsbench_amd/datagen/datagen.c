@@ -438,6 +438,78 @@ void gbx_gen_abea_fill_many(uint64_t seed, int64_t first, int64_t n_reads, const
     }
 }
 
+/* Raw signal for the reads of gbx_gen_abea_*: what the sequencer hands to f5c's event_single (f5c.c:1219-1242), int16 ADC
+ * counts plus range / digitisation / offset.  Per k-mer a dwell of 2 + floor(LogNormal(median 5.5, sigma 0.6)) samples, one in forty dwells
+ * longer by floor(Exp(mean 30)) (floor 2, mean near 9, capped at 400; few dwells are too short for the short window to see); sample = scale * level_mean + shift + N(0, level_stdv) pA with
+ * the read's true scalings, quantised: adc = round(pA / (range / digitisation) - offset), range 1467.61, digitisation 8192,
+ * offset an integer in [3, 20].  Edge reads by read index k (so any sub-range regenerates them):
+ *   k % 64 == 13  a stretch of 300 samples at a hundredth of the amplitude (open-pore-like; fails the exactness predicate)
+ *   k % 64 == 29  offset reported as -600, so that pA is centred on zero (negative pA; fails the predicate)
+ *   k % 64 == 47  no events: (k / 64) % 3 = 0: no samples, 1: 5 samples (fewer than two short windows), 2: 500 samples of one value
+ * mode 0: the sample count; mode 1: fill.  A stream of its own per read: gbx_gen_abea_* keep their outputs.
+ */
+static int64_t abea_raw_read(uint64_t seed, int64_t read, int mode, const char *seq, int32_t len, const float *level_mean,
+                             const float *level_stdv, float sc, float sh, int16_t *out, float *range, float *digitisation, float *offset)
+{
+    rng_t r;
+    rng_seed(&r, seed ^ 0x7261772d61626561ULL, (uint64_t)read * 2 + 1);
+    const float rg = 1467.61f, dg = 8192.0f;
+    float of = (float)(3 + (int)rng_below(&r, 18));
+    const int kind = (int)(read % 64);
+    const double gen_of = kind == 29 ? 3.0 : (double)of;      /* the counts are made with this offset ... */
+    if (kind == 29) of = -600.0f;                             /* ... and reported with this one */
+    if (mode == 1) { *range = rg; *digitisation = dg; *offset = of; }
+    if (kind == 47) {
+        const int sub = (int)((read / 64) % 3);
+        const int64_t n = sub == 0 ? 0 : sub == 1 ? 5 : 500;
+        if (mode == 1) for (int64_t j = 0; j < n; ++j) out[j] = sub == 1 ? (int16_t)(500 + 37 * j) : (int16_t)512;
+        return n;
+    }
+    const double unit = (double)(rg / dg);
+    uint32_t rank = 0;
+    int64_t ns = 0;
+    const int64_t quiet = kind == 13 ? 1000 : -1;
+    for (int i = 0; i < len; ++i) {
+        const uint32_t b = seq[i] == 'C' ? 1u : seq[i] == 'G' ? 2u : seq[i] == 'T' ? 3u : 0u;
+        rank = ((rank << 2) | b) & 4095u;
+        if (i < 5) continue;
+        int dwell = 2 + (int)(5.5 * exp(0.6 * rng_norm(&r)));
+        if (rng_below(&r, 40) == 0) dwell += (int)(-30.0 * log(1.0 - rng_unif(&r)));
+        if (dwell > 400) dwell = 400;
+        for (int c = 0; c < dwell; ++c) {
+            const double noise = rng_norm(&r);
+            if (mode == 1) {
+                double pa = (double)sc * level_mean[rank] + (double)sh + noise * level_stdv[rank];
+                if (quiet >= 0 && ns >= quiet && ns < quiet + 300) pa *= 0.01;
+                double a = floor(pa / unit - gen_of + 0.5);
+                if (a > 32767.0) a = 32767.0;
+                if (a < -32768.0) a = -32768.0;
+                out[ns] = (int16_t)a;
+            }
+            ++ns;
+        }
+    }
+    return ns;
+}
+
+void gbx_gen_abea_raw_counts_many(uint64_t seed, int64_t first, int64_t n_reads, const int64_t *seq_off, const int32_t *seq_len,
+                                  const char *seq, int64_t *n_samples)
+{
+#pragma omp parallel for schedule(dynamic, 8)
+    for (int64_t k = 0; k < n_reads; ++k)
+        n_samples[k] = abea_raw_read(seed, first + k, 0, seq + seq_off[k], seq_len[k], 0, 0, 0, 0, 0, 0, 0, 0);
+}
+
+void gbx_gen_abea_raw_fill_many(uint64_t seed, int64_t first, int64_t n_reads, const int64_t *seq_off, const int32_t *seq_len, const char *seq,
+                                const float *level_mean, const float *level_stdv, const float *scale, const float *shift,
+                                const int64_t *raw_off, int16_t *raw, float *range, float *digitisation, float *offset)
+{
+#pragma omp parallel for schedule(dynamic, 8)
+    for (int64_t k = 0; k < n_reads; ++k)
+        abea_raw_read(seed, first + k, 1, seq + seq_off[k], seq_len[k], level_mean, level_stdv, scale[k], shift[k], raw + raw_off[k],
+                      range + k, digitisation + k, offset + k);
+}
+
 /* ------------------------------------------------------------------- fmi
  * A synthetic genome and short reads for the FM-index seeding benchmark (the reference runs 151-bp reads of
  * SRR7733443 against the index of a human reference, R/scripts/run-cpu.sh:27,58; neither is in the image).

@@ -427,6 +427,48 @@ int gbx_abea_align_device(int64_t n_reads, const int64_t *d_seq_off, const int32
 /* DP cells filled by the last gbx_abea_align_device call on this workspace (the reference's `fills`, align.c:280,401). */
 int gbx_abea_cells(const void *d_work, int64_t *cells, void *stream);
 
+/* abea from raw signal: what f5c runs per read before align() (event_single, f5c.c:1219-1242): ADC counts -> pA
+ * (f5c.c:1227-1231), scrappie's event detection (detect_events, events.c:292-549, the DNA defaults: windows 3 / 6,
+ * thresholds 1.4 / 9.0, peak height 0.2; getevents() discards the result of its MAD trimming, so detection runs over
+ * all samples) and estimate_scalings_using_mom (align.c:49-97).  Bit for bit the reference's order of operations.
+ * Read r: samples raw[raw_off[r] .. raw_off[r+1]) of one int16 arena, pA = ((float)adc + offset[r]) * (range[r] /
+ * digitisation[r]).  Output: n_events[r] records at events + event_off[r] (event_off[n_reads] = their total) and the
+ * compact means beside them - the layout gbx_abea_align_device reads.
+ * The one deviation: the reference is undefined for a read in which no peak is found (it reads peaks[-1]; fewer than
+ * 12 samples, no sample, constant signal).  Such a read has n_events = 0 and GBX_ABEA_EV_NONE in its status, scale =
+ * shift = 0, and the chained entry reports n_pairs = 0 for it.  Single device only. */
+#define GBX_ABEA_EV_NONE     1    /* status: no peak found, the read has no events                               */
+#define GBX_ABEA_EV_INORDER  2    /* status: the cumulative sums were taken in index order (the read fails the    */
+                                  /* exactness predicate of DESIGN 3.5), not by the wavefront scan                */
+#define GBX_ABEA_EV_OVERFLOW 4    /* status: the fill pass left the read's events unwritten (past event_cap)      */
+#define GBX_ABEA_EVENTS_COUNT 1   /* pass: n_events, event_off and status from the signal                         */
+#define GBX_ABEA_EVENTS_FILL  2   /* pass: events and means at the event_off of a count pass                      */
+
+/* Device entry.  pass = COUNT: writes d_n_events[n_reads], d_event_off[n_reads + 1], d_status[n_reads] (d_events and
+ * d_event_mean may be NULL).  pass = FILL: reads d_event_off and d_status of a count pass over the same input and writes
+ * the records; a read whose events would end past event_cap is left unwritten and flagged.  COUNT | FILL does both
+ * (the caller then sizes the two arrays by a bound of its own).  Nothing is synchronised. */
+int gbx_abea_events_device(int pass, int64_t n_reads, const int16_t *d_raw, const int64_t *d_raw_off, const float *d_range,
+                           const float *d_digitisation, const float *d_offset, int64_t *d_n_events, int64_t *d_event_off,
+                           gbx_abea_event *d_events, float *d_event_mean, int64_t event_cap, int32_t *d_status, void *stream);
+/* scale[r], shift[r] from the read's event means and the model levels of its k-mers; event_off as above (absolute). */
+int gbx_abea_scalings_device(int64_t n_reads, const int64_t *d_seq_off, const int32_t *d_seq_len, const char *d_seq_arena,
+                             const int64_t *d_event_off, const float *d_event_mean, const gbx_abea_model *d_models,
+                             float *d_scale, float *d_shift, void *stream);
+/* Host-buffer entries.  event_cap = the records `events` has room for; *n_events_total = the number found.  More than
+ * event_cap gives GBX_ERR_ARG with the needed count in *n_events_total and gbx_last_error(); n_events, event_off and
+ * status are valid then, events (and everything behind them) are not. */
+int gbx_abea_events_host(int64_t n_reads, const int16_t *raw, const int64_t *raw_off, const float *range,
+                         const float *digitisation, const float *offset, int64_t *n_events, int64_t *event_off,
+                         gbx_abea_event *events, int64_t event_cap, int64_t *n_events_total, int32_t *status);
+/* raw signal -> events -> scalings -> align on one device.  out holds 2 * event_cap pairs, read r's at out +
+ * 2 * event_off[r] as in gbx_abea_align_host; seq_len >= KMER for every read. */
+int gbx_abea_signal_align_host(int64_t n_reads, const int16_t *raw, const int64_t *raw_off, const float *range,
+                               const float *digitisation, const float *offset, const int64_t *seq_off, const int32_t *seq_len,
+                               const char *seq_arena, int64_t seq_bytes, const gbx_abea_model *models, int64_t *event_off,
+                               gbx_abea_event *events, int64_t event_cap, int64_t *n_events_total, float *scale, float *shift,
+                               int32_t *status, gbx_abea_pair *out, int32_t *n_pairs);
+
 /* --------------------------------------------------------------------- fmi
  * SMEM seeding on the FM-index of reference + reverse complement (second half): the three
  * seeding rounds bwa-mem2 runs per batch of reads and the driver times,
