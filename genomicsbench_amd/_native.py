@@ -128,6 +128,12 @@ def _declare(L):
         L.gbx_abea_scalings_device.argtypes = [i64] + [vp] * 9
         L.gbx_abea_events_host.argtypes = [i64] + [vp] * 8 + [i64, vp, vp]
         L.gbx_abea_signal_align_host.argtypes = [i64] + [vp] * 8 + [i64, vp, vp, vp, i64] + [vp] * 6
+    if hasattr(L, "gbx_abea_meth_score_host"):
+        L.gbx_abea_meth_plan_host.argtypes = [i64, vp, i64, i64] + [vp] * 4 + [i64] + [vp] * 4
+        L.gbx_abea_meth_score_device.argtypes = [i64] + [vp] * 17
+        L.gbx_abea_meth_score_host.argtypes = [i64, vp, vp, i64, i64] + [vp] * 9
+        L.gbx_abea_meth_cells.argtypes = [i64, vp, vp]
+        L.gbx_abea_meth_sites_host.argtypes = [i64] + [vp] * 7 + [i64, vp, vp, vp, i64, vp, vp]
     if hasattr(L, "gbx_fmi_smem_host"):
         L.gbx_fmi_default_params.argtypes = [vp, C.c_int32]
         L.gbx_fmi_default_params.restype = None

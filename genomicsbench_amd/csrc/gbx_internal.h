@@ -265,6 +265,12 @@ int abea_events_launch(int pass, int64_t n_reads, const int16_t *d_raw, const in
 int abea_scalings_launch(int64_t n_reads, const int64_t *d_seq_off, const int32_t *d_seq_len, const char *d_seq, const int64_t *d_event_off,
                          const float *d_event_mean, const gbx_abea_model *d_models, float *d_scale, float *d_shift, hipStream_t s);
 
+// ---- abea methylation scoring (abea_meth_kernels.hip)
+int abea_meth_launch(int64_t n_jobs, const gbx_abea_meth_job *d_jobs, const char *d_seq, const int64_t *d_event_off, const float *d_event_mean,
+                     const float *d_scale, const float *d_shift, const float *d_var, const float *d_log_var, const gbx_abea_model *d_model,
+                     const float *d_flogsum, const float *d_trans, const float *d_pre, const float *d_post, const int32_t *d_order,
+                     const int64_t *class_off, float *d_scores, hipStream_t s);
+
 // ---- poa (poa_kernels.hip)
 constexpr int POA_PIPE_MAXLEN = 512;     // longest sequence of the pipelined DP (two-plane slots)
 size_t poa_slot_bytes(int ncap, int deg, int lmax, bool long_slot);

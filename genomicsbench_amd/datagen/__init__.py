@@ -42,6 +42,8 @@ def _L():
         _lib.gbx_gen_abea_raw_counts_many.argtypes = [u64, i64, i64] + [vp] * 4
         _lib.gbx_gen_abea_raw_fill_many.argtypes = [u64, i64, i64] + [vp] * 12
         _lib.gbx_gen_abea_raw_counts_many.restype = _lib.gbx_gen_abea_raw_fill_many.restype = None
+        _lib.gbx_gen_abea_kmer_events_many.argtypes = [u64, i64, i64, vp, vp]
+        _lib.gbx_gen_abea_kmer_events_many.restype = None
         _lib.gbx_gen_fmi_genome.argtypes = [u64, i64, vp]
         _lib.gbx_gen_fmi_reads.argtypes = [u64, i64, i64, vp, i64, C.c_int32, vp]
         for f in ("abea_model", "abea_counts_many", "abea_fill_many", "fmi_genome", "fmi_reads"):
@@ -182,6 +184,94 @@ def gen_abea_raw(n_reads, seed, first=0):
     ss = AbeaSignalSet(raw[:int(raw_off[-1])], raw_off, rg, dg, of, rs.seq_off, rs.seq_len, rs.seq_arena, rs.model)
     ss.true_scale, ss.true_shift = rs.scale, rs.shift
     return ss
+
+
+def _mix64(x):
+    """splitmix64 finaliser on uint64 arrays: the seeded draws of gen_abea_meth that need no stream"""
+    x = (np.asarray(x, dtype=np.uint64) + np.uint64(0x9E3779B97F4A7C15))
+    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def _unif(seed, salt, idx):
+    with np.errstate(over="ignore"):
+        h = _mix64(_mix64(np.uint64(seed) * np.uint64(0x100000001B3) + np.uint64(salt)) + np.asarray(idx, dtype=np.uint64))
+    return (h >> np.uint64(11)).astype(np.float64) / float(1 << 53)
+
+
+def gen_abea_cpg_model(rs_model, seed):
+    """Seeded synthetic CpG model over A < C < G < M < T: a k-mer without M has the level of gen_abea's model, one with M
+    that of its C-for-M k-mer moved by U[-4, 4] pA (a draw per k-mer), the same stdv.  The reference's table is not used."""
+    from ..abea_meth import NMODEL_CPG, make_cpg_model
+    r = np.arange(NMODEL_CPG)
+    digits = np.stack([(r // 5 ** (5 - i)) % 5 for i in range(6)], axis=1)        # first base most significant
+    has_m = (digits == 3).any(axis=1)
+    four = np.array([0, 1, 2, 1, 3])[digits]                                      # M reads as C
+    r4 = (four * (4 ** np.arange(5, -1, -1))).sum(axis=1)
+    lm = rs_model["level_mean"][r4].astype(np.float64) + np.where(has_m, 8.0 * _unif(seed, 0xC96, r) - 4.0, 0.0)
+    return make_cpg_model(lm.astype(np.float32), rs_model["level_stdv"][r4])
+
+
+def gen_abea_meth(n_reads, seed, first=0):
+    """Reads as f5c call-methylation holds them behind align(), for the reads of gen_abea(n_reads, seed, first): an
+    AbeaMethReadSet.  One read in four is rc: its reference segment is the reverse complement of its bases and its events
+    run against the reference.  The read's own bases are the reference segment (an all-match alignment), starting at a
+    seeded ref_start_pos; the event-alignment record is what get_event_alignment_record (meth.c:124-185) gives for the
+    generator's own base-to-event map: per reference position 6 <= p < len - 6 the first event of the nearest k-mer at or
+    before it (else after it) that has events.  var ~ U[0.9, 1.3], events_per_base = events / k-mers (at least 1.05).
+    Uniform bases put a CpG every 16 bases: groups of one site (16 k-mers) dominate and chains up to the 200-base span occur."""
+    from ..abea_meth import AbeaMethReadSet
+    from ..abea import PAIR_DTYPE
+    rs = gen_abea(n_reads, seed, first)
+    L = _L()
+    nk = rs.seq_len.astype(np.int64) - 5
+    kmer_off = np.zeros(n_reads + 1, np.int64); np.cumsum(nk, out=kmer_off[1:])
+    kcount = np.zeros(int(kmer_off[-1]) + 1, np.int32)
+    L.gbx_gen_abea_kmer_events_many(seed, first, n_reads, _p(kmer_off), _p(kcount))
+    ridx = np.arange(first, first + n_reads)
+    rc = (_unif(seed, 0x5C, ridx) < 0.25).astype(np.uint8)
+    ref_start_pos = (1000 + 100000 * _unif(seed, 0x57A, ridx)).astype(np.int32)
+    var = (0.9 + 0.4 * _unif(seed, 0x7A5, ridx)).astype(np.float32)
+    log_var = np.log(var.astype(np.float64)).astype(np.float32)
+    n_ev = rs.n_events
+    epb = np.maximum(n_ev / nk.astype(np.float64), 1.05)
+    comp = np.zeros(256, np.uint8); comp[:] = ord("T")
+    for a, b in zip(b"ACGT", b"TGCA"):
+        comp[a] = b
+    ref = np.zeros(int(rs.seq_len.sum()) + 8, np.uint8)
+    ref_off = np.zeros(n_reads, np.int64)
+    recs, rec_off, o = [], np.zeros(n_reads + 1, np.int64), 0
+    for r in range(n_reads):
+        n = int(rs.seq_len[r])
+        bases = rs.seq_arena[rs.seq_off[r]:rs.seq_off[r] + n]
+        ref_off[r] = o
+        ref[o:o + n] = comp[bases[::-1]] if rc[r] else bases
+        o += n
+        kc = kcount[kmer_off[r]:kmer_off[r + 1]]
+        firstev = np.cumsum(kc) - kc
+        has = kc > 0
+        rec_off[r + 1] = rec_off[r]
+        if not has.any() or n < 13:
+            continue
+        at = np.where(has, np.arange(len(kc)), -1)
+        before = np.maximum.accumulate(at)
+        after = np.where(has, np.arange(len(kc)), len(kc))[::-1]
+        after = np.minimum.accumulate(after)[::-1]
+        near = np.where(before >= 0, before, after)
+        p = np.arange(6, n - 6)
+        kpos = n - p - 6 if rc[r] else p
+        e = firstev[near[kpos]]
+        if len(e) == 0 or e[0] == e[-1]:                                        # a degenerate alignment is discarded (meth.c:173-177)
+            continue
+        a = np.zeros(len(p), PAIR_DTYPE)
+        a["ref_pos"], a["read_pos"] = ref_start_pos[r] + p, e
+        recs.append(a)
+        rec_off[r + 1] += len(a)
+    rec = np.concatenate(recs) if recs else np.zeros(0, PAIR_DTYPE)
+    ms = AbeaMethReadSet(rs, var, log_var, epb, rc, ref_off, rs.seq_len, ref[:o], ref_start_pos, rec_off, rec, gen_abea_cpg_model(rs.model, seed))
+    ms.kmer_off, ms.kmer_events = kmer_off, kcount[:int(kmer_off[-1])]
+    return ms
 
 
 def gen_fmi_genome(length, seed):

@@ -391,7 +391,7 @@ void gbx_gen_abea_model(uint64_t seed, float *level_mean, float *level_stdv)
 }
 
 static void abea_read(uint64_t seed, int64_t read, int mode, const float *level_mean, const float *level_stdv,
-                      int32_t *seq_len, int64_t *n_events, char *seq, float *ev, float *scale, float *shift)
+                      int32_t *seq_len, int64_t *n_events, char *seq, float *ev, float *scale, float *shift, int32_t *kcount)
 {
     rng_t r;
     rng_seed(&r, seed, (uint64_t)read * 2 + 1);
@@ -412,6 +412,7 @@ static void abea_read(uint64_t seed, int64_t read, int mode, const float *level_
         if (i < 5) continue;
         int cnt = 0;
         if (rng_below(&r, 100) >= 3) { cnt = 1; while (rng_unif(&r) < 0.45 && cnt < 12) ++cnt; }
+        if (kcount) kcount[i - 5] = cnt;
         for (int c = 0; c < cnt; ++c) {
             const double noise = rng_norm(&r);
             if (mode == 1) ev[ne] = (float)((double)sc * level_mean[rank] + (double)sh + noise * level_stdv[rank]);
@@ -425,7 +426,7 @@ static void abea_read(uint64_t seed, int64_t read, int mode, const float *level_
 void gbx_gen_abea_counts_many(uint64_t seed, int64_t first, int64_t n_reads, int32_t *seq_len, int64_t *n_events)
 {
 #pragma omp parallel for schedule(dynamic, 8)
-    for (int64_t k = 0; k < n_reads; ++k) abea_read(seed, first + k, 0, 0, 0, seq_len + k, n_events + k, 0, 0, 0, 0);
+    for (int64_t k = 0; k < n_reads; ++k) abea_read(seed, first + k, 0, 0, 0, seq_len + k, n_events + k, 0, 0, 0, 0, 0);
 }
 
 void gbx_gen_abea_fill_many(uint64_t seed, int64_t first, int64_t n_reads, const float *level_mean, const float *level_stdv,
@@ -434,7 +435,19 @@ void gbx_gen_abea_fill_many(uint64_t seed, int64_t first, int64_t n_reads, const
 #pragma omp parallel for schedule(dynamic, 8)
     for (int64_t k = 0; k < n_reads; ++k) {
         int32_t l; int64_t ne;
-        abea_read(seed, first + k, 1, level_mean, level_stdv, &l, &ne, seq + seq_off[k], ev + event_off[k], scale + k, shift + k);
+        abea_read(seed, first + k, 1, level_mean, level_stdv, &l, &ne, seq + seq_off[k], ev + event_off[k], scale + k, shift + k, 0);
+    }
+}
+
+/* The events the generator drew per k-mer (0: the k-mer was skipped) for the reads of gbx_gen_abea_*: kcount + kmer_off[k] takes
+ * read k's seq_len - 5 counts.  What f5c's postalign would report as the base-to-event map, known exactly here; a read whose
+ * k-mers were all skipped carries one event that belongs to no k-mer. */
+void gbx_gen_abea_kmer_events_many(uint64_t seed, int64_t first, int64_t n_reads, const int64_t *kmer_off, int32_t *kcount)
+{
+#pragma omp parallel for schedule(dynamic, 8)
+    for (int64_t k = 0; k < n_reads; ++k) {
+        int32_t l; int64_t ne;
+        abea_read(seed, first + k, 0, 0, 0, &l, &ne, 0, 0, 0, 0, kcount + kmer_off[k]);
     }
 }
 

@@ -469,6 +469,77 @@ int gbx_abea_signal_align_host(int64_t n_reads, const int16_t *raw, const int64_
                                gbx_abea_event *events, int64_t event_cap, int64_t *n_events_total, float *scale, float *shift,
                                int32_t *status, gbx_abea_pair *out, int32_t *n_pairs);
 
+/* abea, methylation scoring: what f5c call-methylation runs per read behind align() (meth_single, f5c.c:1375-1380).
+ * Replaces  float profile_hmm_score(m_seq, m_rc_seq, event, scaling, cpgmodel, event_start_idx, event_stop_idx, strand,
+ *                                   event_stride, rc, events_per_base, hmm_flags)            hmm.c:301-727
+ *           void  calculate_methylation_for_read(site_score_map, ref, record, ...)           meth.c:500-658 (the planner)
+ * A job is one profile_hmm_score call: the forward score of a run of events under a sequence over A/C/G/M/T, three
+ * states per k-mer, every log-sum the table-driven p7_FLogsum (ESL_LOG_SUM, f5c.h:70; logsum.h:61-71).  The score is the
+ * CPU function's, bit for bit: the six candidates of a cell folded left to right, lp_end accumulated in row order, the
+ * float emission with its division (hmm.c:55-100).  HMM_REVERSE_FIX is not defined: with rc the k-mers are read from the
+ * reverse-complement string backwards and the events are walked downwards (hmm.c:382-393, 429).  A base outside ACGMT
+ * ranks as A.  Reads with events_per_base <= 1 give an unspecified score. */
+#define GBX_ABEA_NMODEL_CPG      15625   /* 5^KMER_SIZE states, A < C < G < M < T (hmm.c:21-52) */
+#define GBX_ABEA_FLOGSUM_TBL     16000   /* p7_LOGSUM_TBL, logsum.h:18 */
+#define GBX_ABEA_METH_PRE_CLIP   1       /* HAF_ALLOW_PRE_CLIP, f5cmisc.h:15 */
+#define GBX_ABEA_METH_POST_CLIP  2       /* HAF_ALLOW_POST_CLIP */
+#define GBX_ABEA_METH_NTRANS     10      /* per read: lp_mk mb mm_self mm_next bb bk bm_next bm_self kk km (hmm.c:212-229) */
+#define GBX_ABEA_METH_MAX_KMERS  256     /* k-mers of one job; the planner's span rule keeps a group at 216 (meth.c:571) */
+#define GBX_ABEA_METH_NCLASS     4       /* kernel classes by k-mer count: <= 16, <= 64, <= 128, <= 256 */
+
+typedef struct gbx_abea_meth_job {
+    int64_t seq_off, rc_off;          /* m_seq and m_rc_seq in the string arena, seq_len bytes each */
+    int32_t seq_len;                  /* >= KMER */
+    int32_t read;                     /* the read whose events, scalings and transitions it uses */
+    int32_t event_start, event_stop;  /* event_start_idx, event_stop_idx: indices into the read's own events, inclusive */
+    int32_t rc;                       /* event_stride = -1 iff rc (hmm.c:322): event_stop <= event_start then */
+    int32_t flags;                    /* GBX_ABEA_METH_PRE_CLIP | GBX_ABEA_METH_POST_CLIP */
+} gbx_abea_meth_job;
+typedef struct gbx_abea_meth_site {   /* ScoredSite, f5c.h:193-218, without the scores: job 2s is the unmethylated, 2s+1 the methylated */
+    int32_t read, start_position, end_position, n_cpg;
+    int64_t ctx_off;                  /* ScoredSite::sequence = the disambiguated reference segment of the read at */
+    int32_t ctx_len, pad_;            /* [ctx_off, ctx_off + ctx_len) */
+} gbx_abea_meth_site;
+
+/* Everything that needs the host C library, so that it carries the reference's bits: the p7_FLogsum table (logsum.h:44-46),
+ * the transition logs of every read (hmm.c:247-295; float logarithms: the reference is compiled as C++, where log of a
+ * float is the float overload), the two flank tables (flank_len entries each, flank_len > the largest row count of the
+ * batch; pre_flank[i] as hmm.c:172-205, post_flank[j] = the reference's post_flank[n_events - 1 - j], hmm.c:132-168) and
+ * the processing order: jobs by kernel class, longest first within a class; class_off[c] .. class_off[c + 1] of `order`
+ * are class c's.  Checks every job against the arena, its read's events and GBX_ABEA_METH_MAX_KMERS. */
+int gbx_abea_meth_plan_host(int64_t n_jobs, const gbx_abea_meth_job *jobs, int64_t seq_bytes, int64_t n_reads,
+                            const int64_t *event_off, const double *events_per_base, float *flogsum, float *trans,
+                            int64_t flank_len, float *pre_flank, float *post_flank, int32_t *order,
+                            int64_t *class_off /* [GBX_ABEA_METH_NCLASS + 1] */);
+/* Device entry: d_scores[j] = the score of job j.  Jobs, strings, reads, plan and model resident in device memory;
+ * class_off is the plan's, on the host.  d_event_off indexes d_event_mean ABSOLUTELY as in gbx_abea_align_device.  No
+ * workspace; nothing is synchronised. */
+int gbx_abea_meth_score_device(int64_t n_jobs, const gbx_abea_meth_job *d_jobs, const char *d_seq_arena,
+                               const int64_t *d_event_off, const float *d_event_mean, const float *d_scale, const float *d_shift,
+                               const float *d_var, const float *d_log_var, const gbx_abea_model *d_cpg_model,
+                               const float *d_flogsum, const float *d_trans, const float *d_pre_flank, const float *d_post_flank,
+                               const int32_t *d_order, const int64_t *class_off, float *d_scores, void *stream);
+/* Pageable host buffers in, scores out (one device).  events: the 24-byte records, read r's at events + event_off[r]. */
+int gbx_abea_meth_score_host(int64_t n_jobs, const gbx_abea_meth_job *jobs, const char *seq_arena, int64_t seq_bytes,
+                             int64_t n_reads, const int64_t *event_off, const gbx_abea_event *events, const float *scale,
+                             const float *shift, const float *var, const float *log_var, const double *events_per_base,
+                             const gbx_abea_model *cpg_model, float *scores);
+/* sum over the jobs of rows x k-mers x 3 states */
+int gbx_abea_meth_cells(int64_t n_jobs, const gbx_abea_meth_job *jobs, int64_t *cells);
+/* The site planner: calculate_methylation_for_read without the BAM record.  Read r: reference segment ref_arena[ref_off[r]
+ * .. +ref_len[r]) (any case, IUPAC codes; disambiguated as meth.c:288-306), ref_start_pos[r], rc[r], and its
+ * event-alignment record rec[rec_off[r] .. rec_off[r + 1]): (ref_pos, event_idx) sorted by ref_pos, what
+ * get_event_alignment_record returns (meth.c:124-185).  Writes *n_sites sites, 2 * *n_sites jobs (flags 3) and their four
+ * strings each into seq_arena (*seq_bytes bytes).  Reproduces the CpG scan and grouping at min_separation 10, the skips
+ * sub_start_pos <= 10 and span > 200, find_by_ref_bounds, the |e2 - e1| <= 10 filter and the ratio filter as written (it
+ * divides by a negative number and never rejects).  More sites than site_cap or more bytes than seq_cap: GBX_ERR_ARG with
+ * the needed counts in *n_sites and *seq_bytes (call with 0 / NULL to size).  A record that runs against rc (the reference
+ * asserts, hmm.c:322) is GBX_ERR_ARG. */
+int gbx_abea_meth_sites_host(int64_t n_reads, const int64_t *ref_off, const int32_t *ref_len, const char *ref_arena,
+                             const int32_t *ref_start_pos, const uint8_t *rc, const int64_t *rec_off, const gbx_abea_pair *rec,
+                             int64_t site_cap, gbx_abea_meth_site *sites, gbx_abea_meth_job *jobs, int64_t *n_sites,
+                             int64_t seq_cap, char *seq_arena, int64_t *seq_bytes);
+
 /* --------------------------------------------------------------------- fmi
  * SMEM seeding on the FM-index of reference + reverse complement (second half): the three
  * seeding rounds bwa-mem2 runs per batch of reads and the driver times,
