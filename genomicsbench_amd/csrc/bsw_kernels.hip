@@ -23,6 +23,7 @@
 // initial values, E=0) or hold zeros; cells left of it are never read again.
 #include "gbx_internal.h"
 #include <atomic>
+#include <climits>
 #include <cstdlib>
 
 namespace gbx {
@@ -31,7 +32,7 @@ namespace {
 constexpr int NEG = -(1 << 29);
 constexpr int BIGJ = 1 << 20;
 
-// qlen classes: 0..15 = qlen <= 8,16,..,128; 16..18 = <= 160,192,256; 19 = <= 1024; 20 = LDS kernel (shapes: class_shapes())
+// qlen classes: 0..15 = qlen <= 8,16,..,128; 16..18 = <= 160,192,256; 19 = <= 1024; 20 = LDS kernel (shapes: row_kernels[])
 constexpr int NCLS = 21;
 constexpr int CLS_LDS = NCLS - 1;
 constexpr int NTB = 32;                     // target-length buckets per class (width 16), longest first
@@ -1369,28 +1370,24 @@ __global__ void __launch_bounds__(64, 3) bsw_lane_reg_kernel(BswDev prm, BswPair
 }
 
 // ---- kernel shapes ----------------------------------------------------------
-// class c (query length) -> (lanes per pair, columns per lane).  Short queries use narrow groups:
+// class c (query length) -> (lanes per pair, columns per lane): row_kernels[c].  Short queries use narrow groups:
 // the per-row fixed cost (scan, reductions, epilogue) is paid once per wavefront row, so 16 pairs per
 // wavefront amortise it 4x better than 4 pairs; the width is bounded by the registers CPL columns need.
-struct RowShape { int lpp, cpl; };
 typedef void (*RowsFn)(BswDev, BswPairs, BswWork, int);
-struct RowKernel { int lpp, cpl; RowsFn fn[2]; std::atomic<int> bpc[2]; const char *name; };   // bpc: resident blocks per CU, cached (same on every MI355X of a node)
+struct RowKernel { int lpp, cpl; RowsFn fn[2]; std::atomic<int> bpc[2]; const char *name; };   // fn[sym]; bpc: resident blocks per CU, cached (same on every MI355X of a node)
 #define GBX_ROW_KERNEL(L, C) { L, C, { bsw_rows_kernel<L, C, false>, bsw_rows_kernel<L, C, true> }, { 0, 0 }, "bsw_rows_" #L "x" #C }
 RowKernel row_kernels[] = {
-    // the default table (class_shapes) ...
+    // classes 0..19, the widest query of each: 8, 16, .., 128 (sixteen classes); 160, 192, 256; 1024
     GBX_ROW_KERNEL(2, 4),  GBX_ROW_KERNEL(2, 8),  GBX_ROW_KERNEL(2, 12), GBX_ROW_KERNEL(2, 16), GBX_ROW_KERNEL(2, 20), GBX_ROW_KERNEL(2, 24),
     GBX_ROW_KERNEL(4, 14), GBX_ROW_KERNEL(4, 16), GBX_ROW_KERNEL(4, 18), GBX_ROW_KERNEL(4, 20), GBX_ROW_KERNEL(4, 22), GBX_ROW_KERNEL(4, 24),
     GBX_ROW_KERNEL(8, 13), GBX_ROW_KERNEL(8, 14), GBX_ROW_KERNEL(8, 15), GBX_ROW_KERNEL(8, 16),
     GBX_ROW_KERNEL(16, 10), GBX_ROW_KERNEL(16, 12), GBX_ROW_KERNEL(16, 16), GBX_ROW_KERNEL(64, 16),
-    // ... and alternatives for scripts/tune_bsw_shapes.sh
-    GBX_ROW_KERNEL(4, 8), GBX_ROW_KERNEL(4, 12), GBX_ROW_KERNEL(8, 10), GBX_ROW_KERNEL(8, 12), GBX_ROW_KERNEL(16, 8),
-    // ... and for the direct launch of small jobs (bsw_launch_direct): a job of a few hundred pairs is as long as one pair's rows,
-    // so its pairs get many lanes and few columns each
-    GBX_ROW_KERNEL(64, 3), GBX_ROW_KERNEL(64, 4),
+    // ... and for the direct launch of small jobs alone (bsw_launch_direct, which also takes 16x10 .. 16x16): a job of a few
+    // hundred pairs is as long as one pair's rows, so its pairs get many lanes and few columns each
+    GBX_ROW_KERNEL(16, 8), GBX_ROW_KERNEL(64, 3), GBX_ROW_KERNEL(64, 4),
 };
 #undef GBX_ROW_KERNEL
-// widest query a class holds: classes 0..7 = 16,32,..,128; 8..11 = 160,192,256,1024
-constexpr int class_qmax[NCLS - 1] = {8, 16, 24, 32, 40, 48, 56, 64, 72, 80, 88, 96, 104, 112, 120, 128, 160, 192, 256, 1024};
+static_assert(sizeof(row_kernels) / sizeof(row_kernels[0]) >= NCLS - 1, "one row kernel per register class");
 
 // Class modes.  Every class is a kernel launch that lasts at least as long as its longest pair, and a stream runs
 // its classes one after the other: with few pairs the 20 fine classes are latency, not work (512 pairs: 1.3 ms on
@@ -1416,26 +1413,30 @@ RowKernel *find_row_kernel(int lpp, int cpl)
     return nullptr;
 }
 
-// GBX_BSW_SHAPES="4x4,4x8,..." (12 entries) overrides the table; a tuning aid, entries that do not
-// cover their class or have no kernel are ignored.
-const RowShape *class_shapes()
+// The lane kernels: [packed bases][kind][gap symmetry].  Kind: compact cells, compact cells with four-bit query codes, wide cells.
+typedef void (*LaneFn)(BswDev, BswPairs, BswWork, int, int, int, int);
+enum { LANE_COMPACT = 0, LANE_COMPACT4 = 1, LANE_WIDE = 2 };
+#define GBX_LANE_KERNEL(COMPACT, CODE4, PACKED) { bsw_lane_kernel<false, COMPACT, CODE4, PACKED>, bsw_lane_kernel<true, COMPACT, CODE4, PACKED> }
+const LaneFn lane_kernels[2][3][2] = {
+    { GBX_LANE_KERNEL(true, false, false), GBX_LANE_KERNEL(true, true, false), GBX_LANE_KERNEL(false, false, false) },
+    { GBX_LANE_KERNEL(true, false, true),  GBX_LANE_KERNEL(true, true, true),  GBX_LANE_KERNEL(false, false, true) },
+};
+#undef GBX_LANE_KERNEL
+
+// Resident blocks of `fn` per CU at `threads` a block and no dynamic LDS, at most `cap`, `fallback` if the query fails: asked
+// once per kernel and kept in `cache`.
+int resident_blocks(std::atomic<int> &cache, const void *fn, int threads, int fallback, int cap)
 {
-    static RowShape shapes[NCLS - 1] = {{2, 4},  {2, 8},  {2, 12}, {2, 16}, {2, 20}, {2, 24}, {4, 14}, {4, 16}, {4, 18}, {4, 20},
-                                        {4, 22}, {4, 24}, {8, 13}, {8, 14}, {8, 15}, {8, 16}, {16, 10}, {16, 12}, {16, 16}, {64, 16}};
-    static bool parsed = false;
-    if (!parsed) {
-        parsed = true;
-        const char *e = getenv("GBX_BSW_SHAPES");
-        for (int c = 0; e && *e && c < NCLS - 1; ++c) {
-            int l = 0, k = 0, used = 0;
-            if (sscanf(e, "%dx%d%n", &l, &k, &used) != 2) break;
-            if (find_row_kernel(l, k) && l * k >= class_qmax[c]) shapes[c] = {l, k};
-            e += used;
-            if (*e == ',') ++e;
-        }
-    }
-    return shapes;
+    int bpc = cache.load(std::memory_order_relaxed);
+    if (bpc) return bpc;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, fn, threads, 0) != hipSuccess || bpc < 1) { (void)hipGetLastError(); bpc = fallback; }
+    bpc = bpc > cap ? cap : bpc;
+    cache.store(bpc, std::memory_order_relaxed);
+    return bpc;
 }
+
+// GBX_<switch>=0 turns a default path off
+bool switched_off(const char *name) { const char *e = getenv(name); return e && atoi(e) == 0; }
 
 int make_dev_params(const gbx_bsw_params *p, BswDev *d)
 {
@@ -1489,6 +1490,8 @@ size_t bsw_workspace_bytes(int64_t n)
 // pipelined host call this kernel runs beside the previous chunk's lane kernels and gets a wavefront slot or two per
 // SIMD: few wavefronts with four loads in flight each, not many with one - 0.5-1.0 ms -> see profiles/r05af_*).
 constexpr int UNPACK_ROUNDS = 4;
+// byte b = lo | hi << 4  ->  two bytes (lo, hi): two packed bytes give one dword
+__device__ inline unsigned spread4(unsigned h) { return (h & 0xfu) | ((h & 0xf0u) << 4) | ((h & 0xf00u) << 8) | ((h & 0xf000u) << 12); }
 __global__ void __launch_bounds__(256) bsw_unpack4_kernel(const uint8_t *__restrict__ packed, uint8_t *__restrict__ out, int64_t lo, int64_t hi)
 {
     const int64_t base = lo + (int64_t)blockIdx.x * (256 * 16 * UNPACK_ROUNDS) + threadIdx.x * 16;
@@ -1497,12 +1500,10 @@ __global__ void __launch_bounds__(256) bsw_unpack4_kernel(const uint8_t *__restr
         uint2 v[UNPACK_ROUNDS];
 #pragma unroll
         for (int r = 0; r < UNPACK_ROUNDS; ++r) v[r] = *(const uint2 *)(packed + ((base + r * 4096) >> 1));
-        // byte b = lo | hi << 4  ->  two bytes (lo, hi); four packed bytes give two dwords
-        auto spread = [](unsigned h) -> unsigned { return (h & 0xfu) | ((h & 0xf0u) << 4) | ((h & 0xf00u) << 8) | ((h & 0xf000u) << 12); };
 #pragma unroll
         for (int r = 0; r < UNPACK_ROUNDS; ++r) {
             uint4 q;
-            q.x = spread(v[r].x & 0xffffu); q.y = spread(v[r].x >> 16); q.z = spread(v[r].y & 0xffffu); q.w = spread(v[r].y >> 16);
+            q.x = spread4(v[r].x & 0xffffu); q.y = spread4(v[r].x >> 16); q.z = spread4(v[r].y & 0xffffu); q.w = spread4(v[r].y >> 16);
             *(uint4 *)(out + base + r * 4096) = q;
         }
         return;
@@ -1512,9 +1513,8 @@ __global__ void __launch_bounds__(256) bsw_unpack4_kernel(const uint8_t *__restr
         if (o >= hi) return;
         if (aligned && o + 16 <= hi) {
             const uint2 v = *(const uint2 *)(packed + (o >> 1));
-            auto spread = [](unsigned h) -> unsigned { return (h & 0xfu) | ((h & 0xf0u) << 4) | ((h & 0xf00u) << 8) | ((h & 0xf000u) << 12); };
             uint4 q;
-            q.x = spread(v.x & 0xffffu); q.y = spread(v.x >> 16); q.z = spread(v.y & 0xffffu); q.w = spread(v.y >> 16);
+            q.x = spread4(v.x & 0xffffu); q.y = spread4(v.x >> 16); q.z = spread4(v.y & 0xffffu); q.w = spread4(v.y >> 16);
             *(uint4 *)(out + o) = q;
         } else {
             for (int64_t k = o; k < o + 16 && k < hi; ++k) out[k] = (uint8_t)((packed[k >> 1] >> ((k & 1) * 4)) & 0xf);
@@ -1533,7 +1533,7 @@ int bsw_unpack4(const uint8_t *d_packed, uint8_t *d_out, int64_t lo, int64_t hi,
 }
 
 // Small jobs whose queries all fit one register class (1..256 columns, no empty sequence, scores below the
-// packed-key limit; the caller has checked): one launch of the 8x16 or 16x16 kernel over the pairs in input order, without
+// packed-key limit; the caller has checked): one launch of one row kernel (64x3 / 64x4 or 16x8 .. 16x16, below) over the pairs in input order, without
 // the binning passes, the stream fork and the join - the dependent launch chain is what a 512-pair call costs.
 int bsw_launch_direct(const gbx_bsw_params *p, int64_t n, int max_qlen,
                       const uint8_t *d_ref, const uint8_t *d_qer, const int64_t *d_idr, const int64_t *d_idq,
@@ -1590,9 +1590,203 @@ int bsw_lane_rule(const gbx_bsw_params *p, int64_t n, BswLaneRule *r)
     r->max_mat = dev.max_mat > 0 ? dev.max_mat : 0;
     r->qmax = LANE_QMAX;
     r->limit = LANE_SCORE_LIMIT;
-    r->compact_limit = LANE_COMPACT_LIMIT;
-    static_assert(LANE_NRANGE == 5, "BswLaneRule::range_hi / BswChunkPrep::class_pairs");
-    for (int f = 0; f < 2; ++f) for (int k = 0; k < LANE_NRANGE; ++k) r->range_hi[f][k] = LANE_RANGE_HI[f][k];
+    return GBX_OK;
+}
+
+// ---- bsw_launch and its parts --------------------------------------------------------------------------------------
+// What the parts of one bsw_launch call share.  The classes are independent and every kernel ends in a tail of a few long
+// pairs: they go to the caller's stream `s` and the three side streams `ss->side[]`, so that a tail overlaps the next class.
+struct BswCall {
+    BswDev dev; BswPairs P; BswWork W;
+    int64_t n;
+    int mode, cus;                              // row of CLASS_REMAP; compute units of the device
+    bool sym;                                   // symmetric gap penalties: the kernels' SYM instances
+    hipStream_t s; SideStreams *ss; hipEvent_t *join_events; const BswChunkPrep *prep;
+    bool ahead;                                 // the preparing passes run on the urgent streams ss->pre[], behind prep->uploaded only
+    bool no_rows;                               // the lane kernels take every pair: no row-kernel class, no bsw_lds
+    bool packed_lanes;                          // ... and they read the packed bases as they were uploaded
+    int phase;                                  // BswChunkPrep::phase
+    hipStream_t s_cls;                          // classify's stream
+    hipEvent_t ev_pre, ev_aux;                  // behind classify (recorded when `ahead`), behind the lane sort
+};
+
+// The streams and events of this call.  Returns 1 for a phase-1 call that cannot be split (nothing is queued).
+static int plan_call(BswCall &c)
+{
+    const BswChunkPrep *prep = c.prep;
+    // A chunk of a pipelined host call: its preparing passes go to the two urgent streams and wait for the uploads only.
+    // On the caller's stream they would queue behind the previous chunk's kernels there, and with them every kernel of
+    // this chunk: the chunks then ran one after the other, each with its own tails (2.5 ms a chunk of 'large' against
+    // 1.9 ms for a third of the job; GBX_BSW_PREP=0 keeps that order).
+    static const bool prep_off = switched_off("GBX_BSW_PREP");
+    c.ahead = prep && prep->uploaded && c.join_events && !prep_off;
+    c.s_cls = c.ahead ? c.ss->pre[0] : c.s;
+    // A chunk whose pairs all go to the lane kernels (the host entry has counted: rows_pairs == 0) leaves out the row-kernel
+    // classes, twenty-one near-empty launches that each wait for LDS behind the lane kernels, and its bases stay packed: the
+    // lane kernels read the nibbles (PACKED).  Beside the previous chunk's lane kernels the unpacking took 0.5-1.0 ms
+    // instead of 0.05, and the chunk's kernels wait for it (profiles/r05af_host_timeline.txt).
+    c.no_rows = c.dev.lane_on && prep && prep->rows_pairs == 0 && !switched_off("GBX_BSW_SKIP_ROWS");
+    c.packed_lanes = c.no_rows && prep->ref_packed && !switched_off("GBX_BSW_PACKED_LANES");
+    // Such a chunk's launch can also come in two calls (BswChunkPrep::phase): the preparing passes as soon as the chunk's index
+    // arrays are up - they read nothing else - and the kernels when its bases are.  A phase-1 call that cannot be split
+    // (a chunk with row-kernel pairs, a switch set) queues nothing and returns 1: the caller then makes one whole call.
+    c.phase = prep ? prep->phase : 0;
+    if (c.phase && !(c.ahead && c.packed_lanes && prep->ev_pre && prep->ev_aux)) {
+        if (c.phase == 1) return 1;
+        set_error("bsw: the kernels of a chunk whose preparing passes were not queued");
+        return GBX_ERR_ARG;
+    }
+    c.ev_pre = c.phase ? prep->ev_pre : c.ss->ev_pre;
+    c.ev_aux = c.phase ? prep->ev_aux : c.ss->ev_aux;
+    if (c.packed_lanes) { c.P.ref = prep->ref_packed; c.P.qer = prep->qer_packed; c.P.packed = 1; }
+    return GBX_OK;
+}
+
+// The preparing passes: unpacking, the memsets, the lane sort, classify.
+static int queue_prepare(BswCall &c)
+{
+    const BswChunkPrep *prep = c.prep;
+    SideStreams *ss = c.ss;
+    const int64_t n = c.n;
+    int rc;
+    if (c.ahead) {
+        GBX_HIP(hipStreamWaitEvent(ss->pre[0], prep->uploaded, 0));
+        GBX_HIP(hipStreamWaitEvent(ss->pre[1], prep->uploaded, 0));
+    }
+    if (!c.packed_lanes && prep && prep->ref_packed) {
+        // from the call's watermark (everything below it is expanded; chunks that ran PACKED expanded nothing) - s_cls waits
+        // for this chunk's uploads, and the host entry queues the chunks' uploads in order, so all of [from, hi) is up
+        const int64_t from_r = prep->unp_r ? *prep->unp_r : prep->lo_r, from_q = prep->unp_q ? *prep->unp_q : prep->lo_q;
+        if ((rc = bsw_unpack4(prep->ref_packed, prep->ref_bytes, from_r, prep->hi_r, c.s_cls)) ||
+            (rc = bsw_unpack4(prep->qer_packed, prep->qer_bytes, from_q, prep->hi_q, c.s_cls)))
+            return rc;
+        if (prep->unp_r && prep->hi_r > *prep->unp_r) *prep->unp_r = prep->hi_r;
+        if (prep->unp_q && prep->hi_q > *prep->unp_q) *prep->unp_q = prep->hi_q;
+    }
+    GBX_HIP(hipMemsetAsync(c.W.counts, 0, WS_HDR * sizeof(int32_t), c.s_cls));        // the workspace's header arrays
+    // The lane sort (0.3 ms on 'large': two passes of scattered atomics) runs on a side stream of its own, beside
+    // classify and the row-kernel classes on the caller's stream, which do not need it; the lane launches wait for it.
+    if (c.dev.lane_on) {
+        hipStream_t so;
+        if (c.ahead) {
+            so = ss->pre[1];
+            GBX_HIP(hipMemsetAsync(c.W.lbase, 0, (size_t)WS_LANE * sizeof(int32_t), so));
+        } else {
+            GBX_HIP(hipMemsetAsync(c.W.lbase, 0, (size_t)WS_LANE * sizeof(int32_t), c.s));
+            if ((rc = ss->fork(c.s))) return rc;
+            so = ss->side[SideStreams::N - 1];
+        }
+        Stage st("bsw_lane_sort", so);
+        const int sblocks = (int)((n + 255) / 256);
+        hipLaunchKernelGGL(bsw_lane_sort_kernel, dim3(sblocks), dim3(256), 0, so, c.dev, c.P, n, c.W, 0);
+        hipLaunchKernelGGL(bsw_lane_scan_kernel, dim3(1), dim3(1024), 0, so, c.W);
+        hipLaunchKernelGGL(bsw_lane_sort_kernel, dim3(sblocks), dim3(256), 0, so, c.dev, c.P, n, c.W, 1);
+        GBX_HIP(hipEventRecord(c.ev_aux, so));
+    }
+    const int cblocks = (int)((n + CLS_THREADS - 1) / CLS_THREADS);
+    {
+        Stage st("bsw_classify", c.s_cls);
+        hipLaunchKernelGGL(bsw_classify_kernel, dim3(cblocks), dim3(CLS_THREADS), 0, c.s_cls, c.dev, c.P, n, c.W, 0);
+        hipLaunchKernelGGL(bsw_scan_kernel, dim3(1), dim3(HDR), 0, c.s_cls, c.W);
+        hipLaunchKernelGGL(bsw_classify_kernel, dim3(cblocks), dim3(CLS_THREADS), 0, c.s_cls, c.dev, c.P, n, c.W, 1);
+    }
+    if (c.ahead) GBX_HIP(hipEventRecord(c.ev_pre, c.s_cls));
+    GBX_HIP(hipGetLastError());
+    return GBX_OK;
+}
+
+// `s` and the side streams wait for `ev`
+static int kernel_streams_wait(const BswCall &c, hipEvent_t ev, int n_side = SideStreams::N)
+{
+    GBX_HIP(hipStreamWaitEvent(c.s, ev, 0));
+    for (int k = 0; k < n_side; ++k) GBX_HIP(hipStreamWaitEvent(c.ss->side[k], ev, 0));
+    return GBX_OK;
+}
+
+// The row-kernel classes.  With the lane path on they hold next to nothing (what the lane kernels cannot take): twenty
+// near-empty launches, all on the caller's stream, in the shadow of the lane sort.
+static void launch_row_classes(BswCall &c)
+{
+    // Four kernel streams when the inputs are resident.  The host pipeline (join_events) uses three: the
+    // runtime maps streams onto four hardware queues, and with all four busy with class kernels its copy
+    // stream shares one and the uploads stall behind kernels (measured).
+    const int nk = c.join_events ? 3 : 4;
+    int launched = 0;
+    for (int cls = 0; cls < NCLS - 1; ++cls) {
+        if (CLASS_REMAP[c.mode][cls] != cls) continue;        // this class's pairs run on a wider class's kernel
+        const int sk = (c.mode ? launched++ : cls) % nk;
+        hipStream_t sc = c.dev.lane_on || sk == 0 ? c.s : c.ss->side[sk - 1];
+        RowKernel &k = row_kernels[cls];
+        // persistent groups: the grid is the number of blocks that are resident at once (occupancy query), so that the static
+        // round-robin over the longest-first list starts every group on the longest pairs together; never more groups than pairs
+        const int bpc = resident_blocks(k.bpc[c.sym], (const void *)k.fn[c.sym], 256, 2, 8);
+        const int gpb = 256 / k.lpp;
+        const int64_t want = (c.n + gpb - 1) / gpb, cap = (int64_t)c.cus * bpc;
+        Stage st(k.name, sc);
+        hipLaunchKernelGGL(k.fn[c.sym], dim3((int)(want < cap ? want : cap)), dim3(256), 0, sc, c.dev, c.P, c.W, cls);
+    }
+}
+
+// The compact 80..99 class with its cells in registers (bsw_lane_reg_kernel), as many wavefronts as its registers allow
+static void launch_lane_reg(const BswCall &c, hipStream_t sc, int64_t want, int rlo, int rhi, int slot)
+{
+    static_assert(LANE_RANGE_HI[0][2] == 99, "bsw_lane_reg_kernel instance");
+    typedef void (*LaneRegFn)(BswDev, BswPairs, BswWork, int, int, int);
+    static const LaneRegFn reg_fn[2] = {bsw_lane_reg_kernel<false, 99>, bsw_lane_reg_kernel<true, 99>};
+    static std::atomic<int> reg_bpc[2];
+    const int64_t cap = (int64_t)c.cus * resident_blocks(reg_bpc[c.sym], (const void *)reg_fn[c.sym], 64, 8, INT_MAX);
+    hipLaunchKernelGGL(reg_fn[c.sym], dim3((unsigned)(want < cap ? want : cap)), dim3(64), 0, sc, c.dev, c.P, c.W, rlo, rhi, slot);
+    g_lane_reg_launches.fetch_add(1, std::memory_order_relaxed);
+}
+
+// The lane launches: longest queries first, one launch per format and LDS class, spread over the streams; grids = resident wavefronts
+static void launch_lanes(const BswCall &c)
+{
+    static const char *names[2][LANE_NRANGE] = {{"bsw_lane_c47", "bsw_lane_c79", "bsw_lane_c99", "bsw_lane_c135", "bsw_lane_c159"},
+                                                {"bsw_lane_w39", "bsw_lane_w79", "bsw_lane_w103", "bsw_lane_w127", "bsw_lane_w159"}};
+    const int64_t want = (c.n + 63) / 64;
+    // The wide launches go first, while the chip is empty: a launch has to be given its LDS before its wavefronts can
+    // see that their list is empty (the usual case for short reads), and behind a working compact launch that wait
+    // held up the stream for up to a millisecond (6.36 -> 6.03 ms on 'large').
+    for (int fmt = 1; fmt >= 0; --fmt) {
+        for (int r = LANE_NRANGE - 1; r >= 0; --r) {
+            const int qlo = r ? LANE_RANGE_HI[fmt][r - 1] + 1 : 1, qhi = LANE_RANGE_HI[fmt][r];
+            const int cols = (qhi + 3) & ~1;                   // columns 0..qlen, and even
+            // compact: cols / 2 dword rows of cells, cols / 2 halfword rows of query codes, and what the look-ahead of the
+            // query plane reads past its end (the cells' look-ahead lands in the query plane); wide: 2 columns of look-ahead
+            // (four-bit query codes for the two longest compact classes: see bsw_lane_kernel)
+            const int kind = fmt ? LANE_WIDE : qhi > 99 ? LANE_COMPACT4 : LANE_COMPACT;
+            const size_t lds = fmt ? (size_t)(cols + 2) * 256 : (size_t)(cols / 2) * (kind == LANE_COMPACT4 ? 320 : 384) + 640;
+            const int fit = (int)((size_t)160 * 1024 / lds), per_cu = fit > 16 ? 16 : fit;
+            const int sk = (LANE_NRANGE - 1 - r) & 3;          // the launch's ordinal in its format, longest first
+            hipStream_t sc = sk == 0 ? c.s : c.ss->side[sk - 1];
+            const int64_t cap = (int64_t)c.cus * per_cu;
+            const int rlo = fmt * (LANE_QMAX + 1) + qlo, rhi = fmt * (LANE_QMAX + 1) + qhi, slot = fmt * LANE_NRANGE + r;
+            Stage st(names[fmt][r], sc);
+            // unpacked bases: the compact 80..99 class runs on the register kernel; GBX_BSW_LANE_REG=0 keeps it on bsw_lane_kernel
+            if (fmt == 0 && !c.P.packed && qhi == 99 && !switched_off("GBX_BSW_LANE_REG")) { launch_lane_reg(c, sc, want, rlo, rhi, slot); continue; }
+            hipLaunchKernelGGL(lane_kernels[c.P.packed][kind][c.sym], dim3((unsigned)(want < cap ? want : cap)), dim3(64), lds, sc,
+                               c.dev, c.P, c.W, rlo, rhi, cols, slot);
+        }
+    }
+}
+
+// The one-pair-per-wavefront kernel for what no register class holds (CLS_LDS), on the caller's stream
+static int launch_lds(const BswCall &c)
+{
+    const size_t lds_bytes = (size_t)(GBX_BSW_MAX_QLEN + 1) * 2 * sizeof(int);
+    // per device (a process may drive several GPUs through gbx_set_device), set at most once each
+    static std::atomic<uint64_t> attr_set[2];
+    int cur = 0;
+    GBX_HIP(hipGetDevice(&cur));
+    const uint64_t bit = (uint64_t)1 << (cur & 63);
+    if (cur >= 128 || !(attr_set[cur >> 6].load(std::memory_order_acquire) & bit)) {
+        GBX_HIP(hipFuncSetAttribute((const void *)bsw_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        if (cur < 128) attr_set[cur >> 6].fetch_or(bit, std::memory_order_release);
+    }
+    const int blocks = (int)(c.n < (int64_t)c.cus * 2 ? c.n : (int64_t)c.cus * 2);
+    Stage st("bsw_lds", c.s);
+    hipLaunchKernelGGL(bsw_lds_kernel, dim3(blocks), dim3(64), lds_bytes, c.s, c.dev, c.P, c.W, CLS_LDS);
     return GBX_OK;
 }
 
@@ -1606,248 +1800,50 @@ int bsw_launch(const gbx_bsw_params *p, int64_t n,
     if (n == 0) return GBX_OK;
     if (n > 0x7fffffffLL - 1024) { set_error("bsw: more than 2^31 pairs in one call"); return GBX_ERR_UNSUPPORTED; }
     if (work_bytes < bsw_workspace_bytes(n)) { set_error("bsw: workspace too small"); return GBX_ERR_ARG; }
-    BswDev dev;
-    int rc = make_dev_params(p, &dev);
+    BswCall c;
+    int rc = make_dev_params(p, &c.dev);
     if (rc) return rc;
-    const int mode = class_mode_for(n);
-    for (int c = 0; c < NCLS; ++c) dev.remap[c] = CLASS_REMAP[mode][c];
-    BswPairs P = {d_ref, d_qer, d_idr, d_idq, d_len1, d_len2, d_h0, d_out};
-    int32_t *wi = (int32_t *)d_work;
-    int32_t *wl = wi + WS_HDR + 4 * n;
-    BswWork W = {wi, wi + HDR, wi + 2 * HDR, wi + 3 * HDR, wi + WS_HDR, wi + WS_HDR + n, wl, wi + WS_HDR + 3 * n, wi + WS_HDR + 2 * n,
-                 wl + LANE_BINS + 64};
-    dev.lane_on = dev.lane_on && lane_wanted(n) ? 1 : 0;
-    // the classes are independent and every kernel ends in a tail of a few long pairs: they go to four
-    // streams so that a tail overlaps the next class (GBX_BSW_SERIAL=1 keeps them on the caller's stream)
-    static const bool serial = getenv("GBX_BSW_SERIAL") != nullptr;
-    SideStreams *ss = nullptr;
-    std::unique_lock<std::mutex> side_lock;
-    if (!serial) {
-        if ((rc = side_streams(&ss))) return rc;
-        side_lock = std::unique_lock<std::mutex>(ss->mu);
+    c.n = n; c.mode = class_mode_for(n); c.cus = 256;
+    for (int k = 0; k < NCLS; ++k) c.dev.remap[k] = CLASS_REMAP[c.mode][k];
+    c.P = {d_ref, d_qer, d_idr, d_idq, d_len1, d_len2, d_h0, d_out};
+    int32_t *wi = (int32_t *)d_work, *wl = wi + WS_HDR + 4 * n;
+    c.W = {wi, wi + HDR, wi + 2 * HDR, wi + 3 * HDR, wi + WS_HDR, wi + WS_HDR + n, wl, wi + WS_HDR + 3 * n, wi + WS_HDR + 2 * n, wl + LANE_BINS + 64};
+    c.dev.lane_on = c.dev.lane_on && lane_wanted(n) ? 1 : 0;
+    c.sym = c.dev.oe_ins == c.dev.oe_del;
+    c.s = s; c.join_events = join_events; c.prep = prep;
+    if ((rc = side_streams(&c.ss))) return rc;
+    std::unique_lock<std::mutex> side_lock(c.ss->mu);
+    if ((rc = plan_call(c))) return rc;
+    if (c.phase != 2) {
+        if ((rc = queue_prepare(c))) return rc;
+        if (c.phase == 1) return GBX_OK;
     }
-    // A chunk of a pipelined host call: its preparing passes go to the two urgent streams and wait for the uploads only.
-    // On the caller's stream they would queue behind the previous chunk's kernels there, and with them every kernel of
-    // this chunk: the chunks then ran one after the other, each with its own tails (2.5 ms a chunk of 'large' against
-    // 1.9 ms for a third of the job; GBX_BSW_PREP=0 keeps that order).
-    static const bool prep_off = getenv("GBX_BSW_PREP") && atoi(getenv("GBX_BSW_PREP")) == 0;
-    const bool ahead = prep && prep->uploaded && join_events && !serial && !prep_off;
-    hipStream_t s_cls = ahead ? ss->pre[0] : s;
-    // A chunk whose pairs all go to the lane kernels (the host entry has counted: rows_pairs == 0) leaves out the row-kernel
-    // classes, twenty-one near-empty launches that each wait for LDS behind the lane kernels, and its bases stay packed: the
-    // lane kernels read the nibbles (PACKED).  Beside the previous chunk's lane kernels the unpacking took 0.5-1.0 ms
-    // instead of 0.05, and the chunk's kernels wait for it (profiles/r05af_host_timeline.txt).
-    const bool no_rows = dev.lane_on && prep && prep->rows_pairs == 0 && !(getenv("GBX_BSW_SKIP_ROWS") && atoi(getenv("GBX_BSW_SKIP_ROWS")) == 0);
-    const bool packed_lanes = no_rows && prep->ref_packed && !(getenv("GBX_BSW_PACKED_LANES") && atoi(getenv("GBX_BSW_PACKED_LANES")) == 0);
-    // Such a chunk's launch can also come in two calls (BswChunkPrep::phase): the preparing passes as soon as the chunk's index
-    // arrays are up - they read nothing else - and the kernels when its bases are.  A phase-1 call that cannot be split
-    // (a chunk with row-kernel pairs, a switch set) queues nothing and returns 1: the caller then makes one whole call.
-    const int phase = prep ? prep->phase : 0;
-    if (phase && !(ahead && packed_lanes && prep->ev_pre && prep->ev_aux)) {
-        if (phase == 1) return 1;
-        set_error("bsw: the kernels of a chunk whose preparing passes were not queued");
-        return GBX_ERR_ARG;
+    if (c.ahead) {                                               // the kernel streams wait for classify (and, below, for the sort)
+        if ((rc = kernel_streams_wait(c, c.ev_pre))) return rc;
+        // ... and for the bases, which the preparing passes did not
+        if (c.phase == 2 && (rc = kernel_streams_wait(c, prep->uploaded))) return rc;
     }
-    hipEvent_t ev_pre = phase ? prep->ev_pre : ss ? ss->ev_pre : nullptr, ev_aux = phase ? prep->ev_aux : ss ? ss->ev_aux : nullptr;
-    const bool sort_aside = dev.lane_on && !serial;
-    if (packed_lanes) { P.ref = prep->ref_packed; P.qer = prep->qer_packed; P.packed = 1; }
-    if (phase != 2) {
-        if (ahead) {
-            GBX_HIP(hipStreamWaitEvent(ss->pre[0], prep->uploaded, 0));
-            GBX_HIP(hipStreamWaitEvent(ss->pre[1], prep->uploaded, 0));
-        }
-        if (!packed_lanes && prep && prep->ref_packed) {
-            // from the call's watermark (everything below it is expanded; chunks that ran PACKED expanded nothing) - s_cls waits
-            // for this chunk's uploads, and the host entry queues the chunks' uploads in order, so all of [from, hi) is up
-            const int64_t from_r = prep->unp_r ? *prep->unp_r : prep->lo_r, from_q = prep->unp_q ? *prep->unp_q : prep->lo_q;
-            if ((rc = bsw_unpack4(prep->ref_packed, prep->ref_bytes, from_r, prep->hi_r, s_cls)) ||
-                (rc = bsw_unpack4(prep->qer_packed, prep->qer_bytes, from_q, prep->hi_q, s_cls)))
-                return rc;
-            if (prep->unp_r && prep->hi_r > *prep->unp_r) *prep->unp_r = prep->hi_r;
-            if (prep->unp_q && prep->hi_q > *prep->unp_q) *prep->unp_q = prep->hi_q;
-        }
-        GBX_HIP(hipMemsetAsync(d_work, 0, WS_HDR * sizeof(int32_t), s_cls));
-        // The lane sort (0.3 ms on 'large': two passes of scattered atomics) runs on a side stream of its own, beside
-        // classify and the row-kernel classes on the caller's stream, which do not need it; the lane launches wait for it.
-        if (dev.lane_on) {
-            hipStream_t so = s;
-            if (ahead) {
-                so = ss->pre[1];
-                GBX_HIP(hipMemsetAsync(wl, 0, (size_t)WS_LANE * sizeof(int32_t), so));
-            } else {
-                GBX_HIP(hipMemsetAsync(wl, 0, (size_t)WS_LANE * sizeof(int32_t), s));
-                if (sort_aside) {
-                    if ((rc = ss->fork(s))) return rc;
-                    so = ss->side[SideStreams::N - 1];
-                }
-            }
-            Stage st("bsw_lane_sort", so);
-            const int sblocks = (int)((n + 255) / 256);
-            hipLaunchKernelGGL(bsw_lane_sort_kernel, dim3(sblocks), dim3(256), 0, so, dev, P, n, W, 0);
-            hipLaunchKernelGGL(bsw_lane_scan_kernel, dim3(1), dim3(1024), 0, so, W);
-            hipLaunchKernelGGL(bsw_lane_sort_kernel, dim3(sblocks), dim3(256), 0, so, dev, P, n, W, 1);
-            if (sort_aside) GBX_HIP(hipEventRecord(ev_aux, so));
-        }
-        const int cblocks = (int)((n + CLS_THREADS - 1) / CLS_THREADS);
-        {
-            Stage st("bsw_classify", s_cls);
-            hipLaunchKernelGGL(bsw_classify_kernel, dim3(cblocks), dim3(CLS_THREADS), 0, s_cls, dev, P, n, W, 0);
-            hipLaunchKernelGGL(bsw_scan_kernel, dim3(1), dim3(HDR), 0, s_cls, W);
-            hipLaunchKernelGGL(bsw_classify_kernel, dim3(cblocks), dim3(CLS_THREADS), 0, s_cls, dev, P, n, W, 1);
-        }
-        if (ahead) GBX_HIP(hipEventRecord(ev_pre, s_cls));
-        GBX_HIP(hipGetLastError());
-        if (phase == 1) return GBX_OK;
-    }
-    if (ahead) {                                                 // the kernel streams wait for classify (and, below, for the sort)
-        GBX_HIP(hipStreamWaitEvent(s, ev_pre, 0));
-        for (int k = 0; k < SideStreams::N; ++k) GBX_HIP(hipStreamWaitEvent(ss->side[k], ev_pre, 0));
-        if (phase == 2) {                                        // ... and for the bases, which the preparing passes did not
-            GBX_HIP(hipStreamWaitEvent(s, prep->uploaded, 0));
-            for (int k = 0; k < SideStreams::N; ++k) GBX_HIP(hipStreamWaitEvent(ss->side[k], prep->uploaded, 0));
-        }
-    }
-
-    int dev_id = 0, cus = 256;
+    int dev_id = 0;
     (void)hipGetDevice(&dev_id);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev_id);
-    // persistent groups: enough blocks to fill the chip, never more groups than pairs
-    auto grid_for = [&](int groups_per_block, int blocks_per_cu) {
-        int64_t want = (n + groups_per_block - 1) / groups_per_block;
-        int64_t cap = (int64_t)cus * blocks_per_cu;
-        return (int)(want < cap ? want : cap);
-    };
-    // the grid is the number of blocks that are resident at once (occupancy query), so that the static
-    // round-robin over the longest-first list starts every group on the longest pairs together
-    const bool sym = dev.oe_ins == dev.oe_del;
-    const RowShape *shapes = class_shapes();
-    if (!serial && !sort_aside && !ahead && (rc = ss->fork(s))) return rc;
-    // The row-kernel classes first.  With the lane path on they hold next to nothing (what the lane kernels cannot take):
-    // twenty near-empty launches, all on the caller's stream, in the shadow of the lane sort.
-    // (none at all when the host entry has counted the chunk's pairs and the lane kernels take every one: no_rows)
-    int launched = 0;
-    for (int c = 0; c < NCLS - 1 && !no_rows; ++c) {
-        if (CLASS_REMAP[mode][c] != c) continue;          // this class's pairs run on a wider class's kernel
-        // Four kernel streams when the inputs are resident.  The host pipeline (join_events) uses three: the
-        // runtime maps streams onto four hardware queues, and with all four busy with class kernels its copy
-        // stream shares one and the uploads stall behind kernels (measured; GBX_BSW_KSTREAMS overrides).
-        static const int nk_env = getenv("GBX_BSW_KSTREAMS") ? atoi(getenv("GBX_BSW_KSTREAMS")) : 0;
-        const int nk = nk_env > 0 ? nk_env : join_events ? 3 : 4;
-        const int lane_k = mode ? launched++ % (nk > 4 ? 4 : nk) : nk >= 4 ? (c & 3) : c % nk;
-        hipStream_t sc = serial || sort_aside || lane_k == 0 ? s : ss->side[lane_k - 1];
-        RowKernel *k = find_row_kernel(shapes[c].lpp, shapes[c].cpl);
-        if (!k) { set_error("bsw: no row kernel for class %d", c); return GBX_ERR_UNSUPPORTED; }
-        int bpc = k->bpc[sym].load(std::memory_order_relaxed);
-        if (!bpc) {
-            int q = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, k->fn[sym], 256, 0) != hipSuccess || q < 1) {
-                (void)hipGetLastError();
-                q = 2;
-            }
-            bpc = q > 8 ? 8 : q;
-            k->bpc[sym].store(bpc, std::memory_order_relaxed);
-        }
-        Stage st(k->name, sc);
-        hipLaunchKernelGGL(k->fn[sym], dim3(grid_for(256 / k->lpp, bpc)), dim3(256), 0, sc, dev, P, W, c);
-    }
-    if (sort_aside) {                                          // the lane launches need the sorted lists (the sort's own stream has them in order)
-        GBX_HIP(hipStreamWaitEvent(s, ev_aux, 0));
-        for (int k = 0; k + (ahead ? 0 : 1) < SideStreams::N; ++k) GBX_HIP(hipStreamWaitEvent(ss->side[k], ev_aux, 0));
-    }
-    if (dev.lane_on) {
-        // longest queries first, one launch per format and LDS class, spread over the streams; grids = resident wavefronts
-        static const char *names[2][LANE_NRANGE] = {{"bsw_lane_c47", "bsw_lane_c79", "bsw_lane_c99", "bsw_lane_c135", "bsw_lane_c159"},
-                                                    {"bsw_lane_w39", "bsw_lane_w79", "bsw_lane_w103", "bsw_lane_w127", "bsw_lane_w159"}};
-        // The wide launches go first, while the chip is empty: a launch has to be given its LDS before its wavefronts can
-        // see that their list is empty (the usual case for short reads), and behind a working compact launch that wait
-        // held up the stream for up to a millisecond (6.36 -> 6.03 ms on 'large').
-        for (int fmt = 1; fmt >= 0; --fmt) {
-            int nl = 0;
-            for (int r = LANE_NRANGE - 1; r >= 0; --r) {
-                const int qlo = r ? LANE_RANGE_HI[fmt][r - 1] + 1 : 1, qhi = LANE_RANGE_HI[fmt][r];
-                // GBX_BSW_SKIP_EMPTY=1: a class the host entry has counted empty is not launched and takes no stream's turn
-                // (BswChunkPrep::class_pairs).  Measured on 'large', where six of the ten classes are empty, and NOT faster: medians
-                // 9.97 / 10.25 ms with, 9.75 / 9.96 without (profiles/r06h_bsw_skip_empty_ab.txt) - the time an empty launch shows on
-                // its stream is a wait for LDS its working successor would have spent just the same.  Off by default.
-                static const bool skip_on = getenv("GBX_BSW_SKIP_EMPTY") && atoi(getenv("GBX_BSW_SKIP_EMPTY")) == 1;
-                if (skip_on && prep && prep->class_known && prep->class_pairs[fmt * LANE_NRANGE + r] == 0) continue;
-                ++nl;                                          // the launch's ordinal, longest first
-                const int cols = (qhi + 3) & ~1;                   // columns 0..qlen, and even
-                // compact: cols / 2 dword rows of cells, cols / 2 halfword rows of query codes, and what the look-ahead of the
-                // query plane reads past its end (the cells' look-ahead lands in the query plane); wide: 2 columns of look-ahead
-                // (four-bit query codes for the two longest compact classes: see bsw_lane_kernel; GBX_BSW_CODE4=0 / 1 forces none / all)
-                const char *c4e = getenv("GBX_BSW_CODE4");
-                const bool code4 = fmt == 0 && (c4e ? atoi(c4e) != 0 : qhi > 99);
-                const size_t lds = fmt ? (size_t)(cols + 2) * 256 : (size_t)(cols / 2) * (code4 ? 320 : 384) + 640;
-                int per_cu = (int)((size_t)160 * 1024 / lds);
-                if (per_cu > 16) per_cu = 16;
-                const int sk = (nl - 1) & 3;
-                hipStream_t sc = serial || sk == 0 ? s : ss->side[sk - 1];
-                int64_t blocks = (int64_t)cus * per_cu, want = (n + 63) / 64;
-                if (blocks > want) blocks = want;
-                const int rlo = fmt * (LANE_QMAX + 1) + qlo, rhi = fmt * (LANE_QMAX + 1) + qhi, slot = fmt * LANE_NRANGE + r;
-                Stage st(names[fmt][r], sc);
-                // the compact 80..99 class of unpacked bases with its cells in registers (bsw_lane_reg_kernel), as many wavefronts
-                // as its registers allow; GBX_BSW_LANE_REG=0 keeps it on bsw_lane_kernel
-                const char *rege = getenv("GBX_BSW_LANE_REG");           /* read per call: the tests vary it */
-                if (fmt == 0 && !P.packed && qhi == 99 && !(rege && atoi(rege) == 0)) {
-                    static_assert(LANE_RANGE_HI[0][2] == 99, "bsw_lane_reg_kernel instance");
-                    typedef void (*LaneRegFn)(BswDev, BswPairs, BswWork, int, int, int);
-                    static const LaneRegFn reg_fn[2] = {bsw_lane_reg_kernel<false, 99>, bsw_lane_reg_kernel<true, 99>};
-                    static std::atomic<int> reg_bpc[2];                    // resident blocks per CU, cached
-                    const LaneRegFn fn = reg_fn[sym];
-                    std::atomic<int> &bc = reg_bpc[sym];
-                    int bpc = bc.load(std::memory_order_relaxed);
-                    if (!bpc) {
-                        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, (const void *)fn, 64, 0) != hipSuccess || bpc < 1) { (void)hipGetLastError(); bpc = 8; }
-                        bc.store(bpc, std::memory_order_relaxed);
-                    }
-                    int64_t rblocks = (int64_t)cus * bpc;
-                    if (rblocks > want) rblocks = want;
-                    hipLaunchKernelGGL(fn, dim3((unsigned)rblocks), dim3(64), 0, sc, dev, P, W, rlo, rhi, slot);
-                    g_lane_reg_launches.fetch_add(1, std::memory_order_relaxed);
-                    continue;
-                }
-                auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64), lds, sc, dev, P, W, rlo, rhi, cols, slot); };
-                if (P.packed) {
-                    if (fmt == 0 && code4) { if (sym) go(bsw_lane_kernel<true, true, true, true>); else go(bsw_lane_kernel<false, true, true, true>); }
-                    else if (fmt == 0) { if (sym) go(bsw_lane_kernel<true, true, false, true>); else go(bsw_lane_kernel<false, true, false, true>); }
-                    else { if (sym) go(bsw_lane_kernel<true, false, false, true>); else go(bsw_lane_kernel<false, false, false, true>); }
-                } else if (fmt == 0 && code4) {
-                    if (sym) go(bsw_lane_kernel<true, true, true>); else go(bsw_lane_kernel<false, true, true>);
-                } else if (fmt == 0) {
-                    if (sym) go(bsw_lane_kernel<true, true>); else go(bsw_lane_kernel<false, true>);
-                } else {
-                    if (sym) go(bsw_lane_kernel<true, false>); else go(bsw_lane_kernel<false, false>);
-                }
-            }
-        }
+    (void)hipDeviceGetAttribute(&c.cus, hipDeviceAttributeMultiprocessorCount, dev_id);
+    // (with the lane path on, the lane sort has forked the side streams already)
+    if (!c.dev.lane_on && !c.ahead && (rc = c.ss->fork(s))) return rc;
+    if (!c.no_rows) launch_row_classes(c);
+    if (c.dev.lane_on) {
+        // the lane launches need the sorted lists (the sort's own stream, the last side stream unless `ahead`, has them in order)
+        if ((rc = kernel_streams_wait(c, c.ev_aux, c.ahead ? SideStreams::N : SideStreams::N - 1))) return rc;
+        launch_lanes(c);
     }
     // join_events == nullptr: the caller's stream waits for the side streams (everything of this call is then
     // ordered on `s`).  Otherwise nothing waits: one event per stream is recorded (join_events[0] on `s`,
     // join_events[1+k] on side stream k), and `s` and the side streams run on into the caller's next launch:
     // the host pipeline queues chunk after chunk like that, so that the single-wavefront tails of one chunk
     // overlap the next chunk's kernels, and its downloader waits for the events.
-    if (!serial && !join_events && (rc = ss->join(s))) return rc;
-    if (!no_rows) {
-        const size_t lds_bytes = (size_t)(GBX_BSW_MAX_QLEN + 1) * 2 * sizeof(int);
-        // per device (a process may drive several GPUs through gbx_set_device), set at most once each
-        static std::atomic<uint64_t> attr_set[2];
-        int cur = 0;
-        GBX_HIP(hipGetDevice(&cur));
-        const uint64_t bit = (uint64_t)1 << (cur & 63);
-        if (cur >= 128 || !(attr_set[cur >> 6].load(std::memory_order_acquire) & bit)) {
-            GBX_HIP(hipFuncSetAttribute((const void *)bsw_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-            if (cur < 128) attr_set[cur >> 6].fetch_or(bit, std::memory_order_release);
-        }
-        int blocks = (int)(n < (int64_t)cus * 2 ? n : (int64_t)cus * 2);
-        Stage st("bsw_lds", s);
-        hipLaunchKernelGGL(bsw_lds_kernel, dim3(blocks), dim3(64), lds_bytes, s, dev, P, W, CLS_LDS);
-    }
+    if (!join_events && (rc = c.ss->join(s))) return rc;
+    if (!c.no_rows && (rc = launch_lds(c))) return rc;
     if (join_events) {
-        if (!ss && (rc = side_streams(&ss))) return rc;
         GBX_HIP(hipEventRecord(join_events[0], s));
-        for (int k = 0; k < SideStreams::N; ++k) GBX_HIP(hipEventRecord(join_events[1 + k], ss->side[k]));
+        for (int k = 0; k < SideStreams::N; ++k) GBX_HIP(hipEventRecord(join_events[1 + k], c.ss->side[k]));
     }
     GBX_HIP(hipGetLastError());
     return GBX_OK;

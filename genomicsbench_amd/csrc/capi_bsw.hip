@@ -47,7 +47,131 @@ int gbx_bsw_extend_device(const gbx_bsw_params *p, int64_t n,
                       (hipStream_t)stream);
 }
 
-// One device (the calling thread's current one).  `base` = index of pairs[0] in the caller's job (error texts only).
+// Is a pair inside the arenas, and within what the kernels hold?  Outside the arenas is the error a call reports first.
+enum BswPairFault { BSW_PAIR_OK = 0, BSW_PAIR_OUTSIDE, BSW_PAIR_TOO_LONG };
+static inline BswPairFault bsw_pair_fault(int64_t idr, int64_t idq, int64_t len1, int64_t len2, int64_t ref_bytes, int64_t qer_bytes)
+{
+    if (len1 < 0 || len2 < 0 || idr < 0 || idq < 0 || idr + len1 > ref_bytes || idq + len2 > qer_bytes) return BSW_PAIR_OUTSIDE;
+    return len2 > GBX_BSW_MAX_QLEN || len1 > GBX_BSW_MAX_TLEN ? BSW_PAIR_TOO_LONG : BSW_PAIR_OK;
+}
+
+// The arguments of a host call.  `base` = index of pairs[0] in the caller's job (error texts only).
+struct BswHostJob {
+    const gbx_bsw_params *p; int64_t n;
+    const uint8_t *ref; int64_t ref_bytes; const uint8_t *qer; int64_t qer_bytes;
+    const int64_t *idr, *idq; const int32_t *len1, *len2, *h0; gbx_bsw_result *out; int64_t base;
+};
+
+// The device buffers of a host call (ref_p / qer_p: the packed images of the arenas, when the bases go up two per byte)
+struct BswHostBufs {
+    DevBuf ref, qer, idr, idq, l1, l2, h0, out, work, ref_p, qer_p;
+    explicit BswHostBufs(Lane *L) : ref(L), qer(L), idr(L), idq(L), l1(L), l2(L), h0(L), out(L), work(L), ref_p(L), qer_p(L) {}
+};
+
+// The plan of a host call.  One pass over the pairs, in slices of 32 Ki pairs and with a few threads when there are many:
+// validation, and what the pipeline needs to know of them.  Then the pipeline's chunks (chunk c = pairs [cut[c], cut[c + 1])):
+// what each needs of the arenas, and its uploads.
+struct BswHostPlan {
+    static constexpr int64_t SL = 32768;
+    const BswHostJob &j;
+    const std::vector<int64_t> cut = bsw_host_cuts(j.n);
+    const int64_t n_chunks = (int64_t)cut.size() - 1, n_slices = (j.n + SL - 1) / SL;
+    int64_t chunk = 0;                                                  // the largest chunk
+    BswLaneRule rule = {0, 0, 0, 0};                                    // of a launch of `chunk` pairs
+    // per slice: the furthest arena bytes its pairs need; its first failing pair, or -1; the pairs the lane kernels will not take
+    // (BswChunkPrep::rows_pairs); the longest query if every pair has 1 <= qlen <= 256, tlen >= 1 and a small h0 (bsw_launch_direct), else 0
+    std::vector<int64_t> far_r, far_q, bad, slice_rows, plain;
+    // per chunk: the furthest arena bytes it needs, its rows_pairs, and the ranges of the packed arenas that went up with it
+    std::vector<int64_t> need_r, need_q, rows_pairs, lo_r, hi_r, lo_q, hi_q;
+    int64_t up_r = 0, up_q = 0;                                         // the arenas are uploaded up to here
+    explicit BswHostPlan(const BswHostJob &job)
+        : j(job), far_r((size_t)n_slices), far_q(far_r), bad((size_t)n_slices, -1), slice_rows(far_r), plain(far_r), need_r((size_t)n_chunks),
+          need_q(need_r), rows_pairs((size_t)n_chunks, -1), lo_r(need_r), hi_r(need_r), lo_q(need_r), hi_q(need_r)
+    {
+        for (int64_t c = 0; c < n_chunks; ++c) chunk = pairs(c) > chunk ? pairs(c) : chunk;
+        if (bsw_lane_rule(j.p, chunk, &rule) != GBX_OK) rule.on = 0;    // (bad parameters: the launch reports them)
+    }
+    int64_t pairs(int64_t c) const { return cut[(size_t)c + 1] - cut[(size_t)c]; }
+    void check_slice(int64_t sl)
+    {
+        const int64_t a = sl * SL, b = a + SL < j.n ? a + SL : j.n;
+        const int64_t *idr = j.idr, *idq = j.idq;
+        const int32_t *len1 = j.len1, *len2 = j.len2, *h0 = j.h0;
+        int64_t mr = 0, mq = 0, nrows = 0;
+        bool all_plain = true;
+        int maxq = 1;
+        for (int64_t k = a; k < b; ++k) {
+            nrows += !bsw_lane_takes(rule, len2[k], len1[k], h0[k]) && len1[k] != 0 && len2[k] != 0;
+            all_plain = all_plain && len2[k] >= 1 && len2[k] <= 256 && len1[k] >= 1 && h0[k] < 1000000;
+            maxq = len2[k] > maxq ? len2[k] : maxq;
+            if (bsw_pair_fault(idr[k], idq[k], len1[k], len2[k], j.ref_bytes, j.qer_bytes)) { bad[(size_t)sl] = k; return; }
+            const int64_t er = idr[k] + len1[k], eq = idq[k] + len2[k];
+            mr = er > mr ? er : mr; mq = eq > mq ? eq : mq;
+        }
+        far_r[(size_t)sl] = mr; far_q[(size_t)sl] = mq; plain[(size_t)sl] = all_plain ? maxq : 0; slice_rows[(size_t)sl] = nrows;
+    }
+    // slices [s0, s1): checked by a few threads; the lowest failing pair is reported
+    int validate(int64_t s0, int64_t s1)
+    {
+        const int64_t cnt = s1 - s0;
+        const int vt = cnt >= 24 ? 12 : cnt >= 8 ? (int)(cnt / 2) : 1;      // 2.5 ns a pair and thread: 0.9 ms with 4 threads at 2 M pairs
+        std::vector<Helper> th;
+        for (int t = 1; t < vt; ++t) th.emplace_back([this, s0, s1, vt, t] { for (int64_t sl = s0 + t; sl < s1; sl += vt) check_slice(sl); }, true);
+        for (int64_t sl = s0; sl < s1; sl += vt) check_slice(sl);
+        for (auto &x : th) x.join();
+        for (int64_t sl = s0; sl < s1; ++sl) {
+            const int64_t k = bad[(size_t)sl];
+            if (k < 0) continue;
+            const bool too_long = bsw_pair_fault(j.idr[k], j.idq[k], j.len1[k], j.len2[k], j.ref_bytes, j.qer_bytes) == BSW_PAIR_TOO_LONG;
+            set_error(too_long ? "gbx_bsw_extend_host: pair %lld exceeds GBX_BSW_MAX_QLEN/TLEN" : "gbx_bsw_extend_host: pair %lld lies outside the arenas",
+                      (long long)(j.base + k));
+            return too_long ? GBX_ERR_UNSUPPORTED : GBX_ERR_ARG;
+        }
+        return GBX_OK;
+    }
+    void needs(int64_t c)
+    {
+        int64_t mr = 0, mq = 0, rows = 0;
+        // chunks are multiples of 64 pairs, slices of 32768: a slice may straddle two chunks, which only makes
+        // the earlier chunk wait for a few more bytes
+        for (int64_t sl = cut[(size_t)c] / SL; sl < n_slices && sl * SL < cut[(size_t)c + 1]; ++sl) {
+            mr = far_r[(size_t)sl] > mr ? far_r[(size_t)sl] : mr;
+            mq = far_q[(size_t)sl] > mq ? far_q[(size_t)sl] : mq;
+            rows += slice_rows[(size_t)sl];
+        }
+        need_r[(size_t)c] = mr; need_q[(size_t)c] = mq;
+        // (an upper bound: a slice that straddles two chunks counts for both; a short last chunk may run without the lane path)
+        BswLaneRule last = rule;
+        if (pairs(c) != chunk && bsw_lane_rule(j.p, pairs(c), &last) != GBX_OK) last.on = 0;
+        rows_pairs[(size_t)c] = rule.on && last.on ? rows : -1;
+    }
+    // Two upload stages per chunk: its index arrays (stage 2c: all the preparing passes read) and then its bases (2c + 1)
+    void stage(int64_t c, HostPipe &pipe, BswHostBufs &d, bool pack_bases)
+    {
+        const int64_t a = cut[(size_t)c], m = pairs(c);
+        pipe.stage(2 * c, d.idr.as<int64_t>() + a, j.idr + a, m * 8);
+        pipe.stage(2 * c, d.idq.as<int64_t>() + a, j.idq + a, m * 8);
+        pipe.stage(2 * c, d.l1.as<int32_t>() + a, j.len1 + a, m * 4);
+        pipe.stage(2 * c, d.l2.as<int32_t>() + a, j.len2 + a, m * 4);
+        pipe.stage(2 * c, d.h0.as<int32_t>() + a, j.h0 + a, m * 4);
+        int64_t nr = need_r[(size_t)c] > up_r ? need_r[(size_t)c] : up_r;
+        int64_t nq = need_q[(size_t)c] > up_q ? need_q[(size_t)c] : up_q;
+        if (pack_bases) {
+            // packed ranges start at even offsets: round the ends up to even while the arena allows it
+            if ((nr & 1) && nr < j.ref_bytes) ++nr;
+            if ((nq & 1) && nq < j.qer_bytes) ++nq;
+            pipe.stage_pack4(2 * c + 1, d.ref_p.as<uint8_t>() + up_r / 2, j.ref + up_r, (size_t)(nr - up_r));
+            pipe.stage_pack4(2 * c + 1, d.qer_p.as<uint8_t>() + up_q / 2, j.qer + up_q, (size_t)(nq - up_q));
+            lo_r[(size_t)c] = up_r; hi_r[(size_t)c] = nr; lo_q[(size_t)c] = up_q; hi_q[(size_t)c] = nq;
+        } else {
+            pipe.stage(2 * c + 1, d.ref.as<uint8_t>() + up_r, j.ref + up_r, (size_t)(nr - up_r));
+            pipe.stage(2 * c + 1, d.qer.as<uint8_t>() + up_q, j.qer + up_q, (size_t)(nq - up_q));
+        }
+        up_r = nr; up_q = nq;
+    }
+};
+
+// One device (the calling thread's current one).
 static int bsw_host_one(const gbx_bsw_params *p, int64_t n,
                         const uint8_t *ref, int64_t ref_bytes,
                         const uint8_t *qer, int64_t qer_bytes,
@@ -62,95 +186,19 @@ static int bsw_host_one(const gbx_bsw_params *p, int64_t n,
         set_error("gbx_bsw_extend_host: null pointer");
         return GBX_ERR_ARG;
     }
+    const BswHostJob j = {p, n, ref, ref_bytes, qer, qer_bytes, idr, idq, len1, len2, h0, out, base};
     const bool trace = getenv("GBX_HOST_TRACE") != nullptr;     /* timeline of this call on stderr */
     const double t_begin = wall_s();
-    // one pass over the pairs: validation, and per pipeline chunk the furthest arena byte its pairs need
-    const std::vector<int64_t> cut = bsw_host_cuts(n);          // chunk c = pairs [cut[c], cut[c + 1])
-    const int64_t n_chunks = (int64_t)cut.size() - 1;
-    int64_t chunk = 0;                                          // the largest chunk
-    for (int64_t c = 0; c < n_chunks; ++c) chunk = cut[(size_t)c + 1] - cut[(size_t)c] > chunk ? cut[(size_t)c + 1] - cut[(size_t)c] : chunk;
-    std::vector<int64_t> need_r((size_t)n_chunks), need_q((size_t)n_chunks);
-    // slices of 32 Ki pairs, a few threads when there are many; the lowest failing pair is reported
-    const int64_t SL = 32768, n_slices = (n + SL - 1) / SL;
-    std::vector<int64_t> slice_r((size_t)n_slices), slice_q((size_t)n_slices), slice_bad((size_t)n_slices, -1);
-    std::vector<int64_t> slice_rows((size_t)n_slices, 0);   // pairs the lane kernels will not take (BswChunkPrep::rows_pairs)
-    std::vector<int64_t> slice_cls((size_t)n_slices * 10, 0);      // ... and the others per lane launch (BswChunkPrep::class_pairs)
-    // (counted only when the switch that uses the counts is on: the count is ten nanoseconds a pair on the call's critical path -
-    // the first chunk's pairs are checked before anything is uploaded - and took that check from 0.25 to 0.86 ms on 'large')
-    const bool count_classes = getenv("GBX_BSW_SKIP_EMPTY") && atoi(getenv("GBX_BSW_SKIP_EMPTY")) == 1;
-    BswLaneRule rule = {0, 0, 0, 0};
-    if (bsw_lane_rule(p, chunk, &rule) != GBX_OK) rule.on = 0;      // (bad parameters: the launch reports them)
-    std::vector<int> slice_plain((size_t)n_slices, 0);      // longest query if every pair has 1 <= qlen <= 256, tlen >= 1 and a small h0 (bsw_launch_direct), else 0
-    auto check_slice = [&](int64_t sl) {
-        const int64_t a = sl * SL, b = a + SL < n ? a + SL : n;
-        int64_t mr = 0, mq = 0, rows = 0;
-        int64_t cls[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        bool plain = true;
-        int maxq = 1;
-        for (int64_t k = a; k < b; ++k) {
-            const bool takes = bsw_lane_takes(rule, len2[k], len1[k], h0[k]);
-            if (count_classes && takes) ++cls[bsw_lane_class(rule, len2[k], h0[k])];
-            rows += !takes && len1[k] != 0 && len2[k] != 0;
-            plain = plain && len2[k] >= 1 && len2[k] <= 256 && len1[k] >= 1 && h0[k] < 1000000;
-            maxq = len2[k] > maxq ? len2[k] : maxq;
-            const int64_t er = idr[k] + len1[k], eq = idq[k] + len2[k];
-            if (len1[k] < 0 || len2[k] < 0 || idr[k] < 0 || idq[k] < 0 || er > ref_bytes || eq > qer_bytes ||
-                len2[k] > GBX_BSW_MAX_QLEN || len1[k] > GBX_BSW_MAX_TLEN) {
-                slice_bad[(size_t)sl] = k;
-                return;
-            }
-            mr = er > mr ? er : mr; mq = eq > mq ? eq : mq;
-        }
-        slice_r[(size_t)sl] = mr; slice_q[(size_t)sl] = mq; slice_plain[(size_t)sl] = plain ? maxq : 0; slice_rows[(size_t)sl] = rows;
-        for (int c = 0; c < 10; ++c) slice_cls[(size_t)sl * 10 + (size_t)c] = cls[c];
-    };
-    // slices [s0, s1): checked by a few threads; the lowest failing pair is reported
-    auto validate = [&](int64_t s0, int64_t s1) -> int {
-        const int64_t cnt = s1 - s0;
-        const int vt = cnt >= 24 ? 12 : cnt >= 8 ? (int)(cnt / 2) : 1;      // 2.5 ns a pair and thread: 0.9 ms with 4 threads at 2 M pairs
-        std::vector<Helper> th;
-        for (int t = 1; t < vt; ++t) th.emplace_back([&, t] { for (int64_t sl = s0 + t; sl < s1; sl += vt) check_slice(sl); }, true);
-        for (int64_t sl = s0; sl < s1; sl += vt) check_slice(sl);
-        for (auto &x : th) x.join();
-        for (int64_t sl = s0; sl < s1; ++sl) {
-            const int64_t k = slice_bad[(size_t)sl];
-            if (k < 0) continue;
-            if (len1[k] >= 0 && len2[k] >= 0 && idr[k] >= 0 && idq[k] >= 0 && idr[k] + len1[k] <= ref_bytes &&
-                idq[k] + len2[k] <= qer_bytes) {
-                set_error("gbx_bsw_extend_host: pair %lld exceeds GBX_BSW_MAX_QLEN/TLEN", (long long)(base + k));
-                return GBX_ERR_UNSUPPORTED;
-            }
-            set_error("gbx_bsw_extend_host: pair %lld lies outside the arenas", (long long)(base + k));
-            return GBX_ERR_ARG;
-        }
-        return GBX_OK;
-    };
+    auto mark = [&](const char *what, int64_t k) { if (trace) fprintf(stderr, "[gbx host] %8.3f ms %s %lld\n", (wall_s() - t_begin) * 1e3, what, (long long)k); };
+    BswHostPlan plan(j);
+    const int64_t n_chunks = plan.n_chunks, n_slices = plan.n_slices, SL = plan.SL, chunk = plan.chunk;
     // A pipelined call checks the first chunk's pairs, starts its upload, and checks the rest while it is on its way (the
     // whole pass is 0.75 ms at 2 M pairs, and nothing else of the call can start before the first chunk is on the device).
-    const int64_t s_first = n_chunks > 1 && (cut[1] + SL - 1) / SL < n_slices ? (cut[1] + SL - 1) / SL : n_slices;
-    int rc = validate(0, s_first);
+    const int64_t s_first = n_chunks > 1 && (plan.cut[1] + SL - 1) / SL < n_slices ? (plan.cut[1] + SL - 1) / SL : n_slices;
+    int rc = plan.validate(0, s_first);
     if (rc) return rc;
-    std::vector<int64_t> rows_pairs((size_t)n_chunks, -1), cls_pairs((size_t)n_chunks * 10, 0);
-    auto chunk_needs = [&](int64_t c) {
-        int64_t mr = 0, mq = 0, rows = 0;
-        // chunks are multiples of 64 pairs, slices of 32768: a slice may straddle two chunks, which only makes
-        // the earlier chunk wait for a few more bytes
-        for (int64_t sl = cut[(size_t)c] / SL; sl < n_slices && sl * SL < cut[(size_t)c + 1]; ++sl) {
-            mr = slice_r[(size_t)sl] > mr ? slice_r[(size_t)sl] : mr;
-            mq = slice_q[(size_t)sl] > mq ? slice_q[(size_t)sl] : mq;
-            rows += slice_rows[(size_t)sl];
-            for (int k = 0; k < 10; ++k) cls_pairs[(size_t)c * 10 + (size_t)k] += slice_cls[(size_t)sl * 10 + (size_t)k];
-        }
-        need_r[(size_t)c] = mr; need_q[(size_t)c] = mq;
-        // (an upper bound: a slice that straddles two chunks counts for both; a short last chunk may run without the lane path)
-        BswLaneRule last = rule;
-        const int64_t m = cut[(size_t)c + 1] - cut[(size_t)c];
-        if (m != chunk && bsw_lane_rule(p, m, &last) != GBX_OK) last.on = 0;
-        rows_pairs[(size_t)c] = rule.on && last.on ? rows : -1;
-    };
-    chunk_needs(0);
+    plan.needs(0);
     if ((rc = require_device())) return rc;
-    auto mark = [&](const char *what, int64_t k) { if (trace) fprintf(stderr, "[gbx host] %8.3f ms %s %lld\n", (wall_s() - t_begin) * 1e3, what, (long long)k); };
     mark("validated", s_first * SL < n ? s_first * SL : n);
     // Upload, compute and download are pipelined over chunks of pairs (host_pipeline.h).  Chunk k's bases and
     // index slices go up while earlier chunks run; the arenas are uploaded front to back up to the furthest
@@ -162,11 +210,11 @@ static int bsw_host_one(const gbx_bsw_params *p, int64_t n,
     HostLane lane;
     if ((rc = lane.acquire())) return rc;
     Lane *L = lane.l;
-    DevBuf dref(L), dqer(L), didr(L), didq(L), dl1(L), dl2(L), dh0(L), dout(L), dwork(L);
-    if ((rc = dref.alloc((size_t)ref_bytes)) || (rc = dqer.alloc((size_t)qer_bytes)) ||
-        (rc = didr.alloc(n * 8)) || (rc = didq.alloc(n * 8)) || (rc = dl1.alloc(n * 4)) ||
-        (rc = dl2.alloc(n * 4)) || (rc = dh0.alloc(n * 4)) || (rc = dout.alloc(n * sizeof(gbx_bsw_result))) ||
-        (rc = dwork.alloc(wb1 * (size_t)n_chunks)))
+    BswHostBufs d(L);
+    if ((rc = d.ref.alloc((size_t)ref_bytes)) || (rc = d.qer.alloc((size_t)qer_bytes)) ||
+        (rc = d.idr.alloc(n * 8)) || (rc = d.idq.alloc(n * 8)) || (rc = d.l1.alloc(n * 4)) ||
+        (rc = d.l2.alloc(n * 4)) || (rc = d.h0.alloc(n * 4)) || (rc = d.out.alloc(n * sizeof(gbx_bsw_result))) ||
+        (rc = d.work.alloc(wb1 * (size_t)n_chunks)))
         return rc;
     mark("allocated", 0);
     HostPipe pipe(L, (size_t)ref_bytes + (size_t)qer_bytes + (size_t)n * 28, n_chunks > 1, BSW_HOST_WORKERS);
@@ -175,85 +223,55 @@ static int bsw_host_one(const gbx_bsw_params *p, int64_t n,
     // (host_pipeline.h: pack4), the device expands them into the byte arenas the kernels read (bsw_unpack4) - the
     // arenas are most of the upload (2 M pairs: 590 of 640 MB), and PCIe is the longest leg of the call.
     const bool pack_bases = pipe.staged && !(getenv("GBX_BSW_PACK") && atoi(getenv("GBX_BSW_PACK")) == 0);
-    DevBuf dref_p(L), dqer_p(L);
-    if (pack_bases && ((rc = dref_p.alloc((size_t)ref_bytes / 2 + 16)) || (rc = dqer_p.alloc((size_t)qer_bytes / 2 + 16)))) return rc;
-    std::vector<int64_t> lo_r((size_t)n_chunks), hi_r((size_t)n_chunks), lo_q((size_t)n_chunks), hi_q((size_t)n_chunks);
-    int64_t up_r = 0, up_q = 0;
+    if (pack_bases && ((rc = d.ref_p.alloc((size_t)ref_bytes / 2 + 16)) || (rc = d.qer_p.alloc((size_t)qer_bytes / 2 + 16)))) return rc;
     int64_t unp_r = 0, unp_q = 0;       // the byte arenas are expanded up to here (BswChunkPrep::unp_r)
-    // Two upload stages per chunk: its index arrays (stage 2c: all the preparing passes read) and then its bases (2c + 1)
     pipe.upload_stages(2 * n_chunks);
-    auto stage_chunk = [&](int64_t c) {
-        const int64_t a = cut[(size_t)c], m = cut[(size_t)c + 1] - a;
-        pipe.stage(2 * c, didr.as<int64_t>() + a, idr + a, m * 8);
-        pipe.stage(2 * c, didq.as<int64_t>() + a, idq + a, m * 8);
-        pipe.stage(2 * c, dl1.as<int32_t>() + a, len1 + a, m * 4);
-        pipe.stage(2 * c, dl2.as<int32_t>() + a, len2 + a, m * 4);
-        pipe.stage(2 * c, dh0.as<int32_t>() + a, h0 + a, m * 4);
-        int64_t nr = need_r[(size_t)c] > up_r ? need_r[(size_t)c] : up_r;
-        int64_t nq = need_q[(size_t)c] > up_q ? need_q[(size_t)c] : up_q;
-        if (pack_bases) {
-            // packed ranges start at even offsets: round the ends up to even while the arena allows it
-            if ((nr & 1) && nr < ref_bytes) ++nr;
-            if ((nq & 1) && nq < qer_bytes) ++nq;
-            pipe.stage_pack4(2 * c + 1, dref_p.as<uint8_t>() + up_r / 2, ref + up_r, (size_t)(nr - up_r));
-            pipe.stage_pack4(2 * c + 1, dqer_p.as<uint8_t>() + up_q / 2, qer + up_q, (size_t)(nq - up_q));
-            lo_r[(size_t)c] = up_r; hi_r[(size_t)c] = nr; lo_q[(size_t)c] = up_q; hi_q[(size_t)c] = nq;
-        } else {
-            pipe.stage(2 * c + 1, dref.as<uint8_t>() + up_r, ref + up_r, (size_t)(nr - up_r));
-            pipe.stage(2 * c + 1, dqer.as<uint8_t>() + up_q, qer + up_q, (size_t)(nq - up_q));
-        }
-        up_r = nr; up_q = nq;
-    };
-    stage_chunk(0);
+    plan.stage(0, pipe, d, pack_bases);
     if (n_chunks > 1) pipe.keep_open();
     pipe.start();
     mark("pipeline started, chunks", n_chunks);
     if (n_chunks > 1) {
-        if ((rc = validate(s_first, n_slices))) return pipe.finish(rc);
-        for (int64_t c = 1; c < n_chunks; ++c) { chunk_needs(c); stage_chunk(c); }
+        if ((rc = plan.validate(s_first, n_slices))) return pipe.finish(rc);
+        for (int64_t c = 1; c < n_chunks; ++c) { plan.needs(c); plan.stage(c, pipe, d, pack_bases); }
         pipe.seal();
         mark("all chunks staged", n);
     }
     // small jobs of plain pairs: one kernel launch instead of the binning passes and the class kernels
     bool direct = n <= 16384 && n_chunks == 1 && !(getenv("GBX_BSW_DIRECT") && atoi(getenv("GBX_BSW_DIRECT")) == 0);
-    int direct_q = 1;
+    int64_t direct_q = 1;
     for (int64_t sl = 0; sl < n_slices && direct; ++sl) {
-        direct = slice_plain[(size_t)sl] != 0;
-        direct_q = slice_plain[(size_t)sl] > direct_q ? slice_plain[(size_t)sl] : direct_q;
+        direct = plan.plain[(size_t)sl] != 0;
+        direct_q = plan.plain[(size_t)sl] > direct_q ? plan.plain[(size_t)sl] : direct_q;
     }
     if (direct) {
         if ((rc = pipe.wait_stage(0)) || (rc = pipe.wait_stage(1))) return pipe.finish(rc);
         if (pack_bases &&
-            ((rc = bsw_unpack4(dref_p.as<uint8_t>(), dref.as<uint8_t>(), lo_r[0], hi_r[0], L->compute)) ||
-             (rc = bsw_unpack4(dqer_p.as<uint8_t>(), dqer.as<uint8_t>(), lo_q[0], hi_q[0], L->compute))))
+            ((rc = bsw_unpack4(d.ref_p.as<uint8_t>(), d.ref.as<uint8_t>(), plan.lo_r[0], plan.hi_r[0], L->compute)) ||
+             (rc = bsw_unpack4(d.qer_p.as<uint8_t>(), d.qer.as<uint8_t>(), plan.lo_q[0], plan.hi_q[0], L->compute))))
             return pipe.finish(rc);
-        rc = bsw_launch_direct(p, n, direct_q, dref.as<uint8_t>(), dqer.as<uint8_t>(), didr.as<int64_t>(), didq.as<int64_t>(),
-                               dl1.as<int32_t>(), dl2.as<int32_t>(), dh0.as<int32_t>(), dout.as<gbx_bsw_result>(), L->compute);
-        if (!rc) { pipe.fetch(0, out, dout.p, n * sizeof(gbx_bsw_result)); rc = pipe.chunk_launched(0, 0); }
+        rc = bsw_launch_direct(p, n, (int)direct_q, d.ref.as<uint8_t>(), d.qer.as<uint8_t>(), d.idr.as<int64_t>(), d.idq.as<int64_t>(),
+                               d.l1.as<int32_t>(), d.l2.as<int32_t>(), d.h0.as<int32_t>(), d.out.as<gbx_bsw_result>(), L->compute);
+        if (!rc) { pipe.fetch(0, out, d.out.p, n * sizeof(gbx_bsw_result)); rc = pipe.chunk_launched(0, 0); }
         return pipe.finish(rc);
     }
     for (int64_t c = 0; c < n_chunks; ++c) {
-        const int64_t a = cut[(size_t)c], m = cut[(size_t)c + 1] - a;
+        const int64_t a = plan.cut[(size_t)c], m = plan.pairs(c);
         // pipelined calls: no barrier between the chunks, the launch records one event per kernel stream, and what
         // prepares a chunk (classify, the lane sort; unpacking, if it has row-kernel pairs) waits for its uploads only
         // (BswChunkPrep) - in two calls where the launch allows it: the preparing passes behind the index arrays, while
         // the bases are still on their way, the kernels behind the bases
         hipEvent_t *je = n_chunks > 1 ? pipe.join_events(c) : nullptr;
-        BswChunkPrep prep = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, rows_pairs[(size_t)c], 0, L->ev_pre, L->ev_aux};
+        BswChunkPrep prep = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, plan.rows_pairs[(size_t)c], 0, L->ev_pre, L->ev_aux};
         if (pack_bases) {
-            prep.ref_packed = dref_p.as<uint8_t>(); prep.ref_bytes = dref.as<uint8_t>();
-            prep.qer_packed = dqer_p.as<uint8_t>(); prep.qer_bytes = dqer.as<uint8_t>();
-            prep.lo_r = lo_r[(size_t)c]; prep.hi_r = hi_r[(size_t)c]; prep.lo_q = lo_q[(size_t)c]; prep.hi_q = hi_q[(size_t)c];
+            prep.ref_packed = d.ref_p.as<uint8_t>(); prep.ref_bytes = d.ref.as<uint8_t>();
+            prep.qer_packed = d.qer_p.as<uint8_t>(); prep.qer_bytes = d.qer.as<uint8_t>();
+            prep.lo_r = plan.lo_r[(size_t)c]; prep.hi_r = plan.hi_r[(size_t)c]; prep.lo_q = plan.lo_q[(size_t)c]; prep.hi_q = plan.hi_q[(size_t)c];
             prep.unp_r = &unp_r; prep.unp_q = &unp_q;
         }
-        if (count_classes && rows_pairs[(size_t)c] >= 0) {   // (counted with the rule this chunk's launch applies)
-            prep.class_known = 1;
-            for (int k = 0; k < 10; ++k) prep.class_pairs[k] = cls_pairs[(size_t)c * 10 + (size_t)k];
-        }
         auto launch = [&]() {
-            return bsw_launch(p, m, dref.as<uint8_t>(), dqer.as<uint8_t>(), didr.as<int64_t>() + a, didq.as<int64_t>() + a,
-                              dl1.as<int32_t>() + a, dl2.as<int32_t>() + a, dh0.as<int32_t>() + a,
-                              dout.as<gbx_bsw_result>() + a, (char *)dwork.p + wb1 * (size_t)c, wb1, L->compute, je, &prep);
+            return bsw_launch(p, m, d.ref.as<uint8_t>(), d.qer.as<uint8_t>(), d.idr.as<int64_t>() + a, d.idq.as<int64_t>() + a,
+                              d.l1.as<int32_t>() + a, d.l2.as<int32_t>() + a, d.h0.as<int32_t>() + a,
+                              d.out.as<gbx_bsw_result>() + a, (char *)d.work.p + wb1 * (size_t)c, wb1, L->compute, je, &prep);
         };
         static const bool split_off = getenv("GBX_BSW_SPLIT_PREP") && atoi(getenv("GBX_BSW_SPLIT_PREP")) == 0;
         bool split = je && pipe.stage_event() && !split_off;
@@ -271,7 +289,7 @@ static int bsw_host_one(const gbx_bsw_params *p, int64_t n,
         prep.uploaded = je ? pipe.stage_event() : nullptr;
         rc = launch();
         if (!rc) {
-            pipe.fetch(c, out + a, dout.as<gbx_bsw_result>() + a, m * sizeof(gbx_bsw_result));
+            pipe.fetch(c, out + a, d.out.as<gbx_bsw_result>() + a, m * sizeof(gbx_bsw_result));
             rc = pipe.chunk_launched(c, je ? Lane::JOIN_EVENTS : 0);
         }
         if (rc) return pipe.finish(rc);
@@ -290,8 +308,7 @@ static bool bsw_call_ok(const gbx_bsw_params *p, int64_t n, const uint8_t *ref, 
 {
     if (!p || n <= 0 || !ref || !qer || !idr || !idq || !len1 || !len2 || !h0 || !out || ref_bytes < 0 || qer_bytes < 0) return false;
     return !any_bad_unit(n, host_workers(BSW_HOST_WORKERS), [&](int64_t j) {
-        return idr[j] < 0 || idq[j] < 0 || len1[j] < 0 || len2[j] < 0 || idr[j] + len1[j] > ref_bytes || idq[j] + len2[j] > qer_bytes ||
-               len2[j] > GBX_BSW_MAX_QLEN || len1[j] > GBX_BSW_MAX_TLEN;
+        return bsw_pair_fault(idr[j], idq[j], len1[j], len2[j], ref_bytes, qer_bytes) != BSW_PAIR_OK;
     });
 }
 
@@ -410,8 +427,8 @@ int gbx_bsw_extend_seqpairs(const gbx_bsw_params *p, gbx_seqpair *pairs, int64_t
         int64_t sr = 0, sq = 0;
         for (int64_t k = lo; k < hi; ++k) {
             const gbx_seqpair &sp = pairs[k];
-            if (sp.len1 < 0 || sp.len2 < 0 || sp.idr < 0 || sp.idq < 0 || sp.idr + sp.len1 > ref_bytes ||
-                sp.idq + sp.len2 > qer_bytes) { part_bad[(size_t)t] = k; return; }
+            // (a pair over GBX_BSW_MAX_QLEN/TLEN goes on: the host entry below names it)
+            if (bsw_pair_fault(sp.idr, sp.idq, sp.len1, sp.len2, ref_bytes, qer_bytes) == BSW_PAIR_OUTSIDE) { part_bad[(size_t)t] = k; return; }
             idr[k] = sp.idr; idq[k] = sp.idq; l1[k] = sp.len1; l2[k] = sp.len2; h0[k] = sp.h0;
             sr += (sp.len1 + 3) & ~3; sq += (sp.len2 + 3) & ~3;
         }

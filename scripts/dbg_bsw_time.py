@@ -1,5 +1,5 @@
 """Development aid: device-resident time of the bsw 'large' job (2 M pairs), median of 15 runs; for A/B runs of tuning
-environment variables (GBX_BSW_LANE_CLASSES, GBX_LIB, ...) on one box."""
+environment variables (GBX_BSW_LANE_REG, GBX_LIB, ...) on one box."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

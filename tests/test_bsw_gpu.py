@@ -200,8 +200,8 @@ def test_seqpair_dropin_strided_slots():
 
 def test_direct_launch_for_small_plain_jobs(monkeypatch):
     """Host-entry jobs of up to 16 Ki pairs whose queries are 1..256 long (no empty sequence) run as a single
-    launch of the 8x16 or 16x16 kernel in input order, without the binning passes: same results as the class path and the
-    oracle; a job with one empty or long query takes the class path."""
+    launch of one row kernel (64x3 / 64x4, or 16x8 .. 16x16: test_direct_launch_shapes) in input order, without the binning passes:
+    same results as the class path and the oracle; a job with one empty or long query takes the class path."""
     p = make_params()
     for n, seed in ((1, 5), (63, 6), (512, 7), (5000, 8), (16384, 9)):
         b = gen_bsw(n, seed)
@@ -350,3 +350,38 @@ def test_direct_launch_shapes(n, max_q, monkeypatch):
     for shape in ("64x4", "16x16"):
         monkeypatch.setenv("GBX_BSW_DIRECT_SHAPE", shape)
         assert_same(extend_host(p, b), want, b)
+
+
+# ---- launch census: which kernels one call of the class path launches ----------------------------------------------------
+# The row shape of class c (bsw_kernels.hip: row_kernels[c]) and the classes each mode keeps (CLASS_REMAP): the sets below are
+# read off those two tables, not measured.
+ROW_SHAPES = ["2x4", "2x8", "2x12", "2x16", "2x20", "2x24", "4x14", "4x16", "4x18", "4x20", "4x22", "4x24",
+              "8x13", "8x14", "8x15", "8x16", "16x10", "16x12", "16x16", "64x16"]
+CENSUS_ROWS = {"0": ROW_SHAPES, "1": ["2x16", "4x16", "4x24", "8x16", "16x16", "64x16"], "2": ["8x16", "16x16", "64x16"]}
+LANE_NAMES = ["bsw_lane_c47", "bsw_lane_c79", "bsw_lane_c99", "bsw_lane_c135", "bsw_lane_c159",
+              "bsw_lane_w39", "bsw_lane_w79", "bsw_lane_w103", "bsw_lane_w127", "bsw_lane_w159"]
+
+
+@pytest.mark.parametrize("mode", ["0", "1", "2"])
+def test_launch_census_of_the_class_path(mode, lane, monkeypatch):
+    """One single-chunk host call with the lane path on launches every lane kernel once (ten names: an empty class is launched
+    too), bsw_lds once, and one row kernel per class that the class mode keeps - no other bsw_rows_* name.  The results are pinned
+    against the oracle everywhere; this pins which kernels produced them.  The generated pairs all qualify for the lane kernels,
+    and a call that has counted that leaves the row classes out (BswChunkPrep::rows_pairs), so GBX_BSW_SKIP_ROWS=0 keeps them in."""
+    monkeypatch.setenv("GBX_BSW_CLASSMODE", mode)
+    monkeypatch.setenv("GBX_COMBINE", "0")
+    monkeypatch.setenv("GBX_BSW_SKIP_ROWS", "0")
+    monkeypatch.delenv("GBX_BSW_HOST_CHUNK", raising=False)
+    p = make_params()
+    b = gen_bsw(2000, 51)
+    want = O.bsw_oracle(p, b, 4)
+    N.profile_begin()
+    got = extend_host(p, b)
+    prof = N.profile_end(256)
+    assert_same(got, want, b)
+    launches = {k: c for k, (ms, c) in prof.items()}
+    print(sorted(launches.items()))
+    for name in LANE_NAMES + ["bsw_lds"]:
+        assert launches.get(name) == 1, (name, launches)
+    rows = {k: c for k, c in launches.items() if k.startswith("bsw_rows_")}
+    assert rows == {"bsw_rows_" + s: 1 for s in CENSUS_ROWS[mode]}, rows
