@@ -51,7 +51,7 @@ struct Stage {
 //   GBX_GUARD_TRIP(var, kernel, loop, unit) true when the bound is exhausted (constant false in the product build)
 //   GBX_GUARD_CHECK(what)                   in a launch function, after its launches: hipDeviceSynchronize() (the whole device, other
 //                                           callers' streams included: the guard build is diagnostic only and its timings mean nothing), then a record becomes an error
-enum { GBX_GK_BSW = 1, GBX_GK_CHAIN = 2, GBX_GK_PHMM = 3, GBX_GK_POA = 4, GBX_GK_ABEA = 5, GBX_GK_FMI = 6, GBX_GK_PILEUP = 8, GBX_GK_DBG = 9 };
+enum { GBX_GK_BSW = 1, GBX_GK_CHAIN = 2, GBX_GK_PHMM = 3, GBX_GK_POA = 4, GBX_GK_ABEA = 5, GBX_GK_FMI = 6, GBX_GK_PILEUP = 8, GBX_GK_DBG = 9, GBX_GK_MEM = 10 };
 #ifdef GBX_LOOP_GUARD
 namespace { __device__ unsigned long long gbx_guard_word; }      // one per translation unit
 __device__ inline bool gbx_guard_report(int kernel, int loop, long long unit)
@@ -176,6 +176,18 @@ int fmi_sal_launch(const gbx_fmi_index *idx, const void *d_index, const gbx_fmi_
                    const int64_t *d_n_smem, int64_t smem_cap, int32_t max_occ, int64_t *d_pos, int64_t pos_cap, int64_t *d_pos_off,
                    int64_t *d_n_pos, void *d_work, size_t work_bytes, hipStream_t s);
 int fmi_sal_read_steps(const void *d_work, int64_t *steps, int64_t *max_steps, hipStream_t s);
+
+// ---- seed chaining (mem_chain_kernels.hip)
+struct MemChainIo {                  // the device arguments of gbx_mem_chain_device
+    const gbx_fmi_smem *smems; const int64_t *n_smem; int64_t smem_cap; const int64_t *smem_off;
+    const int64_t *pos; const int64_t *n_pos; int64_t pos_cap; const int64_t *pos_off;
+    const int64_t *read_off; const int32_t *read_len;
+    int64_t l_pac; int32_t n_contigs; const int64_t *contig_off;
+    gbx_mem_chain *chains; int64_t chain_cap; int64_t *chain_off;
+    gbx_bsw_seed *seeds; int64_t seed_cap; int32_t *l_rep; int64_t *n_chains, *n_seeds;
+};
+size_t mem_chain_workspace_bytes(int64_t n_reads, int64_t smem_cap, int64_t pos_cap);
+int mem_chain_launch(const gbx_mem_chain_params *p, int64_t n_reads, const MemChainIo &io, void *d_work, size_t work_bytes, hipStream_t s);
 
 // ---- kmer (kmer_kernels.hip)
 size_t kmer_workspace_bytes(int32_t k, int64_t n_reads);

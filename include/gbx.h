@@ -654,6 +654,79 @@ int gbx_fmi_sal_device(const gbx_fmi_index *idx, const void *d_index, const gbx_
 /* LF steps of the last gbx_fmi_sal_device call on this workspace: their total and the longest walk of one hit. */
 int gbx_fmi_sal_steps(const void *d_work, int64_t *steps, int64_t *max_steps, void *stream);
 
+/* ---- seed chaining (bwa-mem's mem_chain, mem_chain_flt and the window of mem_chain2aln: the step between the suffix-array
+ * lookup and gbx_bsw_extend_seeds_*).  UNPINNED by a compiled reference (bwa's source is not part of the reference tree):
+ * the rules are restated in full in DESIGN 3.10 and tests/mem_chain_ref.py, and pinned by that restatement.
+ * Per read r: its SMEMs smems[smem_off[r] .. smem_off[r+1]) in order, SMEM j's hits pos[pos_off[j] .. pos_off[j+1]) in order
+ * (a hit of -1 is skipped), text coordinates in [0, 2 L), L = l_pac, forward strand [0, L).  A seed is (qbeg = m,
+ * len = n + 1 - m, rbeg = hit).  Contigs: contig_off[n_contigs + 1], forward coordinates, strictly increasing from 0 to L.
+ *   chaining  a seed whose interval crosses L or a contig boundary is skipped; `lower` = the chain with the greatest
+ *             pos <= rbeg (pos = its first seed's rbeg; among equal pos the one created last: bwa's pick depends on its
+ *             B-tree's shape); the seed merges into it (contained: dropped; same contig and strand, y >= 0, |x - y| <= w,
+ *             x - last.len and y - last.len below max_chain_gap: appended) or starts a new chain
+ *   l_rep     bwa's frac_rep numerator: the query bases covered by SMEMs with s > max_occ
+ *   filter    weight = min(query cover, reference cover); chains below min_chain_weight go; the rest, by weight descending
+ *             (ties: by pos, then creation), through mem_chain_flt's overlap scan with mask_level, drop_ratio (fp32) and
+ *             min_seed_len, the rescue through `first`, and the max_chain_extend cap; kept = 3 no overlap, 2 overlaps a
+ *             better chain, 1 the first chain shadowed by a kept one.  Alt contigs are not modelled (is_alt = 0).
+ *   window    [rmax0, rmax1): min / max over the chain's seeds of the seed's start / end moved out by the rest of the read and
+ *             the longest gap its score pays for (at most 2 w), clamped to [0, 2 L], cut at L and clipped to the contig
+ * Output: the kept chains of every read, in read order and the filter's order, and for every seed of every kept chain, in
+ * chain order then seed order, a gbx_bsw_seed (qoff = read_off[r], lq = read_len[r], roff = rmax0, rlen = rmax1 - rmax0,
+ * rbeg relative to rmax0) for an extension whose ref arena is the 2 L-byte text and whose qer arena is the reads.
+ * Not modelled: bwa's ordering of a chain's seeds by score, the skip of seeds an earlier alignment covers, seedcov. */
+typedef struct gbx_mem_chain_params {
+    int32_t w;                       /* 100 */
+    int32_t max_chain_gap;           /* 10000 */
+    int32_t max_occ;                 /* 500: the value the hits were sampled with (l_rep only) */
+    int32_t min_seed_len;            /* 19 */
+    int32_t min_chain_weight;        /* 0 */
+    int32_t max_chain_extend;        /* 1 << 30 */
+    float   mask_level, drop_ratio;  /* 0.5, 0.5 */
+    int32_t a, o_del, e_del, o_ins, e_ins;   /* 1, 6, 1, 6, 1: the match score and gap costs of the extension */
+    int32_t pad_;
+} gbx_mem_chain_params;
+void gbx_mem_chain_default_params(gbx_mem_chain_params *p);
+
+typedef struct gbx_mem_chain {       /* 56 bytes */
+    int64_t pos;                     /* the first seed's rbeg */
+    int64_t seed_off;                /* its seeds are seeds[seed_off .. seed_off + n_seeds) */
+    int64_t rmax0, rmax1;            /* the window, text coordinates */
+    int32_t read, contig, n_seeds, weight, kept, pad_;
+} gbx_mem_chain;
+
+/* Device path.  All pointers are device pointers; asynchronous on `stream`, no host synchronisation inside.  The SMEM and
+ * hit counts are read on the device (*d_n_smem, *d_n_pos: the d_n_out of gbx_fmi_smem_device and the d_n_pos of
+ * gbx_fmi_sal_device on the same stream; at most smem_cap / pos_cap are used), so the call chains behind the two.
+ * Written: d_chains[chain_cap], d_chain_off[n_reads + 1], d_seeds[seed_cap], d_l_rep[n_reads], *d_n_chains, *d_n_seeds.  A
+ * count above its capacity reports the need: nothing past the capacity is written (d_chain_off and chain.seed_off keep the
+ * true offsets).  The seed records from *d_n_seeds up to seed_cap are zeroed (len = 0 breaks the seed rules: the extension
+ * answers all -1), so gbx_bsw_extend_seeds_device can follow on the stream for seed_cap seeds without the count.  There are
+ * never more seeds than hits: seed_cap = pos_cap always suffices.  work: gbx_mem_chain_workspace_bytes(n_reads, smem_cap,
+ * pos_cap) bytes; every read whose hits lie inside pos_cap is chained in full, whatever its hit and chain count. */
+size_t gbx_mem_chain_workspace_bytes(int64_t n_reads, int64_t smem_cap, int64_t pos_cap);
+int gbx_mem_chain_device(const gbx_mem_chain_params *p, int64_t n_reads,
+                         const gbx_fmi_smem *d_smems, const int64_t *d_n_smem, int64_t smem_cap, const int64_t *d_smem_off,
+                         const int64_t *d_pos, const int64_t *d_n_pos, int64_t pos_cap, const int64_t *d_pos_off,
+                         const int64_t *d_read_off, const int32_t *d_read_len,
+                         int64_t l_pac, int32_t n_contigs, const int64_t *d_contig_off,
+                         gbx_mem_chain *d_chains, int64_t chain_cap, int64_t *d_chain_off,
+                         gbx_bsw_seed *d_seeds, int64_t seed_cap, int32_t *d_l_rep, int64_t *d_n_chains, int64_t *d_n_seeds,
+                         void *d_work, size_t work_bytes, void *stream);
+
+/* Host-buffer entry.  Checked before a device is touched: the parameters (w >= 0, e_del and e_ins >= 1), smem_off and
+ * pos_off (monotone, inside n_smem / n_pos), read_len >= 0, the contig table.  *n_chains / *n_seeds = the counts; one above
+ * its capacity gives GBX_ERR_ARG with the needed counts there and in gbx_last_error() (chains and seeds are then not
+ * written; chain_off and l_rep are).  chain_off (n_reads + 1) and l_rep (n_reads) are nullable.  Safe under concurrent host
+ * threads; one device. */
+int gbx_mem_chain_host(const gbx_mem_chain_params *p, int64_t n_reads,
+                       const gbx_fmi_smem *smems, int64_t n_smem, const int64_t *smem_off,
+                       const int64_t *pos, int64_t n_pos, const int64_t *pos_off,
+                       const int64_t *read_off, const int32_t *read_len,
+                       int64_t l_pac, int32_t n_contigs, const int64_t *contig_off,
+                       gbx_mem_chain *chains, int64_t chain_cap, int64_t *chain_off,
+                       gbx_bsw_seed *seeds, int64_t seed_cap, int32_t *l_rep, int64_t *n_chains, int64_t *n_seeds);
+
 /* -------------------------------------------------------------------- kmer
  * Canonical k-mer counting of long reads: Flye's KmerCounter::count as the kmer-cnt benchmark times it
  * (R/benchmarks/kmer-cnt/kmer_cnt.cpp:224-237, vertex_index.cpp:513-612).
