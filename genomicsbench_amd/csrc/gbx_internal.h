@@ -189,6 +189,21 @@ struct MemChainIo {                  // the device arguments of gbx_mem_chain_de
 size_t mem_chain_workspace_bytes(int64_t n_reads, int64_t smem_cap, int64_t pos_cap);
 int mem_chain_launch(const gbx_mem_chain_params *p, int64_t n_reads, const MemChainIo &io, void *d_work, size_t work_bytes, hipStream_t s);
 
+// ---- CIGAR of extended seeds (mem_cigar_kernels.hip)
+struct MemCigarIo {                  // the device arguments of gbx_mem_cigar_device
+    const gbx_bsw_seed *seeds; const gbx_bsw_seed_result *res;
+    const uint8_t *text; int64_t text_bytes; const uint8_t *qer; int64_t qer_bytes;
+    int64_t l_pac; int32_t n_contigs; const int64_t *contig_off;
+    gbx_mem_aln *alns; uint32_t *cigar; int64_t cigar_cap; int64_t *n_cigar;
+};
+size_t mem_cigar_fixed_bytes(int64_t n);                                    // the workspace without the direction room
+size_t mem_cigar_record_z_bytes(const gbx_mem_cigar_params *p, int32_t lq, int32_t lt);
+// host side of the record rules: 0 invalid (rid = -1), 1 valid, -1 a range outside its arena; *z_need = its direction room
+int mem_cigar_record_host(const gbx_mem_cigar_params *p, const gbx_bsw_seed &s, const gbx_bsw_seed_result &r, int64_t text_bytes,
+                          int64_t qer_bytes, int64_t l_pac, size_t *z_need);
+int mem_cigar_launch(const gbx_mem_cigar_params *p, int64_t n, const MemCigarIo &io, void *d_work, size_t work_bytes, int64_t z_bytes,
+                     hipStream_t s);
+
 // ---- kmer (kmer_kernels.hip)
 size_t kmer_workspace_bytes(int32_t k, int64_t n_reads);
 int kmer_launch(const gbx_kmer_params *p, int64_t n_reads, const uint8_t *d_enc, const int64_t *d_read_off, const int32_t *d_read_len,

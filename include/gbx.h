@@ -727,6 +727,74 @@ int gbx_mem_chain_host(const gbx_mem_chain_params *p, int64_t n_reads,
                        gbx_mem_chain *chains, int64_t chain_cap, int64_t *chain_off,
                        gbx_bsw_seed *seeds, int64_t seed_cap, int32_t *l_rep, int64_t *n_chains, int64_t *n_seeds);
 
+/* ---- CIGAR, edit distance and position of extended seeds (bwa-mem's mem_reg2aln / bwa_gen_cigar2 / ksw_global2: the banded
+ * global alignment behind gbx_bsw_extend_seeds_*).  UNPINNED by a compiled reference (bwa's source is not part of the
+ * reference tree): the rules are restated in full in DESIGN 3.11 and tests/mem_cigar_ref.py, and pinned by that restatement.
+ * Record k: seed s = seeds[k], result r = res[k]; read = qer[s.qoff .. s.qoff + s.lq), the region is query [r.qb, r.qe) against
+ * text [s.roff + r.rb, s.roff + r.re) of the 2 L-byte text (L = l_pac, forward strand [0, L)).  Base codes above 4 count as 4.
+ *   invalid   r.qb < 0, qe <= qb, rb >= re, rb < L < re, or a range outside its arena (the text ends at min(text_bytes, 2 L)):
+ *             rid = -1, n_cigar = 0, every other field 0, no CIGAR words
+ *   band      w2 = max(infer_bw(del), infer_bw(ins)) from the region's lengths and r.truesc; above p.w it is cut to r.w
+ *   tries     up to three global alignments with the band min(w2, 4 w), doubled while the score stays below r.truesc - a and
+ *             changes; the last try's CIGAR and score are kept.  w = the band of the last try, tries = their number
+ *   strand    a region at or above L is aligned reversed (query and text), so that indels land leftmost on the forward
+ *             strand; the CIGAR is left in that order
+ *   global    ksw_global2's recurrence and tie-breaks, gaps opened from the diagonal arrival; equal lengths under a band of 0
+ *             are one M run without a DP
+ *   nm        mismatching M positions + inserted bases + deleted bases of every D that is neither the first nor the last op
+ *   position  p = rb, or 2 L - re on the reverse strand; a leading D is removed and added to p, otherwise a trailing D is
+ *             removed; rid / pos from the contig table; soft clips (S) for the read's bases outside [qb, qe)
+ * CIGAR words are len << 4 | op with BAM's numbers (M 0, I 1, D 2, S 4), as gbx_pileup_reads takes them.
+ * Not modelled: the MD string, mapq, sub, alt contigs, supplementary / hard-clip logic, the choice of regions: every valid
+ * record is aligned. */
+typedef struct gbx_mem_cigar_params {    /* 120 bytes */
+    int32_t mat[25];                 /* 5 x 5, mat[t * 5 + q]; a = mat[0].  bwa: 1 / -4 / -1 (N) */
+    int32_t o_del, e_del, o_ins, e_ins;  /* 6, 1, 6, 1 */
+    int32_t w;                       /* 100 */
+} gbx_mem_cigar_params;
+void gbx_mem_cigar_default_params(gbx_mem_cigar_params *p);
+
+typedef struct gbx_mem_aln {         /* 48 bytes */
+    int64_t pos;                     /* 0-based, forward strand, inside contig rid */
+    int64_t cigar_off;               /* its words are cigar[cigar_off .. cigar_off + n_cigar) */
+    int32_t rid;                     /* contig; -1 invalid record, -2 no room for its direction bytes (device entry only) */
+    int32_t is_rev, n_cigar, nm;
+    int32_t score;                   /* of the global alignment */
+    int32_t w, tries, pad_;
+} gbx_mem_aln;
+
+/* Direction bytes one record of query length lq and text length lt can need at most (its band at its widest, 4 w).  The
+ * device entry gives every record, in index order, the room its own band asks for (never more than this); a caller sizes
+ * z_bytes as the number of regions it expects times this value for its longest read and window, or, knowing nothing, grows
+ * z_bytes and repeats the call while records come back with rid = -2. */
+size_t gbx_mem_cigar_record_z_bytes(const gbx_mem_cigar_params *p, int32_t lq, int32_t lt);
+
+/* Device entry.  All pointers are device pointers; asynchronous on `stream`, no host synchronisation inside.  n may be the
+ * seed_cap of the extension before it on the stream: the zeroed seeds past the count have results of all -1 and give invalid
+ * records.  d_text / d_qer: the arenas of gbx_bsw_extend_seeds_device.  Written: d_alns[n], d_cigar[cigar_cap], *d_n_cigar.
+ * alns[k].cigar_off and *d_n_cigar are always the true values; nothing past cigar_cap is written.  work:
+ * gbx_mem_cigar_workspace_bytes(n, z_bytes) bytes, z_bytes of them the direction room; a record whose room ends past z_bytes
+ * gets rid = -2, n_cigar = 0 (the records after it that still fit are aligned).  The output bytes do not depend on the
+ * scheduling. */
+size_t gbx_mem_cigar_workspace_bytes(int64_t n, int64_t z_bytes);
+int gbx_mem_cigar_device(const gbx_mem_cigar_params *p, int64_t n,
+                         const gbx_bsw_seed *d_seeds, const gbx_bsw_seed_result *d_res,
+                         const uint8_t *d_text, int64_t text_bytes, const uint8_t *d_qer, int64_t qer_bytes,
+                         int64_t l_pac, int32_t n_contigs, const int64_t *d_contig_off,
+                         gbx_mem_aln *d_alns, uint32_t *d_cigar, int64_t cigar_cap, int64_t *d_n_cigar,
+                         void *d_work, size_t work_bytes, void *stream);
+
+/* Host-buffer entry.  Checked before a device is touched: the parameters (w >= 0, e_del and e_ins >= 1), the contig table,
+ * and every record that is not the extension's all -1 answer: its read and its region inside the arenas (GBX_ERR_ARG naming
+ * the lowest bad record).  The direction room is sized exactly, so rid = -2 does not occur.  *n_cigar = the word count; more
+ * than cigar_cap gives GBX_ERR_ARG with the need there and in gbx_last_error() (alns are written, cigar is not).  Safe under
+ * concurrent host threads; one device. */
+int gbx_mem_cigar_host(const gbx_mem_cigar_params *p, int64_t n,
+                       const gbx_bsw_seed *seeds, const gbx_bsw_seed_result *res,
+                       const uint8_t *text, int64_t text_bytes, const uint8_t *qer, int64_t qer_bytes,
+                       int64_t l_pac, int32_t n_contigs, const int64_t *contig_off,
+                       gbx_mem_aln *alns, uint32_t *cigar, int64_t cigar_cap, int64_t *n_cigar);
+
 /* -------------------------------------------------------------------- kmer
  * Canonical k-mer counting of long reads: Flye's KmerCounter::count as the kmer-cnt benchmark times it
  * (R/benchmarks/kmer-cnt/kmer_cnt.cpp:224-237, vertex_index.cpp:513-612).
