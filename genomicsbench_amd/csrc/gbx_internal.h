@@ -204,6 +204,18 @@ int mem_cigar_record_host(const gbx_mem_cigar_params *p, const gbx_bsw_seed &s, 
 int mem_cigar_launch(const gbx_mem_cigar_params *p, int64_t n, const MemCigarIo &io, void *d_work, size_t work_bytes, int64_t z_bytes,
                      hipStream_t s);
 
+// ---- alignment regions (mem_regs_kernels.hip)
+struct MemRegsIo {                   // the device arguments of gbx_mem_regs_device
+    const gbx_mem_chain *chains; const int64_t *n_chains; int64_t chain_cap; const int64_t *chain_off;
+    const gbx_bsw_seed *seeds; const int64_t *n_seeds; int64_t seed_cap;
+    const gbx_bsw_seed_result *res; const int32_t *l_rep;
+    gbx_mem_reg *regs; int64_t reg_cap; int64_t *reg_off; int64_t *n_regs;
+    gbx_bsw_seed *sel_seeds; gbx_bsw_seed_result *sel_res; int64_t sel_cap; int64_t *n_sel;
+};
+size_t mem_regs_workspace_bytes(int64_t n_reads, int64_t seed_cap);
+int mem_regs_launch(const gbx_mem_regs_params *p, int64_t n_reads, int64_t read_id0, const MemRegsIo &io, void *d_work, size_t work_bytes,
+                    hipStream_t s);
+
 // ---- kmer (kmer_kernels.hip)
 size_t kmer_workspace_bytes(int32_t k, int64_t n_reads);
 int kmer_launch(const gbx_kmer_params *p, int64_t n_reads, const uint8_t *d_enc, const int64_t *d_read_off, const int32_t *d_read_len,

@@ -674,7 +674,8 @@ int gbx_fmi_sal_steps(const void *d_work, int64_t *steps, int64_t *max_steps, vo
  * Output: the kept chains of every read, in read order and the filter's order, and for every seed of every kept chain, in
  * chain order then seed order, a gbx_bsw_seed (qoff = read_off[r], lq = read_len[r], roff = rmax0, rlen = rmax1 - rmax0,
  * rbeg relative to rmax0) for an extension whose ref arena is the 2 L-byte text and whose qer arena is the reads.
- * Not modelled: bwa's ordering of a chain's seeds by score, the skip of seeds an earlier alignment covers, seedcov. */
+ * bwa's ordering of a chain's seeds by score, the skip of seeds an earlier alignment covers and seedcov are not done here:
+ * they belong to gbx_mem_regs_* (below), which runs behind the extension. */
 typedef struct gbx_mem_chain_params {
     int32_t w;                       /* 100 */
     int32_t max_chain_gap;           /* 10000 */
@@ -745,8 +746,9 @@ int gbx_mem_chain_host(const gbx_mem_chain_params *p, int64_t n_reads,
  *   position  p = rb, or 2 L - re on the reverse strand; a leading D is removed and added to p, otherwise a trailing D is
  *             removed; rid / pos from the contig table; soft clips (S) for the read's bases outside [qb, qe)
  * CIGAR words are len << 4 | op with BAM's numbers (M 0, I 1, D 2, S 4), as gbx_pileup_reads takes them.
- * Not modelled: the MD string, mapq, sub, alt contigs, supplementary / hard-clip logic, the choice of regions: every valid
- * record is aligned. */
+ * Every valid record it is handed is aligned: the choice of regions, sub, mapq and the supplementary flag are made by
+ * gbx_mem_regs_* (below), whose CIGAR list is the input meant for this stage.  Not modelled: the MD string, alt contigs,
+ * hard clips. */
 typedef struct gbx_mem_cigar_params {    /* 120 bytes */
     int32_t mat[25];                 /* 5 x 5, mat[t * 5 + q]; a = mat[0].  bwa: 1 / -4 / -1 (N) */
     int32_t o_del, e_del, o_ins, e_ins;  /* 6, 1, 6, 1 */
@@ -794,6 +796,87 @@ int gbx_mem_cigar_host(const gbx_mem_cigar_params *p, int64_t n,
                        const uint8_t *text, int64_t text_bytes, const uint8_t *qer, int64_t qer_bytes,
                        int64_t l_pac, int32_t n_contigs, const int64_t *contig_off,
                        gbx_mem_aln *alns, uint32_t *cigar, int64_t cigar_cap, int64_t *n_cigar);
+
+/* ---- alignment regions, primary marking and mapping quality (bwa-mem's redundancy skip of mem_chain2aln, mem_sort_dedup_patch,
+ * mem_mark_primary_se, mem_approx_mapq_se and the region choice of mem_reg2sam: the step between gbx_bsw_extend_seeds_* and
+ * gbx_mem_cigar_*).  UNPINNED by a compiled reference (bwa's source is not part of the reference tree): the rules are restated
+ * in full in DESIGN 3.12 and tests/mem_regs_ref.py, and pinned by that restatement.
+ * Read r owns chains[chain_off[r] .. chain_off[r+1]); seed k of a chain is seeds[seed_off + k] with the result res[seed_off + k];
+ * absolute coordinates are s.roff + s.rbeg and s.roff + res.rb / res.re.  A seed whose result has qb < 0 is absent.
+ *   seeds     per chain by (len, index) from the largest down; a seed inside an earlier region of the read on both axes, not
+ *             longer than its seedlen0 by more than .1 lq and within min(gap, region.w) of its diagonal ahead or behind, makes
+ *             no region unless a taken seed t of the chain (t.len >= .95 s.len) overlaps it by s.len >> 2 query bases off its
+ *             diagonal; a taken seed's region is its extension result, seedlen0 = len, rid = the chain's contig, seedcov = the
+ *             length of the chain's seeds inside the region
+ *   dedup     by (re, creation): of two regions of one contig within max_chain_gap that overlap by more than mask_level_redun
+ *             (fp32) of the shorter on both axes the lower score goes (the earlier one on a tie); then by (score desc, rb, qb):
+ *             a region equal to its predecessor in all three goes.  mem_patch_reg (the merge of two collinear regions) and
+ *             n_comp are NOT modelled
+ *   primary   by (score desc, hash_64(read_id0 + r + i), i): a region overlapping an earlier primary by mask_level (fp32) of the
+ *             shorter query span is secondary to it, sets its sub once and counts in its sub_n within max(a + b, o_del + e_del,
+ *             o_ins + e_ins); this is the output order
+ *   mapq      mem_approx_mapq_se with csub = 0 and frac_rep = (float)l_rep[r] / lq; 0 for a secondary.  A region of length 0 gets 0
+ *   report    score >= T and not secondary; the second and later reported regions of a read are supplementary (0x800) and
+ *             their mapq is capped by the first's
+ * Not modelled: mem_patch_reg, alt contigs, MEM_F_ALL, XA, paired-end, bwa's other mapq formula (mapq_coef_len <= 0). */
+typedef struct gbx_mem_regs_params {     /* 64 bytes */
+    int32_t a, b;                        /* 1, 4 */
+    int32_t o_del, e_del, o_ins, e_ins;  /* 6, 1, 6, 1 */
+    int32_t w;                           /* 100 */
+    int32_t max_chain_gap;               /* 10000 */
+    int32_t min_seed_len;                /* 19 */
+    int32_t T;                           /* 30: regions scoring below it are not reported */
+    int32_t mapq_coef_len;               /* 50; must be > 0 (bwa's other mapq formula is not modelled: GBX_ERR_UNSUPPORTED) */
+    float   mapq_coef_fac;               /* (float)log((double)mapq_coef_len), set by the host */
+    float   mask_level, mask_level_redun, drop_ratio;   /* 0.5, 0.95, 0.5 */
+    int32_t pad_;
+} gbx_mem_regs_params;
+void gbx_mem_regs_default_params(gbx_mem_regs_params *p);
+
+typedef struct gbx_mem_reg {             /* 88 bytes */
+    int64_t rb, re;                      /* text coordinates, [0, 2 L) */
+    int64_t seed;                        /* index of the seed record this region was extended from */
+    int32_t qb, qe, read, rid;           /* read: its index in the call; rid = the chain's contig */
+    int32_t score, truesc, sub, sub_n, w, seedcov, seedlen0;
+    int32_t secondary;                   /* -1, or the index (within the read's regions) of the region it is secondary to */
+    int32_t mapq;                        /* 0 for a secondary region */
+    int32_t flag;                        /* bit 0: reported (went to the CIGAR list); 0x800: supplementary */
+    int32_t sel;                         /* its index in the CIGAR list, -1 if not reported */
+    int32_t pad_;
+} gbx_mem_reg;
+
+/* Device path.  All pointers are device pointers; asynchronous on `stream`, no host synchronisation inside.  The chain and seed
+ * counts are read on the device (the d_n_chains / d_n_seeds of gbx_mem_chain_device on the same stream), d_res is the output of
+ * gbx_bsw_extend_seeds_device for those seeds, d_l_rep the chaining's.  Written: d_regs[reg_cap] (every read's regions in the
+ * output order above), d_reg_off[n_reads + 1], *d_n_regs, and the CIGAR list: for every reported region in output order a copy
+ * of its seed record in d_sel_seeds and a result (qb, qe, rb - seed.roff, re - seed.roff, score, truesc, w, sc0 = 0) in
+ * d_sel_res - the fields gbx_mem_cigar_* reads - with *d_n_sel their count.  The records from *d_n_sel up to sel_cap are zeroed
+ * seeds with results of all -1, so gbx_mem_cigar_device can follow on the stream for sel_cap records without the count.  A read
+ * never makes more regions than it has seeds: reg_cap = sel_cap = seed_cap always suffices.  A count above its capacity reports
+ * the need: nothing past the capacity is written (d_reg_off and reg.sel keep the true values).  *d_n_chains > chain_cap or
+ * *d_n_seeds > seed_cap means the chaining before it overflowed: *d_n_regs = *d_n_sel = -1, d_reg_off all 0, no region is made
+ * and the whole CIGAR list is the zeroed tail.  seed_cap below 2^31.  work: gbx_mem_regs_workspace_bytes(n_reads, seed_cap)
+ * bytes; every read is done in full whatever its seed and region count.  The output bytes do not depend on the scheduling. */
+size_t gbx_mem_regs_workspace_bytes(int64_t n_reads, int64_t seed_cap);
+int gbx_mem_regs_device(const gbx_mem_regs_params *p, int64_t n_reads, int64_t read_id0,
+                        const gbx_mem_chain *d_chains, const int64_t *d_n_chains, int64_t chain_cap, const int64_t *d_chain_off,
+                        const gbx_bsw_seed *d_seeds, const int64_t *d_n_seeds, int64_t seed_cap,
+                        const gbx_bsw_seed_result *d_res, const int32_t *d_l_rep,
+                        gbx_mem_reg *d_regs, int64_t reg_cap, int64_t *d_reg_off, int64_t *d_n_regs,
+                        gbx_bsw_seed *d_sel_seeds, gbx_bsw_seed_result *d_sel_res, int64_t sel_cap, int64_t *d_n_sel,
+                        void *d_work, size_t work_bytes, void *stream);
+
+/* Host-buffer entry.  Checked before a device is touched: the parameters (e_del and e_ins >= 1, a >= 1, a + b >= 1, w >= 0,
+ * mapq_coef_len > 0: GBX_ERR_UNSUPPORTED otherwise), chain_off (monotone, inside n_chains) and every chain's seed range (inside
+ * n_seeds): GBX_ERR_ARG naming the lowest offender.  *n_regs / *n_sel = the counts; one above its capacity gives GBX_ERR_ARG
+ * with the needed counts there and in gbx_last_error() (regs and the CIGAR list are then not written; reg_off is).  On success
+ * the CIGAR list is written up to sel_cap, tail included.  reg_off (n_reads + 1) is nullable.  Safe under concurrent host
+ * threads; one device. */
+int gbx_mem_regs_host(const gbx_mem_regs_params *p, int64_t n_reads, int64_t read_id0,
+                      const gbx_mem_chain *chains, int64_t n_chains, const int64_t *chain_off,
+                      const gbx_bsw_seed *seeds, int64_t n_seeds, const gbx_bsw_seed_result *res, const int32_t *l_rep,
+                      gbx_mem_reg *regs, int64_t reg_cap, int64_t *reg_off, int64_t *n_regs,
+                      gbx_bsw_seed *sel_seeds, gbx_bsw_seed_result *sel_res, int64_t sel_cap, int64_t *n_sel);
 
 /* -------------------------------------------------------------------- kmer
  * Canonical k-mer counting of long reads: Flye's KmerCounter::count as the kmer-cnt benchmark times it
