@@ -216,6 +216,20 @@ size_t mem_regs_workspace_bytes(int64_t n_reads, int64_t seed_cap);
 int mem_regs_launch(const gbx_mem_regs_params *p, int64_t n_reads, int64_t read_id0, const MemRegsIo &io, void *d_work, size_t work_bytes,
                     hipStream_t s);
 
+// ---- paired-end (mem_pair_kernels.hip)
+struct MemPairIo {                   // the device arguments of gbx_mem_pair_device
+    const gbx_mem_reg *regs; const int64_t *reg_off; const int64_t *n_regs; int64_t reg_cap;
+    const gbx_bsw_seed *sel_seeds; const gbx_bsw_seed_result *sel_res; int64_t sel_cap;
+    const gbx_bsw_seed *seeds; int64_t seed_cap; const int32_t *l_rep;
+    int64_t l_pac; int32_t n_contigs; const int64_t *contig_off;
+    gbx_mem_pestat *pes; gbx_mem_pair *pairs; gbx_mem_reg *pregs;
+    gbx_bsw_seed *psel_seeds; gbx_bsw_seed_result *psel_res; int64_t psel_cap; int64_t *n_psel;
+};
+size_t mem_pair_workspace_bytes(int64_t n_pairs, int64_t reg_cap, int32_t max_ins);
+// pes_in: a host pointer to the caller's four records (passed to the kernels by value), or null for an estimate from the call
+int mem_pair_launch(const gbx_mem_pair_params *p, int64_t n_pairs, int64_t pair_id0, const MemPairIo &io, const gbx_mem_pestat *pes_in,
+                    void *d_work, size_t work_bytes, hipStream_t s);
+
 // ---- kmer (kmer_kernels.hip)
 size_t kmer_workspace_bytes(int32_t k, int64_t n_reads);
 int kmer_launch(const gbx_kmer_params *p, int64_t n_reads, const uint8_t *d_enc, const int64_t *d_read_off, const int32_t *d_read_len,

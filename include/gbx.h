@@ -878,6 +878,120 @@ int gbx_mem_regs_host(const gbx_mem_regs_params *p, int64_t n_reads, int64_t rea
                       gbx_mem_reg *regs, int64_t reg_cap, int64_t *reg_off, int64_t *n_regs,
                       gbx_bsw_seed *sel_seeds, gbx_bsw_seed_result *sel_res, int64_t sel_cap, int64_t *n_sel);
 
+/* ---- paired-end: insert-size estimate, pairing and the pair decision (bwa-mem's mem_pestat, mem_pair and the decision part of
+ * mem_sam_pe as `bwa mem -S` runs them, that is, without mate rescue: the step between gbx_mem_regs_* and gbx_mem_cigar_*).
+ * UNPINNED by a compiled reference (bwa's source is not part of the reference tree): the rules are restated in full in DESIGN
+ * 3.13 and tests/mem_pair_ref.py, and pinned by that restatement.
+ * A call of n_pairs pairs is the regs stage's output for 2 n_pairs interleaved reads, read 2p + e being end e of pair p, made
+ * with read_id0 = 2 pair_id0 (its hash is then bwa's hash_64((id << 1 | e) + i), so the primary marking stands).  L = l_pac;
+ * a_e[i] = region i of end e in that stage's output order.
+ *   infer_dir(b1, b2)  r1 = b1 >= L, r2 = b2 >= L, p2 = r1 == r2 ? b2 : 2L - 1 - b2; dist = |p2 - b1|,
+ *             dir = (r1 == r2 ? 0 : 1) ^ (p2 > b1 ? 0 : 3)  (0 FF, 1 FR, 2 RF, 3 RR)
+ *   estimate  once per call over all its pairs (skipped when the caller gives pes_in).  Per end top = the region first by
+ *             (score desc, rb, qb); cal_sub = the largest score among the other regions whose query interval overlaps top's by
+ *             e_min - b_max >= min_l * mask_level (fp32), else min_seed_len * a.  A pair is skipped if an end has no region, if
+ *             cal_sub > 0.8 * top.score (double) for either end, or if the tops' rid differ; else (dir, is) = infer_dir(top0.rb,
+ *             top1.rb) counts in direction dir if 1 <= is <= max_ins.  Per direction with n values sorted: n < 10 fails (the rest
+ *             of the record 0); pK = sorted[(int)(K n + .499)], K = .25, .5, .75; low = max((int)(p25 - 2 (p75 - p25) + .499), 1),
+ *             high = (int)(p75 + 2 (p75 - p25) + .499); avg = the mean of the values in [low, high], std = sqrt(S / x) over the
+ *             same x values; then low / high = (int)(p25 -/+ 3 (p75 - p25) + .499), moved out to (int)(avg -/+ 4 std + .499) where
+ *             that lies further out, low at least 1.  All in double, (int) truncating.  Last, a direction that has not failed
+ *             with n < 0.05 max_d n_d fails (its numbers stay).  S = the sum over the values v ascending of
+ *             (double)c[v] * ((v - avg) * (v - avg)), c[v] = the number of values equal to v, every product and sum rounded on
+ *             its own: the one departure from bwa, which adds one value at a time
+ *   pairing   per pair with regions at both ends, unless no_pairing.  Keys over all regions of both ends: fwd = rb < L ? rb :
+ *             2L - 1 - rb, x = rid << 32 | (fwd - contig_off[rid]), y = score << 32 | i << 2 | (rb >= L) << 1 | e; sorted by
+ *             (x, y).  last[4] = -1; for i over the keys, for r = 0, 1: dir = r << 1 | (y_i >> 1 & 1), skipped if pes[dir]
+ *             failed; which = r << 1 | ((y_i & 1) ^ 1); for k from last[which] down to 0 with (y_k & 3) == which: dist = x_i -
+ *             x_k on the whole keys; dist > high ends the walk, dist < low skips k, else k is a candidate with ns = (dist - avg)
+ *             / std, qd = (double)(score_i + score_k) + .721 * log(2. * erfc(fabs(ns) * M_SQRT1_2)) * a + .499, q = qd > 0 ?
+ *             (int)qd : 0 (erfc underflows to 0 far out: log gives -inf, q = 0), X = q << 32 | (hash_64(Y ^ (pair_id << 8)) &
+ *             0xffffffff), Y = k << 32 | i, pair_id = pair_id0 + p; after both r, last[y_i & 3] = i.  No candidate: score = sub =
+ *             n_sub = 0.  Else the best is the largest (X, Y): z[y & 1] = (y & 0xffffffff) >> 2 for its two keys, score = its q,
+ *             sub = the second largest's q (0 with one candidate), n_sub = the candidates other than the best with sub - q <=
+ *             max(a + b, o_del + e_del, o_ins + e_ins)
+ *   decision  mapq_se(reg) = the regs stage's mapq rule on the region's current sub and sub_n, without its secondary test;
+ *             raw(d) = (int)(6.02 * d / a + .499).  Paired branch - pairing ran with score > 0 and neither end has a region
+ *             j >= 1 with secondary < 0 && score >= T: score_un = a_0[0].score + a_1[0].score - pen_unpaired, subo = max(sub,
+ *             score_un), q_pe = raw(score - subo), less (int)(4.343 * log(n_sub + 1) + .499) if n_sub > 0, clamped to [0, 60],
+ *             then (int)(q_pe * (1. - .5 * (frac_rep_0 + frac_rep_1)) + .499), frac_rep_e = (float)l_rep / lq and their sum in
+ *             fp32.  If score > score_un, for each end c = a_e[z_e]: a secondary c takes sub = a_e[c.secondary].score and
+ *             secondary = -2; q_se = mapq_se(c); q_se = q_se > q_pe ? q_se : min(q_pe, q_se + 40); q_se = min(q_se,
+ *             raw(c.score)); proper = 1.  Else z = (0, 0), q_se = mapq_se(a_e[0]), proper = 0.  paired = 1; each read reports
+ *             exactly z_e: in d_pregs it has flag 1 and mapq = q_se, every other region of the read flag 0 and sel -1.
+ *             Otherwise (paired = 0) the regions stay as the regs stage left them; z_e = 0 if a_e[0].score >= T else -1; q_se =
+ *             that region's mapq or 0; q_pe = 0; proper = 1 iff !no_pairing, both z_e == 0, equal rid, and infer_dir(a_0[0].rb,
+ *             a_1[0].rb) gives a direction that has not failed with low <= dist <= high.  dir / dist of the pair record:
+ *             infer_dir of the two z regions' rb, or -1 / 0 if either is missing
+ *   list      the new CIGAR list holds the reads in order, each read's reported regions in output order, each record a copy of
+ *             the region's record in the regs stage's list (a region that stage did not report is built as it builds them);
+ *             sel is renumbered
+ * Not modelled: mate rescue (mem_matesw), alt contigs, MEM_F_ALL, XA, mem_patch_reg, the MD string, bwa's secondary_all. */
+typedef struct gbx_mem_pair_params {     /* 56 bytes */
+    int32_t a, b;                        /* 1, 4 */
+    int32_t o_del, e_del, o_ins, e_ins;  /* 6, 1, 6, 1 */
+    int32_t min_seed_len, T;             /* 19, 30 */
+    int32_t pen_unpaired;                /* 17 */
+    int32_t max_ins;                     /* 10000; 1 <= max_ins <= 2^20 */
+    int32_t mapq_coef_len;               /* 50; must be > 0 (GBX_ERR_UNSUPPORTED otherwise) */
+    float   mapq_coef_fac;               /* (float)log((double)mapq_coef_len), set by the host */
+    float   mask_level;                  /* 0.5 */
+    int32_t no_pairing;                  /* bwa -P: 1 = pairing is skipped, everything goes the unpaired way */
+} gbx_mem_pair_params;
+void gbx_mem_pair_default_params(gbx_mem_pair_params *p);
+
+typedef struct gbx_mem_pestat {          /* 32 bytes; four per call: FF, FR, RF, RR */
+    int32_t low, high, failed, pad_;
+    double  avg, std;
+} gbx_mem_pestat;
+
+typedef struct gbx_mem_pair {            /* 56 bytes */
+    int64_t dist;                        /* of the two reported regions, 0 if either is missing */
+    int32_t score, sub, n_sub, n_cand;   /* what the pairing returned (0 when it did not run); n_cand = its candidate pairs */
+    int32_t z0, z1;                      /* the region of each end that is reported first (index within the read), -1 none */
+    int32_t q_pe, q_se0, q_se1;
+    int32_t paired;                      /* 1: the paired branch ran to its end */
+    int32_t proper;                      /* SAM 0x2 */
+    int32_t dir;                         /* infer_dir of the two reported regions, -1 if either is missing */
+} gbx_mem_pair;
+
+/* Device path.  All pointers are device pointers but pes_in; asynchronous on `stream`, no host synchronisation inside.  d_regs,
+ * d_reg_off (2 n_pairs + 1), d_n_regs, d_sel_seeds / d_sel_res (sel_cap): the outputs of gbx_mem_regs_device on the same stream;
+ * d_seeds (seed_cap records, read for lq through reg.seed) and d_l_rep the chaining's.  The region count is read on the device;
+ * the inputs are never written.  pes_in: null, or a host pointer to four records given by the caller (bwa -I), read during the
+ * call; no estimate is made then.  Written: d_pes[4], d_pairs[n_pairs], d_pregs (the first *d_n_regs records: a copy of d_regs
+ * with the decision's changes and sel renumbered), the new CIGAR list d_psel_seeds / d_psel_res with its count *d_n_psel.  The
+ * records from *d_n_psel up to psel_cap are zeroed seeds with results of all -1, so gbx_mem_cigar_device can follow on the stream
+ * for psel_cap records.  The list never holds more records than there are regions: psel_cap = reg_cap always suffices (and so does
+ * a sel_cap that was the regs stage's seed_cap); a count above psel_cap reports the need, nothing past the capacity
+ * is written (reg.sel keeps the true index).  *d_n_regs < 0 or above reg_cap (the stage before overflowed): *d_n_psel = -1,
+ * zeroed pairs, every direction failed, the whole CIGAR list the zeroed tail.  reg_cap below 2^30.  work:
+ * gbx_mem_pair_workspace_bytes(n_pairs, reg_cap, max_ins) bytes; every pair is done in full whatever its region count.  The
+ * output bytes do not depend on the scheduling. */
+size_t gbx_mem_pair_workspace_bytes(int64_t n_pairs, int64_t reg_cap, int32_t max_ins);
+int gbx_mem_pair_device(const gbx_mem_pair_params *p, int64_t n_pairs, int64_t pair_id0,
+                        const gbx_mem_reg *d_regs, const int64_t *d_reg_off, const int64_t *d_n_regs, int64_t reg_cap,
+                        const gbx_bsw_seed *d_sel_seeds, const gbx_bsw_seed_result *d_sel_res, int64_t sel_cap,
+                        const gbx_bsw_seed *d_seeds, int64_t seed_cap, const int32_t *d_l_rep,
+                        int64_t l_pac, int32_t n_contigs, const int64_t *d_contig_off,
+                        const gbx_mem_pestat *pes_in, gbx_mem_pestat *d_pes, gbx_mem_pair *d_pairs, gbx_mem_reg *d_pregs,
+                        gbx_bsw_seed *d_psel_seeds, gbx_bsw_seed_result *d_psel_res, int64_t psel_cap, int64_t *d_n_psel,
+                        void *d_work, size_t work_bytes, void *stream);
+
+/* Host-buffer entry.  Checked before a device is touched: the parameters (a >= 1, e_del and e_ins >= 1, 1 <= max_ins <= 2^20,
+ * mapq_coef_len > 0: GBX_ERR_UNSUPPORTED otherwise), pair_id0 >= 0 and pair_id0 + n_pairs <= 2^23 (beyond it bwa's int id << 8
+ * overflows), the contig table, reg_off (monotone, inside n_regs), every reg.rid inside the contig table, every reg.seed inside
+ * the seeds, and a caller's pes_in (std > 0 wherever failed == 0): GBX_ERR_ARG naming the lowest offender.  *n_psel = the count;
+ * one above psel_cap gives GBX_ERR_ARG with the need there and in gbx_last_error() (pes, pairs and pregs are written, the list
+ * is not).  On success the list is written up to psel_cap, tail included.  Safe under concurrent host threads; one device. */
+int gbx_mem_pair_host(const gbx_mem_pair_params *p, int64_t n_pairs, int64_t pair_id0,
+                      const gbx_mem_reg *regs, const int64_t *reg_off, int64_t n_regs,
+                      const gbx_bsw_seed *sel_seeds, const gbx_bsw_seed_result *sel_res, int64_t n_sel,
+                      const gbx_bsw_seed *seeds, int64_t n_seeds, const int32_t *l_rep,
+                      int64_t l_pac, int32_t n_contigs, const int64_t *contig_off,
+                      const gbx_mem_pestat *pes_in, gbx_mem_pestat *pes, gbx_mem_pair *pairs, gbx_mem_reg *pregs,
+                      gbx_bsw_seed *psel_seeds, gbx_bsw_seed_result *psel_res, int64_t psel_cap, int64_t *n_psel);
+
 /* -------------------------------------------------------------------- kmer
  * Canonical k-mer counting of long reads: Flye's KmerCounter::count as the kmer-cnt benchmark times it
  * (R/benchmarks/kmer-cnt/kmer_cnt.cpp:224-237, vertex_index.cpp:513-612).
