@@ -912,7 +912,10 @@ WorkLayout work_layout(int64_t n_pairs, int64_t n_reads, int max_hap_len, int64_
     L.ulist = take((size_t)n_pairs * 4);
     // every pair contributes haplen+1 symbols, every read with pairs < 48 bytes of closing boundary + padding
     if (stream_syms < 0) stream_syms = n_pairs * ((int64_t)max_hap_len + 1);
-    L.stream = take((size_t)stream_syms + (size_t)(n_pairs < n_reads ? n_pairs : n_reads) * 48 + 64);
+    // a half-wavefront keeps loading stream words for as many steps as its partner's unit takes (the symbols past its own unit
+    // are masked, not the loads): behind the last read's stream there is room for the longest unit there can be
+    L.stream = take((size_t)stream_syms + (size_t)(n_pairs < n_reads ? n_pairs : n_reads) * 48 + 64 +
+                    (size_t)SEG_MAX_PAIRS * ((size_t)max_hap_len + 1) + 64);
     L.total = off;
     return L;
 }

@@ -11,7 +11,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(autouse=True, params=["0", "1"])
 def job_mode(request, monkeypatch):
-    """Jobs under 24 000 pairs take the one-pair-per-wavefront kernels (GBX_PHMM_SMALL=1) instead of the grouped
+    """Jobs under 12 000 pairs take the one-pair-per-wavefront kernels (GBX_PHMM_SMALL=1) instead of the grouped
     stream kernels (0); the cases here are small, so every test runs both ways."""
     monkeypatch.setenv("GBX_PHMM_SMALL", request.param)
     return request.param
@@ -71,8 +71,9 @@ def test_row_classes_and_tiles():
 
 def test_stream_units_segments_and_lane_classes():
     """The stream path: read lengths on both sides of every 31-rows-per-lane class edge (and past its 248-row
-    limit), more haplotypes per read than one unit holds (several segments per read), an odd number of
-    units (idle half wavefront), very short haplotypes between long ones, and pairs in scrambled order."""
+    limit), 37 haplotypes per read - at this job's size phmm_launch puts one pair in a unit, so each of them is a
+    unit of its own -, an odd number of units (idle half wavefront), very short haplotypes between long ones, and
+    pairs in scrambled order.  Units of several pairs: test_phmm_units_gpu.py."""
     rng = np.random.default_rng(11)
     base = rand_seq(rng, 700)
     haps = []
