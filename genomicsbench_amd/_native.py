@@ -186,6 +186,37 @@ def _declare(L):
         L.gbx_chain_evaluated_pairs.argtypes = [vp, C.POINTER(C.c_int64), vp]
 
 
+def declare_once(declare):
+    """Decorator for a module's ``lib()``: ``declare(L)`` sets the argument types of the module's entries on libgbx.so, once per
+    loaded library; the decorated name takes no argument and returns the library (raises if it or an entry is missing)."""
+    done = [None]
+
+    def declared():
+        L = lib()
+        if done[0] is not L:
+            declare(L)
+            done[0] = L
+        return L
+    declared.__doc__ = declare.__doc__
+    return declared
+
+
+def fill_params(struct_type, default_fn, kw, name):
+    """A ``struct_type`` filled by ``default_fn(byref(p))`` with the fields in `kw` replaced; a field the struct does not have (or
+    its padding) is a TypeError that names the C struct `name`.  Where the struct has both, mapq_coef_fac follows mapq_coef_len
+    (float32 of its logarithm) unless it is given."""
+    p = struct_type()
+    default_fn(C.byref(p))
+    names = {f[0] for f in struct_type._fields_} - {"pad_"}
+    for k, v in kw.items():
+        if k not in names:
+            raise TypeError("%s has no field %r" % (name, k))
+        setattr(p, k, v)
+    if {"mapq_coef_len", "mapq_coef_fac"} <= names and "mapq_coef_len" in kw and "mapq_coef_fac" not in kw and p.mapq_coef_len > 0:
+        p.mapq_coef_fac = float(np.float32(np.log(np.float64(p.mapq_coef_len))))
+    return p
+
+
 def check(rc):
     if rc != 0:
         raise GbxError(rc, lib().gbx_last_error().decode())

@@ -7,10 +7,9 @@ namespace {
 int params_check(const gbx_mem_chain_params *p, const char *who)
 {
     if (!p) { set_error("%s: null pointer", who); return GBX_ERR_ARG; }
-    if (p->w < 0) { set_error("%s: w = %d is negative", who, p->w); return GBX_ERR_ARG; }
-    if (p->e_del < 1 || p->e_ins < 1) { set_error("%s: e_del = %d, e_ins = %d (both at least 1)", who, p->e_del, p->e_ins); return GBX_ERR_ARG; }
-    if (!(p->mask_level == p->mask_level) || !(p->drop_ratio == p->drop_ratio)) { set_error("%s: mask_level / drop_ratio is not a number", who); return GBX_ERR_ARG; }
-    return GBX_OK;
+    int rc;
+    if ((rc = band_check(p->w, who)) || (rc = gap_extend_check(p->e_del, p->e_ins, who))) return rc;
+    return number_check("mask_level / drop_ratio", {p->mask_level, p->drop_ratio}, who);
 }
 }  // namespace
 
@@ -79,20 +78,14 @@ int gbx_mem_chain_host(const gbx_mem_chain_params *p, int64_t n_reads,
         return GBX_ERR_ARG;
     }
     // everything is checked before the device is touched
-    if (contig_off[0] != 0 || contig_off[n_contigs] != l_pac) {
-        set_error("%s: contig_off must run from 0 to l_pac = %lld", who, (long long)l_pac);
-        return GBX_ERR_ARG;
-    }
-    for (int32_t c = 0; c < n_contigs; ++c)
-        if (contig_off[c + 1] <= contig_off[c]) { set_error("%s: contig_off is not strictly increasing at contig %d", who, c); return GBX_ERR_ARG; }
+    if ((rc = contig_off_check(contig_off, n_contigs, l_pac, who))) return rc;
+    // (smem_off is checked in the loop over the reads, not by offsets_check: the lowest read with either fault is named)
     if (smem_off[0] < 0 || smem_off[n_reads] > n_smem) { set_error("%s: smem_off leaves the %lld SMEMs", who, (long long)n_smem); return GBX_ERR_ARG; }
     for (int64_t r = 0; r < n_reads; ++r) {
         if (smem_off[r + 1] < smem_off[r]) { set_error("%s: smem_off is not monotone at read %lld", who, (long long)r); return GBX_ERR_ARG; }
         if (read_len[r] < 0 || read_off[r] < 0) { set_error("%s: read %lld has a negative length or offset", who, (long long)r); return GBX_ERR_ARG; }
     }
-    if (pos_off[0] < 0 || pos_off[n_smem] > n_pos) { set_error("%s: pos_off leaves the %lld hits", who, (long long)n_pos); return GBX_ERR_ARG; }
-    for (int64_t j = 0; j < n_smem; ++j)
-        if (pos_off[j + 1] < pos_off[j]) { set_error("%s: pos_off is not monotone at SMEM %lld", who, (long long)j); return GBX_ERR_ARG; }
+    if ((rc = offsets_check(pos_off, n_smem, n_pos, "pos_off", "hits", "SMEM", who))) return rc;
     *n_chains = 0; *n_seeds = 0;
     if (n_reads == 0) {
         if (chain_off) chain_off[0] = 0;
@@ -107,21 +100,14 @@ int gbx_mem_chain_host(const gbx_mem_chain_params *p, int64_t n_reads,
     const int64_t ccap = std::min(chain_cap, n_pos), scap = std::min(seed_cap, n_pos);
     DevBuf dsm(L), dso(L), dpos(L), dpo(L), dro(L), drl(L), dco(L), dn(L), dch(L), dcho(L), dsd(L), dlr(L), dw(L);
     const size_t wb = mem_chain_workspace_bytes(n_reads, n_smem, n_pos);
-    if ((rc = dsm.alloc((size_t)n_smem * sizeof(gbx_fmi_smem))) || (rc = dso.alloc((size_t)(n_reads + 1) * 8)) || (rc = dpos.alloc((size_t)n_pos * 8)) ||
-        (rc = dpo.alloc((size_t)(n_smem + 1) * 8)) || (rc = dro.alloc((size_t)n_reads * 8)) || (rc = drl.alloc((size_t)n_reads * 4)) ||
-        (rc = dco.alloc((size_t)(n_contigs + 1) * 8)) || (rc = dn.alloc(32)) || (rc = dch.alloc((size_t)ccap * sizeof(gbx_mem_chain))) ||
-        (rc = dcho.alloc((size_t)(n_reads + 1) * 8)) || (rc = dsd.alloc((size_t)scap * sizeof(gbx_bsw_seed))) || (rc = dlr.alloc((size_t)n_reads * 4)) ||
-        (rc = dw.alloc(wb)))
-        return rc;
     const int64_t counts[4] = {n_smem, n_pos, 0, 0};
-    if (n_smem) GBX_HIP(hipMemcpyAsync(dsm.p, smems, (size_t)n_smem * sizeof(gbx_fmi_smem), hipMemcpyHostToDevice, st));
-    GBX_HIP(hipMemcpyAsync(dso.p, smem_off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st));
-    if (n_pos) GBX_HIP(hipMemcpyAsync(dpos.p, pos, (size_t)n_pos * 8, hipMemcpyHostToDevice, st));
-    GBX_HIP(hipMemcpyAsync(dpo.p, pos_off, (size_t)(n_smem + 1) * 8, hipMemcpyHostToDevice, st));
-    GBX_HIP(hipMemcpyAsync(dro.p, read_off, (size_t)n_reads * 8, hipMemcpyHostToDevice, st));
-    GBX_HIP(hipMemcpyAsync(drl.p, read_len, (size_t)n_reads * 4, hipMemcpyHostToDevice, st));
-    GBX_HIP(hipMemcpyAsync(dco.p, contig_off, (size_t)(n_contigs + 1) * 8, hipMemcpyHostToDevice, st));
-    GBX_HIP(hipMemcpyAsync(dn.p, counts, 32, hipMemcpyHostToDevice, st));
+    if ((rc = upload(dsm, smems, (size_t)n_smem * sizeof(gbx_fmi_smem), st)) || (rc = upload(dso, smem_off, (size_t)(n_reads + 1) * 8, st)) ||
+        (rc = upload(dpos, pos, (size_t)n_pos * 8, st)) || (rc = upload(dpo, pos_off, (size_t)(n_smem + 1) * 8, st)) ||
+        (rc = upload(dro, read_off, (size_t)n_reads * 8, st)) || (rc = upload(drl, read_len, (size_t)n_reads * 4, st)) ||
+        (rc = upload(dco, contig_off, (size_t)(n_contigs + 1) * 8, st)) || (rc = upload(dn, counts, 32, st)) ||
+        (rc = dch.alloc((size_t)ccap * sizeof(gbx_mem_chain))) || (rc = dcho.alloc((size_t)(n_reads + 1) * 8)) ||
+        (rc = dsd.alloc((size_t)scap * sizeof(gbx_bsw_seed))) || (rc = dlr.alloc((size_t)n_reads * 4)) || (rc = dw.alloc(wb)))
+        return rc;
     int64_t *const d_n = dn.as<int64_t>();
     const MemChainIo io{dsm.as<gbx_fmi_smem>(), d_n, n_smem, dso.as<int64_t>(), dpos.as<int64_t>(), d_n + 1, n_pos, dpo.as<int64_t>(),
                         dro.as<int64_t>(), drl.as<int32_t>(), l_pac, n_contigs, dco.as<int64_t>(), dch.as<gbx_mem_chain>(), ccap,

@@ -9,8 +9,7 @@ int params_check(const gbx_mem_cigar_params *p, const char *who)
 {
     if (!p) { set_error("%s: null pointer", who); return GBX_ERR_ARG; }
     if (p->w < 0 || p->w > (1 << 27)) { set_error("%s: w = %d (0 .. 2^27)", who, p->w); return GBX_ERR_ARG; }
-    if (p->e_del < 1 || p->e_ins < 1) { set_error("%s: e_del = %d, e_ins = %d (both at least 1)", who, p->e_del, p->e_ins); return GBX_ERR_ARG; }
-    return GBX_OK;
+    return gap_extend_check(p->e_del, p->e_ins, who);
 }
 }  // namespace
 
@@ -81,12 +80,7 @@ int gbx_mem_cigar_host(const gbx_mem_cigar_params *p, int64_t n,
         return GBX_ERR_ARG;
     }
     // everything is checked before the device is touched
-    if (contig_off[0] != 0 || contig_off[n_contigs] != l_pac) {
-        set_error("%s: contig_off must run from 0 to l_pac = %lld", who, (long long)l_pac);
-        return GBX_ERR_ARG;
-    }
-    for (int32_t c = 0; c < n_contigs; ++c)
-        if (contig_off[c + 1] <= contig_off[c]) { set_error("%s: contig_off is not strictly increasing at contig %d", who, c); return GBX_ERR_ARG; }
+    if ((rc = contig_off_check(contig_off, n_contigs, l_pac, who))) return rc;
     size_t z_bytes = 0;
     for (int64_t k = 0; k < n; ++k) {
         size_t need = 0;
@@ -105,15 +99,11 @@ int gbx_mem_cigar_host(const gbx_mem_cigar_params *p, int64_t n,
     hipStream_t st = L->compute;
     DevBuf dsd(L), drs(L), dtx(L), dqr(L), dco(L), dal(L), dcg(L), dn(L), dw(L);
     const size_t wb = mem_cigar_fixed_bytes(n) + z_bytes;
-    if ((rc = dsd.alloc((size_t)n * sizeof(gbx_bsw_seed))) || (rc = drs.alloc((size_t)n * sizeof(gbx_bsw_seed_result))) ||
-        (rc = dtx.alloc((size_t)text_bytes)) || (rc = dqr.alloc((size_t)qer_bytes)) || (rc = dco.alloc((size_t)(n_contigs + 1) * 8)) ||
-        (rc = dal.alloc((size_t)n * sizeof(gbx_mem_aln))) || (rc = dcg.alloc((size_t)cigar_cap * 4)) || (rc = dn.alloc(8)) || (rc = dw.alloc(wb)))
+    if ((rc = upload(dsd, seeds, (size_t)n * sizeof(gbx_bsw_seed), st)) || (rc = upload(drs, res, (size_t)n * sizeof(gbx_bsw_seed_result), st)) ||
+        (rc = upload(dtx, text, (size_t)text_bytes, st)) || (rc = upload(dqr, qer, (size_t)qer_bytes, st)) ||
+        (rc = upload(dco, contig_off, (size_t)(n_contigs + 1) * 8, st)) || (rc = dal.alloc((size_t)n * sizeof(gbx_mem_aln))) ||
+        (rc = dcg.alloc((size_t)cigar_cap * 4)) || (rc = dn.alloc(8)) || (rc = dw.alloc(wb)))
         return rc;
-    GBX_HIP(hipMemcpyAsync(dsd.p, seeds, (size_t)n * sizeof(gbx_bsw_seed), hipMemcpyHostToDevice, st));
-    GBX_HIP(hipMemcpyAsync(drs.p, res, (size_t)n * sizeof(gbx_bsw_seed_result), hipMemcpyHostToDevice, st));
-    if (text_bytes) GBX_HIP(hipMemcpyAsync(dtx.p, text, (size_t)text_bytes, hipMemcpyHostToDevice, st));
-    if (qer_bytes) GBX_HIP(hipMemcpyAsync(dqr.p, qer, (size_t)qer_bytes, hipMemcpyHostToDevice, st));
-    GBX_HIP(hipMemcpyAsync(dco.p, contig_off, (size_t)(n_contigs + 1) * 8, hipMemcpyHostToDevice, st));
     const MemCigarIo io{dsd.as<gbx_bsw_seed>(), drs.as<gbx_bsw_seed_result>(), dtx.as<uint8_t>(), text_bytes, dqr.as<uint8_t>(), qer_bytes,
                         l_pac, n_contigs, dco.as<int64_t>(), dal.as<gbx_mem_aln>(), dcg.as<uint32_t>(), cigar_cap, dn.as<int64_t>()};
     if ((rc = mem_cigar_launch(p, n, io, dw.p, wb, (int64_t)z_bytes, st))) return rc;

@@ -9,18 +9,11 @@ namespace {
 int params_check(const gbx_mem_pair_params *p, const char *who)
 {
     if (!p) { set_error("%s: null pointer", who); return GBX_ERR_ARG; }
-    if (p->e_del < 1 || p->e_ins < 1) { set_error("%s: e_del = %d, e_ins = %d (both at least 1)", who, p->e_del, p->e_ins); return GBX_ERR_ARG; }
-    if (p->a < 1 || (long long)p->a + p->b < 1) { set_error("%s: a = %d, b = %d (a and a + b at least 1)", who, p->a, p->b); return GBX_ERR_ARG; }
+    int rc;
+    if ((rc = gap_extend_check(p->e_del, p->e_ins, who)) || (rc = match_check(p->a, p->b, who))) return rc;
     if (p->max_ins < 1 || p->max_ins > (1 << 20)) { set_error("%s: max_ins = %d (1 .. 2^20)", who, p->max_ins); return GBX_ERR_ARG; }
-    if (p->mapq_coef_len <= 0) {
-        set_error("%s: mapq_coef_len = %d: bwa's mapq formula for mapq_coef_len <= 0 is not modelled", who, p->mapq_coef_len);
-        return GBX_ERR_UNSUPPORTED;
-    }
-    if (!(p->mask_level == p->mask_level) || !(p->mapq_coef_fac == p->mapq_coef_fac)) {
-        set_error("%s: mask_level / mapq_coef_fac is not a number", who);
-        return GBX_ERR_ARG;
-    }
-    return GBX_OK;
+    if ((rc = mapq_coef_len_check(p->mapq_coef_len, who))) return rc;
+    return number_check("mask_level / mapq_coef_fac", {p->mask_level, p->mapq_coef_fac}, who);
 }
 
 int ids_check(int64_t n_pairs, int64_t pair_id0, const char *who)
@@ -104,16 +97,9 @@ int gbx_mem_pair_host(const gbx_mem_pair_params *p, int64_t n_pairs, int64_t pai
         return GBX_ERR_ARG;
     }
     // everything is checked before the device is touched
-    if (contig_off[0] != 0 || contig_off[n_contigs] != l_pac) {
-        set_error("%s: contig_off must run from 0 to l_pac = %lld", who, (long long)l_pac);
-        return GBX_ERR_ARG;
-    }
-    for (int32_t c = 0; c < n_contigs; ++c)
-        if (contig_off[c + 1] <= contig_off[c]) { set_error("%s: contig_off is not strictly increasing at contig %d", who, c); return GBX_ERR_ARG; }
+    if ((rc = contig_off_check(contig_off, n_contigs, l_pac, who))) return rc;
     const int64_t n_reads = 2 * n_pairs;
-    if (reg_off[0] < 0 || reg_off[n_reads] > n_regs) { set_error("%s: reg_off leaves the %lld regions", who, (long long)n_regs); return GBX_ERR_ARG; }
-    for (int64_t r = 0; r < n_reads; ++r)
-        if (reg_off[r + 1] < reg_off[r]) { set_error("%s: reg_off is not monotone at read %lld", who, (long long)r); return GBX_ERR_ARG; }
+    if ((rc = offsets_check(reg_off, n_reads, n_regs, "reg_off", "regions", "read", who))) return rc;
     for (int64_t g = 0; g < n_regs; ++g) {
         if (regs[g].rid < 0 || regs[g].rid >= n_contigs) {
             set_error("%s: region %lld: rid = %d lies outside the %d contigs", who, (long long)g, regs[g].rid, n_contigs);
@@ -125,12 +111,6 @@ int gbx_mem_pair_host(const gbx_mem_pair_params *p, int64_t n_pairs, int64_t pai
         }
     }
     *n_psel = 0;
-    auto fill_tail = [&](int64_t from) {
-        if (from < psel_cap) {
-            memset(psel_seeds + from, 0, (size_t)(psel_cap - from) * sizeof(gbx_bsw_seed));
-            memset(psel_res + from, 0xff, (size_t)(psel_cap - from) * sizeof(gbx_bsw_seed_result));
-        }
-    };
     if ((rc = require_device())) return rc;
     HostLane lane;
     if ((rc = lane.acquire())) return rc;
@@ -140,23 +120,16 @@ int gbx_mem_pair_host(const gbx_mem_pair_params *p, int64_t n_pairs, int64_t pai
     const int64_t pcap = std::min(psel_cap, n_regs);
     DevBuf drg(L), dro(L), dss(L), dsr(L), dsd(L), dlr(L), dco(L), dn(L), dpe(L), dpa(L), dpr(L), dps(L), dpq(L), dw(L);
     const size_t wb = mem_pair_workspace_bytes(n_pairs, n_regs, p->max_ins);
-    if ((rc = drg.alloc((size_t)n_regs * sizeof(gbx_mem_reg))) || (rc = dro.alloc((size_t)(n_reads + 1) * 8)) ||
-        (rc = dss.alloc((size_t)n_sel * sizeof(gbx_bsw_seed))) || (rc = dsr.alloc((size_t)n_sel * sizeof(gbx_bsw_seed_result))) ||
-        (rc = dsd.alloc((size_t)n_seeds * sizeof(gbx_bsw_seed))) || (rc = dlr.alloc((size_t)n_reads * 4)) ||
-        (rc = dco.alloc((size_t)(n_contigs + 1) * 8)) || (rc = dn.alloc(16)) || (rc = dpe.alloc(4 * sizeof(gbx_mem_pestat))) ||
-        (rc = dpa.alloc((size_t)n_pairs * sizeof(gbx_mem_pair))) || (rc = dpr.alloc((size_t)n_regs * sizeof(gbx_mem_reg))) ||
-        (rc = dps.alloc((size_t)pcap * sizeof(gbx_bsw_seed))) || (rc = dpq.alloc((size_t)pcap * sizeof(gbx_bsw_seed_result))) ||
-        (rc = dw.alloc(wb)))
-        return rc;
     const int64_t counts[2] = {n_regs, 0};
-    if (n_regs) GBX_HIP(hipMemcpyAsync(drg.p, regs, (size_t)n_regs * sizeof(gbx_mem_reg), hipMemcpyHostToDevice, st));
-    GBX_HIP(hipMemcpyAsync(dro.p, reg_off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st));
-    if (n_sel) GBX_HIP(hipMemcpyAsync(dss.p, sel_seeds, (size_t)n_sel * sizeof(gbx_bsw_seed), hipMemcpyHostToDevice, st));
-    if (n_sel) GBX_HIP(hipMemcpyAsync(dsr.p, sel_res, (size_t)n_sel * sizeof(gbx_bsw_seed_result), hipMemcpyHostToDevice, st));
-    if (n_seeds) GBX_HIP(hipMemcpyAsync(dsd.p, seeds, (size_t)n_seeds * sizeof(gbx_bsw_seed), hipMemcpyHostToDevice, st));
-    if (n_reads) GBX_HIP(hipMemcpyAsync(dlr.p, l_rep, (size_t)n_reads * 4, hipMemcpyHostToDevice, st));
-    GBX_HIP(hipMemcpyAsync(dco.p, contig_off, (size_t)(n_contigs + 1) * 8, hipMemcpyHostToDevice, st));
-    GBX_HIP(hipMemcpyAsync(dn.p, counts, 16, hipMemcpyHostToDevice, st));
+    if ((rc = upload(drg, regs, (size_t)n_regs * sizeof(gbx_mem_reg), st)) || (rc = upload(dro, reg_off, (size_t)(n_reads + 1) * 8, st)) ||
+        (rc = upload(dss, sel_seeds, (size_t)n_sel * sizeof(gbx_bsw_seed), st)) ||
+        (rc = upload(dsr, sel_res, (size_t)n_sel * sizeof(gbx_bsw_seed_result), st)) ||
+        (rc = upload(dsd, seeds, (size_t)n_seeds * sizeof(gbx_bsw_seed), st)) || (rc = upload(dlr, l_rep, (size_t)n_reads * 4, st)) ||
+        (rc = upload(dco, contig_off, (size_t)(n_contigs + 1) * 8, st)) || (rc = upload(dn, counts, 16, st)) ||
+        (rc = dpe.alloc(4 * sizeof(gbx_mem_pestat))) || (rc = dpa.alloc((size_t)n_pairs * sizeof(gbx_mem_pair))) ||
+        (rc = dpr.alloc((size_t)n_regs * sizeof(gbx_mem_reg))) || (rc = dps.alloc((size_t)pcap * sizeof(gbx_bsw_seed))) ||
+        (rc = dpq.alloc((size_t)pcap * sizeof(gbx_bsw_seed_result))) || (rc = dw.alloc(wb)))
+        return rc;
     int64_t *const d_n = dn.as<int64_t>();
     const MemPairIo io{drg.as<gbx_mem_reg>(), dro.as<int64_t>(), d_n, n_regs, dss.as<gbx_bsw_seed>(), dsr.as<gbx_bsw_seed_result>(), n_sel,
                        dsd.as<gbx_bsw_seed>(), n_seeds, dlr.as<int32_t>(), l_pac, n_contigs, dco.as<int64_t>(), dpe.as<gbx_mem_pestat>(),
@@ -180,7 +153,7 @@ int gbx_mem_pair_host(const gbx_mem_pair_params *p, int64_t n_pairs, int64_t pai
     if (pcap) GBX_HIP(hipMemcpyAsync(psel_seeds, dps.p, (size_t)pcap * sizeof(gbx_bsw_seed), hipMemcpyDeviceToHost, st));
     if (pcap) GBX_HIP(hipMemcpyAsync(psel_res, dpq.p, (size_t)pcap * sizeof(gbx_bsw_seed_result), hipMemcpyDeviceToHost, st));
     GBX_HIP(hipStreamSynchronize(st));
-    fill_tail(pcap);
+    sel_tail_fill(psel_seeds, psel_res, pcap, psel_cap);
     return GBX_OK;
 }
 

@@ -9,19 +9,12 @@ namespace {
 int params_check(const gbx_mem_regs_params *p, const char *who)
 {
     if (!p) { set_error("%s: null pointer", who); return GBX_ERR_ARG; }
-    if (p->e_del < 1 || p->e_ins < 1) { set_error("%s: e_del = %d, e_ins = %d (both at least 1)", who, p->e_del, p->e_ins); return GBX_ERR_ARG; }
-    if (p->a < 1 || (long long)p->a + p->b < 1) { set_error("%s: a = %d, b = %d (a and a + b at least 1)", who, p->a, p->b); return GBX_ERR_ARG; }
-    if (p->w < 0) { set_error("%s: w = %d is negative", who, p->w); return GBX_ERR_ARG; }
-    if (p->mapq_coef_len <= 0) {
-        set_error("%s: mapq_coef_len = %d: bwa's mapq formula for mapq_coef_len <= 0 is not modelled", who, p->mapq_coef_len);
-        return GBX_ERR_UNSUPPORTED;
-    }
-    if (!(p->mask_level == p->mask_level) || !(p->mask_level_redun == p->mask_level_redun) || !(p->drop_ratio == p->drop_ratio) ||
-        !(p->mapq_coef_fac == p->mapq_coef_fac)) {
-        set_error("%s: mask_level / mask_level_redun / drop_ratio / mapq_coef_fac is not a number", who);
-        return GBX_ERR_ARG;
-    }
-    return GBX_OK;
+    int rc;
+    if ((rc = gap_extend_check(p->e_del, p->e_ins, who)) || (rc = match_check(p->a, p->b, who)) || (rc = band_check(p->w, who)) ||
+        (rc = mapq_coef_len_check(p->mapq_coef_len, who)))
+        return rc;
+    return number_check("mask_level / mask_level_redun / drop_ratio / mapq_coef_fac",
+                        {p->mask_level, p->mask_level_redun, p->drop_ratio, p->mapq_coef_fac}, who);
 }
 }  // namespace
 
@@ -82,9 +75,7 @@ int gbx_mem_regs_host(const gbx_mem_regs_params *p, int64_t n_reads, int64_t rea
         return GBX_ERR_ARG;
     }
     // everything is checked before the device is touched
-    if (chain_off[0] < 0 || chain_off[n_reads] > n_chains) { set_error("%s: chain_off leaves the %lld chains", who, (long long)n_chains); return GBX_ERR_ARG; }
-    for (int64_t r = 0; r < n_reads; ++r)
-        if (chain_off[r + 1] < chain_off[r]) { set_error("%s: chain_off is not monotone at read %lld", who, (long long)r); return GBX_ERR_ARG; }
+    if ((rc = offsets_check(chain_off, n_reads, n_chains, "chain_off", "chains", "read", who))) return rc;
     for (int64_t c = 0; c < n_chains; ++c)
         if (chains[c].seed_off < 0 || chains[c].n_seeds < 0 || chains[c].seed_off > n_seeds || chains[c].n_seeds > n_seeds - chains[c].seed_off) {
             set_error("%s: chain %lld: its seeds [%lld, %lld + %d) leave the %lld seeds", who, (long long)c, (long long)chains[c].seed_off,
@@ -92,15 +83,9 @@ int gbx_mem_regs_host(const gbx_mem_regs_params *p, int64_t n_reads, int64_t rea
             return GBX_ERR_ARG;
         }
     *n_regs = 0; *n_sel = 0;
-    auto fill_tail = [&](int64_t from) {
-        if (from < sel_cap) {
-            memset(sel_seeds + from, 0, (size_t)(sel_cap - from) * sizeof(gbx_bsw_seed));
-            memset(sel_res + from, 0xff, (size_t)(sel_cap - from) * sizeof(gbx_bsw_seed_result));
-        }
-    };
     if (n_reads == 0 || n_seeds == 0 || n_chains == 0) {
         if (reg_off) memset(reg_off, 0, (size_t)(n_reads + 1) * 8);
-        fill_tail(0);
+        sel_tail_fill(sel_seeds, sel_res, 0, sel_cap);
         return GBX_OK;
     }
     if ((rc = require_device())) return rc;
@@ -112,19 +97,13 @@ int gbx_mem_regs_host(const gbx_mem_regs_params *p, int64_t n_reads, int64_t rea
     const int64_t rcap = std::min(reg_cap, n_seeds), scap = std::min(sel_cap, n_seeds);
     DevBuf dch(L), dco(L), dsd(L), drs(L), dlr(L), dn(L), drg(L), dro(L), dss(L), dsr(L), dw(L);
     const size_t wb = mem_regs_workspace_bytes(n_reads, n_seeds);
-    if ((rc = dch.alloc((size_t)n_chains * sizeof(gbx_mem_chain))) || (rc = dco.alloc((size_t)(n_reads + 1) * 8)) ||
-        (rc = dsd.alloc((size_t)n_seeds * sizeof(gbx_bsw_seed))) || (rc = drs.alloc((size_t)n_seeds * sizeof(gbx_bsw_seed_result))) ||
-        (rc = dlr.alloc((size_t)n_reads * 4)) || (rc = dn.alloc(32)) || (rc = drg.alloc((size_t)rcap * sizeof(gbx_mem_reg))) ||
-        (rc = dro.alloc((size_t)(n_reads + 1) * 8)) || (rc = dss.alloc((size_t)scap * sizeof(gbx_bsw_seed))) ||
-        (rc = dsr.alloc((size_t)scap * sizeof(gbx_bsw_seed_result))) || (rc = dw.alloc(wb)))
-        return rc;
     const int64_t counts[4] = {n_chains, n_seeds, 0, 0};
-    GBX_HIP(hipMemcpyAsync(dch.p, chains, (size_t)n_chains * sizeof(gbx_mem_chain), hipMemcpyHostToDevice, st));
-    GBX_HIP(hipMemcpyAsync(dco.p, chain_off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st));
-    GBX_HIP(hipMemcpyAsync(dsd.p, seeds, (size_t)n_seeds * sizeof(gbx_bsw_seed), hipMemcpyHostToDevice, st));
-    GBX_HIP(hipMemcpyAsync(drs.p, res, (size_t)n_seeds * sizeof(gbx_bsw_seed_result), hipMemcpyHostToDevice, st));
-    GBX_HIP(hipMemcpyAsync(dlr.p, l_rep, (size_t)n_reads * 4, hipMemcpyHostToDevice, st));
-    GBX_HIP(hipMemcpyAsync(dn.p, counts, 32, hipMemcpyHostToDevice, st));
+    if ((rc = upload(dch, chains, (size_t)n_chains * sizeof(gbx_mem_chain), st)) || (rc = upload(dco, chain_off, (size_t)(n_reads + 1) * 8, st)) ||
+        (rc = upload(dsd, seeds, (size_t)n_seeds * sizeof(gbx_bsw_seed), st)) ||
+        (rc = upload(drs, res, (size_t)n_seeds * sizeof(gbx_bsw_seed_result), st)) || (rc = upload(dlr, l_rep, (size_t)n_reads * 4, st)) ||
+        (rc = upload(dn, counts, 32, st)) || (rc = drg.alloc((size_t)rcap * sizeof(gbx_mem_reg))) || (rc = dro.alloc((size_t)(n_reads + 1) * 8)) ||
+        (rc = dss.alloc((size_t)scap * sizeof(gbx_bsw_seed))) || (rc = dsr.alloc((size_t)scap * sizeof(gbx_bsw_seed_result))) || (rc = dw.alloc(wb)))
+        return rc;
     int64_t *const d_n = dn.as<int64_t>();
     const MemRegsIo io{dch.as<gbx_mem_chain>(), d_n, n_chains, dco.as<int64_t>(), dsd.as<gbx_bsw_seed>(), d_n + 1, n_seeds,
                        drs.as<gbx_bsw_seed_result>(), dlr.as<int32_t>(), drg.as<gbx_mem_reg>(), rcap, dro.as<int64_t>(), d_n + 2,
@@ -149,7 +128,7 @@ int gbx_mem_regs_host(const gbx_mem_regs_params *p, int64_t n_reads, int64_t rea
     if (scap) GBX_HIP(hipMemcpyAsync(sel_seeds, dss.p, (size_t)scap * sizeof(gbx_bsw_seed), hipMemcpyDeviceToHost, st));
     if (scap) GBX_HIP(hipMemcpyAsync(sel_res, dsr.p, (size_t)scap * sizeof(gbx_bsw_seed_result), hipMemcpyDeviceToHost, st));
     GBX_HIP(hipStreamSynchronize(st));
-    fill_tail(scap);
+    sel_tail_fill(sel_seeds, sel_res, scap, sel_cap);
     return GBX_OK;
 }
 

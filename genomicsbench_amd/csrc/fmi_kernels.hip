@@ -28,7 +28,7 @@
 //     per read, a second kernel sorts each read's few records by (m ascending, n descending) and packs them behind a
 //     prefix sum of the counts.
 #include <algorithm>
-#include "gbx_internal.h"
+#include "mem_common.h"
 
 namespace gbx {
 namespace {
@@ -420,26 +420,7 @@ __global__ void __launch_bounds__(SCAN_BLOCK) fmi_scan1_kernel(const int32_t *cn
 // one block: exclusive scan of the block sums; counters[4] = records before this chunk, counters[3] += this chunk's
 __global__ void __launch_bounds__(1024) fmi_scan2_kernel(long long *block_sum, int n_blocks, unsigned long long *counters, int64_t *d_n_out)
 {
-    __shared__ long long sh[1024];
-    __shared__ long long carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < n_blocks; b0 += 1024) {
-        const int i = b0 + threadIdx.x;
-        const long long v = i < n_blocks ? block_sum[i] : 0;
-        sh[threadIdx.x] = v;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {
-            const long long u = threadIdx.x >= d ? sh[threadIdx.x - d] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += u;
-            __syncthreads();
-        }
-        if (i < n_blocks) block_sum[i] = carry + sh[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry += sh[1023];
-        __syncthreads();
-    }
+    const long long carry = scan_block_sums(block_sum, n_blocks);
     if (threadIdx.x == 0) {
         counters[4] = counters[3];
         counters[3] += (unsigned long long)carry;
@@ -461,14 +442,8 @@ __global__ void __launch_bounds__(SCAN_BLOCK) fmi_pack_kernel(const int32_t *cnt
     const long long i = (long long)blockIdx.x * SCAN_BLOCK + threadIdx.x;
     const int c = i < n ? cnt[i] : 0;
     // exclusive prefix inside the block
-    long long v = c;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int d = 1; d < 64; d <<= 1) { const long long u = __shfl_up(v, d); if (lane >= d) v += u; }
-    if (lane == 63) sh[wv] = v;
-    __syncthreads();
-    long long before = 0;
-    for (int w = 0; w < wv; ++w) before += sh[w];
-    const long long off = (long long)counters[4] + block_off[blockIdx.x] + before + v - c;
+    long long total;
+    const long long off = (long long)counters[4] + block_off[blockIdx.x] + block_scan_excl(c, sh, &total);
     soff[threadIdx.x] = off; scnt[threadIdx.x] = c;
     if (i < n) {
         smem_off[read_base + i] = off;

@@ -20,7 +20,7 @@
 //   * per-SMEM hit counts and their exclusive scan (pos_off) are computed on the device from the device SMEM count, so
 //     the lookup chains behind gbx_fmi_smem_device on one stream.
 #include <algorithm>
-#include "gbx_internal.h"
+#include "mem_common.h"
 
 namespace gbx {
 namespace {
@@ -76,40 +76,16 @@ __global__ void __launch_bounds__(SAL_SCAN) fmi_sal_count_kernel(SalArgs A)
     const long long n = sal_n_smem(A);
     const long long i = (long long)blockIdx.x * SAL_SCAN + threadIdx.x;
     const long long c = i < n ? sal_hits(A.smems[i].s, A.max_occ, A.ref_seq_len) : 0;
-    long long v = c;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int d = 1; d < 64; d <<= 1) { const long long u = __shfl_up(v, d); if (lane >= d) v += u; }
-    if (lane == 63) sh[wv] = v;
-    __syncthreads();
-    long long before = 0;
-    for (int w = 0; w < wv; ++w) before += sh[w];
-    if (i <= A.smem_cap) A.pos_off[i] = before + v - c;
-    if (threadIdx.x == SAL_SCAN - 1) A.bsum[blockIdx.x] = before + v;
+    long long total;
+    const long long before = block_scan_excl(c, sh, &total);
+    if (i <= A.smem_cap) A.pos_off[i] = before;
+    if (threadIdx.x == SAL_SCAN - 1) A.bsum[blockIdx.x] = total;
 }
 
 // one block: exclusive scan of the block sums, the total to *n_pos, the counters reset
 __global__ void __launch_bounds__(1024) fmi_sal_scan_kernel(long long *bsum, int n_blocks, unsigned long long *counters, int64_t *n_pos)
 {
-    __shared__ long long sh[1024];
-    __shared__ long long carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < n_blocks; b0 += 1024) {
-        const int i = b0 + threadIdx.x;
-        const long long v = i < n_blocks ? bsum[i] : 0;
-        sh[threadIdx.x] = v;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {
-            const long long u = threadIdx.x >= d ? sh[threadIdx.x - d] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += u;
-            __syncthreads();
-        }
-        if (i < n_blocks) bsum[i] = carry + sh[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry += sh[1023];
-        __syncthreads();
-    }
+    const long long carry = scan_block_sums(bsum, n_blocks);
     if (threadIdx.x == 0) {
         *n_pos = carry;
         counters[0] = 0; counters[1] = 0; counters[2] = 0;

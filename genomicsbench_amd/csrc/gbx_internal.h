@@ -177,6 +177,21 @@ int fmi_sal_launch(const gbx_fmi_index *idx, const void *d_index, const gbx_fmi_
                    int64_t *d_n_pos, void *d_work, size_t work_bytes, hipStream_t s);
 int fmi_sal_read_steps(const void *d_work, int64_t *steps, int64_t *max_steps, hipStream_t s);
 
+// ---- what the bwa-mem stages share (mem_scan.hip; the device helpers: mem_common.h)
+// One exclusive scan over per-unit counts.  cnt holds nq quantities of n counts, n + 1 entries apart; each becomes its offsets
+// (entry n: the total) in place.  Three launches: a block scan, one block per quantity over the block sums, an offset pass.
+struct MemScanGuard { const int64_t *n; int64_t lo, hi; };      // n == nullptr: no guard; else the stage before it fits iff lo <= *n <= hi
+struct MemScanJob {
+    long long *cnt; int64_t n; int nq;              // nq: 1 or 2
+    long long *bsum; int blocks;                    // [nq][blocks] scratch, blocks = mem_scan_blocks(n)
+    int64_t *total[2];                              // where a quantity's total goes (nullptr: nowhere); -1 when a guard fails
+    int64_t *off0;                                  // quantity 0's offsets are also copied here (nullptr: not)
+    MemScanGuard guard[2];
+};
+void mem_scan_launch(const MemScanJob &job, hipStream_t s);
+// the CIGAR list past *n (below 0: 0), up to cap: zeroed seeds (len = 0 is no seed) with results of all -1
+void mem_sel_tail_launch(gbx_bsw_seed *seeds, gbx_bsw_seed_result *res, int64_t cap, const int64_t *n, hipStream_t s);
+
 // ---- seed chaining (mem_chain_kernels.hip)
 struct MemChainIo {                  // the device arguments of gbx_mem_chain_device
     const gbx_fmi_smem *smems; const int64_t *n_smem; int64_t smem_cap; const int64_t *smem_off;

@@ -22,12 +22,11 @@
 //   * output: the read kernel leaves per-read counts, a scan over the reads turns them into offsets (chain_off), a pack
 //     pass writes chain and seed records at their final places: the output does not depend on the scheduling.
 #include <algorithm>
-#include "gbx_internal.h"
+#include "mem_common.h"
 
 namespace gbx {
 namespace {
 
-constexpr int MC_SCAN = 1024;
 constexpr int MC_WMAX = (1 << 30) - 1;
 
 struct McHit { int cid, idx, qbeg, len; };          // per hit: its chain (creation id, -1: none) and place in it
@@ -43,26 +42,23 @@ struct McArgs {
     MemChainIo io;
     long long n_reads;
     long long *cnt;                  // [2][n_reads + 1]: kept chains / seeds per read, then their exclusive scan
-    long long *bsum;                 // [2][blocks]
     int *nch;                        // [n_reads]: chains a read made (kept or not)
     McHit *hit;                      // [pos_cap]
     McChainSt *ch;                   // [pos_cap]   slab of a read: its first hit
     long long *spos;                 // [pos_cap]   sorted heads
     int *sid, *ord, *K;              // [pos_cap]   sorted heads' ids; chain at rank i of the weight order; the filter's K
     unsigned long long *key;         // [2 pos_cap] slab at twice the first hit: the sort pads to a power of two
-    int blocks;
 };
 
 struct McSpan { long long j0, j1, hb, he; };
-__device__ inline long long mc_clamp(long long v, long long lo, long long hi) { return v < lo ? lo : v > hi ? hi : v; }
 __device__ inline McSpan mc_span(const McArgs &A, long long r)
 {
-    const long long n_smem = mc_clamp(*A.io.n_smem, 0, A.io.smem_cap), n_pos = mc_clamp(*A.io.n_pos, 0, A.io.pos_cap);
+    const long long n_smem = clampll(*A.io.n_smem, 0, A.io.smem_cap), n_pos = clampll(*A.io.n_pos, 0, A.io.pos_cap);
     McSpan s;
-    s.j0 = mc_clamp(A.io.smem_off[r], 0, n_smem);
-    s.j1 = mc_clamp(A.io.smem_off[r + 1], s.j0, n_smem);
-    s.hb = mc_clamp(A.io.pos_off[s.j0], 0, n_pos);
-    s.he = mc_clamp(A.io.pos_off[s.j1], s.hb, n_pos);
+    s.j0 = clampll(A.io.smem_off[r], 0, n_smem);
+    s.j1 = clampll(A.io.smem_off[r + 1], s.j0, n_smem);
+    s.hb = clampll(A.io.pos_off[s.j0], 0, n_pos);
+    s.he = clampll(A.io.pos_off[s.j1], s.hb, n_pos);
     return s;
 }
 
@@ -84,16 +80,6 @@ __device__ inline int mc_contig(const McArgs &A, long long rb, long long re)
     return e <= A.io.contig_off[c + 1] ? c : -1;
 }
 
-__device__ inline long long mc_gap(long long q, const gbx_mem_chain_params &p)
-{
-    const long long gd = (long long)((double)(q * p.a - p.o_del) / p.e_del + 1.);
-    const long long gi = (long long)((double)(q * p.a - p.o_ins) / p.e_ins + 1.);
-    long long g = gd > gi ? gd : gi;
-    g = g > 1 ? g : 1;
-    const long long w2 = 2ll * p.w;
-    return g < w2 ? g : w2;
-}
-
 // the seed joins the chain's running sums: query and reference cover, window candidates, last seed
 __device__ inline void mc_join(McChainSt &C, int qbeg, int len, long long rbeg, int lq, const gbx_mem_chain_params &p)
 {
@@ -106,19 +92,13 @@ __device__ inline void mc_join(McChainSt &C, int qbeg, int len, long long rbeg, 
     const long long wr = (long long)C.wr + add;
     C.wr = wr > 0x7fffffffll ? 0x7fffffff : (int)wr;          // (saturates above every possible wq: the minimum is exact)
     C.endr = re > C.endr ? re : C.endr;
-    const long long lo = rbeg - (qbeg + mc_gap(qbeg, p));
+    const long long lo = rbeg - (qbeg + max_gap(qbeg, p));
     const long long rest = (long long)lq - qe;
-    const long long hi = re + rest + mc_gap(rest, p);
+    const long long hi = re + rest + max_gap(rest, p);
     C.rmin = lo < C.rmin ? lo : C.rmin;
     C.rmax = hi > C.rmax ? hi : C.rmax;
     C.l_qbeg = qbeg; C.l_len = len; C.l_rbeg = rbeg;
     ++C.nseeds;
-}
-
-__device__ inline int mc_scan_incl(int v, int lane)
-{
-    for (int d = 1; d < 64; d <<= 1) { const int u = __shfl_up(v, d); if (lane >= d) v += u; }
-    return v;
 }
 
 // ---- chaining, weights, filter and windows of one read; leaves the read's counts and its state in the slabs
@@ -146,7 +126,7 @@ __global__ void __launch_bounds__(64) mem_chain_read_kernel(McArgs A)
             if (sb > rep_e) { l_rep += rep_e - rep_b; rep_b = sb; rep_e = se; }
             else rep_e = rep_e > se ? rep_e : se;
         }
-        const long long a = mc_clamp(A.io.pos_off[j], S.hb, S.he), e = mc_clamp(A.io.pos_off[j + 1], a, S.he);
+        const long long a = clampll(A.io.pos_off[j], S.hb, S.he), e = clampll(A.io.pos_off[j + 1], a, S.he);
         for (long long h = a; h < e; ++h) {
             const long long rbeg = A.io.pos[h];
             McHit rec = {-1, 0, qbeg, len};
@@ -326,10 +306,10 @@ __global__ void __launch_bounds__(64) mem_chain_read_kernel(McArgs A)
         const bool out = i < m && ch[c].kept > 0;
         const int ns = out ? ch[c].nseeds : 0;
         const unsigned long long bo = __ballot(out);
-        const int incl = mc_scan_incl(ns, lane);
+        const int incl = wave_scan_incl(ns, lane);
         if (out) {
             long long r0 = ch[c].rmin, r1 = ch[c].rmax;
-            r0 = mc_clamp(r0, 0, 2 * L); r1 = mc_clamp(r1, 0, 2 * L);
+            r0 = clampll(r0, 0, 2 * L); r1 = clampll(r1, 0, 2 * L);
             const bool fwd = ch[c].pos < L;
             if (r0 < L && L < r1) { if (fwd) r1 = L; else r0 = L; }
             const int cg = ch[c].contig;
@@ -349,61 +329,6 @@ __global__ void __launch_bounds__(64) mem_chain_read_kernel(McArgs A)
         A.nch[r] = nch;
         A.io.l_rep[r] = l_rep;
     }
-}
-
-// ---- exclusive scan of the per-read counts (n_reads + 1 entries each; blockIdx.y: chains, seeds)
-__global__ void __launch_bounds__(MC_SCAN) mem_chain_scan_kernel(McArgs A)
-{
-    __shared__ long long sh[MC_SCAN / 64];
-    long long *const cnt = A.cnt + (long long)blockIdx.y * (A.n_reads + 1);
-    const long long i = (long long)blockIdx.x * MC_SCAN + threadIdx.x;
-    const long long c = i < A.n_reads ? cnt[i] : 0;
-    long long v = c;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int d = 1; d < 64; d <<= 1) { const long long u = __shfl_up(v, d); if (lane >= d) v += u; }
-    if (lane == 63) sh[wv] = v;
-    __syncthreads();
-    long long before = 0;
-    for (int w = 0; w < wv; ++w) before += sh[w];
-    if (i <= A.n_reads) cnt[i] = before + v - c;
-    if (threadIdx.x == MC_SCAN - 1) A.bsum[(long long)blockIdx.y * A.blocks + blockIdx.x] = before + v;
-}
-
-// one block per quantity: exclusive scan of the block sums, the total to *n_chains / *n_seeds
-__global__ void __launch_bounds__(1024) mem_chain_top_kernel(McArgs A)
-{
-    __shared__ long long sh[1024];
-    __shared__ long long carry;
-    long long *const bsum = A.bsum + (long long)blockIdx.x * A.blocks;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < A.blocks; b0 += 1024) {
-        const int i = b0 + threadIdx.x;
-        const long long v = i < A.blocks ? bsum[i] : 0;
-        sh[threadIdx.x] = v;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {
-            const long long u = threadIdx.x >= d ? sh[threadIdx.x - d] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += u;
-            __syncthreads();
-        }
-        if (i < A.blocks) bsum[i] = carry + sh[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry += sh[1023];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *(blockIdx.x == 0 ? A.io.n_chains : A.io.n_seeds) = carry;
-}
-
-__global__ void __launch_bounds__(MC_SCAN) mem_chain_offset_kernel(McArgs A)
-{
-    long long *const cnt = A.cnt + (long long)blockIdx.y * (A.n_reads + 1);
-    const long long i = (long long)blockIdx.x * MC_SCAN + threadIdx.x;
-    if (i > A.n_reads) return;
-    const long long v = cnt[i] + A.bsum[(long long)blockIdx.y * A.blocks + blockIdx.x];
-    cnt[i] = v;
-    if (blockIdx.y == 0) A.io.chain_off[i] = v;
 }
 
 // ---- the records at their final places: lanes over the read's chains, then over its hits
@@ -454,20 +379,19 @@ struct McLayout { size_t o_cnt, o_bsum, o_nch, o_hit, o_ch, o_spos, o_sid, o_ord
 McLayout mc_layout(int64_t n_reads, int64_t pos_cap)
 {
     McLayout L;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t nr = (size_t)n_reads, np = (size_t)pos_cap;
-    L.blocks = (int)((n_reads + 1 + MC_SCAN - 1) / MC_SCAN);
+    L.blocks = mem_scan_blocks(n_reads);
     L.o_cnt = 0;
-    L.o_bsum = L.o_cnt + up(2 * (nr + 1) * 8);
-    L.o_nch = L.o_bsum + up(2 * (size_t)L.blocks * 8);
-    L.o_hit = L.o_nch + up(nr * 4);
-    L.o_ch = L.o_hit + up(np * sizeof(McHit));
-    L.o_spos = L.o_ch + up(np * sizeof(McChainSt));
-    L.o_sid = L.o_spos + up(np * 8);
-    L.o_ord = L.o_sid + up(np * 4);
-    L.o_K = L.o_ord + up(np * 4);
-    L.o_key = L.o_K + up(np * 4);
-    L.total = L.o_key + up(2 * np * 8);
+    L.o_bsum = L.o_cnt + align256(2 * (nr + 1) * 8);
+    L.o_nch = L.o_bsum + align256(2 * (size_t)L.blocks * 8);
+    L.o_hit = L.o_nch + align256(nr * 4);
+    L.o_ch = L.o_hit + align256(np * sizeof(McHit));
+    L.o_spos = L.o_ch + align256(np * sizeof(McChainSt));
+    L.o_sid = L.o_spos + align256(np * 8);
+    L.o_ord = L.o_sid + align256(np * 4);
+    L.o_K = L.o_ord + align256(np * 4);
+    L.o_key = L.o_K + align256(np * 4);
+    L.total = L.o_key + align256(2 * np * 8);
     return L;
 }
 
@@ -486,20 +410,17 @@ int mem_chain_launch(const gbx_mem_chain_params *p, int64_t n_reads, const MemCh
     char *wb = (char *)d_work;
     McArgs A;
     A.p = *p; A.io = io; A.n_reads = n_reads;
-    A.cnt = (long long *)(wb + L.o_cnt); A.bsum = (long long *)(wb + L.o_bsum); A.nch = (int *)(wb + L.o_nch);
+    A.cnt = (long long *)(wb + L.o_cnt); A.nch = (int *)(wb + L.o_nch);
     A.hit = (McHit *)(wb + L.o_hit); A.ch = (McChainSt *)(wb + L.o_ch); A.spos = (long long *)(wb + L.o_spos);
     A.sid = (int *)(wb + L.o_sid); A.ord = (int *)(wb + L.o_ord); A.K = (int *)(wb + L.o_K);
     A.key = (unsigned long long *)(wb + L.o_key);
-    A.blocks = L.blocks;
     if (n_reads > 0) {
         Stage st("mem_chain_read", s);
         hipLaunchKernelGGL(mem_chain_read_kernel, dim3((unsigned)n_reads), dim3(64), 0, s, A);
     }
     {
         Stage st("mem_chain_scan", s);
-        hipLaunchKernelGGL(mem_chain_scan_kernel, dim3(L.blocks, 2), dim3(MC_SCAN), 0, s, A);
-        hipLaunchKernelGGL(mem_chain_top_kernel, dim3(2), dim3(1024), 0, s, A);
-        hipLaunchKernelGGL(mem_chain_offset_kernel, dim3(L.blocks, 2), dim3(MC_SCAN), 0, s, A);
+        mem_scan_launch({A.cnt, n_reads, 2, (long long *)(wb + L.o_bsum), L.blocks, {io.n_chains, io.n_seeds}, io.chain_off, {}}, s);
     }
     if (n_reads > 0) {
         Stage st("mem_chain_pack", s);

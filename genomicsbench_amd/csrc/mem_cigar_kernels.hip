@@ -19,12 +19,11 @@
 //     with a scan of the counts in between - count, scan, pack as in mem_chain_kernels.hip.
 //   * every loop is counted: tries, strips, steps; the walk ends after |Q| + |T| bases at the latest.
 #include <algorithm>
-#include "gbx_internal.h"
+#include "mem_common.h"
 
 namespace gbx {
 namespace {
 
-constexpr int CG_SCAN = 1024;
 constexpr int CG_INF = -0x40000000;
 constexpr int CG_MAXLEN = 0x3fffffff;
 
@@ -119,10 +118,8 @@ struct CgArgs {
     MemCigarIo io;
     long long n, z_bytes;
     long long *off;                  // [2][n + 1]: direction room / CIGAR words per record, then their exclusive scans
-    long long *bsum;                 // [2][blocks]
     CgSt *st;                        // [n]
     unsigned char *z;                // [z_bytes]
-    int blocks;
 };
 
 __device__ inline int cg_code(unsigned c) { return c > 4 ? 4 : (int)c; }
@@ -152,58 +149,6 @@ __global__ void __launch_bounds__(256) mem_cigar_need_kernel(CgArgs A)
     if (k >= A.n) return;
     const CgRec R = cg_load(A, k);
     A.off[k] = R.valid == 1 ? cg_need(A.p, R) : 0;
-}
-
-// ---- exclusive scan of off[q][0 .. n] (n + 1 entries)
-__global__ void __launch_bounds__(CG_SCAN) mem_cigar_scan_kernel(CgArgs A, int q)
-{
-    __shared__ long long sh[CG_SCAN / 64];
-    long long *const cnt = A.off + (long long)q * (A.n + 1);
-    const long long i = (long long)blockIdx.x * CG_SCAN + threadIdx.x;
-    const long long c = i < A.n ? cnt[i] : 0;
-    long long v = c;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int d = 1; d < 64; d <<= 1) { const long long u = __shfl_up(v, d); if (lane >= d) v += u; }
-    if (lane == 63) sh[wv] = v;
-    __syncthreads();
-    long long before = 0;
-    for (int w = 0; w < wv; ++w) before += sh[w];
-    if (i <= A.n) cnt[i] = before + v - c;
-    if (threadIdx.x == CG_SCAN - 1) A.bsum[(long long)q * A.blocks + blockIdx.x] = before + v;
-}
-
-__global__ void __launch_bounds__(1024) mem_cigar_top_kernel(CgArgs A, int q)
-{
-    __shared__ long long sh[1024];
-    __shared__ long long carry;
-    long long *const bsum = A.bsum + (long long)q * A.blocks;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < A.blocks; b0 += 1024) {
-        const int i = b0 + threadIdx.x;
-        const long long v = i < A.blocks ? bsum[i] : 0;
-        sh[threadIdx.x] = v;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {
-            const long long u = threadIdx.x >= d ? sh[threadIdx.x - d] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += u;
-            __syncthreads();
-        }
-        if (i < A.blocks) bsum[i] = carry + sh[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry += sh[1023];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0 && q == 1) *A.io.n_cigar = carry;
-}
-
-__global__ void __launch_bounds__(CG_SCAN) mem_cigar_offset_kernel(CgArgs A, int q)
-{
-    long long *const cnt = A.off + (long long)q * (A.n + 1);
-    const long long i = (long long)blockIdx.x * CG_SCAN + threadIdx.x;
-    if (i > A.n) return;
-    cnt[i] += A.bsum[(long long)q * A.blocks + blockIdx.x];
 }
 
 // ---- ksw_global2 over the record's room: the score; the direction bytes stay behind for the walk
@@ -475,13 +420,12 @@ struct CgLayout { size_t o_off, o_bsum, o_st, o_z; int blocks; };
 CgLayout cg_layout(int64_t n)
 {
     CgLayout L;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t nr = (size_t)n;
-    L.blocks = (int)((n + 1 + CG_SCAN - 1) / CG_SCAN);
+    L.blocks = mem_scan_blocks(n);
     L.o_off = 0;
-    L.o_bsum = L.o_off + up(2 * (nr + 1) * 8);
-    L.o_st = L.o_bsum + up(2 * (size_t)L.blocks * 8);
-    L.o_z = L.o_st + up(nr * sizeof(CgSt));
+    L.o_bsum = L.o_off + align256(2 * (nr + 1) * 8);
+    L.o_st = L.o_bsum + align256(2 * (size_t)L.blocks * 8);
+    L.o_z = L.o_st + align256(nr * sizeof(CgSt));
     return L;
 }
 
@@ -513,13 +457,11 @@ int mem_cigar_launch(const gbx_mem_cigar_params *p, int64_t n, const MemCigarIo 
     char *wb = (char *)d_work;
     CgArgs A;
     A.p = *p; A.io = io; A.n = n; A.z_bytes = z_bytes;
-    A.off = (long long *)(wb + L.o_off); A.bsum = (long long *)(wb + L.o_bsum); A.st = (CgSt *)(wb + L.o_st);
+    A.off = (long long *)(wb + L.o_off); A.st = (CgSt *)(wb + L.o_st);
     A.z = (unsigned char *)(wb + L.o_z);
-    A.blocks = L.blocks;
-    auto scan = [&](int q) {
-        hipLaunchKernelGGL(mem_cigar_scan_kernel, dim3(L.blocks), dim3(CG_SCAN), 0, s, A, q);
-        hipLaunchKernelGGL(mem_cigar_top_kernel, dim3(1), dim3(1024), 0, s, A, q);
-        hipLaunchKernelGGL(mem_cigar_offset_kernel, dim3(L.blocks), dim3(CG_SCAN), 0, s, A, q);
+    auto scan = [&](int q) {                                     // off[q][0 .. n]; only the words' total leaves
+        mem_scan_launch({A.off + q * (n + 1), n, 1, (long long *)(wb + L.o_bsum) + q * L.blocks, L.blocks, {q == 1 ? io.n_cigar : nullptr, nullptr},
+                         nullptr, {}}, s);
     };
     {
         Stage st("mem_cigar_need", s);

@@ -8,9 +8,9 @@
 //     and insert size - integer counts, so the bins do not depend on the scheduling.  One block of four waves, a direction per
 //     wave, then walks its bins: the total, the percentiles from running prefix counts, the integer sums of avg, and S in
 //     ascending order of the value (one add per occupied bin, every lane the same chain), as the rules fix it.
-//   * pairing: one pair per wavefront.  The keys of both ends' regions are sorted in registers with shuffles up to 64 and by a
-//     bitonic network over the pair's slab (twice its first region, room for the next power of two) above that.  The look-back
-//     is serial in i with lanes over k downwards; the first lane beyond `high` comes from a ballot and only the lanes below it
+//   * pairing: one pair per wavefront.  The keys of both ends' regions are sorted by wave_sort of mem_common.h: in registers with
+//     shuffles up to 64 and by a bitonic network over the pair's slab (twice its first region, room for the next power of two)
+//     above that.  The look-back is serial in i with lanes over k downwards; the first lane beyond `high` comes from a ballot and only the lanes below it
 //     make candidates.  No candidate list is kept: a first scan leaves the best two (unique (X, Y), wave reduction) and the
 //     count, a second scan of the same kind counts n_sub.  No per-pair capacity, no second path.
 //   * decision: uniform over the wave; the changed regions go to d_pregs at the places they have in d_regs, the reported ones
@@ -18,14 +18,12 @@
 //   * output: per-read counts of reported regions, a scan over the reads, a pack pass that renumbers sel and writes the seed and
 //     result records at their final places, a tail pass: no dependence on the scheduling.
 #include <cstring>
-#include "gbx_internal.h"
+#include "mem_common.h"
 
 namespace gbx {
 namespace {
 
-constexpr int MP_SCAN = 1024;
-
-struct MpKey { unsigned long long x, y; };
+using MpKey = WaveKey<2>;                           // (x, y) of mem_pair: w[0] the place, w[1] score, index, strand and end
 static_assert(sizeof(MpKey) == 16 && sizeof(gbx_mem_pair_params) == 56 && sizeof(gbx_mem_pestat) == 32 && sizeof(gbx_mem_pair) == 56 &&
               sizeof(gbx_mem_reg) == 88, "records");
 
@@ -36,13 +34,10 @@ struct MpArgs {
     int has_pes;                     // the caller's estimate is used, none is made
     gbx_mem_pestat pes_in[4];
     long long *cnt;                  // [2 n_pairs + 1]: reported regions per read, then their exclusive scan
-    long long *bsum;                 // [blocks]
     unsigned *bins;                  // [4][max_ins + 1]: pairs per direction and insert size
     MpKey *key;                      // [2 reg_cap]  slab of a pair: twice its first region
-    int blocks;
 };
 
-__device__ inline long long mp_clamp(long long v, long long lo, long long hi) { return v < lo ? lo : v > hi ? hi : v; }
 __device__ inline bool mp_upstream_ok(const MpArgs &A) { const long long n = *A.io.n_regs; return n >= 0 && n <= A.io.reg_cap; }
 
 struct MpSpan { long long g0, g1, g2; bool ok; };    // the pair's regions: end 0 [g0, g1), end 1 [g1, g2)
@@ -51,16 +46,10 @@ __device__ inline MpSpan mp_span(const MpArgs &A, long long p)
     MpSpan s;
     s.ok = mp_upstream_ok(A);
     const long long n = s.ok ? *A.io.n_regs : 0;
-    s.g0 = mp_clamp(A.io.reg_off[2 * p], 0, n);
-    s.g1 = mp_clamp(A.io.reg_off[2 * p + 1], s.g0, n);
-    s.g2 = mp_clamp(A.io.reg_off[2 * p + 2], s.g1, n);
+    s.g0 = clampll(A.io.reg_off[2 * p], 0, n);
+    s.g1 = clampll(A.io.reg_off[2 * p + 1], s.g0, n);
+    s.g2 = clampll(A.io.reg_off[2 * p + 2], s.g1, n);
     return s;
-}
-
-__device__ inline unsigned long long mp_hash64(unsigned long long k)
-{
-    k += ~(k << 32); k ^= k >> 22; k += ~(k << 13); k ^= k >> 8; k += k << 3; k ^= k >> 15; k += ~(k << 27); k ^= k >> 31;
-    return k;
 }
 
 __device__ inline int mp_infer_dir(long long L, long long b1, long long b2, long long *dist)
@@ -83,24 +72,6 @@ __device__ inline float mp_frac_rep(const MpArgs &A, long long read, const gbx_m
 {
     const int lq = R.seed >= 0 && R.seed < A.io.seed_cap ? A.io.seeds[R.seed].lq : 0;
     return lq > 0 ? (float)A.io.l_rep[read] / (float)lq : 0.f;
-}
-
-// mem_approx_mapq_se with csub = 0 on the region's current sub and sub_n; everything in double but frac_rep
-__device__ inline int mp_mapq(const gbx_mem_reg &R, float frac_rep, const gbx_mem_pair_params &p)
-{
-    const int sub = R.sub ? R.sub : p.min_seed_len * p.a;
-    if (sub >= R.score) return 0;
-    const long long lr = R.re - R.rb;
-    const int l = R.qe - R.qb > lr ? R.qe - R.qb : (int)lr;
-    if (l < 1 || R.score == 0) return 0;
-    const double identity = 1. - (double)(l * p.a - R.score) / (double)(p.a + p.b) / (double)l;
-    double t = l < p.mapq_coef_len ? 1. : (double)p.mapq_coef_fac / log((double)l);
-    t *= identity * identity;
-    int mapq = (int)(6.02 * (double)(R.score - sub) / (double)p.a * t * t + .499);
-    if (R.sub_n > 0) mapq -= (int)(4.343 * log((double)(R.sub_n + 1)) + .499);
-    mapq = mapq > 60 ? 60 : mapq;
-    mapq = mapq < 0 ? 0 : mapq;
-    return (int)((double)mapq * (1. - (double)frac_rep) + .499);
 }
 
 __device__ inline int mp_raw_mapq(int d, int a) { return (int)(6.02 * (double)d / (double)a + .499); }
@@ -161,9 +132,8 @@ __global__ void __launch_bounds__(256) mem_pair_stat_kernel(MpArgs A)
         for (int v0 = 0; v0 < nb; v0 += 64) {
             const int v = v0 + lane;
             const long long c = v < nb ? b[v] : 0;
-            long long inc = c;
-            for (int s = 1; s < 64; s <<= 1) { const long long u = __shfl_up(inc, s); if (lane >= s) inc += u; }
-            const long long lo = run + inc - c, hi = run + inc;                  // this bin holds sorted[lo .. hi)
+            const long long inc = wave_scan_incl(c, lane);
+                        const long long lo = run + inc - c, hi = run + inc;                  // this bin holds sorted[lo .. hi)
             const unsigned long long b25 = __ballot(lo <= i25 && i25 < hi), b75 = __ballot(lo <= i75 && i75 < hi);
             if (b25) p25 = v0 + __builtin_ctzll(b25);
             if (b75) p75 = v0 + __builtin_ctzll(b75);
@@ -207,41 +177,6 @@ __global__ void __launch_bounds__(256) mem_pair_stat_kernel(MpArgs A)
     if (lane == 0) A.io.pes[d] = r;
 }
 
-__device__ inline bool mp_less(const MpKey &a, const MpKey &b) { return a.x != b.x ? a.x < b.x : a.y < b.y; }
-
-// ascending sort of key[0 .. n) in place (the slab has room for the next power of two); ends in a barrier
-__device__ inline void mp_sort(MpKey *key, int n, int lane)
-{
-    const MpKey pad = {~0ull, ~0ull};
-    if (n <= 64) {
-        MpKey v = lane < n ? key[lane] : pad;
-        for (int k = 2; k <= 64; k <<= 1)
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                MpKey o;
-                o.x = __shfl_xor(v.x, j); o.y = __shfl_xor(v.y, j);
-                const bool up = (lane & k) == 0, lower = (lane & j) == 0;
-                if ((lower == up) ? mp_less(o, v) : mp_less(v, o)) v = o;
-            }
-        if (lane < n) key[lane] = v;
-    } else {
-        int P = 64;
-        for (int it = 0; it < 25; ++it) { if (P >= n) break; P <<= 1; }
-        for (int i = n + lane; i < P; i += 64) key[i] = pad;
-        __syncthreads();
-        for (int k = 2; k <= P; k <<= 1)
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int t = lane; t < (P >> 1); t += 64) {
-                    const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), o = i | j;
-                    const MpKey x = key[i], y = key[o];
-                    const bool up = (i & k) == 0;
-                    if (mp_less(y, x) == up && (mp_less(y, x) || mp_less(x, y))) { key[i] = y; key[o] = x; }
-                }
-                __syncthreads();
-            }
-    }
-    __syncthreads();
-}
-
 __device__ inline bool mp_above(unsigned long long X, unsigned long long Y, unsigned long long X2, unsigned long long Y2)
 {
     return X != X2 ? X > X2 : Y > Y2;
@@ -259,25 +194,25 @@ __device__ inline void mp_lookback(const MpKey *key, int n, const gbx_mem_pestat
     for (int i = 0; i < n; ++i) {
         const MpKey ki = key[i];
         for (int r = 0; r < 2; ++r) {
-            const int dir = r << 1 | (int)(ki.y >> 1 & 1);
+            const int dir = r << 1 | (int)(ki.w[1] >> 1 & 1);
             const gbx_mem_pestat pe = pes[dir];
             if (pe.failed) continue;
-            const int which = r << 1 | (int)((ki.y & 1) ^ 1);
+            const int which = r << 1 | (int)((ki.w[1] & 1) ^ 1);
             const int lw = which == 0 ? l0 : which == 1 ? l1 : which == 2 ? l2 : l3;
             for (int jb = 0; jb <= lw; jb += 64) {
                 const int k = lw - jb - lane;
-                MpKey kk = {0, 0};
+                MpKey kk = {{0, 0}};
                 if (k >= 0) kk = key[k];
-                const bool match = k >= 0 && (int)(kk.y & 3) == which;
-                const long long dist = (long long)(ki.x - kk.x);
+                const bool match = k >= 0 && (int)(kk.w[1] & 3) == which;
+                const long long dist = (long long)(ki.w[0] - kk.w[0]);
                 const unsigned long long bs = __ballot(match && dist > pe.high);
                 const int first = bs ? __builtin_ctzll(bs) : 64;
                 if (match && lane < first && dist >= pe.low) {
                     const double ns = ((double)dist - pe.avg) / pe.std;
-                    const double qd = (double)((ki.y >> 32) + (kk.y >> 32)) + .721 * log(2. * erfc(fabs(ns) * M_SQRT1_2)) * (double)p.a + .499;
+                    const double qd = (double)((ki.w[1] >> 32) + (kk.w[1] >> 32)) + .721 * log(2. * erfc(fabs(ns) * M_SQRT1_2)) * (double)p.a + .499;
                     const int q = qd > 0. ? (int)qd : 0;                          // -inf (erfc underflowed) and NaN give 0
                     const unsigned long long Y = (unsigned long long)k << 32 | (unsigned)i;
-                    const unsigned long long X = (unsigned long long)q << 32 | (mp_hash64(Y ^ id8) & 0xffffffffull);
+                    const unsigned long long X = (unsigned long long)q << 32 | (hash64(Y ^ id8) & 0xffffffffull);
                     if (count_sub) {
                         if (!(X == bX && Y == bY) && sub - q <= tmp) ++B.n;
                     } else {
@@ -289,7 +224,7 @@ __device__ inline void mp_lookback(const MpKey *key, int n, const gbx_mem_pestat
                 if (bs) break;
             }
         }
-        const int w = (int)(ki.y & 3);
+        const int w = (int)(ki.w[1] & 3);
         if (w == 0) l0 = i; else if (w == 1) l1 = i; else if (w == 2) l2 = i; else l3 = i;
     }
 }
@@ -330,12 +265,12 @@ __global__ void __launch_bounds__(64) mem_pair_pair_kernel(MpArgs A)
             const long long fwd = rev ? 2 * L - 1 - R.rb : R.rb;
             const long long off = R.rid >= 0 && R.rid < A.io.n_contigs ? A.io.contig_off[R.rid] : 0;
             MpKey v;
-            v.x = (unsigned long long)R.rid << 32 | (unsigned long long)(fwd - off);
-            v.y = (unsigned long long)R.score << 32 | (unsigned long long)i << 2 | (rev ? 2u : 0u) | (unsigned)e;
+            v.w[0] = (unsigned long long)R.rid << 32 | (unsigned long long)(fwd - off);
+            v.w[1] = (unsigned long long)R.score << 32 | (unsigned long long)i << 2 | (rev ? 2u : 0u) | (unsigned)e;
             key[t] = v;
         }
         __syncthreads();
-        mp_sort(key, n, lane);
+        wave_sort(key, n, lane);
         const unsigned long long id8 = (unsigned long long)(A.pair_id0 + pr) << 8;
         MpBest B = {0, 0, 0, 0, 0};
         mp_lookback(key, n, pes, p, id8, lane, false, 0, 0, 0, 0, B);
@@ -354,7 +289,7 @@ __global__ void __launch_bounds__(64) mem_pair_pair_kernel(MpArgs A)
         }
         out.n_cand = n_cand;
         if (n_cand > 0) {
-            const unsigned long long y1 = key[gY >> 32].y, y2 = key[gY & 0xffffffffull].y;
+            const unsigned long long y1 = key[gY >> 32].w[1], y2 = key[gY & 0xffffffffull].w[1];
             z[y1 & 1] = (int)((y1 & 0xffffffffull) >> 2);
             z[y2 & 1] = (int)((y2 & 0xffffffffull) >> 2);
             out.score = (int)(gX >> 32);
@@ -399,7 +334,7 @@ __global__ void __launch_bounds__(64) mem_pair_pair_kernel(MpArgs A)
                     c.sub = a[e][c.secondary < ne[e] ? c.secondary : 0].score;
                     c.secondary = -2;
                 }
-                int q = mp_mapq(c, fr[e], p);
+                int q = approx_mapq_se(c, fr[e], p);
                 q = q > q_pe ? q : q_pe < q + 40 ? q_pe : q + 40;
                 const int cap = mp_raw_mapq(c.score, p.a);
                 q_se[e] = q < cap ? q : cap;
@@ -409,7 +344,7 @@ __global__ void __launch_bounds__(64) mem_pair_pair_kernel(MpArgs A)
         } else {
             for (int e = 0; e < 2; ++e) {
                 z[e] = 0;
-                q_se[e] = mp_mapq(a[e][0], fr[e], p);
+                q_se[e] = approx_mapq_se(a[e][0], fr[e], p);
                 c_sub[e] = a[e][0].sub; c_sec[e] = a[e][0].secondary;
             }
         }
@@ -465,57 +400,6 @@ __global__ void __launch_bounds__(64) mem_pair_pair_kernel(MpArgs A)
     if (lane == 0) A.io.pairs[pr] = out;
 }
 
-// ---- exclusive scan of the per-read counts (2 n_pairs + 1 entries)
-__global__ void __launch_bounds__(MP_SCAN) mem_pair_scan_kernel(MpArgs A)
-{
-    __shared__ long long sh[MP_SCAN / 64];
-    const long long n_reads = 2 * A.n_pairs;
-    const long long i = (long long)blockIdx.x * MP_SCAN + threadIdx.x;
-    const long long c = i < n_reads ? A.cnt[i] : 0;
-    long long v = c;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int d = 1; d < 64; d <<= 1) { const long long u = __shfl_up(v, d); if (lane >= d) v += u; }
-    if (lane == 63) sh[wv] = v;
-    __syncthreads();
-    long long before = 0;
-    for (int w = 0; w < wv; ++w) before += sh[w];
-    if (i <= n_reads) A.cnt[i] = before + v - c;
-    if (threadIdx.x == MP_SCAN - 1) A.bsum[blockIdx.x] = before + v;
-}
-
-// one block: exclusive scan of the block sums, the total (-1: the stage before it overflowed) to *n_psel
-__global__ void __launch_bounds__(1024) mem_pair_top_kernel(MpArgs A)
-{
-    __shared__ long long sh[1024];
-    __shared__ long long carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < A.blocks; b0 += 1024) {
-        const int i = b0 + threadIdx.x;
-        const long long v = i < A.blocks ? A.bsum[i] : 0;
-        sh[threadIdx.x] = v;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {
-            const long long u = threadIdx.x >= d ? sh[threadIdx.x - d] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += u;
-            __syncthreads();
-        }
-        if (i < A.blocks) A.bsum[i] = carry + sh[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry += sh[1023];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *A.io.n_psel = mp_upstream_ok(A) ? carry : -1;
-}
-
-__global__ void __launch_bounds__(MP_SCAN) mem_pair_offset_kernel(MpArgs A)
-{
-    const long long i = (long long)blockIdx.x * MP_SCAN + threadIdx.x;
-    if (i > 2 * A.n_pairs) return;
-    A.cnt[i] += A.bsum[blockIdx.x];
-}
-
 // ---- sel renumbered and the CIGAR list's records at their final places: lanes over the pair's regions
 __global__ void __launch_bounds__(64) mem_pair_pack_kernel(MpArgs A)
 {
@@ -535,8 +419,7 @@ __global__ void __launch_bounds__(64) mem_pair_pack_kernel(MpArgs A)
             s = A.io.sel_seeds[old]; e = A.io.sel_res[old];
         } else if (R->seed >= 0 && R->seed < A.io.seed_cap) {                    // not reported there: built as that stage builds them
             s = A.io.seeds[R->seed];
-            e.score = R->score; e.truesc = R->truesc; e.qb = R->qb; e.qe = R->qe;
-            e.rb = (int32_t)(R->rb - s.roff); e.re = (int32_t)(R->re - s.roff); e.w = R->w; e.sc0 = 0;
+            e = reg_result(*R, s);
         } else {
             memset(&s, 0, sizeof(s));
             memset(&e, 0xff, sizeof(e));
@@ -546,30 +429,18 @@ __global__ void __launch_bounds__(64) mem_pair_pack_kernel(MpArgs A)
     }
 }
 
-// the CIGAR list past the count, up to the capacity: zeroed seeds (len = 0 is no seed) with results of all -1
-__global__ void __launch_bounds__(256) mem_pair_tail_kernel(MpArgs A)
-{
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long n = *A.io.n_psel;
-    if (t >= A.io.psel_cap || t < (n < 0 ? 0 : n)) return;
-    long long *const s = (long long *)(A.io.psel_seeds + t), *const e = (long long *)(A.io.psel_res + t);
-    for (int k = 0; k < 5; ++k) s[k] = 0;
-    for (int k = 0; k < 4; ++k) e[k] = -1;
-}
-
 struct MpLayout { size_t o_cnt, o_bsum, o_bins, o_key, bins_bytes, total; int blocks; };
 MpLayout mp_layout(int64_t n_pairs, int64_t reg_cap, int32_t max_ins)
 {
     MpLayout L;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t nr = 2 * (size_t)n_pairs;
-    L.blocks = (int)((2 * n_pairs + 1 + MP_SCAN - 1) / MP_SCAN);
+    L.blocks = mem_scan_blocks(2 * n_pairs);
     L.bins_bytes = 4 * ((size_t)max_ins + 1) * 4;
     L.o_cnt = 0;
-    L.o_bsum = L.o_cnt + up((nr + 1) * 8);
-    L.o_bins = L.o_bsum + up((size_t)L.blocks * 8);
-    L.o_key = L.o_bins + up(L.bins_bytes);
-    L.total = L.o_key + up(2 * (size_t)reg_cap * sizeof(MpKey));
+    L.o_bsum = L.o_cnt + align256((nr + 1) * 8);
+    L.o_bins = L.o_bsum + align256((size_t)L.blocks * 8);
+    L.o_key = L.o_bins + align256(L.bins_bytes);
+    L.total = L.o_key + align256(2 * (size_t)reg_cap * sizeof(MpKey));
     return L;
 }
 
@@ -591,9 +462,8 @@ int mem_pair_launch(const gbx_mem_pair_params *p, int64_t n_pairs, int64_t pair_
     A.p = *p; A.io = io; A.n_pairs = n_pairs; A.pair_id0 = pair_id0;
     A.has_pes = pes_in != nullptr;
     for (int d = 0; d < 4; ++d) A.pes_in[d] = pes_in ? pes_in[d] : gbx_mem_pestat{0, 0, 1, 0, 0., 0.};
-    A.cnt = (long long *)(wb + L.o_cnt); A.bsum = (long long *)(wb + L.o_bsum); A.bins = (unsigned *)(wb + L.o_bins);
+    A.cnt = (long long *)(wb + L.o_cnt); A.bins = (unsigned *)(wb + L.o_bins);
     A.key = (MpKey *)(wb + L.o_key);
-    A.blocks = L.blocks;
     {
         Stage st("mem_pair_pestat", s);
         if (!pes_in && n_pairs > 0) {
@@ -609,9 +479,9 @@ int mem_pair_launch(const gbx_mem_pair_params *p, int64_t n_pairs, int64_t pair_
     }
     {
         Stage st("mem_pair_scan", s);
-        hipLaunchKernelGGL(mem_pair_scan_kernel, dim3(L.blocks), dim3(MP_SCAN), 0, s, A);
-        hipLaunchKernelGGL(mem_pair_top_kernel, dim3(1), dim3(1024), 0, s, A);
-        hipLaunchKernelGGL(mem_pair_offset_kernel, dim3(L.blocks), dim3(MP_SCAN), 0, s, A);
+        // the total is -1 when the regs stage overflowed: the condition of mp_upstream_ok
+        mem_scan_launch({A.cnt, 2 * n_pairs, 1, (long long *)(wb + L.o_bsum), L.blocks, {io.n_psel, nullptr}, nullptr,
+                         {{io.n_regs, 0, io.reg_cap}, {}}}, s);
     }
     if (n_pairs > 0) {
         Stage st("mem_pair_pack", s);
@@ -619,7 +489,7 @@ int mem_pair_launch(const gbx_mem_pair_params *p, int64_t n_pairs, int64_t pair_
     }
     if (io.psel_cap > 0) {
         Stage st("mem_pair_tail", s);
-        hipLaunchKernelGGL(mem_pair_tail_kernel, dim3((unsigned)((io.psel_cap + 255) / 256)), dim3(256), 0, s, A);
+        mem_sel_tail_launch(io.psel_seeds, io.psel_res, io.psel_cap, io.n_psel, s);
     }
     GBX_HIP(hipGetLastError());
     GBX_GUARD_CHECK("mem pair");

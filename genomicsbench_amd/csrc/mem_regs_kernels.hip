@@ -14,19 +14,18 @@
 //     exceed, no second path.  Regions stay where they were created; the orders are index lists (ord / ordb).
 //   * a scan that stops at an element takes the first such element from a ballot; what the elements before it are owed (the
 //     walk's exclusions) is applied to the lanes below it only.
-//   * sorts: 192-bit keys (three words, compared in order), unique, so any correct sort gives the same order - in registers
-//     with shuffles up to 64 keys, a bitonic network over the slab above that.
+//   * sorts: 192-bit keys (three words, compared in order), unique, so any correct sort gives the same order - wave_sort of
+//     mem_common.h: in registers with shuffles up to 64 keys, a bitonic network over the slab above that.
 //   * output: the read kernel leaves per-read counts, a scan over the reads turns them into offsets (reg_off and the CIGAR
 //     list's), a pack pass writes region, seed and result records at their final places: no dependence on the scheduling.
-#include "gbx_internal.h"
+#include "mem_common.h"
 
 namespace gbx {
 namespace {
 
-constexpr int MR_SCAN = 1024;
 constexpr unsigned long long MR_SIGN = 1ull << 63;
 
-struct MrKey { unsigned long long a, b, c; };       // compared a, then b, then c; the low 32 bits of c: the element's index
+using MrKey = WaveKey<3>;                           // the low 32 bits of the last word: the element's index
 static_assert(sizeof(MrKey) == 24, "MrKey");
 static_assert(sizeof(gbx_mem_reg) == 88 && sizeof(gbx_mem_regs_params) == 64 && sizeof(gbx_bsw_seed_result) == 32, "records");
 
@@ -35,15 +34,11 @@ struct MrArgs {
     MemRegsIo io;
     long long n_reads, read_id0;
     long long *cnt;                  // [2][n_reads + 1]: regions / reported regions per read, then their exclusive scan
-    long long *bsum;                 // [2][blocks]
     gbx_mem_reg *rg;                 // [seed_cap]   slab of a read: its first seed; regions in creation order
     int *took;                       // [seed_cap]   per seed: it made a region
     int *ord, *ordb, *z, *excl;      // [seed_cap]   two index lists; the primaries; the dedup's exclusions (by creation index)
     MrKey *key;                      // [2 seed_cap] slab at twice the first seed: the sort pads to a power of two
-    int blocks;
 };
-
-__device__ inline long long mr_clamp(long long v, long long lo, long long hi) { return v < lo ? lo : v > hi ? hi : v; }
 
 struct MrSpan { long long c0, c1, s0, room, n_seeds; bool ok; };
 __device__ inline bool mr_upstream_ok(const MrArgs &A) { return *A.io.n_chains <= A.io.chain_cap && *A.io.n_seeds <= A.io.seed_cap; }
@@ -51,68 +46,13 @@ __device__ inline MrSpan mr_span(const MrArgs &A, long long r)
 {
     MrSpan s;
     s.ok = mr_upstream_ok(A);
-    const long long n_chains = mr_clamp(*A.io.n_chains, 0, A.io.chain_cap);
-    s.n_seeds = mr_clamp(*A.io.n_seeds, 0, A.io.seed_cap);
-    s.c0 = mr_clamp(A.io.chain_off[r], 0, n_chains);
-    s.c1 = mr_clamp(A.io.chain_off[r + 1], s.c0, n_chains);
-    s.s0 = s.c1 > s.c0 ? mr_clamp(A.io.chains[s.c0].seed_off, 0, s.n_seeds) : 0;
+    const long long n_chains = clampll(*A.io.n_chains, 0, A.io.chain_cap);
+    s.n_seeds = clampll(*A.io.n_seeds, 0, A.io.seed_cap);
+    s.c0 = clampll(A.io.chain_off[r], 0, n_chains);
+    s.c1 = clampll(A.io.chain_off[r + 1], s.c0, n_chains);
+    s.s0 = s.c1 > s.c0 ? clampll(A.io.chains[s.c0].seed_off, 0, s.n_seeds) : 0;
     s.room = s.n_seeds - s.s0;                      // the slab's length: what the read's chains can hold when they lie in order
     return s;
-}
-
-__device__ inline long long mr_gap(long long q, const gbx_mem_regs_params &p)
-{
-    const long long gd = (long long)((double)(q * p.a - p.o_del) / p.e_del + 1.);
-    const long long gi = (long long)((double)(q * p.a - p.o_ins) / p.e_ins + 1.);
-    long long g = gd > gi ? gd : gi;
-    g = g > 1 ? g : 1;
-    const long long w2 = 2ll * p.w;
-    return g < w2 ? g : w2;
-}
-
-__device__ inline unsigned long long mr_hash64(unsigned long long k)
-{
-    k += ~(k << 32); k ^= k >> 22; k += ~(k << 13); k ^= k >> 8; k += k << 3; k ^= k >> 15; k += ~(k << 27); k ^= k >> 31;
-    return k;
-}
-
-__device__ inline bool mr_less(const MrKey &x, const MrKey &y)
-{
-    return x.a != y.a ? x.a < y.a : x.b != y.b ? x.b < y.b : x.c < y.c;
-}
-
-// ascending sort of key[0 .. n) in place (the slab has room for the next power of two); the caller's stores to key are
-// ordered before it by a barrier, and it ends in one
-__device__ inline void mr_sort(MrKey *key, int n, int lane)
-{
-    const MrKey pad = {~0ull, ~0ull, ~0ull};
-    if (n <= 64) {
-        MrKey v = lane < n ? key[lane] : pad;
-        for (int k = 2; k <= 64; k <<= 1)
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                MrKey o;
-                o.a = __shfl_xor(v.a, j); o.b = __shfl_xor(v.b, j); o.c = __shfl_xor(v.c, j);
-                const bool up = (lane & k) == 0, lower = (lane & j) == 0;
-                if ((lower == up) ? mr_less(o, v) : mr_less(v, o)) v = o;
-            }
-        if (lane < n) key[lane] = v;
-    } else {
-        int P = 64;
-        for (int it = 0; it < 25; ++it) { if (P >= n) break; P <<= 1; }
-        for (int i = n + lane; i < P; i += 64) key[i] = pad;
-        __syncthreads();
-        for (int k = 2; k <= P; k <<= 1)
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int t = lane; t < (P >> 1); t += 64) {
-                    const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), o = i | j;
-                    const MrKey x = key[i], y = key[o];
-                    const bool up = (i & k) == 0;
-                    if (mr_less(y, x) == up && (mr_less(y, x) || mr_less(x, y))) { key[i] = y; key[o] = x; }
-                }
-                __syncthreads();
-            }
-    }
-    __syncthreads();
 }
 
 // the seed [sq, sq + sl) x [sr, sr + sl) lies inside the region and around its diagonal, ahead or behind (mem_chain2aln)
@@ -121,32 +61,13 @@ __device__ inline bool mr_around(const gbx_mem_reg &P, int sq, long long sr, int
     if (sr < P.rb || sr + sl > P.re || sq < P.qb || sq + sl > P.qe) return false;
     if ((double)(sl - P.seedlen0) > .1 * (double)lq) return false;
     long long qd = sq - P.qb, rd = sr - P.rb;
-    long long wg = mr_gap(qd < rd ? qd : rd, p);
+    long long wg = max_gap(qd < rd ? qd : rd, p);
     wg = wg < P.w ? wg : P.w;
     if (qd - rd < wg && rd - qd < wg) return true;
     qd = P.qe - (sq + sl); rd = P.re - (sr + sl);
-    wg = mr_gap(qd < rd ? qd : rd, p);
+    wg = max_gap(qd < rd ? qd : rd, p);
     wg = wg < P.w ? wg : P.w;
     return qd - rd < wg && rd - qd < wg;
-}
-
-// mem_approx_mapq_se with csub = 0; everything in double but frac_rep
-__device__ inline int mr_mapq(const gbx_mem_reg &R, int l_rep, int lq, const gbx_mem_regs_params &p)
-{
-    const int sub = R.sub ? R.sub : p.min_seed_len * p.a;
-    if (sub >= R.score) return 0;
-    const long long lr = R.re - R.rb;
-    const int l = R.qe - R.qb > lr ? R.qe - R.qb : (int)lr;
-    if (l < 1 || R.score == 0) return 0;
-    const double identity = 1. - (double)(l * p.a - R.score) / (double)(p.a + p.b) / (double)l;
-    double t = l < p.mapq_coef_len ? 1. : (double)p.mapq_coef_fac / log((double)l);
-    t *= identity * identity;
-    int mapq = (int)(6.02 * (double)(R.score - sub) / (double)p.a * t * t + .499);
-    if (R.sub_n > 0) mapq -= (int)(4.343 * log((double)(R.sub_n + 1)) + .499);
-    mapq = mapq > 60 ? 60 : mapq;
-    mapq = mapq < 0 ? 0 : mapq;
-    const float frac_rep = (float)l_rep / (float)lq;
-    return (int)((double)mapq * (1. - (double)frac_rep) + .499);
 }
 
 // ---- the regions of one read, in their output order; leaves the read's counts and its state in the slabs
@@ -164,14 +85,14 @@ __global__ void __launch_bounds__(64) mem_regs_read_kernel(MrArgs A)
     int *const ord = A.ord + S.s0, *const ordb = A.ordb + S.s0, *const z = A.z + S.s0, *const excl = A.excl + S.s0;
     MrKey *const key = A.key + 2 * S.s0;
     const unsigned long long below = (1ull << lane) - 1;
-    const MrKey pad = {~0ull, ~0ull, ~0ull};
+    const MrKey pad = {{~0ull, ~0ull, ~0ull}};
 
     // ---- 1: the choice of seeds, serial in the seeds of every chain
     int nav = 0;
     for (long long c = S.c0; c < S.c1; ++c) {
         const gbx_mem_chain ch = A.io.chains[c];
-        const long long so = mr_clamp(ch.seed_off, 0, S.n_seeds);
-        const int ns = (int)mr_clamp(ch.n_seeds, 0, S.n_seeds - so);
+        const long long so = clampll(ch.seed_off, 0, S.n_seeds);
+        const int ns = (int)clampll(ch.n_seeds, 0, S.n_seeds - so);
         const gbx_bsw_seed *const seeds = A.io.seeds + so;
         const gbx_bsw_seed_result *const res = A.io.res + so;
         int *const took = A.took + so;
@@ -183,15 +104,15 @@ __global__ void __launch_bounds__(64) mem_regs_read_kernel(MrArgs A)
             if (k < ns) {
                 took[k] = 0;
                 MrKey v = pad;
-                if (present) { v.a = (unsigned)seeds[k].len ^ 0x80000000u; v.b = 0; v.c = (unsigned)k; }
+                if (present) { v.w[0] = (unsigned)seeds[k].len ^ 0x80000000u; v.w[1] = 0; v.w[2] = (unsigned)k; }
                 key[k] = v;
             }
             m += __builtin_popcountll(__ballot(present));
         }
         __syncthreads();
-        mr_sort(key, ns, lane);
+        wave_sort(key, ns, lane);
         for (int t = m - 1; t >= 0; --t) {                                       // by (len, index) from the largest down
-            const int k = (int)(unsigned)key[t].c;
+            const int k = (int)(unsigned)key[t].w[2];
             const gbx_bsw_seed s = seeds[k];
             const gbx_bsw_seed_result e = res[k];
             const long long sr = s.roff + s.rbeg;
@@ -245,13 +166,13 @@ __global__ void __launch_bounds__(64) mem_regs_read_kernel(MrArgs A)
     if (n >= 2) {
         for (int i = lane; i < n; i += 64) {
             MrKey v;
-            v.a = (unsigned long long)rg[i].re ^ MR_SIGN; v.b = 0; v.c = (unsigned)i;
+            v.w[0] = (unsigned long long)rg[i].re ^ MR_SIGN; v.w[1] = 0; v.w[2] = (unsigned)i;
             key[i] = v;
             excl[i] = 0;
         }
         __syncthreads();
-        mr_sort(key, n, lane);
-        for (int i = lane; i < n; i += 64) ord[i] = (int)(unsigned)key[i].c;
+        wave_sort(key, n, lane);
+        for (int i = lane; i < n; i += 64) ord[i] = (int)(unsigned)key[i].w[2];
         __syncthreads();
         for (int i = 1; i < n; ++i) {
             const int ci = ord[i];
@@ -297,14 +218,14 @@ __global__ void __launch_bounds__(64) mem_regs_read_kernel(MrArgs A)
         for (int i = lane; i < n2; i += 64) {
             const gbx_mem_reg &Q = rg[ordb[i]];
             MrKey v;
-            v.a = (unsigned long long)(0x7fffffffll - Q.score);
-            v.b = (unsigned long long)Q.rb ^ MR_SIGN;
-            v.c = (unsigned long long)((unsigned)Q.qb ^ 0x80000000u) << 32 | (unsigned)i;
+            v.w[0] = (unsigned long long)(0x7fffffffll - Q.score);
+            v.w[1] = (unsigned long long)Q.rb ^ MR_SIGN;
+            v.w[2] = (unsigned long long)((unsigned)Q.qb ^ 0x80000000u) << 32 | (unsigned)i;
             key[i] = v;
         }
         __syncthreads();
-        mr_sort(key, n2, lane);
-        for (int i = lane; i < n2; i += 64) ord[i] = ordb[(unsigned)key[i].c];
+        wave_sort(key, n2, lane);
+        for (int i = lane; i < n2; i += 64) ord[i] = ordb[(unsigned)key[i].w[2]];
         __syncthreads();
         int n3 = 0;                                                               // a hit identical to the one before it goes
         for (int b0 = 0; b0 < n2; b0 += 64) {
@@ -330,14 +251,14 @@ __global__ void __launch_bounds__(64) mem_regs_read_kernel(MrArgs A)
     // ---- 3: mem_mark_primary_se.  ord becomes the output order; z holds places in it
     for (int i = lane; i < n; i += 64) {
         MrKey v;
-        v.a = (unsigned long long)(0x7fffffffll - rg[ordb[i]].score);
-        v.b = mr_hash64((unsigned long long)(A.read_id0 + r + i));
-        v.c = (unsigned)i;
+        v.w[0] = (unsigned long long)(0x7fffffffll - rg[ordb[i]].score);
+        v.w[1] = hash64((unsigned long long)(A.read_id0 + r + i));
+        v.w[2] = (unsigned)i;
         key[i] = v;
     }
     __syncthreads();
-    mr_sort(key, n, lane);
-    for (int i = lane; i < n; i += 64) ord[i] = ordb[(unsigned)key[i].c];
+    wave_sort(key, n, lane);
+    for (int i = lane; i < n; i += 64) ord[i] = ordb[(unsigned)key[i].w[2]];
     if (n > 0 && lane == 0) z[0] = 0;
     __syncthreads();
     int tmp = p.a + p.b;
@@ -391,7 +312,7 @@ __global__ void __launch_bounds__(64) mem_regs_read_kernel(MrArgs A)
         bool rep = false;
         if (act) {
             const gbx_mem_reg R = rg[c];
-            if (R.secondary < 0) mq = mr_mapq(R, l_rep, A.io.seeds[R.seed].lq, p);
+            if (R.secondary < 0) mq = approx_mapq_se(R, (float)l_rep / (float)A.io.seeds[R.seed].lq, p);
             rep = R.score >= p.T && R.secondary < 0;
             if (rep && R.secondary >= 0 && (float)R.score < (float)rg[ord[R.secondary]].score * p.drop_ratio) rep = false;   // (dead: kept for the record)
         }
@@ -409,61 +330,6 @@ __global__ void __launch_bounds__(64) mem_regs_read_kernel(MrArgs A)
         n_rep += __builtin_popcountll(br);
     }
     if (lane == 0) { A.cnt[r] = n; A.cnt[A.n_reads + 1 + r] = n_rep; }
-}
-
-// ---- exclusive scan of the per-read counts (n_reads + 1 entries each; blockIdx.y: regions, reported regions)
-__global__ void __launch_bounds__(MR_SCAN) mem_regs_scan_kernel(MrArgs A)
-{
-    __shared__ long long sh[MR_SCAN / 64];
-    long long *const cnt = A.cnt + (long long)blockIdx.y * (A.n_reads + 1);
-    const long long i = (long long)blockIdx.x * MR_SCAN + threadIdx.x;
-    const long long c = i < A.n_reads ? cnt[i] : 0;
-    long long v = c;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int d = 1; d < 64; d <<= 1) { const long long u = __shfl_up(v, d); if (lane >= d) v += u; }
-    if (lane == 63) sh[wv] = v;
-    __syncthreads();
-    long long before = 0;
-    for (int w = 0; w < wv; ++w) before += sh[w];
-    if (i <= A.n_reads) cnt[i] = before + v - c;
-    if (threadIdx.x == MR_SCAN - 1) A.bsum[(long long)blockIdx.y * A.blocks + blockIdx.x] = before + v;
-}
-
-// one block per quantity: exclusive scan of the block sums, the total (-1: the chaining overflowed) to *n_regs / *n_sel
-__global__ void __launch_bounds__(1024) mem_regs_top_kernel(MrArgs A)
-{
-    __shared__ long long sh[1024];
-    __shared__ long long carry;
-    long long *const bsum = A.bsum + (long long)blockIdx.x * A.blocks;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < A.blocks; b0 += 1024) {
-        const int i = b0 + threadIdx.x;
-        const long long v = i < A.blocks ? bsum[i] : 0;
-        sh[threadIdx.x] = v;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {
-            const long long u = threadIdx.x >= d ? sh[threadIdx.x - d] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += u;
-            __syncthreads();
-        }
-        if (i < A.blocks) bsum[i] = carry + sh[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry += sh[1023];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *(blockIdx.x == 0 ? A.io.n_regs : A.io.n_sel) = mr_upstream_ok(A) ? carry : -1;
-}
-
-__global__ void __launch_bounds__(MR_SCAN) mem_regs_offset_kernel(MrArgs A)
-{
-    long long *const cnt = A.cnt + (long long)blockIdx.y * (A.n_reads + 1);
-    const long long i = (long long)blockIdx.x * MR_SCAN + threadIdx.x;
-    if (i > A.n_reads) return;
-    const long long v = cnt[i] + A.bsum[(long long)blockIdx.y * A.blocks + blockIdx.x];
-    cnt[i] = v;
-    if (blockIdx.y == 0) A.io.reg_off[i] = v;
 }
 
 // ---- the records at their final places: lanes over the read's regions in output order
@@ -486,43 +352,28 @@ __global__ void __launch_bounds__(64) mem_regs_pack_kernel(MrArgs A)
         if (g < A.io.reg_cap) A.io.regs[g] = R;
         if (rep && gs < A.io.sel_cap) {
             const gbx_bsw_seed s = A.io.seeds[R.seed];
-            gbx_bsw_seed_result e;
-            e.score = R.score; e.truesc = R.truesc; e.qb = R.qb; e.qe = R.qe;
-            e.rb = (int32_t)(R.rb - s.roff); e.re = (int32_t)(R.re - s.roff); e.w = R.w; e.sc0 = 0;
             A.io.sel_seeds[gs] = s;
-            A.io.sel_res[gs] = e;
+            A.io.sel_res[gs] = reg_result(R, s);
         }
     }
-}
-
-// the CIGAR list past the count, up to the capacity: zeroed seeds (len = 0 is no seed) with results of all -1
-__global__ void __launch_bounds__(256) mem_regs_tail_kernel(MrArgs A)
-{
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long n = *A.io.n_sel;
-    if (t >= A.io.sel_cap || t < (n < 0 ? 0 : n)) return;
-    long long *const s = (long long *)(A.io.sel_seeds + t), *const e = (long long *)(A.io.sel_res + t);
-    for (int k = 0; k < 5; ++k) s[k] = 0;
-    for (int k = 0; k < 4; ++k) e[k] = -1;
 }
 
 struct MrLayout { size_t o_cnt, o_bsum, o_rg, o_took, o_ord, o_ordb, o_z, o_excl, o_key, total; int blocks; };
 MrLayout mr_layout(int64_t n_reads, int64_t seed_cap)
 {
     MrLayout L;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t nr = (size_t)n_reads, np = (size_t)seed_cap;
-    L.blocks = (int)((n_reads + 1 + MR_SCAN - 1) / MR_SCAN);
+    L.blocks = mem_scan_blocks(n_reads);
     L.o_cnt = 0;
-    L.o_bsum = L.o_cnt + up(2 * (nr + 1) * 8);
-    L.o_rg = L.o_bsum + up(2 * (size_t)L.blocks * 8);
-    L.o_took = L.o_rg + up(np * sizeof(gbx_mem_reg));
-    L.o_ord = L.o_took + up(np * 4);
-    L.o_ordb = L.o_ord + up(np * 4);
-    L.o_z = L.o_ordb + up(np * 4);
-    L.o_excl = L.o_z + up(np * 4);
-    L.o_key = L.o_excl + up(np * 4);
-    L.total = L.o_key + up(2 * np * sizeof(MrKey));
+    L.o_bsum = L.o_cnt + align256(2 * (nr + 1) * 8);
+    L.o_rg = L.o_bsum + align256(2 * (size_t)L.blocks * 8);
+    L.o_took = L.o_rg + align256(np * sizeof(gbx_mem_reg));
+    L.o_ord = L.o_took + align256(np * 4);
+    L.o_ordb = L.o_ord + align256(np * 4);
+    L.o_z = L.o_ordb + align256(np * 4);
+    L.o_excl = L.o_z + align256(np * 4);
+    L.o_key = L.o_excl + align256(np * 4);
+    L.total = L.o_key + align256(2 * np * sizeof(MrKey));
     return L;
 }
 
@@ -543,19 +394,18 @@ int mem_regs_launch(const gbx_mem_regs_params *p, int64_t n_reads, int64_t read_
     char *wb = (char *)d_work;
     MrArgs A;
     A.p = *p; A.io = io; A.n_reads = n_reads; A.read_id0 = read_id0;
-    A.cnt = (long long *)(wb + L.o_cnt); A.bsum = (long long *)(wb + L.o_bsum); A.rg = (gbx_mem_reg *)(wb + L.o_rg);
+    A.cnt = (long long *)(wb + L.o_cnt); A.rg = (gbx_mem_reg *)(wb + L.o_rg);
     A.took = (int *)(wb + L.o_took); A.ord = (int *)(wb + L.o_ord); A.ordb = (int *)(wb + L.o_ordb); A.z = (int *)(wb + L.o_z);
     A.excl = (int *)(wb + L.o_excl); A.key = (MrKey *)(wb + L.o_key);
-    A.blocks = L.blocks;
     if (n_reads > 0) {
         Stage st("mem_regs_read", s);
         hipLaunchKernelGGL(mem_regs_read_kernel, dim3((unsigned)n_reads), dim3(64), 0, s, A);
     }
     {
         Stage st("mem_regs_scan", s);
-        hipLaunchKernelGGL(mem_regs_scan_kernel, dim3(L.blocks, 2), dim3(MR_SCAN), 0, s, A);
-        hipLaunchKernelGGL(mem_regs_top_kernel, dim3(2), dim3(1024), 0, s, A);
-        hipLaunchKernelGGL(mem_regs_offset_kernel, dim3(L.blocks, 2), dim3(MR_SCAN), 0, s, A);
+        // the totals are -1 when the chaining overflowed: the condition of mr_upstream_ok
+        mem_scan_launch({A.cnt, n_reads, 2, (long long *)(wb + L.o_bsum), L.blocks, {io.n_regs, io.n_sel}, io.reg_off,
+                         {{io.n_chains, INT64_MIN, io.chain_cap}, {io.n_seeds, INT64_MIN, io.seed_cap}}}, s);
     }
     if (n_reads > 0) {
         Stage st("mem_regs_pack", s);
@@ -563,7 +413,7 @@ int mem_regs_launch(const gbx_mem_regs_params *p, int64_t n_reads, int64_t read_
     }
     if (io.sel_cap > 0) {
         Stage st("mem_regs_tail", s);
-        hipLaunchKernelGGL(mem_regs_tail_kernel, dim3((unsigned)((io.sel_cap + 255) / 256)), dim3(256), 0, s, A);
+        mem_sel_tail_launch(io.sel_seeds, io.sel_res, io.sel_cap, io.n_sel, s);
     }
     GBX_HIP(hipGetLastError());
     GBX_GUARD_CHECK("mem regs");

@@ -26,38 +26,24 @@ class ChainParams(C.Structure):          # gbx_mem_chain_params
                 ("e_ins", C.c_int32), ("pad_", C.c_int32)]
 
 
-_declared = None
-
-
-def lib():
+@N.declare_once
+def lib(L):
     """libgbx.so with the chaining entries declared (raises if the library or the entries are missing)."""
-    global _declared
-    L = N.lib()
-    if _declared is not L:
-        vp, i64, i32, sz = C.c_void_p, C.c_int64, C.c_int32, C.c_size_t
-        L.gbx_mem_chain_default_params.argtypes = [C.POINTER(ChainParams)]
-        L.gbx_mem_chain_default_params.restype = None
-        L.gbx_mem_chain_workspace_bytes.argtypes = [i64, i64, i64]
-        L.gbx_mem_chain_workspace_bytes.restype = sz
-        L.gbx_mem_chain_device.argtypes = ([C.POINTER(ChainParams), i64, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, i32, vp,
-                                            vp, i64, vp, vp, i64, vp, vp, vp, vp, sz, vp])
-        L.gbx_mem_chain_host.argtypes = ([C.POINTER(ChainParams), i64, vp, i64, vp, vp, i64, vp, vp, vp, i64, i32, vp,
-                                          vp, i64, vp, vp, i64, vp, C.POINTER(i64), C.POINTER(i64)])
-        _declared = L
-    return L
+    vp, i64, i32, sz = C.c_void_p, C.c_int64, C.c_int32, C.c_size_t
+    L.gbx_mem_chain_default_params.argtypes = [C.POINTER(ChainParams)]
+    L.gbx_mem_chain_default_params.restype = None
+    L.gbx_mem_chain_workspace_bytes.argtypes = [i64, i64, i64]
+    L.gbx_mem_chain_workspace_bytes.restype = sz
+    L.gbx_mem_chain_device.argtypes = ([C.POINTER(ChainParams), i64, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, i32, vp,
+                                        vp, i64, vp, vp, i64, vp, vp, vp, vp, sz, vp])
+    L.gbx_mem_chain_host.argtypes = ([C.POINTER(ChainParams), i64, vp, i64, vp, vp, i64, vp, vp, vp, i64, i32, vp,
+                                      vp, i64, vp, vp, i64, vp, C.POINTER(i64), C.POINTER(i64)])
 
 
 def make_params(**kw):
     """bwa mem's defaults (w 100, max_chain_gap 10000, max_occ 500, min_seed_len 19, min_chain_weight 0, max_chain_extend 2^30,
     mask_level = drop_ratio = 0.5, a 1, o_del = o_ins = 6, e_del = e_ins = 1) with the fields in `kw` replaced."""
-    p = ChainParams()
-    lib().gbx_mem_chain_default_params(C.byref(p))
-    names = {f[0] for f in ChainParams._fields_} - {"pad_"}
-    for k, v in kw.items():
-        if k not in names:
-            raise TypeError("gbx_mem_chain_params has no field %r" % k)
-        setattr(p, k, v)
-    return p
+    return N.fill_params(ChainParams, lib().gbx_mem_chain_default_params, kw, "gbx_mem_chain_params")
 
 
 def text_of(genome):

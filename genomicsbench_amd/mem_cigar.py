@@ -27,46 +27,33 @@ class CigarParams(C.Structure):          # gbx_mem_cigar_params
                 ("w", C.c_int32)]
 
 
-_declared = None
-
-
-def lib():
+@N.declare_once
+def lib(L):
     """libgbx.so with the CIGAR entries declared (raises if the library or the entries are missing)."""
-    global _declared
-    L = N.lib()
-    if _declared is not L:
-        vp, i64, i32, sz = C.c_void_p, C.c_int64, C.c_int32, C.c_size_t
-        L.gbx_mem_cigar_default_params.argtypes = [C.POINTER(CigarParams)]
-        L.gbx_mem_cigar_default_params.restype = None
-        L.gbx_mem_cigar_record_z_bytes.argtypes = [C.POINTER(CigarParams), i32, i32]
-        L.gbx_mem_cigar_record_z_bytes.restype = sz
-        L.gbx_mem_cigar_workspace_bytes.argtypes = [i64, i64]
-        L.gbx_mem_cigar_workspace_bytes.restype = sz
-        L.gbx_mem_cigar_device.argtypes = [C.POINTER(CigarParams), i64, vp, vp, vp, i64, vp, i64, i64, i32, vp, vp, vp, i64, vp, vp, sz, vp]
-        L.gbx_mem_cigar_host.argtypes = [C.POINTER(CigarParams), i64, vp, vp, vp, i64, vp, i64, i64, i32, vp, vp, vp, i64, C.POINTER(i64)]
-        _declared = L
-    return L
+    vp, i64, i32, sz = C.c_void_p, C.c_int64, C.c_int32, C.c_size_t
+    L.gbx_mem_cigar_default_params.argtypes = [C.POINTER(CigarParams)]
+    L.gbx_mem_cigar_default_params.restype = None
+    L.gbx_mem_cigar_record_z_bytes.argtypes = [C.POINTER(CigarParams), i32, i32]
+    L.gbx_mem_cigar_record_z_bytes.restype = sz
+    L.gbx_mem_cigar_workspace_bytes.argtypes = [i64, i64]
+    L.gbx_mem_cigar_workspace_bytes.restype = sz
+    L.gbx_mem_cigar_device.argtypes = [C.POINTER(CigarParams), i64, vp, vp, vp, i64, vp, i64, i64, i32, vp, vp, vp, i64, vp, vp, sz, vp]
+    L.gbx_mem_cigar_host.argtypes = [C.POINTER(CigarParams), i64, vp, vp, vp, i64, vp, i64, i64, i32, vp, vp, vp, i64, C.POINTER(i64)]
 
 
 def make_params(a=None, b=None, **kw):
     """bwa mem's defaults (match 1, mismatch -4, N -1, o_del = o_ins = 6, e_del = e_ins = 1, w 100) with the fields in `kw`
     replaced; ``a`` / ``b`` rebuild the matrix as bwa_fill_scmat does (match a, mismatch -b, N -1), ``mat`` sets all 25."""
-    p = CigarParams()
-    lib().gbx_mem_cigar_default_params(C.byref(p))
+    mat = kw.pop("mat", None)
+    p = N.fill_params(CigarParams, lib().gbx_mem_cigar_default_params, kw, "gbx_mem_cigar_params")
     if a is not None or b is not None:
         a, b = (1 if a is None else a), (4 if b is None else b)
         for t in range(5):
             for q in range(5):
                 p.mat[t * 5 + q] = -1 if t == 4 or q == 4 else a if t == q else -b
-    names = {f[0] for f in CigarParams._fields_}
-    for k, v in kw.items():
-        if k not in names:
-            raise TypeError("gbx_mem_cigar_params has no field %r" % k)
-        if k == "mat":
-            for i, x in enumerate(np.asarray(v, dtype=np.int32).reshape(25)):
-                p.mat[i] = int(x)
-        else:
-            setattr(p, k, v)
+    if mat is not None:
+        for i, x in enumerate(np.asarray(mat, dtype=np.int32).reshape(25)):
+            p.mat[i] = int(x)
     return p
 
 

@@ -13,7 +13,7 @@ import numpy as np
 from . import _native as N
 from .bsw_seeds import SEED_DTYPE
 from .mem_cigar import cigar_string
-from .mem_regs import FLAG_REPORTED, FLAG_SUPPLEMENTARY, REG_DTYPE, _SelExtension
+from .mem_regs import FLAG_REPORTED, FLAG_SUPPLEMENTARY, REG_DTYPE, _SelExtension, _results
 
 PESTAT_DTYPE = np.dtype([("low", "<i4"), ("high", "<i4"), ("failed", "<i4"), ("pad_", "<i4"), ("avg", "<f8"), ("std", "<f8")])
 PAIR_DTYPE = np.dtype([("dist", "<i8"), ("score", "<i4"), ("sub", "<i4"), ("n_sub", "<i4"), ("n_cand", "<i4"), ("z0", "<i4"), ("z1", "<i4"),
@@ -27,41 +27,25 @@ class PairParams(C.Structure):           # gbx_mem_pair_params
                 ("mapq_coef_len", C.c_int32), ("mapq_coef_fac", C.c_float), ("mask_level", C.c_float), ("no_pairing", C.c_int32)]
 
 
-_declared = None
-
-
-def lib():
+@N.declare_once
+def lib(L):
     """libgbx.so with the paired-end entries declared (raises if the library or the entries are missing)."""
-    global _declared
-    L = N.lib()
-    if _declared is not L:
-        vp, i64, i32, sz = C.c_void_p, C.c_int64, C.c_int32, C.c_size_t
-        L.gbx_mem_pair_default_params.argtypes = [C.POINTER(PairParams)]
-        L.gbx_mem_pair_default_params.restype = None
-        L.gbx_mem_pair_workspace_bytes.argtypes = [i64, i64, i32]
-        L.gbx_mem_pair_workspace_bytes.restype = sz
-        L.gbx_mem_pair_device.argtypes = [C.POINTER(PairParams), i64, i64, vp, vp, vp, i64, vp, vp, i64, vp, i64, vp, i64, i32, vp,
-                                          vp, vp, vp, vp, vp, vp, i64, vp, vp, sz, vp]
-        L.gbx_mem_pair_host.argtypes = [C.POINTER(PairParams), i64, i64, vp, vp, i64, vp, vp, i64, vp, i64, vp, i64, i32, vp,
-                                        vp, vp, vp, vp, vp, vp, i64, C.POINTER(i64)]
-        _declared = L
-    return L
+    vp, i64, i32, sz = C.c_void_p, C.c_int64, C.c_int32, C.c_size_t
+    L.gbx_mem_pair_default_params.argtypes = [C.POINTER(PairParams)]
+    L.gbx_mem_pair_default_params.restype = None
+    L.gbx_mem_pair_workspace_bytes.argtypes = [i64, i64, i32]
+    L.gbx_mem_pair_workspace_bytes.restype = sz
+    L.gbx_mem_pair_device.argtypes = [C.POINTER(PairParams), i64, i64, vp, vp, vp, i64, vp, vp, i64, vp, i64, vp, i64, i32, vp,
+                                      vp, vp, vp, vp, vp, vp, i64, vp, vp, sz, vp]
+    L.gbx_mem_pair_host.argtypes = [C.POINTER(PairParams), i64, i64, vp, vp, i64, vp, vp, i64, vp, i64, vp, i64, i32, vp,
+                                    vp, vp, vp, vp, vp, vp, i64, C.POINTER(i64)]
 
 
 def make_params(**kw):
     """bwa mem's defaults (a 1, b 4, o_del = o_ins = 6, e_del = e_ins = 1, min_seed_len 19, T 30, pen_unpaired 17, max_ins 10000,
     mapq_coef_len 50, mask_level 0.5, no_pairing 0) with the fields in `kw` replaced; mapq_coef_fac follows mapq_coef_len unless
     it is given."""
-    p = PairParams()
-    lib().gbx_mem_pair_default_params(C.byref(p))
-    names = {f[0] for f in PairParams._fields_}
-    for k, v in kw.items():
-        if k not in names:
-            raise TypeError("gbx_mem_pair_params has no field %r" % k)
-        setattr(p, k, v)
-    if "mapq_coef_len" in kw and "mapq_coef_fac" not in kw and p.mapq_coef_len > 0:
-        p.mapq_coef_fac = float(np.float32(np.log(np.float64(p.mapq_coef_len))))
-    return p
+    return N.fill_params(PairParams, lib().gbx_mem_pair_default_params, kw, "gbx_mem_pair_params")
 
 
 def pestat_records(pes):
@@ -85,7 +69,7 @@ def pair_host(params, regs, reg_off, sel_seeds, sel_res, seeds, l_rep, l_pac, co
     regs = np.ascontiguousarray(regs, dtype=REG_DTYPE)
     reg_off = np.ascontiguousarray(reg_off, dtype=np.int64)
     sel_seeds = np.ascontiguousarray(sel_seeds, dtype=SEED_DTYPE)
-    sel_res = np.ascontiguousarray(np.ascontiguousarray(sel_res).view(np.int32).reshape(-1, 8))
+    sel_res = _results(sel_res)
     seeds = np.ascontiguousarray(seeds, dtype=SEED_DTYPE)
     l_rep = np.ascontiguousarray(l_rep, dtype=np.int32)
     contig_off = np.ascontiguousarray(contig_off, dtype=np.int64)

@@ -29,41 +29,25 @@ class RegsParams(C.Structure):           # gbx_mem_regs_params
                 ("mask_level_redun", C.c_float), ("drop_ratio", C.c_float), ("pad_", C.c_int32)]
 
 
-_declared = None
-
-
-def lib():
+@N.declare_once
+def lib(L):
     """libgbx.so with the region entries declared (raises if the library or the entries are missing)."""
-    global _declared
-    L = N.lib()
-    if _declared is not L:
-        vp, i64, sz = C.c_void_p, C.c_int64, C.c_size_t
-        L.gbx_mem_regs_default_params.argtypes = [C.POINTER(RegsParams)]
-        L.gbx_mem_regs_default_params.restype = None
-        L.gbx_mem_regs_workspace_bytes.argtypes = [i64, i64]
-        L.gbx_mem_regs_workspace_bytes.restype = sz
-        L.gbx_mem_regs_device.argtypes = [C.POINTER(RegsParams), i64, i64, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp,
-                                          vp, vp, i64, vp, vp, sz, vp]
-        L.gbx_mem_regs_host.argtypes = [C.POINTER(RegsParams), i64, i64, vp, i64, vp, vp, i64, vp, vp, vp, i64, vp, C.POINTER(i64),
-                                        vp, vp, i64, C.POINTER(i64)]
-        _declared = L
-    return L
+    vp, i64, sz = C.c_void_p, C.c_int64, C.c_size_t
+    L.gbx_mem_regs_default_params.argtypes = [C.POINTER(RegsParams)]
+    L.gbx_mem_regs_default_params.restype = None
+    L.gbx_mem_regs_workspace_bytes.argtypes = [i64, i64]
+    L.gbx_mem_regs_workspace_bytes.restype = sz
+    L.gbx_mem_regs_device.argtypes = [C.POINTER(RegsParams), i64, i64, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp,
+                                      vp, vp, i64, vp, vp, sz, vp]
+    L.gbx_mem_regs_host.argtypes = [C.POINTER(RegsParams), i64, i64, vp, i64, vp, vp, i64, vp, vp, vp, i64, vp, C.POINTER(i64),
+                                    vp, vp, i64, C.POINTER(i64)]
 
 
 def make_params(**kw):
     """bwa mem's defaults (a 1, b 4, o_del = o_ins = 6, e_del = e_ins = 1, w 100, max_chain_gap 10000, min_seed_len 19, T 30,
     mapq_coef_len 50, mask_level 0.5, mask_level_redun 0.95, drop_ratio 0.5) with the fields in `kw` replaced; mapq_coef_fac
     follows mapq_coef_len unless it is given."""
-    p = RegsParams()
-    lib().gbx_mem_regs_default_params(C.byref(p))
-    names = {f[0] for f in RegsParams._fields_} - {"pad_"}
-    for k, v in kw.items():
-        if k not in names:
-            raise TypeError("gbx_mem_regs_params has no field %r" % k)
-        setattr(p, k, v)
-    if "mapq_coef_len" in kw and "mapq_coef_fac" not in kw and p.mapq_coef_len > 0:
-        p.mapq_coef_fac = float(np.float32(np.log(np.float64(p.mapq_coef_len))))
-    return p
+    return N.fill_params(RegsParams, lib().gbx_mem_regs_default_params, kw, "gbx_mem_regs_params")
 
 
 def _results(res):
