@@ -245,6 +245,26 @@ size_t mem_pair_workspace_bytes(int64_t n_pairs, int64_t reg_cap, int32_t max_in
 int mem_pair_launch(const gbx_mem_pair_params *p, int64_t n_pairs, int64_t pair_id0, const MemPairIo &io, const gbx_mem_pestat *pes_in,
                     void *d_work, size_t work_bytes, hipStream_t s);
 
+// ---- mate rescue (mem_rescue_kernels.hip)
+struct MemRescueIo {                 // the device arguments of gbx_mem_rescue_device
+    const gbx_mem_reg *regs; const int64_t *reg_off; const int64_t *n_regs; int64_t reg_cap;
+    const gbx_bsw_seed *seeds; int64_t seed_cap; const int32_t *l_rep;
+    const int64_t *read_off; const int32_t *read_len;
+    const uint8_t *text; int64_t text_bytes; const uint8_t *qer; int64_t qer_bytes;
+    int64_t l_pac; int32_t n_contigs; const int64_t *contig_off;
+    const gbx_mem_pestat *pes;
+    gbx_mem_reg *xregs; int64_t xreg_cap; int64_t *xreg_off; int64_t *n_xregs;
+    gbx_bsw_seed *xseeds; int64_t xseed_cap; int64_t *n_xseeds;
+    gbx_bsw_seed *xsel_seeds; gbx_bsw_seed_result *xsel_res; int64_t xsel_cap; int64_t *n_xsel;
+    gbx_mem_rescue_stat *stats;
+};
+size_t mem_rescue_workspace_bytes(int64_t n_pairs, int64_t reg_cap, int32_t max_matesw);
+int mem_rescue_launch(const gbx_mem_rescue_params *p, int64_t n_pairs, int64_t pair_id0, const MemRescueIo &io, void *d_work, size_t work_bytes,
+                      hipStream_t s);
+// step 1 of the paired stage alone: d_pes[4] from the regions (mem_pair_kernels.hip); reads regs, reg_off, n_regs, reg_cap, l_pac of io
+size_t mem_pestat_workspace_bytes(int32_t max_ins);
+int mem_pestat_launch(const gbx_mem_pair_params *p, int64_t n_pairs, const MemPairIo &io, void *d_work, size_t work_bytes, hipStream_t s);
+
 // ---- kmer (kmer_kernels.hip)
 size_t kmer_workspace_bytes(int32_t k, int64_t n_reads);
 int kmer_launch(const gbx_kmer_params *p, int64_t n_reads, const uint8_t *d_enc, const int64_t *d_read_off, const int32_t *d_read_len,

@@ -1,4 +1,4 @@
-// mem_common.h — what the bwa-mem stage files (mem_chain / mem_cigar / mem_regs / mem_pair _kernels.hip) share on the device:
+// mem_common.h — what the bwa-mem stage files (mem_chain / mem_cigar / mem_regs / mem_pair / mem_rescue _kernels.hip) share on the device:
 // the small helpers, the mapq formula, the one-wave key sort, the CIGAR-list record and the pieces of the exclusive scan over
 // per-unit counts.  fmi_kernels.hip and fmi_sal_kernels.hip use the scan's pieces inside their fused kernels.  The scan's own
 // kernels and the CIGAR list's tail kernel are in mem_scan.hip (mem_scan_launch, mem_sel_tail_launch: gbx_internal.h).
@@ -31,12 +31,28 @@ __device__ inline long long max_gap(long long q, const P &p)
     return g < w2 ? g : w2;
 }
 
-// mem_approx_mapq_se with csub = 0 on the region's sub and sub_n; everything in double but frac_rep.  P has a, b,
-// min_seed_len, mapq_coef_len, mapq_coef_fac
+// bwa's mem_infer_dir: the direction (0 FF, 1 FR, 2 RF, 3 RR) and the distance of two places on the 2 L text
+__device__ inline int mem_infer_dir(long long L, long long b1, long long b2, long long *dist)
+{
+    const bool r1 = b1 >= L, r2 = b2 >= L;
+    const long long p2 = r1 == r2 ? b2 : 2 * L - 1 - b2;
+    *dist = p2 > b1 ? p2 - b1 : b1 - p2;
+    return (r1 == r2 ? 0 : 1) ^ (p2 > b1 ? 0 : 3);
+}
+
+// a region's frac_rep: l_rep of its read over its seed's lq; 0 for a region without a seed (mate rescue: seedlen0 == 0)
+__device__ inline float reg_frac_rep(const gbx_mem_reg &R, int l_rep, int lq)
+{
+    return R.seedlen0 == 0 ? 0.f : (float)l_rep / (float)lq;
+}
+
+// mem_approx_mapq_se on the region's sub, sub_n and csub (0 but for a rescued region); everything in double but frac_rep.
+// P has a, b, min_seed_len, mapq_coef_len, mapq_coef_fac
 template <class P>
 __device__ inline int approx_mapq_se(const gbx_mem_reg &R, float frac_rep, const P &p)
 {
-    const int sub = R.sub ? R.sub : p.min_seed_len * p.a;
+    int sub = R.sub ? R.sub : p.min_seed_len * p.a;
+    sub = sub > R.csub ? sub : R.csub;
     if (sub >= R.score) return 0;
     const long long lr = R.re - R.rb;
     const int l = R.qe - R.qb > lr ? R.qe - R.qb : (int)lr;
@@ -100,6 +116,201 @@ __device__ inline void wave_sort(WaveKey<W> *key, int n, int lane)
             }
     }
     __syncthreads();
+}
+
+// ---- the wave-wide steps on a read's regions that the regs stage and the rescue stage share.  One wavefront, uniform control
+// flow; the regions stay where they are in rg and the orders are index lists; lane 0 (or the one lane a ballot picks) stores, and
+// a barrier (free for a one-wave block) orders the store before the next step's loads.  key: room for the next power of two
+// above n.  P has max_chain_gap, mask_level_redun (dedup), a, b, the gap costs, mask_level (primary), T and approx_mapq_se's.
+using RegKey = WaveKey<3>;                          // the low 32 bits of the last word: the element's index
+constexpr unsigned long long REG_SIGN = 1ull << 63;
+
+// mem_sort_dedup_patch without the patch on the list in[0, n) (null: 0 .. n - 1), ties of re by the position in the list; the
+// survivors end up in ordb by (score desc, rb, qb) -> their number.  excl is indexed as rg is
+template <class P>
+__device__ inline int wave_reg_dedup(const gbx_mem_reg *rg, const int *in, int n, int *ord, int *ordb, int *excl, RegKey *key, const P &p,
+                                     int lane)
+{
+    const unsigned long long below = (1ull << lane) - 1;
+    if (n < 2) {
+        if (n == 1 && lane == 0) ordb[0] = in ? in[0] : 0;
+        __syncthreads();
+        return n;
+    }
+    for (int i = lane; i < n; i += 64) {
+        const int c = in ? in[i] : i;
+        RegKey v;
+        v.w[0] = (unsigned long long)rg[c].re ^ REG_SIGN; v.w[1] = 0; v.w[2] = (unsigned)i;
+        key[i] = v;
+        excl[c] = 0;
+    }
+    __syncthreads();
+    wave_sort(key, n, lane);
+    for (int i = lane; i < n; i += 64) { const int k = (int)(unsigned)key[i].w[2]; ord[i] = in ? in[k] : k; }
+    __syncthreads();
+    for (int i = 1; i < n; ++i) {
+        const int ci = ord[i];
+        const gbx_mem_reg P_ = rg[ci];
+        for (int jb = 0; jb < i; jb += 64) {
+            const int j = i - 1 - jb - lane;
+            bool wstop = false, pstop = false, qex = false;
+            int cj = 0;
+            if (j >= 0) {
+                cj = ord[j];
+                const gbx_mem_reg Q = rg[cj];
+                if (!(Q.rid == P_.rid && P_.rb < Q.re + p.max_chain_gap)) wstop = true;
+                else if (!excl[cj]) {
+                    const long long orr = Q.re - P_.rb;
+                    const long long oq = Q.qb < P_.qb ? Q.qe - P_.qb : P_.qe - Q.qb;
+                    const long long lrq = Q.re - Q.rb, lrp = P_.re - P_.rb, mr = lrq < lrp ? lrq : lrp;
+                    const long long lqq = Q.qe - Q.qb, lqp = P_.qe - P_.qb, mq = lqq < lqp ? lqq : lqp;
+                    if ((float)orr > p.mask_level_redun * (float)mr && (float)oq > p.mask_level_redun * (float)mq) {
+                        if (P_.score < Q.score) pstop = true; else qex = true;
+                    }
+                }
+            }
+            const unsigned long long bs = __ballot(wstop || pstop);
+            const int first = bs ? __builtin_ctzll(bs) : 64;
+            if (qex && lane < first) excl[cj] = 1;
+            if (bs) {
+                if (lane == first && pstop) excl[ci] = 1;
+                break;
+            }
+        }
+        __syncthreads();
+    }
+    int n2 = 0;
+    for (int b0 = 0; b0 < n; b0 += 64) {
+        const int i = b0 + lane;
+        const int c = i < n ? ord[i] : 0;
+        const bool keep = i < n && !excl[c];
+        const unsigned long long bk = __ballot(keep);
+        if (keep) ordb[n2 + __builtin_popcountll(bk & below)] = c;
+        n2 += __builtin_popcountll(bk);
+    }
+    __syncthreads();
+    for (int i = lane; i < n2; i += 64) {
+        const gbx_mem_reg &Q = rg[ordb[i]];
+        RegKey v;
+        v.w[0] = (unsigned long long)(0x7fffffffll - Q.score);
+        v.w[1] = (unsigned long long)Q.rb ^ REG_SIGN;
+        v.w[2] = (unsigned long long)((unsigned)Q.qb ^ 0x80000000u) << 32 | (unsigned)i;
+        key[i] = v;
+    }
+    __syncthreads();
+    wave_sort(key, n2, lane);
+    for (int i = lane; i < n2; i += 64) ord[i] = ordb[(unsigned)key[i].w[2]];
+    __syncthreads();
+    int n3 = 0;                                                                   // a hit identical to the one before it goes
+    for (int b0 = 0; b0 < n2; b0 += 64) {
+        const int i = b0 + lane;
+        bool keep = i < n2;
+        const int c = keep ? ord[i] : 0;
+        if (keep && i > 0) {
+            const gbx_mem_reg &X = rg[c], &Y = rg[ord[i - 1]];
+            keep = !(X.score == Y.score && X.rb == Y.rb && X.qb == Y.qb);
+        }
+        const unsigned long long bk = __ballot(keep);
+        __builtin_amdgcn_wave_barrier();
+        if (keep) ordb[n3 + __builtin_popcountll(bk & below)] = c;
+        n3 += __builtin_popcountll(bk);
+    }
+    __syncthreads();
+    return n3;
+}
+
+// mem_mark_primary_se on the list ordb[0, n) whose regions have sub = sub_n = 0 and secondary = -1: ord becomes the output order
+// by (score desc, hash_64(read_id + i), i), z holds the primaries' places in it
+template <class P>
+__device__ inline void wave_reg_mark_primary(gbx_mem_reg *rg, const int *ordb, int n, int *ord, int *z, RegKey *key, long long read_id,
+                                             const P &p, int lane)
+{
+    for (int i = lane; i < n; i += 64) {
+        RegKey v;
+        v.w[0] = (unsigned long long)(0x7fffffffll - rg[ordb[i]].score);
+        v.w[1] = hash64((unsigned long long)(read_id + i));
+        v.w[2] = (unsigned)i;
+        key[i] = v;
+    }
+    __syncthreads();
+    wave_sort(key, n, lane);
+    for (int i = lane; i < n; i += 64) ord[i] = ordb[(unsigned)key[i].w[2]];
+    if (n > 0 && lane == 0) z[0] = 0;
+    __syncthreads();
+    int tmp = p.a + p.b;
+    tmp = p.o_del + p.e_del > tmp ? p.o_del + p.e_del : tmp;
+    tmp = p.o_ins + p.e_ins > tmp ? p.o_ins + p.e_ins : tmp;
+    int nz = n > 0 ? 1 : 0;
+    for (int i = 1; i < n; ++i) {
+        const int ci = ord[i];
+        const int bi = rg[ci].qb, ei = rg[ci].qe, sci = rg[ci].score;
+        bool hit = false;
+        for (int kb = 0; kb < nz; kb += 64) {
+            const int k = kb + lane;
+            bool stop = false;
+            int j = 0, cj = 0;
+            if (k < nz) {
+                j = z[k];
+                cj = ord[j];
+                const int bj = rg[cj].qb, ej = rg[cj].qe;
+                const int b_max = bj > bi ? bj : bi, e_min = ej < ei ? ej : ei;
+                if (e_min > b_max) {
+                    const int li = ei - bi, lj = ej - bj, min_l = li < lj ? li : lj;
+                    stop = (float)(e_min - b_max) >= (float)min_l * p.mask_level;
+                }
+            }
+            const unsigned long long bs = __ballot(stop);
+            if (bs) {
+                if (lane == __builtin_ctzll(bs)) {
+                    if (rg[cj].sub == 0) rg[cj].sub = sci;
+                    if (rg[cj].score - sci <= tmp) ++rg[cj].sub_n;
+                    rg[ci].secondary = j;
+                }
+                hit = true;
+                break;
+            }
+        }
+        if (!hit) {
+            if (lane == 0) z[nz] = i;
+            ++nz;
+        }
+        __syncthreads();
+    }
+}
+
+// mapq and the report rule on the output order ord[0, n): mapq, flag and sel (the place among the read's reported regions) of
+// every region -> the number reported.  frac_of(R): the region's frac_rep.  (bwa's drop_ratio test of a reported
+// region is dead behind `secondary < 0` and is left out.)
+template <class P, class FR>
+__device__ inline int wave_reg_report(gbx_mem_reg *rg, const int *ord, int n, FR frac_of, const P &p, int lane)
+{
+    const unsigned long long below = (1ull << lane) - 1;
+    int n_rep = 0, first_mapq = 0;
+    for (int b0 = 0; b0 < n; b0 += 64) {
+        const int i = b0 + lane;
+        const bool act = i < n;
+        const int c = act ? ord[i] : 0;
+        int mq = 0;
+        bool rep = false;
+        if (act) {
+            const gbx_mem_reg R = rg[c];
+            if (R.secondary < 0) mq = approx_mapq_se(R, frac_of(R), p);
+            rep = R.score >= p.T && R.secondary < 0;
+        }
+        const unsigned long long br = __ballot(rep);
+        if (n_rep == 0 && br) first_mapq = __shfl(mq, __builtin_ctzll(br));
+        const int my = n_rep + __builtin_popcountll(br & below);
+        if (act) {
+            int flag = 0, sel = -1;
+            if (rep) {
+                flag = 1; sel = my;
+                if (my > 0) { flag |= 0x800; mq = mq < first_mapq ? mq : first_mapq; }
+            }
+            rg[c].mapq = mq; rg[c].flag = flag; rg[c].sel = sel;
+        }
+        n_rep += __builtin_popcountll(br);
+    }
+    return n_rep;
 }
 
 // ---- the CIGAR list's result record of a region: what the extension would have answered for it on the region's seed

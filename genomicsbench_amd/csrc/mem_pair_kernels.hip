@@ -1,5 +1,5 @@
 // mem_pair_kernels.hip — paired-end: the insert-size estimate, pairing and the pair decision between the alignment regions and
-// the CIGAR stage (bwa-mem's mem_pestat, mem_pair and the decision part of mem_sam_pe, without mate rescue) for gfx950 (MI355X).
+// the CIGAR stage (bwa-mem's mem_pestat, mem_pair and the decision part of mem_sam_pe; mate rescue is the stage before it, mem_rescue_kernels.hip) for gfx950 (MI355X).
 //
 // Semantics: include/gbx.h and DESIGN 3.13 (restated in tests/mem_pair_ref.py, which pins them).
 //
@@ -52,14 +52,6 @@ __device__ inline MpSpan mp_span(const MpArgs &A, long long p)
     return s;
 }
 
-__device__ inline int mp_infer_dir(long long L, long long b1, long long b2, long long *dist)
-{
-    const bool r1 = b1 >= L, r2 = b2 >= L;
-    const long long p2 = r1 == r2 ? b2 : 2 * L - 1 - b2;
-    *dist = p2 > b1 ? p2 - b1 : b1 - p2;
-    return (r1 == r2 ? 0 : 1) ^ (p2 > b1 ? 0 : 3);
-}
-
 __device__ inline bool mp_overlaps(int qb, int qe, int tb, int te, float mask_level)
 {
     const int b_max = qb > tb ? qb : tb, e_min = qe < te ? qe : te;
@@ -71,7 +63,7 @@ __device__ inline bool mp_overlaps(int qb, int qe, int tb, int te, float mask_le
 __device__ inline float mp_frac_rep(const MpArgs &A, long long read, const gbx_mem_reg &R)
 {
     const int lq = R.seed >= 0 && R.seed < A.io.seed_cap ? A.io.seeds[R.seed].lq : 0;
-    return lq > 0 ? (float)A.io.l_rep[read] / (float)lq : 0.f;
+    return lq > 0 ? reg_frac_rep(R, A.io.l_rep[read], lq) : 0.f;
 }
 
 __device__ inline int mp_raw_mapq(int d, int a) { return (int)(6.02 * (double)d / (double)a + .499); }
@@ -103,7 +95,7 @@ __global__ void __launch_bounds__(256) mem_pair_count_kernel(MpArgs A)
     }
     if (rid[0] != rid[1]) return;
     long long is;
-    const int d = mp_infer_dir(A.io.l_pac, rb[0], rb[1], &is);
+    const int d = mem_infer_dir(A.io.l_pac, rb[0], rb[1], &is);
     if (is >= 1 && is <= A.p.max_ins) atomicAdd(A.bins + (long long)d * (A.p.max_ins + 1) + is, 1u);
 }
 
@@ -336,7 +328,7 @@ __global__ void __launch_bounds__(64) mem_pair_pair_kernel(MpArgs A)
                 }
                 int q = approx_mapq_se(c, fr[e], p);
                 q = q > q_pe ? q : q_pe < q + 40 ? q_pe : q + 40;
-                const int cap = mp_raw_mapq(c.score, p.a);
+                const int cap = mp_raw_mapq(c.score - c.csub, p.a);
                 q_se[e] = q < cap ? q : cap;
                 c_sub[e] = c.sub; c_sec[e] = c.secondary;
             }
@@ -356,7 +348,7 @@ __global__ void __launch_bounds__(64) mem_pair_pair_kernel(MpArgs A)
         q_se[1] = z[1] == 0 ? rg[n0].mapq : 0;
         if (!p.no_pairing && z[0] == 0 && z[1] == 0 && rg[0].rid == rg[n0].rid) {
             long long dist;
-            const int d = mp_infer_dir(L, rg[0].rb, rg[n0].rb, &dist);
+            const int d = mem_infer_dir(L, rg[0].rb, rg[n0].rb, &dist);
             out.proper = !pes[d].failed && dist >= pes[d].low && dist <= pes[d].high;
         }
     }
@@ -364,7 +356,7 @@ __global__ void __launch_bounds__(64) mem_pair_pair_kernel(MpArgs A)
     out.dir = -1;
     if (z[0] >= 0 && z[1] >= 0) {
         long long dist;
-        out.dir = mp_infer_dir(L, rg[z[0]].rb, rg[n0 + z[1]].rb, &dist);
+        out.dir = mem_infer_dir(L, rg[z[0]].rb, rg[n0 + z[1]].rb, &dist);
         out.dist = dist;
     }
 
@@ -451,6 +443,41 @@ size_t mem_pair_workspace_bytes(int64_t n_pairs, int64_t reg_cap, int32_t max_in
     return mp_layout(n_pairs < 0 ? 0 : n_pairs, reg_cap < 0 ? 0 : reg_cap, max_ins < 1 ? 1 : max_ins > (1 << 20) ? 1 << 20 : max_ins).total;
 }
 
+namespace {
+// step 1 on the stream: the bins, the counts, the walk - or, with the caller's estimate, its copy into io.pes
+int mp_pestat(const MpArgs &A, size_t bins_bytes, hipStream_t s)
+{
+    if (!A.has_pes) {
+        GBX_HIP(hipMemsetAsync(A.bins, 0, bins_bytes, s));
+        if (A.n_pairs > 0) hipLaunchKernelGGL(mem_pair_count_kernel, dim3((unsigned)((A.n_pairs + 255) / 256)), dim3(256), 0, s, A);
+    }
+    hipLaunchKernelGGL(mem_pair_stat_kernel, dim3(1), dim3(256), 0, s, A);
+    return GBX_OK;
+}
+}  // namespace
+
+size_t mem_pestat_workspace_bytes(int32_t max_ins)
+{
+    return align256(4 * ((size_t)(max_ins < 1 ? 1 : max_ins > (1 << 20) ? 1 << 20 : max_ins) + 1) * 4);
+}
+
+// step 1 alone, from the kernels of mem_pair_launch: the same bins, the same walk, so the same bytes in io.pes
+int mem_pestat_launch(const gbx_mem_pair_params *p, int64_t n_pairs, const MemPairIo &io, void *d_work, size_t work_bytes, hipStream_t s)
+{
+    if (io.reg_cap >= (1ll << 30)) { set_error("mem pestat: reg_cap too large"); return GBX_ERR_UNSUPPORTED; }
+    const size_t bins_bytes = 4 * ((size_t)p->max_ins + 1) * 4;
+    if (work_bytes < bins_bytes) { set_error("mem pestat: workspace too small"); return GBX_ERR_ARG; }
+    MpArgs A;
+    A.p = *p; A.io = io; A.n_pairs = n_pairs; A.pair_id0 = 0; A.has_pes = 0;
+    for (int d = 0; d < 4; ++d) A.pes_in[d] = gbx_mem_pestat{0, 0, 1, 0, 0., 0.};
+    A.cnt = nullptr; A.bins = (unsigned *)d_work; A.key = nullptr;
+    Stage st("mem_pestat", s);
+    const int rc = mp_pestat(A, bins_bytes, s);
+    if (rc) return rc;
+    GBX_HIP(hipGetLastError());
+    return GBX_OK;
+}
+
 int mem_pair_launch(const gbx_mem_pair_params *p, int64_t n_pairs, int64_t pair_id0, const MemPairIo &io, const gbx_mem_pestat *pes_in,
                     void *d_work, size_t work_bytes, hipStream_t s)
 {
@@ -466,12 +493,8 @@ int mem_pair_launch(const gbx_mem_pair_params *p, int64_t n_pairs, int64_t pair_
     A.key = (MpKey *)(wb + L.o_key);
     {
         Stage st("mem_pair_pestat", s);
-        if (!pes_in && n_pairs > 0) {
-            GBX_HIP(hipMemsetAsync(A.bins, 0, L.bins_bytes, s));
-            hipLaunchKernelGGL(mem_pair_count_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, s, A);
-        } else if (!pes_in)
-            GBX_HIP(hipMemsetAsync(A.bins, 0, L.bins_bytes, s));
-        hipLaunchKernelGGL(mem_pair_stat_kernel, dim3(1), dim3(256), 0, s, A);
+        const int rc = mp_pestat(A, L.bins_bytes, s);
+        if (rc) return rc;
     }
     if (n_pairs > 0) {
         Stage st("mem_pair_pair", s);

@@ -23,9 +23,7 @@
 namespace gbx {
 namespace {
 
-constexpr unsigned long long MR_SIGN = 1ull << 63;
-
-using MrKey = WaveKey<3>;                           // the low 32 bits of the last word: the element's index
+using MrKey = RegKey;
 static_assert(sizeof(MrKey) == 24, "MrKey");
 static_assert(sizeof(gbx_mem_reg) == 88 && sizeof(gbx_mem_regs_params) == 64 && sizeof(gbx_bsw_seed_result) == 32, "records");
 
@@ -84,7 +82,6 @@ __global__ void __launch_bounds__(64) mem_regs_read_kernel(MrArgs A)
     gbx_mem_reg *const rg = A.rg + S.s0;
     int *const ord = A.ord + S.s0, *const ordb = A.ordb + S.s0, *const z = A.z + S.s0, *const excl = A.excl + S.s0;
     MrKey *const key = A.key + 2 * S.s0;
-    const unsigned long long below = (1ull << lane) - 1;
     const MrKey pad = {{~0ull, ~0ull, ~0ull}};
 
     // ---- 1: the choice of seeds, serial in the seeds of every chain
@@ -142,7 +139,7 @@ __global__ void __launch_bounds__(64) mem_regs_read_kernel(MrArgs A)
                 R.rb = s.roff + e.rb; R.re = s.roff + e.re; R.seed = so + k;
                 R.qb = e.qb; R.qe = e.qe; R.read = (int32_t)r; R.rid = ch.contig;
                 R.score = e.score; R.truesc = e.truesc; R.sub = 0; R.sub_n = 0; R.w = e.w; R.seedcov = 0; R.seedlen0 = s.len;
-                R.secondary = -1; R.mapq = 0; R.flag = 0; R.sel = -1; R.pad_ = 0;
+                R.secondary = -1; R.mapq = 0; R.flag = 0; R.sel = -1; R.csub = 0;
                 int cov = 0;
                 for (int b0 = 0; b0 < ns; b0 += 64) {
                     const int i = b0 + lane;
@@ -162,173 +159,14 @@ __global__ void __launch_bounds__(64) mem_regs_read_kernel(MrArgs A)
     }
 
     // ---- 2: mem_sort_dedup_patch without the patch; the survivors end up in ordb
-    int n = nav;
-    if (n >= 2) {
-        for (int i = lane; i < n; i += 64) {
-            MrKey v;
-            v.w[0] = (unsigned long long)rg[i].re ^ MR_SIGN; v.w[1] = 0; v.w[2] = (unsigned)i;
-            key[i] = v;
-            excl[i] = 0;
-        }
-        __syncthreads();
-        wave_sort(key, n, lane);
-        for (int i = lane; i < n; i += 64) ord[i] = (int)(unsigned)key[i].w[2];
-        __syncthreads();
-        for (int i = 1; i < n; ++i) {
-            const int ci = ord[i];
-            const gbx_mem_reg P = rg[ci];
-            for (int jb = 0; jb < i; jb += 64) {
-                const int j = i - 1 - jb - lane;
-                bool wstop = false, pstop = false, qex = false;
-                int cj = 0;
-                if (j >= 0) {
-                    cj = ord[j];
-                    const gbx_mem_reg Q = rg[cj];
-                    if (!(Q.rid == P.rid && P.rb < Q.re + p.max_chain_gap)) wstop = true;
-                    else if (!excl[cj]) {
-                        const long long orr = Q.re - P.rb;
-                        const long long oq = Q.qb < P.qb ? Q.qe - P.qb : P.qe - Q.qb;
-                        const long long lrq = Q.re - Q.rb, lrp = P.re - P.rb, mr = lrq < lrp ? lrq : lrp;
-                        const long long lqq = Q.qe - Q.qb, lqp = P.qe - P.qb, mq = lqq < lqp ? lqq : lqp;
-                        if ((float)orr > p.mask_level_redun * (float)mr && (float)oq > p.mask_level_redun * (float)mq) {
-                            if (P.score < Q.score) pstop = true; else qex = true;
-                        }
-                    }
-                }
-                const unsigned long long bs = __ballot(wstop || pstop);
-                const int first = bs ? __builtin_ctzll(bs) : 64;
-                if (qex && lane < first) excl[cj] = 1;
-                if (bs) {
-                    if (lane == first && pstop) excl[ci] = 1;
-                    break;
-                }
-            }
-            __syncthreads();
-        }
-        int n2 = 0;
-        for (int b0 = 0; b0 < n; b0 += 64) {
-            const int i = b0 + lane;
-            const int c = i < n ? ord[i] : 0;
-            const bool keep = i < n && !excl[c];
-            const unsigned long long bk = __ballot(keep);
-            if (keep) ordb[n2 + __builtin_popcountll(bk & below)] = c;
-            n2 += __builtin_popcountll(bk);
-        }
-        __syncthreads();
-        for (int i = lane; i < n2; i += 64) {
-            const gbx_mem_reg &Q = rg[ordb[i]];
-            MrKey v;
-            v.w[0] = (unsigned long long)(0x7fffffffll - Q.score);
-            v.w[1] = (unsigned long long)Q.rb ^ MR_SIGN;
-            v.w[2] = (unsigned long long)((unsigned)Q.qb ^ 0x80000000u) << 32 | (unsigned)i;
-            key[i] = v;
-        }
-        __syncthreads();
-        wave_sort(key, n2, lane);
-        for (int i = lane; i < n2; i += 64) ord[i] = ordb[(unsigned)key[i].w[2]];
-        __syncthreads();
-        int n3 = 0;                                                               // a hit identical to the one before it goes
-        for (int b0 = 0; b0 < n2; b0 += 64) {
-            const int i = b0 + lane;
-            bool keep = i < n2;
-            const int c = keep ? ord[i] : 0;
-            if (keep && i > 0) {
-                const gbx_mem_reg &X = rg[c], &Y = rg[ord[i - 1]];
-                keep = !(X.score == Y.score && X.rb == Y.rb && X.qb == Y.qb);
-            }
-            const unsigned long long bk = __ballot(keep);
-            __builtin_amdgcn_wave_barrier();
-            if (keep) ordb[n3 + __builtin_popcountll(bk & below)] = c;
-            n3 += __builtin_popcountll(bk);
-        }
-        __syncthreads();
-        n = n3;
-    } else if (n == 1) {
-        if (lane == 0) ordb[0] = 0;
-        __syncthreads();
-    }
+    const int n = wave_reg_dedup(rg, nullptr, nav, ord, ordb, excl, key, p, lane);
 
     // ---- 3: mem_mark_primary_se.  ord becomes the output order; z holds places in it
-    for (int i = lane; i < n; i += 64) {
-        MrKey v;
-        v.w[0] = (unsigned long long)(0x7fffffffll - rg[ordb[i]].score);
-        v.w[1] = hash64((unsigned long long)(A.read_id0 + r + i));
-        v.w[2] = (unsigned)i;
-        key[i] = v;
-    }
-    __syncthreads();
-    wave_sort(key, n, lane);
-    for (int i = lane; i < n; i += 64) ord[i] = ordb[(unsigned)key[i].w[2]];
-    if (n > 0 && lane == 0) z[0] = 0;
-    __syncthreads();
-    int tmp = p.a + p.b;
-    tmp = p.o_del + p.e_del > tmp ? p.o_del + p.e_del : tmp;
-    tmp = p.o_ins + p.e_ins > tmp ? p.o_ins + p.e_ins : tmp;
-    int nz = n > 0 ? 1 : 0;
-    for (int i = 1; i < n; ++i) {
-        const int ci = ord[i];
-        const int bi = rg[ci].qb, ei = rg[ci].qe, sci = rg[ci].score;
-        bool hit = false;
-        for (int kb = 0; kb < nz; kb += 64) {
-            const int k = kb + lane;
-            bool stop = false;
-            int j = 0, cj = 0;
-            if (k < nz) {
-                j = z[k];
-                cj = ord[j];
-                const int bj = rg[cj].qb, ej = rg[cj].qe;
-                const int b_max = bj > bi ? bj : bi, e_min = ej < ei ? ej : ei;
-                if (e_min > b_max) {
-                    const int li = ei - bi, lj = ej - bj, min_l = li < lj ? li : lj;
-                    stop = (float)(e_min - b_max) >= (float)min_l * p.mask_level;
-                }
-            }
-            const unsigned long long bs = __ballot(stop);
-            if (bs) {
-                if (lane == __builtin_ctzll(bs)) {
-                    if (rg[cj].sub == 0) rg[cj].sub = sci;
-                    if (rg[cj].score - sci <= tmp) ++rg[cj].sub_n;
-                    rg[ci].secondary = j;
-                }
-                hit = true;
-                break;
-            }
-        }
-        if (!hit) {
-            if (lane == 0) z[nz] = i;
-            ++nz;
-        }
-        __syncthreads();
-    }
+    wave_reg_mark_primary(rg, ordb, n, ord, z, key, A.read_id0 + r, p, lane);
 
     // ---- 4, 5: mapq, the reported regions and their places in the read's part of the CIGAR list
     const int l_rep = A.io.l_rep[r];
-    int n_rep = 0, first_mapq = 0;
-    for (int b0 = 0; b0 < n; b0 += 64) {
-        const int i = b0 + lane;
-        const bool act = i < n;
-        const int c = act ? ord[i] : 0;
-        int mq = 0;
-        bool rep = false;
-        if (act) {
-            const gbx_mem_reg R = rg[c];
-            if (R.secondary < 0) mq = approx_mapq_se(R, (float)l_rep / (float)A.io.seeds[R.seed].lq, p);
-            rep = R.score >= p.T && R.secondary < 0;
-            if (rep && R.secondary >= 0 && (float)R.score < (float)rg[ord[R.secondary]].score * p.drop_ratio) rep = false;   // (dead: kept for the record)
-        }
-        const unsigned long long br = __ballot(rep);
-        if (n_rep == 0 && br) first_mapq = __shfl(mq, __builtin_ctzll(br));
-        const int my = n_rep + __builtin_popcountll(br & below);
-        if (act) {
-            int flag = 0, sel = -1;
-            if (rep) {
-                flag = 1; sel = my;
-                if (my > 0) { flag |= 0x800; mq = mq < first_mapq ? mq : first_mapq; }
-            }
-            rg[c].mapq = mq; rg[c].flag = flag; rg[c].sel = sel;
-        }
-        n_rep += __builtin_popcountll(br);
-    }
+    const int n_rep = wave_reg_report(rg, ord, n, [&](const gbx_mem_reg &R) { return reg_frac_rep(R, l_rep, A.io.seeds[R.seed].lq); }, p, lane);
     if (lane == 0) { A.cnt[r] = n; A.cnt[A.n_reads + 1 + r] = n_rep; }
 }
 

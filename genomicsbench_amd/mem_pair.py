@@ -1,6 +1,6 @@
 """Paired-end: the insert-size estimate, pairing and the pair decision of bwa-mem (mem_pestat, mem_pair and the decision part of
-mem_sam_pe, without mate rescue) on the GPU through gbx_mem_pair_* (include/gbx.h), the stage between the alignment regions and
-the CIGAR stage.
+mem_sam_pe) on the GPU through gbx_mem_pair_* (include/gbx.h), the stage between the alignment regions and the CIGAR stage.  Mate
+rescue is the stage before it: ``mem_rescue``.
 
 Input: the regs stage's output for 2 n_pairs interleaved reads (read 2p + e is end e of pair p), made with read_id0 =
 2 pair_id0.  Output: four PESTAT_DTYPE records (FF, FR, RF, RR), one PAIR_DTYPE record per pair, the regions with the decision's

@@ -815,10 +815,13 @@ int gbx_mem_cigar_host(const gbx_mem_cigar_params *p, int64_t n,
  *   primary   by (score desc, hash_64(read_id0 + r + i), i): a region overlapping an earlier primary by mask_level (fp32) of the
  *             shorter query span is secondary to it, sets its sub once and counts in its sub_n within max(a + b, o_del + e_del,
  *             o_ins + e_ins); this is the output order
- *   mapq      mem_approx_mapq_se with csub = 0 and frac_rep = (float)l_rep[r] / lq; 0 for a secondary.  A region of length 0 gets 0
+ *   mapq      mem_approx_mapq_se: sub = max(sub ? sub : min_seed_len * a, csub), csub = 0 in every region this stage makes, and
+ *             frac_rep = (float)l_rep[r] / lq (0 for a region with seedlen0 == 0: a rescued one); 0 for a secondary.  A region of
+ *             length 0 gets 0
  *   report    score >= T and not secondary; the second and later reported regions of a read are supplementary (0x800) and
  *             their mapq is capped by the first's
- * Not modelled: mem_patch_reg, alt contigs, MEM_F_ALL, XA, paired-end, bwa's other mapq formula (mapq_coef_len <= 0). */
+ * Not modelled: mem_patch_reg, alt contigs, MEM_F_ALL, XA, bwa's other mapq formula (mapq_coef_len <= 0).  Paired-end reads:
+ * gbx_mem_rescue_* and gbx_mem_pair_* below. */
 typedef struct gbx_mem_regs_params {     /* 64 bytes */
     int32_t a, b;                        /* 1, 4 */
     int32_t o_del, e_del, o_ins, e_ins;  /* 6, 1, 6, 1 */
@@ -842,7 +845,7 @@ typedef struct gbx_mem_reg {             /* 88 bytes */
     int32_t mapq;                        /* 0 for a secondary region */
     int32_t flag;                        /* bit 0: reported (went to the CIGAR list); 0x800: supplementary */
     int32_t sel;                         /* its index in the CIGAR list, -1 if not reported */
-    int32_t pad_;
+    int32_t csub;                        /* bwa's csub: the SW's second-best score of a rescued region (gbx_mem_rescue_*), else 0 */
 } gbx_mem_reg;
 
 /* Device path.  All pointers are device pointers; asynchronous on `stream`, no host synchronisation inside.  The chain and seed
@@ -879,7 +882,9 @@ int gbx_mem_regs_host(const gbx_mem_regs_params *p, int64_t n_reads, int64_t rea
                       gbx_bsw_seed *sel_seeds, gbx_bsw_seed_result *sel_res, int64_t sel_cap, int64_t *n_sel);
 
 /* ---- paired-end: insert-size estimate, pairing and the pair decision (bwa-mem's mem_pestat, mem_pair and the decision part of
- * mem_sam_pe as `bwa mem -S` runs them, that is, without mate rescue: the step between gbx_mem_regs_* and gbx_mem_cigar_*).
+ * mem_sam_pe: the step between gbx_mem_regs_* and gbx_mem_cigar_*.  On the regs stage's output it is `bwa mem -S`; mate rescue is
+ * the stage before it, gbx_mem_rescue_* below, whose output has the regs stage's shape).  A region with seedlen0 == 0 (a rescued
+ * one) has frac_rep = 0, and the cap on q_se is raw(c.score - c.csub), csub being 0 in the regs stage's regions.
  * UNPINNED by a compiled reference (bwa's source is not part of the reference tree): the rules are restated in full in DESIGN
  * 3.13 and tests/mem_pair_ref.py, and pinned by that restatement.
  * A call of n_pairs pairs is the regs stage's output for 2 n_pairs interleaved reads, read 2p + e being end e of pair p, made
@@ -926,7 +931,7 @@ int gbx_mem_regs_host(const gbx_mem_regs_params *p, int64_t n_reads, int64_t rea
  *   list      the new CIGAR list holds the reads in order, each read's reported regions in output order, each record a copy of
  *             the region's record in the regs stage's list (a region that stage did not report is built as it builds them);
  *             sel is renumbered
- * Not modelled: mate rescue (mem_matesw), alt contigs, MEM_F_ALL, XA, mem_patch_reg, the MD string, bwa's secondary_all. */
+ * Not modelled: alt contigs, MEM_F_ALL, XA, mem_patch_reg, the MD string, bwa's secondary_all. */
 typedef struct gbx_mem_pair_params {     /* 56 bytes */
     int32_t a, b;                        /* 1, 4 */
     int32_t o_del, e_del, o_ins, e_ins;  /* 6, 1, 6, 1 */
@@ -991,6 +996,130 @@ int gbx_mem_pair_host(const gbx_mem_pair_params *p, int64_t n_pairs, int64_t pai
                       int64_t l_pac, int32_t n_contigs, const int64_t *contig_off,
                       const gbx_mem_pestat *pes_in, gbx_mem_pestat *pes, gbx_mem_pair *pairs, gbx_mem_reg *pregs,
                       gbx_bsw_seed *psel_seeds, gbx_bsw_seed_result *psel_res, int64_t psel_cap, int64_t *n_psel);
+
+/* ---- the insert-size estimate alone: step `estimate` of the paired-end stage above, from the same kernels.  bwa estimates on the
+ * regions before mate rescue, so this runs on the regs stage's output, gbx_mem_rescue_* reads d_pes on the device, and
+ * gbx_mem_pair_* behind it is given the same four records as pes_in.  Of p only a, min_seed_len, mask_level and max_ins are
+ * read.  d_pes[4] is byte-equal to what gbx_mem_pair_device writes there for the same regions (all four failed after an upstream
+ * overflow).  work: gbx_mem_pestat_workspace_bytes(max_ins) bytes.  The host entry checks what gbx_mem_pair_host checks of these
+ * arguments. */
+size_t gbx_mem_pestat_workspace_bytes(int32_t max_ins);
+int gbx_mem_pestat_device(const gbx_mem_pair_params *p, int64_t n_pairs,
+                          const gbx_mem_reg *d_regs, const int64_t *d_reg_off, const int64_t *d_n_regs, int64_t reg_cap, int64_t l_pac,
+                          gbx_mem_pestat *d_pes, void *d_work, size_t work_bytes, void *stream);
+int gbx_mem_pestat_host(const gbx_mem_pair_params *p, int64_t n_pairs, const gbx_mem_reg *regs, const int64_t *reg_off, int64_t n_regs,
+                        int64_t l_pac, gbx_mem_pestat *pes);
+
+/* ---- mate rescue (bwa-mem's mem_matesw around ksw_align2: the step between gbx_mem_regs_* and gbx_mem_pair_*).  UNPINNED by a
+ * compiled reference (bwa's source is not part of the reference tree): the rules are restated in full in DESIGN 3.14 and
+ * tests/mem_rescue_ref.py, and pinned by that restatement, hand-built cases and a frozen example.
+ * Input: the regs stage's output for 2 n_pairs interleaved reads and four gbx_mem_pestat records.  Output: the same region lists
+ * in the regs stage's shape with the rescued regions added, the lists deduplicated again and primary marking, mapq and the report
+ * choice redone, so gbx_mem_pair_* and gbx_mem_cigar_* follow unchanged.  L = l_pac, the text is the 2L-byte text of the other
+ * stages, infer_dir as above.
+ *   lists     a_e = end e's regions by (score desc, rb, qb); sub, sub_n, secondary, mapq, flag and sel are not read.  b_e = the
+ *             regions of a_e with score >= a_e[0].score - pen_unpaired, in order, the first max_matesw; fixed before any rescue
+ *   order     for e = 0, 1: for j over b_e: matesw(anchor = b_e[j], mate = the read of end 1 - e, ma = a_{1-e}), strictly serial:
+ *             ma carries what earlier calls added or removed
+ *   matesw    skip[r] = pes[r].failed; every region m of ma sets skip[r] for (r, dist) = infer_dir(anchor.rb, m.rb) when low_r <=
+ *             dist <= high_r; all four set: return.  n = 0; for r = 0 .. 3 not skipped: is_rev = (r >> 1) != (r & 1), is_larger =
+ *             !(r >> 1), seq = the mate, reverse-complemented if is_rev (c < 4 ? 3 - c : 4); the window: not is_rev: rb = is_larger
+ *             ? anchor.rb + low : anchor.rb - high, re = (is_larger ? anchor.rb + high : anchor.rb - low) + l_ms; is_rev: rb =
+ *             (is_larger ? anchor.rb + low : anchor.rb - high) - l_ms, re = is_larger ? anchor.rb + high : anchor.rb - low;
+ *             clamped to [0, 2L]; if rb < re it is cut to the contig of (rb + re) >> 1 on that strand, else there is none.  With
+ *             a window on the anchor's contig of at least min_seed_len bases: the SW below on seq against text[rb, re), ++n, and
+ *             if score >= min_seed_len and qb >= 0 a region B: rid = anchor.rid, (qb, qe) = is_rev ? (l_ms - (qe + 1), l_ms - qb)
+ *             : (qb, qe + 1), (rb, re) = is_rev ? (2L - (rb + te + 1), 2L - (rb + tb)) : (rb + tb, rb + te + 1), score, csub =
+ *             score2 (-1: none), secondary = -1, seedcov = min(re - rb, qe - qb) >> 1, everything else 0 (truesc, w, seedlen0,
+ *             sub, sub_n); B goes in front of the first element of ma with a lower score (behind all without one).  Then, in
+ *             the same iteration and whether or not there was a window: if n > 0, ma = dedup(ma) - the regs stage's dedup, ties
+ *             of re by the position in ma
+ *   SW        ksw_align2 with KSW_XSUBO | KSW_XSTART | min_seed_len * a.  Query q[0, m) along the rows, target t[0, n) along the
+ *             columns.  S(x, y) = a if x == y < 4, -b if both < 4 and differ, -1 if either >= 4.  Pw = 16 if m * a < 250 else 8,
+ *             slen = ceil(m / Pw); the query is padded to slen * Pw rows with a symbol scoring 0 against everything (bwa's striped
+ *             profile): the padded rows take part in the recurrence and the column maxima and never hold the maximum.  H(i, j) =
+ *             max(0, H(i-1, j-1) + S, E(i, j), F(i, j)), E(i+1, j) = max(0, E(i, j) - e_del, H(i, j) - o_del - e_del), F(i, j+1) =
+ *             max(0, F(i, j) - e_ins, H(i, j) - o_ins - e_ins), 0 outside.  Per column i in order: imax = max_j H(i, j); if imax >=
+ *             minsc = min_seed_len * a: with no entry yet or the last entry's column + 1 != i append (imax, i), else a last entry
+ *             with a lower value is replaced by (imax, i) (the stored column is that of the run's maximum, not its end); if imax >
+ *             gmax: gmax = imax, te = i.  Then score = gmax, qe = the row of column te with H == score that is first in striped
+ *             memory order (smallest (j mod slen) * Pw + j div slen), w = (score + a - 1) / a, (score2, te2) = the first entry
+ *             in order with the largest value among those whose column lies outside [te - w, te + w], (-1, -1) without one.
+ *             score < minsc: qb = tb = -1.  Else the same pass on reverse(q[0, qe]) against reverse(t[0, te]) with the same Pw,
+ *             its own slen and padding and no entries, stopping at the first column where gmax >= score, gives (score', te',
+ *             qe'); qb = qe - qe', tb = te - te' if score' == score, else both -1.  Not modelled: byte mode's early exit at
+ *             gmax + b >= 255 (b > 5 is refused, so it cannot fire)
+ *   after     a pair in which no SW ran comes out byte-equal to its input.  Else per read mem_mark_primary_se with read_id = 2
+ *             (pair_id0 + p) + e on the final list, then the regs stage's mapq and report rules
+ *   records   d_xseeds[0, seed_cap) is a copy of d_seeds; each rescued region that survives gets a record behind it, in output
+ *             order: qoff / lq of its read, roff / rlen = its window on the region's own strand ([2L - re, 2L - rb) when is_rev),
+ *             qbeg = qb, rbeg = rb - roff, len = 0, and reg.seed points at it.  Its CIGAR-list record is built as the regs stage
+ *             builds them, with w = 0 and truesc = 0 as bwa leaves them; gbx_mem_cigar_* retries its band from there
+ * Not modelled: alt contigs, MEM_F_ALL, XA, mem_patch_reg, the MD string. */
+typedef struct gbx_mem_rescue_params {   /* 64 bytes */
+    int32_t a, b;                        /* 1, 4; a <= 63, b <= 5 (GBX_ERR_UNSUPPORTED above) */
+    int32_t o_del, e_del, o_ins, e_ins;  /* 6, 1, 6, 1 */
+    int32_t min_seed_len, T;             /* 19, 30 */
+    int32_t pen_unpaired;                /* 17 */
+    int32_t max_matesw;                  /* 50; at least 1 */
+    int32_t max_chain_gap;               /* 10000 */
+    int32_t mapq_coef_len;               /* 50; must be > 0 */
+    float   mapq_coef_fac;               /* (float)log((double)mapq_coef_len), set by the host */
+    float   mask_level, mask_level_redun;   /* 0.5, 0.95 */
+    int32_t pad_;
+} gbx_mem_rescue_params;
+void gbx_mem_rescue_default_params(gbx_mem_rescue_params *p);
+
+typedef struct gbx_mem_rescue_stat {     /* 16 bytes, one per pair */
+    int32_t n_sw;                        /* SWs whose answer was used (bwa's n, summed over the pair's matesw calls) */
+    int32_t n_added;                     /* regions added */
+    int32_t n_kept;                      /* rescued regions in the pair's output */
+    int32_t pad_;
+} gbx_mem_rescue_stat;
+
+/* Device path.  All pointers are device pointers; asynchronous on `stream`, no host synchronisation inside.  d_regs, d_reg_off
+ * (2 n_pairs + 1), d_n_regs: the outputs of gbx_mem_regs_device on the same stream, made with read_id0 = 2 pair_id0; d_seeds
+ * (seed_cap records) and d_l_rep the chaining's; d_read_off / d_read_len: the reads in d_qer (a mate with no region still has a
+ * sequence), reads of 1 .. 1024 bases (a longer mate is not rescued by this entry; the host entry refuses it); d_text: at least
+ * 2 l_pac bytes; d_pes: four records on the device (gbx_mem_pestat_device), a direction that has not failed with low < 0, low >
+ * high or high > 2^20 gets no window.  The inputs are never written.  Written: d_xregs (every read's regions in output order),
+ * d_xreg_off[2 n_pairs + 1], *d_n_xregs; d_xseeds[xseed_cap] with *d_n_xseeds = seed_cap + the surviving rescued regions (the
+ * records between that and xseed_cap are zeroed); the CIGAR list d_xsel_seeds / d_xsel_res with *d_n_xsel, its tail zeroed seeds
+ * with results of all -1 up to xsel_cap; d_stats[n_pairs].  A pair adds at most 4 regions per anchor: xreg_cap = xsel_cap =
+ * reg_cap + 4 min(reg_cap, 2 n_pairs max_matesw) and xseed_cap = seed_cap + 4 min(reg_cap, 2 n_pairs max_matesw) always suffice.
+ * A count above its capacity reports the need: nothing past the capacity is written (d_xreg_off, reg.seed and reg.sel keep the
+ * true values).  *d_n_regs < 0 or above reg_cap (the stage before overflowed): the three counts are -1, d_xreg_off all 0, zeroed
+ * stats, the whole CIGAR list the zeroed tail.  reg_cap and n_pairs below 2^28.  work:
+ * gbx_mem_rescue_workspace_bytes(n_pairs, reg_cap, max_matesw) bytes; every pair and every window is done in full whatever its
+ * size.  The output bytes do not depend on the scheduling. */
+size_t gbx_mem_rescue_workspace_bytes(int64_t n_pairs, int64_t reg_cap, int32_t max_matesw);
+int gbx_mem_rescue_device(const gbx_mem_rescue_params *p, int64_t n_pairs, int64_t pair_id0,
+                          const gbx_mem_reg *d_regs, const int64_t *d_reg_off, const int64_t *d_n_regs, int64_t reg_cap,
+                          const gbx_bsw_seed *d_seeds, int64_t seed_cap, const int32_t *d_l_rep,
+                          const int64_t *d_read_off, const int32_t *d_read_len,
+                          const uint8_t *d_text, int64_t text_bytes, const uint8_t *d_qer, int64_t qer_bytes,
+                          int64_t l_pac, int32_t n_contigs, const int64_t *d_contig_off, const gbx_mem_pestat *d_pes,
+                          gbx_mem_reg *d_xregs, int64_t xreg_cap, int64_t *d_xreg_off, int64_t *d_n_xregs,
+                          gbx_bsw_seed *d_xseeds, int64_t xseed_cap, int64_t *d_n_xseeds,
+                          gbx_bsw_seed *d_xsel_seeds, gbx_bsw_seed_result *d_xsel_res, int64_t xsel_cap, int64_t *d_n_xsel,
+                          gbx_mem_rescue_stat *d_stats, void *d_work, size_t work_bytes, void *stream);
+
+/* Host-buffer entry.  Checked before a device is touched: the parameters (a >= 1, e_del and e_ins >= 1, o_del and o_ins >= 0,
+ * max_matesw >= 1, mapq_coef_len > 0; a > 63 or b > 5: GBX_ERR_UNSUPPORTED), pair ids as in gbx_mem_pair_host, the contig table,
+ * text_bytes >= 2 l_pac, reg_off, every reg.rid and reg.seed, every read inside qer with 1 .. 1024 bases (longer:
+ * GBX_ERR_UNSUPPORTED), and pes: 0 <= low <= high <= 2^20 wherever a direction has not failed: GBX_ERR_ARG naming the lowest
+ * offender.  The counts go to *n_xregs, *n_xseeds, *n_xsel; one above its capacity gives GBX_ERR_ARG with the need there and in
+ * gbx_last_error() (xreg_off and stats are written, the lists are not).  Safe under concurrent host threads; one device. */
+int gbx_mem_rescue_host(const gbx_mem_rescue_params *p, int64_t n_pairs, int64_t pair_id0,
+                        const gbx_mem_reg *regs, const int64_t *reg_off, int64_t n_regs,
+                        const gbx_bsw_seed *seeds, int64_t n_seeds, const int32_t *l_rep,
+                        const int64_t *read_off, const int32_t *read_len,
+                        const uint8_t *text, int64_t text_bytes, const uint8_t *qer, int64_t qer_bytes,
+                        int64_t l_pac, int32_t n_contigs, const int64_t *contig_off, const gbx_mem_pestat *pes,
+                        gbx_mem_reg *xregs, int64_t xreg_cap, int64_t *xreg_off, int64_t *n_xregs,
+                        gbx_bsw_seed *xseeds, int64_t xseed_cap, int64_t *n_xseeds,
+                        gbx_bsw_seed *xsel_seeds, gbx_bsw_seed_result *xsel_res, int64_t xsel_cap, int64_t *n_xsel,
+                        gbx_mem_rescue_stat *stats);
 
 /* -------------------------------------------------------------------- kmer
  * Canonical k-mer counting of long reads: Flye's KmerCounter::count as the kmer-cnt benchmark times it
