@@ -265,6 +265,23 @@ int mem_rescue_launch(const gbx_mem_rescue_params *p, int64_t n_pairs, int64_t p
 size_t mem_pestat_workspace_bytes(int32_t max_ins);
 int mem_pestat_launch(const gbx_mem_pair_params *p, int64_t n_pairs, const MemPairIo &io, void *d_work, size_t work_bytes, hipStream_t s);
 
+// ---- SAM records (mem_sam_kernels.hip)
+struct MemSamIo {                    // the device arguments of gbx_mem_sam_device
+    const gbx_mem_reg *regs; const int64_t *reg_off; const int64_t *n_regs; int64_t reg_cap;
+    const gbx_mem_pair *pairs;                      // mode 1
+    const gbx_mem_aln *alns; int64_t n_alns; const uint32_t *cigar; const int64_t *n_cigar; int64_t cigar_cap;
+    const uint8_t *qer; int64_t qer_bytes; const int64_t *read_off; const int32_t *read_len; const uint8_t *qual;
+    const uint8_t *names; const int64_t *name_off; int64_t name_bytes;
+    const uint8_t *cnames; const int64_t *cname_off; int64_t cname_bytes;
+    const uint8_t *text; int64_t text_bytes; int64_t l_pac; int32_t n_contigs; const int64_t *contig_off;
+    gbx_mem_sam_rec *recs; int64_t rec_cap; int64_t *rec_off; int64_t *n_recs;
+    uint8_t *md; int64_t md_cap; int64_t *n_md;
+    uint8_t *lines; int64_t text_cap; int64_t *n_text;
+};
+int64_t mem_sam_rec_max(int64_t n_reads, int64_t reg_cap, int64_t n_alns);      // the records a call can make at most
+size_t mem_sam_workspace_bytes(int64_t n_reads, int64_t reg_cap, int64_t n_alns);
+int mem_sam_launch(const gbx_mem_sam_params *p, int64_t n_reads, int mode, const MemSamIo &io, void *d_work, size_t work_bytes, hipStream_t s);
+
 // ---- kmer (kmer_kernels.hip)
 size_t kmer_workspace_bytes(int32_t k, int64_t n_reads);
 int kmer_launch(const gbx_kmer_params *p, int64_t n_reads, const uint8_t *d_enc, const int64_t *d_read_off, const int32_t *d_read_len,

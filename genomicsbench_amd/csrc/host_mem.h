@@ -1,4 +1,4 @@
-// host_mem.h — what the bwa-mem entries (capi_mem_chain / _cigar / _regs / _pair .hip) share on the host: the argument checks
+// host_mem.h — what the bwa-mem entries (capi_mem_chain / _cigar / _regs / _pair / _rescue / _sam .hip) share on the host: the argument checks
 // with their error texts, the tail fill of a CIGAR list and the upload of one input.  Every check sets the error text and
 // returns GBX_ERR_ARG (mapq_coef_len_check: GBX_ERR_UNSUPPORTED), or returns GBX_OK.
 #pragma once

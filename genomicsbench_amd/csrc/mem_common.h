@@ -1,4 +1,4 @@
-// mem_common.h — what the bwa-mem stage files (mem_chain / mem_cigar / mem_regs / mem_pair / mem_rescue _kernels.hip) share on the device:
+// mem_common.h — what the bwa-mem stage files (mem_chain / mem_cigar / mem_regs / mem_pair / mem_rescue / mem_sam _kernels.hip) share on the device:
 // the small helpers, the mapq formula, the one-wave key sort, the CIGAR-list record and the pieces of the exclusive scan over
 // per-unit counts.  fmi_kernels.hip and fmi_sal_kernels.hip use the scan's pieces inside their fused kernels.  The scan's own
 // kernels and the CIGAR list's tail kernel are in mem_scan.hip (mem_scan_launch, mem_sel_tail_launch: gbx_internal.h).

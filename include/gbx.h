@@ -1121,6 +1121,108 @@ int gbx_mem_rescue_host(const gbx_mem_rescue_params *p, int64_t n_pairs, int64_t
                         gbx_bsw_seed *xsel_seeds, gbx_bsw_seed_result *xsel_res, int64_t xsel_cap, int64_t *n_xsel,
                         gbx_mem_rescue_stat *stats);
 
+/* ---- SAM records (bwa-mem's mem_aln2sam and add_cigar, the MD part of bwa_gen_cigar2: the step behind gbx_mem_cigar_*).
+ * UNPINNED by a compiled reference (bwa's source is not part of the reference tree): the rules are restated in full in DESIGN
+ * 3.15 and tests/mem_sam_ref.py, and pinned by that restatement, hand-built cases with their lines written out and a frozen
+ * example.  L = l_pac; positions are printed 1-based, numbers in decimal.
+ * Input: mode 0: n_reads single-end reads with the regs stage's regions and the CIGAR stage's answer for its list; mode 1:
+ * n_reads = 2 n_pairs interleaved reads with the paired stage's pairs, pregs and the answer for its list.  reg.sel indexes alns.
+ *   records   read r's list: its regions with flag & 1 and sel inside alns, in order; record k (which = k) has rid, pos, is_rev, nm
+ *             and the CIGAR words of alns[reg.sel], mapq = reg.mapq, as_ = reg.score, xs = max(reg.sub, reg.csub), 0x800 from
+ *             reg.flag.  An empty list gives one unmapped record: rid = pos = -1, flag 0x4, mapq 0, no CIGAR, as_ = xs = 0.  An
+ *             aln with rid outside the contigs makes its record unmapped (the host entry refuses it).  0x100 never occurs
+ *   mate      mode 1: m = the first record of the other end's list if it is mapped, else none.  flag: 0x1, 0x40 / 0x80 by end, 0x2
+ *             from pairs[r >> 1].proper, 0x4 unmapped, 0x8 no m.  An unmapped record takes m's rid, pos and strand (no CIGAR);
+ *             without m a mapped record's own rid, pos and strand stand for the mate's.  Then 0x10 from the record's strand and
+ *             0x20 from the mate's.  mrid / mpos = those, -1 when there are none.  tlen = -(p0 - p1 + sign(p0 - p1)), pX = pos +
+ *             (is_rev ? reference length of the CIGAR - 1 : 0), when the record and m have CIGARs on one contig, else 0.  Mode 0:
+ *             only 0x4, 0x10 and 0x800, mrid = mpos = -1
+ *   CIGAR     the words as <len><op> with M I D S (any other op counts as S); with softclip == 0 and which > 0 every S prints as H;
+ *             a record with a position and no words prints *
+ *   SEQ       [sq_b, sq_e) of the stored read: [0, lq), less the first and the last clip when they print as H (forward: the
+ *             first clip from the start; reverse: the first clip from the end).  Forward: ACGTN; reverse: the range backwards as
+ *             TGCAN, QUAL backwards.  An unmapped record on a reverse mate's strand is printed reversed.  QUAL bytes are copied as
+ *             they are; * without a quality arena
+ *   tags      NM:i: and MD:Z: with a CIGAR; MC:Z: when m has a CIGAR (m's words, S as H by THIS record's which: bwa's
+ *             behaviour); AS:i: if as_ >= 0; XS:i: if xs >= 0; SA:Z: for a mapped record whose read has other mapped records
+ *             (n_sa of them), each in list order as name,pos+1,+|-,CIGAR with S kept,mapq,NM;
+ *   MD        the CIGAR over the read as SEQ prints it before any hard clip against the forward text from contig_off[rid] + pos
+ *             (codes above 4 count as 4, 4 equals 4): an M position that differs emits the run count and the reference base; I
+ *             and clips advance the read; a D that is neither the first nor the last op that is no clip emits the count, ^ and
+ *             its bases and resets the count, a first or last D only advances; the final count ends the string
+ *   line      QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL and the tags, tab-separated, \n-terminated; a record
+ *             without a position prints * 0 0 * for RNAME .. CIGAR, one without a mate position * 0 0 for RNEXT .. TLEN.  Lines
+ *             go read by read, a read's records in list order
+ * Not built: RG, XA, pa, comments, MEM_F_ALL, alt contigs, BAM. */
+typedef struct gbx_mem_sam_params {      /* 8 bytes */
+    int32_t softclip;                    /* bwa -Y: 0 (supplementary records are hard-clipped) or 1 */
+    int32_t pad_;
+} gbx_mem_sam_params;
+void gbx_mem_sam_default_params(gbx_mem_sam_params *p);
+
+typedef struct gbx_mem_sam_rec {         /* 112 bytes; a record and its line carry the same values */
+    int64_t pos, mpos;                   /* 0-based, -1: none */
+    int64_t tlen;
+    int64_t cigar_off;                   /* its words are cigar[cigar_off .. cigar_off + n_cigar) of the input */
+    int64_t md_off;                      /* its MD string is md[md_off .. md_off + md_len) */
+    int64_t line_off;                    /* its line is lines[line_off .. line_off + line_len), the \n included */
+    int32_t read, which;                 /* the read's index in the call; the record's index in the read's list */
+    int32_t flag, rid, mapq, mrid;
+    int32_t nm, as_, xs;
+    int32_t n_cigar, md_len;
+    int32_t sq_b, sq_e;                  /* SEQ and QUAL print [sq_b, sq_e) of the stored read */
+    int32_t line_len;
+    int32_t n_sa;                        /* entries of its SA tag */
+    int32_t pad_;
+} gbx_mem_sam_rec;
+
+/* A text_cap (and md_cap) that suffices when the call makes at most rec_cap records, no read has more than max_recs of them, no
+ * record deletes more than max_del bases, and the reads, their names and the CIGAR words take read_bytes, name_bytes and
+ * cigar_words in all; max_contig_name: the longest contig name. */
+size_t gbx_mem_sam_text_cap(int64_t rec_cap, int64_t cigar_words, int64_t read_bytes, int64_t name_bytes, int32_t max_contig_name,
+                            int32_t max_recs, int32_t max_del);
+
+/* Device entry.  All pointers are device pointers; asynchronous on `stream`, no host synchronisation inside.  d_regs, d_reg_off
+ * (n_reads + 1), d_n_regs: the regs stage's (mode 0) or the rescue / regs stage's reg_off and count with the paired stage's
+ * pregs (mode 1; d_pairs: n_reads / 2 records, null in mode 0); d_alns (n_alns records), d_cigar, d_n_cigar: the CIGAR stage's
+ * answer for that stage's list; d_qer / d_read_off / d_read_len: the reads as gbx_mem_rescue_device takes them; d_qual: null, or
+ * the quality bytes at the same offsets; d_names / d_name_off (n_reads + 1) and d_cnames / d_cname_off (n_contigs + 1): the
+ * names as byte arenas; d_text: at least 2 l_pac bytes.  The inputs are never written.  Written: d_recs in line order,
+ * d_rec_off[n_reads + 1], *d_n_recs; d_md with *d_n_md; d_lines with *d_n_text.  n_reads + min(reg_cap, n_alns) records always
+ * suffice.  A count above its capacity reports the need: nothing past the capacity is written, and the offsets in the records
+ * that are written keep the true values.  *d_n_regs < 0 or above reg_cap (the stage before overflowed): the three counts are -1
+ * and d_rec_off, d_recs, d_md and d_lines are zeroed.  A malformed input (offsets outside an arena, words outside d_cigar, a
+ * CIGAR longer than its read or running off its contig) is cut to what is there and never read past.  work:
+ * gbx_mem_sam_workspace_bytes(n_reads, reg_cap, n_alns) bytes.  The output bytes do not depend on the scheduling. */
+size_t gbx_mem_sam_workspace_bytes(int64_t n_reads, int64_t reg_cap, int64_t n_alns);
+int gbx_mem_sam_device(const gbx_mem_sam_params *p, int64_t n_reads, int32_t mode,
+                       const gbx_mem_reg *d_regs, const int64_t *d_reg_off, const int64_t *d_n_regs, int64_t reg_cap,
+                       const gbx_mem_pair *d_pairs,
+                       const gbx_mem_aln *d_alns, int64_t n_alns, const uint32_t *d_cigar, const int64_t *d_n_cigar, int64_t cigar_cap,
+                       const uint8_t *d_qer, int64_t qer_bytes, const int64_t *d_read_off, const int32_t *d_read_len, const uint8_t *d_qual,
+                       const uint8_t *d_names, const int64_t *d_name_off, int64_t name_bytes,
+                       const uint8_t *d_cnames, const int64_t *d_cname_off, int64_t cname_bytes,
+                       const uint8_t *d_text, int64_t text_bytes, int64_t l_pac, int32_t n_contigs, const int64_t *d_contig_off,
+                       gbx_mem_sam_rec *d_recs, int64_t rec_cap, int64_t *d_rec_off, int64_t *d_n_recs,
+                       uint8_t *d_md, int64_t md_cap, int64_t *d_n_md, uint8_t *d_lines, int64_t text_cap, int64_t *d_n_text,
+                       void *d_work, size_t work_bytes, void *stream);
+
+/* Host-buffer entry.  Checked before a device is touched: softclip (0 or 1), mode (0 or 1; n_reads even in mode 1), the contig
+ * table, text_bytes >= 2 l_pac, reg_off, name_off and cname_off (monotone, inside their arenas), every read inside qer with at
+ * least one base, and every reported region: reg.sel inside alns, its aln's rid inside the contigs, its words inside cigar with
+ * ops M I D S only, covering the read exactly and staying on the contig: GBX_ERR_ARG naming the lowest offender.  The counts go
+ * to *n_recs, *n_md and *n_text; one above its capacity gives GBX_ERR_ARG with the need there and in gbx_last_error() (rec_off is
+ * written; recs, md and lines are not).  Safe under concurrent host threads; one device. */
+int gbx_mem_sam_host(const gbx_mem_sam_params *p, int64_t n_reads, int32_t mode,
+                     const gbx_mem_reg *regs, const int64_t *reg_off, int64_t n_regs, const gbx_mem_pair *pairs,
+                     const gbx_mem_aln *alns, int64_t n_alns, const uint32_t *cigar, int64_t n_cigar,
+                     const uint8_t *qer, int64_t qer_bytes, const int64_t *read_off, const int32_t *read_len, const uint8_t *qual,
+                     const uint8_t *names, const int64_t *name_off, int64_t name_bytes,
+                     const uint8_t *cnames, const int64_t *cname_off, int64_t cname_bytes,
+                     const uint8_t *text, int64_t text_bytes, int64_t l_pac, int32_t n_contigs, const int64_t *contig_off,
+                     gbx_mem_sam_rec *recs, int64_t rec_cap, int64_t *rec_off, int64_t *n_recs,
+                     uint8_t *md, int64_t md_cap, int64_t *n_md, uint8_t *lines, int64_t text_cap, int64_t *n_text);
+
 /* -------------------------------------------------------------------- kmer
  * Canonical k-mer counting of long reads: Flye's KmerCounter::count as the kmer-cnt benchmark times it
  * (R/benchmarks/kmer-cnt/kmer_cnt.cpp:224-237, vertex_index.cpp:513-612).
