@@ -53,16 +53,16 @@ size_t gbx_mem_pair_workspace_bytes(int64_t n_pairs, int64_t reg_cap, int32_t ma
     return mem_pair_workspace_bytes(n_pairs, reg_cap, max_ins);
 }
 
-int gbx_mem_pair_device(const gbx_mem_pair_params *p, int64_t n_pairs, int64_t pair_id0,
-                        const gbx_mem_reg *d_regs, const int64_t *d_reg_off, const int64_t *d_n_regs, int64_t reg_cap,
-                        const gbx_bsw_seed *d_sel_seeds, const gbx_bsw_seed_result *d_sel_res, int64_t sel_cap,
-                        const gbx_bsw_seed *d_seeds, int64_t seed_cap, const int32_t *d_l_rep,
-                        int64_t l_pac, int32_t n_contigs, const int64_t *d_contig_off,
-                        const gbx_mem_pestat *pes_in, gbx_mem_pestat *d_pes, gbx_mem_pair *d_pairs, gbx_mem_reg *d_pregs,
-                        gbx_bsw_seed *d_psel_seeds, gbx_bsw_seed_result *d_psel_res, int64_t psel_cap, int64_t *d_n_psel,
-                        void *d_work, size_t work_bytes, void *stream)
+// gbx_mem_pair_device (the estimate: pes_in, a host pointer) and gbx_mem_pair_device_pes (d_pes_in, a device pointer)
+static int pair_device(const char *who, const gbx_mem_pair_params *p, int64_t n_pairs, int64_t pair_id0,
+                       const gbx_mem_reg *d_regs, const int64_t *d_reg_off, const int64_t *d_n_regs, int64_t reg_cap,
+                       const gbx_bsw_seed *d_sel_seeds, const gbx_bsw_seed_result *d_sel_res, int64_t sel_cap,
+                       const gbx_bsw_seed *d_seeds, int64_t seed_cap, const int32_t *d_l_rep,
+                       int64_t l_pac, int32_t n_contigs, const int64_t *d_contig_off,
+                       const gbx_mem_pestat *pes_in, const gbx_mem_pestat *d_pes_in, gbx_mem_pestat *d_pes, gbx_mem_pair *d_pairs,
+                       gbx_mem_reg *d_pregs, gbx_bsw_seed *d_psel_seeds, gbx_bsw_seed_result *d_psel_res, int64_t psel_cap,
+                       int64_t *d_n_psel, void *d_work, size_t work_bytes, void *stream)
 {
-    const char *who = "gbx_mem_pair_device";
     int rc = params_check(p, who);
     if (rc || (rc = ids_check(n_pairs, pair_id0, who)) || (rc = pes_check(pes_in, who))) return rc;
     if (reg_cap < 0 || sel_cap < 0 || seed_cap < 0 || psel_cap < 0 || l_pac < 1 || n_contigs < 1) { set_error("%s: bad argument", who); return GBX_ERR_ARG; }
@@ -75,7 +75,35 @@ int gbx_mem_pair_device(const gbx_mem_pair_params *p, int64_t n_pairs, int64_t p
     if ((rc = require_device())) return rc;
     const MemPairIo io{d_regs, d_reg_off, d_n_regs, reg_cap, d_sel_seeds, d_sel_res, sel_cap, d_seeds, seed_cap, d_l_rep, l_pac, n_contigs,
                        d_contig_off, d_pes, d_pairs, d_pregs, d_psel_seeds, d_psel_res, psel_cap, d_n_psel};
-    return mem_pair_launch(p, n_pairs, pair_id0, io, pes_in, d_work, work_bytes, (hipStream_t)stream);
+    return mem_pair_launch(p, n_pairs, pair_id0, io, pes_in, d_work, work_bytes, (hipStream_t)stream, d_pes_in);
+}
+
+int gbx_mem_pair_device(const gbx_mem_pair_params *p, int64_t n_pairs, int64_t pair_id0,
+                        const gbx_mem_reg *d_regs, const int64_t *d_reg_off, const int64_t *d_n_regs, int64_t reg_cap,
+                        const gbx_bsw_seed *d_sel_seeds, const gbx_bsw_seed_result *d_sel_res, int64_t sel_cap,
+                        const gbx_bsw_seed *d_seeds, int64_t seed_cap, const int32_t *d_l_rep,
+                        int64_t l_pac, int32_t n_contigs, const int64_t *d_contig_off,
+                        const gbx_mem_pestat *pes_in, gbx_mem_pestat *d_pes, gbx_mem_pair *d_pairs, gbx_mem_reg *d_pregs,
+                        gbx_bsw_seed *d_psel_seeds, gbx_bsw_seed_result *d_psel_res, int64_t psel_cap, int64_t *d_n_psel,
+                        void *d_work, size_t work_bytes, void *stream)
+{
+    return pair_device("gbx_mem_pair_device", p, n_pairs, pair_id0, d_regs, d_reg_off, d_n_regs, reg_cap, d_sel_seeds, d_sel_res, sel_cap,
+                       d_seeds, seed_cap, d_l_rep, l_pac, n_contigs, d_contig_off, pes_in, nullptr, d_pes, d_pairs, d_pregs, d_psel_seeds,
+                       d_psel_res, psel_cap, d_n_psel, d_work, work_bytes, stream);
+}
+
+int gbx_mem_pair_device_pes(const gbx_mem_pair_params *p, int64_t n_pairs, int64_t pair_id0,
+                            const gbx_mem_reg *d_regs, const int64_t *d_reg_off, const int64_t *d_n_regs, int64_t reg_cap,
+                            const gbx_bsw_seed *d_sel_seeds, const gbx_bsw_seed_result *d_sel_res, int64_t sel_cap,
+                            const gbx_bsw_seed *d_seeds, int64_t seed_cap, const int32_t *d_l_rep,
+                            int64_t l_pac, int32_t n_contigs, const int64_t *d_contig_off,
+                            const gbx_mem_pestat *d_pes_in, gbx_mem_pestat *d_pes, gbx_mem_pair *d_pairs, gbx_mem_reg *d_pregs,
+                            gbx_bsw_seed *d_psel_seeds, gbx_bsw_seed_result *d_psel_res, int64_t psel_cap, int64_t *d_n_psel,
+                            void *d_work, size_t work_bytes, void *stream)
+{
+    return pair_device("gbx_mem_pair_device_pes", p, n_pairs, pair_id0, d_regs, d_reg_off, d_n_regs, reg_cap, d_sel_seeds, d_sel_res,
+                       sel_cap, d_seeds, seed_cap, d_l_rep, l_pac, n_contigs, d_contig_off, nullptr, d_pes_in, d_pes, d_pairs, d_pregs,
+                       d_psel_seeds, d_psel_res, psel_cap, d_n_psel, d_work, work_bytes, stream);
 }
 
 int gbx_mem_pair_host(const gbx_mem_pair_params *p, int64_t n_pairs, int64_t pair_id0,

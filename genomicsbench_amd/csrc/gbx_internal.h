@@ -243,7 +243,7 @@ struct MemPairIo {                   // the device arguments of gbx_mem_pair_dev
 size_t mem_pair_workspace_bytes(int64_t n_pairs, int64_t reg_cap, int32_t max_ins);
 // pes_in: a host pointer to the caller's four records (passed to the kernels by value), or null for an estimate from the call
 int mem_pair_launch(const gbx_mem_pair_params *p, int64_t n_pairs, int64_t pair_id0, const MemPairIo &io, const gbx_mem_pestat *pes_in,
-                    void *d_work, size_t work_bytes, hipStream_t s);
+                    void *d_work, size_t work_bytes, hipStream_t s, const gbx_mem_pestat *d_pes_in = nullptr);
 
 // ---- mate rescue (mem_rescue_kernels.hip)
 struct MemRescueIo {                 // the device arguments of gbx_mem_rescue_device
@@ -281,6 +281,16 @@ struct MemSamIo {                    // the device arguments of gbx_mem_sam_devi
 int64_t mem_sam_rec_max(int64_t n_reads, int64_t reg_cap, int64_t n_alns);      // the records a call can make at most
 size_t mem_sam_workspace_bytes(int64_t n_reads, int64_t reg_cap, int64_t n_alns);
 int mem_sam_launch(const gbx_mem_sam_params *p, int64_t n_reads, int mode, const MemSamIo &io, void *d_work, size_t work_bytes, hipStream_t s);
+
+// ---- the aligner's gather behind the chain (mem_align_kernels.hip): every stage's count into one record
+struct MemAlignGather {              // a null pointer: the stage does not run, its count is 0
+    const unsigned long long *fmi_counters;         // the fmi workspace: [2] is the slot overflow word fmi_read_overflow reads
+    const int64_t *n_smem, *n_pos, *n_chains, *n_seeds, *n_regs, *n_sel, *n_xregs, *n_xseeds, *n_xsel, *n_psel, *n_cigar;
+    const gbx_mem_aln *alns; int64_t n_alns;        // the CIGAR stage's records: rid == -2 and rid >= 0 are counted
+    const int64_t *n_recs, *n_md, *n_text;
+    gbx_mem_align_counts *out;
+};
+int mem_align_gather_launch(const MemAlignGather &g, hipStream_t s);
 
 // ---- kmer (kmer_kernels.hip)
 size_t kmer_workspace_bytes(int32_t k, int64_t n_reads);

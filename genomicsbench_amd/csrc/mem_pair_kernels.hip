@@ -33,6 +33,7 @@ struct MpArgs {
     long long n_pairs, pair_id0;
     int has_pes;                     // the caller's estimate is used, none is made
     gbx_mem_pestat pes_in[4];
+    const gbx_mem_pestat *d_pes_in;  // the caller's estimate on the device (gbx_mem_pair_device_pes), else pes_in holds it
     long long *cnt;                  // [2 n_pairs + 1]: reported regions per read, then their exclusive scan
     unsigned *bins;                  // [4][max_ins + 1]: pairs per direction and insert size
     MpKey *key;                      // [2 reg_cap]  slab of a pair: twice its first region
@@ -105,7 +106,11 @@ __global__ void __launch_bounds__(256) mem_pair_stat_kernel(MpArgs A)
     __shared__ long long n_of[4];
     const int lane = threadIdx.x & 63, d = threadIdx.x >> 6;
     if (A.has_pes) {
-        if (threadIdx.x < 4) A.io.pes[threadIdx.x] = A.pes_in[threadIdx.x];
+        if (threadIdx.x < 4) {
+            gbx_mem_pestat r = A.d_pes_in ? A.d_pes_in[threadIdx.x] : A.pes_in[threadIdx.x];
+            if (A.d_pes_in && r.failed == 0 && !(r.std > 0.)) r.failed = 1;       // what pes_check refuses of a host pointer
+            A.io.pes[threadIdx.x] = r;
+        }
         return;
     }
     const int nb = A.p.max_ins + 1;
@@ -468,7 +473,7 @@ int mem_pestat_launch(const gbx_mem_pair_params *p, int64_t n_pairs, const MemPa
     const size_t bins_bytes = 4 * ((size_t)p->max_ins + 1) * 4;
     if (work_bytes < bins_bytes) { set_error("mem pestat: workspace too small"); return GBX_ERR_ARG; }
     MpArgs A;
-    A.p = *p; A.io = io; A.n_pairs = n_pairs; A.pair_id0 = 0; A.has_pes = 0;
+    A.p = *p; A.io = io; A.n_pairs = n_pairs; A.pair_id0 = 0; A.has_pes = 0; A.d_pes_in = nullptr;
     for (int d = 0; d < 4; ++d) A.pes_in[d] = gbx_mem_pestat{0, 0, 1, 0, 0., 0.};
     A.cnt = nullptr; A.bins = (unsigned *)d_work; A.key = nullptr;
     Stage st("mem_pestat", s);
@@ -479,7 +484,7 @@ int mem_pestat_launch(const gbx_mem_pair_params *p, int64_t n_pairs, const MemPa
 }
 
 int mem_pair_launch(const gbx_mem_pair_params *p, int64_t n_pairs, int64_t pair_id0, const MemPairIo &io, const gbx_mem_pestat *pes_in,
-                    void *d_work, size_t work_bytes, hipStream_t s)
+                    void *d_work, size_t work_bytes, hipStream_t s, const gbx_mem_pestat *d_pes_in)
 {
     if (io.reg_cap >= (1ll << 30) || io.psel_cap >= (1ll << 31) * 256) { set_error("mem pair: reg_cap or psel_cap too large"); return GBX_ERR_UNSUPPORTED; }
     const MpLayout L = mp_layout(n_pairs, io.reg_cap, p->max_ins);
@@ -487,7 +492,8 @@ int mem_pair_launch(const gbx_mem_pair_params *p, int64_t n_pairs, int64_t pair_
     char *wb = (char *)d_work;
     MpArgs A;
     A.p = *p; A.io = io; A.n_pairs = n_pairs; A.pair_id0 = pair_id0;
-    A.has_pes = pes_in != nullptr;
+    A.has_pes = pes_in != nullptr || d_pes_in != nullptr;
+    A.d_pes_in = d_pes_in;
     for (int d = 0; d < 4; ++d) A.pes_in[d] = pes_in ? pes_in[d] : gbx_mem_pestat{0, 0, 1, 0, 0., 0.};
     A.cnt = (long long *)(wb + L.o_cnt); A.bins = (unsigned *)(wb + L.o_bins);
     A.key = (MpKey *)(wb + L.o_key);

@@ -982,6 +982,20 @@ int gbx_mem_pair_device(const gbx_mem_pair_params *p, int64_t n_pairs, int64_t p
                         const gbx_mem_pestat *pes_in, gbx_mem_pestat *d_pes, gbx_mem_pair *d_pairs, gbx_mem_reg *d_pregs,
                         gbx_bsw_seed *d_psel_seeds, gbx_bsw_seed_result *d_psel_res, int64_t psel_cap, int64_t *d_n_psel,
                         void *d_work, size_t work_bytes, void *stream);
+/* gbx_mem_pair_device with the caller's estimate on the device: d_pes_in is null (an estimate is made, as with pes_in null) or a
+ * DEVICE pointer to four records, e.g. the d_pes of gbx_mem_pestat_device on the same stream; the kernel that fills d_pes reads
+ * them, the host never does, so the call chains behind the rescue without a copy or a synchronisation.  The check the other
+ * entries make of a caller's records on the host (std > 0 wherever failed == 0) cannot be made here: on the device a record that
+ * breaks it is taken as failed (d_pes gets it with failed = 1, its other fields as given).  d_pes_in may be d_pes itself.  Every
+ * other argument and every output is that of gbx_mem_pair_device given the same records as pes_in. */
+int gbx_mem_pair_device_pes(const gbx_mem_pair_params *p, int64_t n_pairs, int64_t pair_id0,
+                            const gbx_mem_reg *d_regs, const int64_t *d_reg_off, const int64_t *d_n_regs, int64_t reg_cap,
+                            const gbx_bsw_seed *d_sel_seeds, const gbx_bsw_seed_result *d_sel_res, int64_t sel_cap,
+                            const gbx_bsw_seed *d_seeds, int64_t seed_cap, const int32_t *d_l_rep,
+                            int64_t l_pac, int32_t n_contigs, const int64_t *d_contig_off,
+                            const gbx_mem_pestat *d_pes_in, gbx_mem_pestat *d_pes, gbx_mem_pair *d_pairs, gbx_mem_reg *d_pregs,
+                            gbx_bsw_seed *d_psel_seeds, gbx_bsw_seed_result *d_psel_res, int64_t psel_cap, int64_t *d_n_psel,
+                            void *d_work, size_t work_bytes, void *stream);
 
 /* Host-buffer entry.  Checked before a device is touched: the parameters (a >= 1, e_del and e_ins >= 1, 1 <= max_ins <= 2^20,
  * mapq_coef_len > 0: GBX_ERR_UNSUPPORTED otherwise), pair_id0 >= 0 and pair_id0 + n_pairs <= 2^23 (beyond it bwa's int id << 8
@@ -1222,6 +1236,133 @@ int gbx_mem_sam_host(const gbx_mem_sam_params *p, int64_t n_reads, int32_t mode,
                      const uint8_t *text, int64_t text_bytes, int64_t l_pac, int32_t n_contigs, const int64_t *contig_off,
                      gbx_mem_sam_rec *recs, int64_t rec_cap, int64_t *rec_off, int64_t *n_recs,
                      uint8_t *md, int64_t md_cap, int64_t *n_md, uint8_t *lines, int64_t text_cap, int64_t *n_text);
+
+/* ---- the whole path in one call: reads in, SAM out.  A gbx_mem_aligner queues smem -> sal -> chain -> extend -> regs ->
+ * [pestat -> rescue ->] pair -> cigar -> sam (mode 1, interleaved pairs) or smem -> sal -> chain -> extend -> regs -> cigar -> sam
+ * (mode 0, single-end) on a stream of its own, exactly as the stage entries above chain, with no host synchronisation between
+ * the stages: behind the chain one kernel gathers every stage's count into a gbx_mem_align_counts record, that record is copied
+ * and the stream synchronised once, and only then exactly n_recs records and n_text bytes come back.  A capacity that was too
+ * small makes the aligner grow it to the reported need and queue the chain again from the first stage that overflowed; what
+ * lies before that stage is kept.  The sam and recs bytes of a run depend only on the index, the parameters, the reads and id0:
+ * not on the first capacities, the reruns, what the aligner ran before, or the scheduling.
+ * Not built: multi-device spreading, alt contigs, XA, mem_patch_reg, RG, BAM, @PG. */
+typedef struct gbx_mem_index gbx_mem_index;         /* the device copies of an index; read-only once made, shareable */
+typedef struct gbx_mem_aligner gbx_mem_aligner;     /* one stream, all stage buffers, pinned in / out buffers; one thread at a time */
+
+typedef struct gbx_mem_align_params {    /* 600 bytes */
+    gbx_fmi_params fmi;
+    gbx_mem_chain_params chain;
+    gbx_bsw_seed_params bsw;
+    gbx_mem_regs_params regs;
+    gbx_mem_pair_params pair;            /* also the estimate's (gbx_mem_pestat_*) */
+    gbx_mem_rescue_params rescue;
+    gbx_mem_cigar_params cigar;
+    gbx_mem_sam_params sam;
+    int32_t max_occ;                     /* 500: the suffix-array lookup's; equals chain.max_occ */
+    int32_t mode;                        /* 0 single-end, 1 interleaved pairs (read 2p + e is end e of pair p) */
+    int32_t have_pes;                    /* 1: pes below is the estimate (bwa -I); none is made */
+    int32_t no_rescue;                   /* 1: mode 1 without pestat and rescue (bwa -S): regs, pair, cigar, sam */
+    gbx_mem_pestat pes[4];
+} gbx_mem_align_params;
+/* every stage's own defaults, max_occ 500, mode 1 */
+void gbx_mem_align_default_params(gbx_mem_align_params *p);
+/* Writes every copy of these values the stage structs hold: a / b into the chain's a, the bsw and cigar matrices (bwa_fill_scmat,
+ * N scoring -1), regs, pair and rescue; the gap costs into chain, bsw, regs, pair, rescue and cigar; w into chain, bsw, regs and
+ * cigar; zdrop and the clip bonuses into bsw; pen_unpaired into pair and rescue; T into regs, pair and rescue; min_seed_len into
+ * fmi (with split_len = (int)(min_seed_len * 1.5 + .499)), chain, regs, pair and rescue. */
+void gbx_mem_align_set_scoring(gbx_mem_align_params *p, int32_t a, int32_t b, int32_t o_del, int32_t e_del, int32_t o_ins, int32_t e_ins,
+                               int32_t pen_clip5, int32_t pen_clip3, int32_t pen_unpaired, int32_t w, int32_t zdrop, int32_t min_seed_len,
+                               int32_t T);
+/* Host only.  GBX_ERR_ARG naming the first pair of copies that disagree (the fields above, max_chain_gap, mask_level,
+ * mask_level_redun, drop_ratio, mapq_coef_len / _fac, max_occ), a mode or flag that is not 0 or 1, or a given pes that breaks
+ * std > 0 where failed == 0.  gbx_mem_aligner_create makes it. */
+int gbx_mem_align_check_params(const gbx_mem_align_params *p);
+
+typedef struct gbx_mem_align_caps {      /* 128 bytes: every capacity of the chain, in stage order */
+    int64_t slot;                        /* fmi: records per read slot; 0 = the stage's own max(48, 4 max_read_len / min_seed_len + 16) */
+    int64_t out_cap, pos_cap, chain_cap, seed_cap, reg_cap, sel_cap;
+    int64_t xreg_cap, xseed_cap, xsel_cap;       /* the rescue's; 0 where it does not run */
+    int64_t psel_cap;                    /* 0 in mode 0 */
+    int64_t cigar_cap, z_bytes;
+    int64_t rec_cap, md_cap, text_cap;
+} gbx_mem_align_caps;
+typedef struct gbx_mem_align_counts {    /* 144 bytes: what the gather kernel reads behind the chain; -1: a stage before it overflowed */
+    int64_t slot_worst;                  /* gbx_fmi_overflow's word: 0, or a lower bound of the slot a read asked for */
+    int64_t n_smem, n_pos, n_chains, n_seeds, n_regs, n_sel;
+    int64_t n_xregs, n_xseeds, n_xsel;   /* 0 where the rescue does not run */
+    int64_t n_psel;                      /* 0 in mode 0 */
+    int64_t n_cigar;
+    int64_t n_z_miss;                    /* CIGAR records with rid == -2: no room for their direction bytes */
+    int64_t n_recs, n_md, n_text;
+    int64_t n_alns;                      /* CIGAR records that were aligned (rid >= 0) */
+    int64_t pad_;
+} gbx_mem_align_counts;
+#define GBX_MEM_ALIGN_MAX_RERUNS 64
+/* the stages as rerun_stage names them */
+#define GBX_MEM_ST_SMEM 0
+#define GBX_MEM_ST_SAL 1
+#define GBX_MEM_ST_CHAIN 2
+#define GBX_MEM_ST_EXTEND 3
+#define GBX_MEM_ST_REGS 4
+#define GBX_MEM_ST_PESTAT 5
+#define GBX_MEM_ST_RESCUE 6
+#define GBX_MEM_ST_PAIR 7
+#define GBX_MEM_ST_CIGAR 8
+#define GBX_MEM_ST_SAM 9
+typedef struct gbx_mem_align_stats {
+    gbx_mem_align_counts counts;         /* the last pass's */
+    gbx_mem_align_caps caps;             /* in force at the end of the run */
+    int64_t runs;                        /* runs of this aligner that reached the device, this one included */
+    int64_t bytes_up, bytes_down;        /* moved over the bus by this run */
+    int32_t reruns;                      /* passes after the first */
+    int32_t slot_reruns;                 /* those the fmi slot started */
+    int32_t rerun_stage[GBX_MEM_ALIGN_MAX_RERUNS];   /* the stage each rerun started from; the first GBX_MEM_ALIGN_MAX_RERUNS */
+} gbx_mem_align_stats;
+/* Per-stage device times: gbx_profile_begin / gbx_profile_end around a run name every stage's kernels. */
+typedef struct gbx_mem_align_out {
+    const uint8_t *sam; int64_t n_text;  /* the lines, no header */
+    const gbx_mem_sam_rec *recs; int64_t n_recs;
+    const int64_t *rec_off;              /* n_reads + 1 */
+    gbx_mem_pestat pes[4];               /* the estimate in force (all failed where none is made: mode 0) */
+    gbx_mem_align_stats stats;
+} gbx_mem_align_out;
+
+/* sizeof of params, caps, counts, stats, out, in that order: a binding checks its mirror against it */
+void gbx_mem_align_sizes(int64_t out[5]);
+
+/* Host only, no device.  Capacities for a batch of n_reads reads of `bases` bases in all, the longest max_read_len, their names
+ * name_bytes.  Where the header states a relation that always suffices and costs nothing it is used: seed_cap = pos_cap, reg_cap =
+ * sel_cap = seed_cap, the rescue's three from reg_cap and max_matesw, psel_cap = the rescue's xreg_cap (reg_cap without it),
+ * rec_cap = n_reads + min(reg_cap', list length), md_cap = text_cap = gbx_mem_sam_text_cap(rec_cap, cigar_cap, bases, name_bytes,
+ * 32, 4, 256).  out_cap, pos_cap, chain_cap, cigar_cap and z_bytes have no such bound: a first guess per base or per read, or,
+ * with `last` (the counts of an earlier batch of last_bases bases), those counts scaled by bases / last_bases with a margin of
+ * one quarter; never less than the scaled count. */
+int gbx_mem_align_plan(const gbx_mem_align_params *p, int64_t n_reads, int64_t bases, int32_t max_read_len, int64_t name_bytes,
+                       const gbx_mem_align_counts *last, int64_t last_bases, gbx_mem_align_caps *caps);
+
+/* Uploads and lays out everything once: the index (gbx_fmi_index_build), the samples (gbx_fmi_sa_build), the 2 l_pac-byte text,
+ * the contig table and names.  idx->cp_occ, sa->ms_byte, sa->ls_word, text, contig_off, cnames, cname_off: HOST pointers. */
+int gbx_mem_index_create(const gbx_fmi_index *idx, const gbx_fmi_sa *sa, const uint8_t *text, int64_t l_pac, int32_t n_contigs,
+                         const int64_t *contig_off, const uint8_t *cnames, const int64_t *cname_off, gbx_mem_index **out);
+void gbx_mem_index_destroy(gbx_mem_index *index);
+/* The @SQ lines, one per contig.  *need = their bytes; GBX_ERR_ARG when cap is less (nothing is written). */
+int gbx_mem_sam_header(const gbx_mem_index *index, uint8_t *buf, int64_t cap, int64_t *need);
+
+/* first: the capacities to start from (null: gbx_mem_align_plan's for the first batch).  The index must outlive the aligner. */
+int gbx_mem_aligner_create(const gbx_mem_index *index, const gbx_mem_align_params *p, const gbx_mem_align_caps *first, gbx_mem_aligner **out);
+void gbx_mem_aligner_destroy(gbx_mem_aligner *al);
+/* Synchronous.  Reads as base codes 0..4, read r = enc[read_off[r] ..+ read_len[r]); qual: null, or bytes at the same offsets;
+ * names / name_off (n_reads + 1): the QNAMEs.  Mode 1: n_reads even, id0 the first PAIR's id (the stages get pair_id0 = id0,
+ * read_id0 = 2 id0); mode 0: id0 the first read's id.  Checked before any device work, GBX_ERR_ARG naming the lowest offender:
+ * n_reads even in mode 1, read_off / name_off monotone and inside their arenas, every read at least one base and inside enc,
+ * id0 >= 0 and id0 + n_pairs <= 2^23 (mode 0: id0 + n_reads <= 2^24); GBX_ERR_UNSUPPORTED: a read longer than GBX_BSW_MAX_QLEN,
+ * or than 1024 where the rescue runs.  out's pointers are pinned host memory of the aligner, valid until its next run or its
+ * destruction.  A failed run leaves stats.runs as it was unless device work had begun. */
+int gbx_mem_aligner_run(gbx_mem_aligner *al, int64_t n_reads, int64_t id0, const uint8_t *enc, int64_t enc_bytes,
+                        const int64_t *read_off, const int32_t *read_len, const uint8_t *qual,
+                        const uint8_t *names, const int64_t *name_off, gbx_mem_align_out *out);
+/* The stats of the last run (the run counter also after a refused one). */
+int gbx_mem_aligner_stats(const gbx_mem_aligner *al, gbx_mem_align_stats *stats);
 
 /* -------------------------------------------------------------------- kmer
  * Canonical k-mer counting of long reads: Flye's KmerCounter::count as the kmer-cnt benchmark times it
