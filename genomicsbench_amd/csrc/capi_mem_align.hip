@@ -524,6 +524,53 @@ int gbx_mem_align_plan(const gbx_mem_align_params *p, int64_t n_reads, int64_t b
     return GBX_OK;
 }
 
+// the contig table and names of an index entry's arguments -> the longest name
+static int index_contigs_check(int64_t l_pac, int32_t n_contigs, const int64_t *contig_off, const uint8_t *cnames, const int64_t *cname_off,
+                               const char *who, int32_t *max_name)
+{
+    int rc = contig_off_check(contig_off, n_contigs, l_pac, who);
+    if (rc) return rc;
+    if (cname_off[0] != 0) { set_error("%s: cname_off must start at 0", who); return GBX_ERR_ARG; }
+    *max_name = 0;
+    for (int32_t c = 0; c < n_contigs; ++c) {
+        const int64_t l = cname_off[c + 1] - cname_off[c];
+        if (l < 1 || l > 255) { set_error("%s: contig %d: a name of %lld bytes (1 .. 255)", who, c, (long long)l); return GBX_ERR_ARG; }
+        *max_name = std::max<int32_t>(*max_name, (int32_t)l);
+    }
+    if (cname_off[n_contigs] > 0 && !cnames) { set_error("%s: null pointer", who); return GBX_ERR_ARG; }
+    return GBX_OK;
+}
+
+static gbx_mem_index *index_new(const gbx_fmi_index *idx, const gbx_fmi_sa *sa, int64_t l_pac, int32_t n_contigs, const int64_t *contig_off,
+                                const uint8_t *cnames, const int64_t *cname_off, int32_t max_name)
+{
+    gbx_mem_index *ix = new (std::nothrow) gbx_mem_index();
+    if (!ix) return nullptr;
+    const int64_t cname_bytes = cname_off[n_contigs];
+    ix->idx = *idx; ix->idx.cp_occ = nullptr;
+    ix->sa = *sa; ix->sa.ms_byte = nullptr; ix->sa.ls_word = nullptr;
+    ix->d_index = ix->d_sa = nullptr; ix->d_text = nullptr; ix->d_contig_off = nullptr; ix->d_cnames = nullptr; ix->d_cname_off = nullptr;
+    ix->l_pac = l_pac; ix->text_bytes = 2 * l_pac; ix->n_contigs = n_contigs; ix->max_cname = max_name; ix->cname_bytes = cname_bytes;
+    ix->contig_off.assign(contig_off, contig_off + n_contigs + 1);
+    ix->cname_off.assign(cname_off, cname_off + n_contigs + 1);
+    ix->cnames.assign(cnames, cnames + cname_bytes);
+    return ix;
+}
+
+// the text's 64 bytes of slack and the contig tables of ix, queued on s
+static int index_tables(gbx_mem_index *ix, hipStream_t s)
+{
+    const size_t nc = (size_t)ix->n_contigs + 1;
+    GBX_HIP(hipMemsetAsync(ix->d_text + ix->text_bytes, 0, 64, s));
+    GBX_HIP(hipMalloc((void **)&ix->d_contig_off, nc * 8));
+    GBX_HIP(hipMemcpyAsync(ix->d_contig_off, ix->contig_off.data(), nc * 8, hipMemcpyHostToDevice, s));
+    GBX_HIP(hipMalloc((void **)&ix->d_cname_off, nc * 8));
+    GBX_HIP(hipMemcpyAsync(ix->d_cname_off, ix->cname_off.data(), nc * 8, hipMemcpyHostToDevice, s));
+    GBX_HIP(hipMalloc((void **)&ix->d_cnames, (size_t)std::max<int64_t>(ix->cname_bytes, 1)));
+    if (ix->cname_bytes) GBX_HIP(hipMemcpyAsync(ix->d_cnames, ix->cnames.data(), (size_t)ix->cname_bytes, hipMemcpyHostToDevice, s));
+    return GBX_OK;
+}
+
 int gbx_mem_index_create(const gbx_fmi_index *idx, const gbx_fmi_sa *sa, const uint8_t *text, int64_t l_pac, int32_t n_contigs,
                          const int64_t *contig_off, const uint8_t *cnames, const int64_t *cname_off, gbx_mem_index **out)
 {
@@ -538,26 +585,11 @@ int gbx_mem_index_create(const gbx_fmi_index *idx, const gbx_fmi_sa *sa, const u
     }
     const int64_t want = sa->sa_compx ? (idx->ref_seq_len >> 3) + 1 : idx->ref_seq_len;
     if ((sa->sa_compx != 0 && sa->sa_compx != 3) || sa->n_sa != want) { set_error("%s: sa_compx = %d, n_sa = %lld", who, sa->sa_compx, (long long)sa->n_sa); return GBX_ERR_ARG; }
-    if ((rc = contig_off_check(contig_off, n_contigs, l_pac, who))) return rc;
-    if (cname_off[0] != 0) { set_error("%s: cname_off must start at 0", who); return GBX_ERR_ARG; }
     int32_t max_name = 0;
-    for (int32_t c = 0; c < n_contigs; ++c) {
-        const int64_t l = cname_off[c + 1] - cname_off[c];
-        if (l < 1 || l > 255) { set_error("%s: contig %d: a name of %lld bytes (1 .. 255)", who, c, (long long)l); return GBX_ERR_ARG; }
-        max_name = std::max<int32_t>(max_name, (int32_t)l);
-    }
-    const int64_t cname_bytes = cname_off[n_contigs];
-    if (cname_bytes > 0 && !cnames) { set_error("%s: null pointer", who); return GBX_ERR_ARG; }
+    if ((rc = index_contigs_check(l_pac, n_contigs, contig_off, cnames, cname_off, who, &max_name))) return rc;
     if ((rc = require_device())) return rc;
-    gbx_mem_index *ix = new (std::nothrow) gbx_mem_index();
+    gbx_mem_index *ix = index_new(idx, sa, l_pac, n_contigs, contig_off, cnames, cname_off, max_name);
     if (!ix) { set_error("%s: out of host memory", who); return GBX_ERR_NOMEM; }
-    ix->idx = *idx; ix->idx.cp_occ = nullptr;
-    ix->sa = *sa; ix->sa.ms_byte = nullptr; ix->sa.ls_word = nullptr;
-    ix->d_index = ix->d_sa = nullptr; ix->d_text = nullptr; ix->d_contig_off = nullptr; ix->d_cnames = nullptr; ix->d_cname_off = nullptr;
-    ix->l_pac = l_pac; ix->text_bytes = 2 * l_pac; ix->n_contigs = n_contigs; ix->max_cname = max_name; ix->cname_bytes = cname_bytes;
-    ix->contig_off.assign(contig_off, contig_off + n_contigs + 1);
-    ix->cname_off.assign(cname_off, cname_off + n_contigs + 1);
-    ix->cnames.assign(cnames, cnames + cname_bytes);
     void *t_cp = nullptr, *t_ms = nullptr, *t_ls = nullptr;
     hipStream_t s = nullptr;
     auto work = [&]() -> int {
@@ -580,14 +612,8 @@ int gbx_mem_index_create(const gbx_fmi_index *idx, const gbx_fmi_sa *sa, const u
         ds.ms_byte = (const int8_t *)t_ms; ds.ls_word = (const uint32_t *)t_ls;
         if ((rc2 = fmi_sa_build(&ds, idx->ref_seq_len, ix->d_sa, sb, s))) return rc2;
         GBX_HIP(hipMalloc((void **)&ix->d_text, (size_t)ix->text_bytes + 64));
-        GBX_HIP(hipMemsetAsync(ix->d_text + ix->text_bytes, 0, 64, s));
         GBX_HIP(hipMemcpyAsync(ix->d_text, text, (size_t)ix->text_bytes, hipMemcpyHostToDevice, s));
-        GBX_HIP(hipMalloc((void **)&ix->d_contig_off, (size_t)(n_contigs + 1) * 8));
-        GBX_HIP(hipMemcpyAsync(ix->d_contig_off, contig_off, (size_t)(n_contigs + 1) * 8, hipMemcpyHostToDevice, s));
-        GBX_HIP(hipMalloc((void **)&ix->d_cname_off, (size_t)(n_contigs + 1) * 8));
-        GBX_HIP(hipMemcpyAsync(ix->d_cname_off, cname_off, (size_t)(n_contigs + 1) * 8, hipMemcpyHostToDevice, s));
-        GBX_HIP(hipMalloc((void **)&ix->d_cnames, (size_t)std::max<int64_t>(cname_bytes, 1)));
-        if (cname_bytes) GBX_HIP(hipMemcpyAsync(ix->d_cnames, cnames, (size_t)cname_bytes, hipMemcpyHostToDevice, s));
+        if ((rc2 = index_tables(ix, s))) return rc2;
         GBX_HIP(hipStreamSynchronize(s));
         return GBX_OK;
     };
@@ -596,6 +622,69 @@ int gbx_mem_index_create(const gbx_fmi_index *idx, const gbx_fmi_sa *sa, const u
     if (t_cp) (void)hipFree(t_cp);
     if (t_ms) (void)hipFree(t_ms);
     if (t_ls) (void)hipFree(t_ls);
+    if (rc) { gbx_mem_index_destroy(ix); return rc; }
+    *out = ix;
+    return GBX_OK;
+}
+
+int gbx_mem_index_build(const uint8_t *genome, int64_t l_pac, int32_t n_contigs, const int64_t *contig_off, const uint8_t *cnames,
+                        const int64_t *cname_off, gbx_mem_index **out)
+{
+    const char *who = "gbx_mem_index_build";
+    if (!genome || !contig_off || !cname_off || !out) { set_error("%s: null pointer", who); return GBX_ERR_ARG; }
+    *out = nullptr;
+    int rc = fmi_build_check(genome, l_pac, 3, who);
+    if (rc) return rc;
+    if (n_contigs < 1) { set_error("%s: n_contigs = %d", who, n_contigs); return GBX_ERR_ARG; }
+    int32_t max_name = 0;
+    if ((rc = index_contigs_check(l_pac, n_contigs, contig_off, cnames, cname_off, who, &max_name))) return rc;
+    if ((rc = require_device())) return rc;
+    gbx_fmi_index idx{};
+    idx.ref_seq_len = 2 * l_pac + 1;
+    gbx_fmi_sa sa{};
+    sa.sa_compx = 3; sa.n_sa = (idx.ref_seq_len >> 3) + 1;
+    gbx_mem_index *ix = index_new(&idx, &sa, l_pac, n_contigs, contig_off, cnames, cname_off, max_name);
+    if (!ix) { set_error("%s: out of host memory", who); return GBX_ERR_NOMEM; }
+    void *t_g = nullptr, *t_cp = nullptr, *t_ms = nullptr, *t_ls = nullptr, *t_info = nullptr, *t_work = nullptr;
+    hipStream_t s = nullptr;
+    auto work = [&]() -> int {
+        GBX_HIP(hipGetDevice(&ix->dev));
+        GBX_HIP(hipStreamCreate(&s));
+        const size_t ib = fmi_index_bytes(idx.ref_seq_len), sb = fmi_sa_bytes(sa.n_sa, idx.ref_seq_len), n_sa = (size_t)sa.n_sa;
+        const size_t wb = fmi_build_workspace_bytes(l_pac);
+        GBX_HIP(hipMalloc(&t_g, (size_t)l_pac));
+        GBX_HIP(hipMalloc(&t_cp, ib));                                       // as gbx_mem_index_create sizes it
+        GBX_HIP(hipMalloc(&t_ms, n_sa));
+        GBX_HIP(hipMalloc(&t_ls, n_sa * 4));
+        GBX_HIP(hipMalloc(&t_info, 64));
+        GBX_HIP(hipMalloc(&t_work, wb));
+        GBX_HIP(hipMalloc((void **)&ix->d_text, (size_t)ix->text_bytes + 64));
+        GBX_HIP(hipMemcpyAsync(t_g, genome, (size_t)l_pac, hipMemcpyHostToDevice, s));
+        int rc2 = fmi_build_launch((const uint8_t *)t_g, l_pac, 3, (gbx_fmi_cp_occ *)t_cp, (int8_t *)t_ms, (uint32_t *)t_ls, ix->d_text, (int64_t *)t_info,
+                                   t_work, wb, s);
+        if (rc2) return rc2;
+        int64_t w[8];
+        GBX_HIP(hipMemcpyAsync(w, t_info, 64, hipMemcpyDeviceToHost, s));
+        GBX_HIP(hipStreamSynchronize(s));
+        (void)hipFree(t_work); t_work = nullptr;                             // the workspace goes before the layouts come
+        for (int c = 0; c < 5; ++c) ix->idx.count[c] = w[c];
+        ix->idx.sentinel_index = w[5];
+        if ((rc2 = fmi_index_check(&ix->idx, (1ll << 40) - 1, who))) return rc2;
+        gbx_fmi_index di = ix->idx;
+        di.cp_occ = (const gbx_fmi_cp_occ *)t_cp;
+        GBX_HIP(hipMalloc(&ix->d_index, ib));
+        if ((rc2 = fmi_index_build(&di, ix->d_index, ib, s))) return rc2;
+        GBX_HIP(hipMalloc(&ix->d_sa, std::max<size_t>(sb, 1)));
+        gbx_fmi_sa ds = sa;
+        ds.ms_byte = (const int8_t *)t_ms; ds.ls_word = (const uint32_t *)t_ls;
+        if ((rc2 = fmi_sa_build(&ds, idx.ref_seq_len, ix->d_sa, sb, s))) return rc2;
+        if ((rc2 = index_tables(ix, s))) return rc2;
+        GBX_HIP(hipStreamSynchronize(s));
+        return GBX_OK;
+    };
+    rc = work();
+    if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
+    for (void *q : {t_g, t_cp, t_ms, t_ls, t_info, t_work}) if (q) (void)hipFree(q);
     if (rc) { gbx_mem_index_destroy(ix); return rc; }
     *out = ix;
     return GBX_OK;

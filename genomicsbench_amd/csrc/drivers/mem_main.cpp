@@ -1,4 +1,5 @@
 // mem — GPU driver with the command line of `bwa mem`:  mem [options] <idxprefix> <in1.fq> [in2.fq]
+//                                                       mem index [-p prefix] [--parse-only] <in.fa>
 // over gbx_mem_index / gbx_mem_aligner (include/gbx.h): reads in, SAM (the @SQ lines, then the records) on stdout or -o FILE.
 //
 // Index files, all UNPINNED (bwa-mem2 cannot be built or run here; the layouts are the published ones):
@@ -9,6 +10,12 @@
 //   <prefix>.pac          otherwise: 2 bits per base, the first base in the top bits of a byte: base l = pac[l >> 2] >>
 //                         ((~l & 3) << 1) & 3; the reverse-complement half is derived from it
 //   <prefix>.amb          is NOT read: the holes of the reference align as the bases bwa put there
+// `mem index` writes all five files from a FASTA (ref_files.h has the rules; the prefix defaults to the FASTA's path): .ann, .amb,
+// .pac and .0123 on the host, .bwt.2bit.64 with sa_compx 3 through gbx_fmi_build_host (the suffix array, the BWT, the checkpoints
+// and the samples are built on the GPU).  Parity UNPINNED, as for every index file.  --parse-only writes the four host files,
+// prints "l_pac=.. contigs=.. holes=.. text_checksum=.." with a line per contig, and needs no GPU.  The other options of
+// `bwa index` (-a, -b, -6) are refused by name.  Errors (an empty file, a sequence line before any header, a contig with no
+// bases, a reference above 2147483647 bases) exit 1 with one line.
 // Reads: FASTQ (four lines a record) or FASTA (sequence lines may wrap), plain text.  One file is single-end, one file with -p is
 // interleaved pairs, two files are read in step (their record counts must agree).  QNAME is the header up to the first white
 // space, a trailing /1 or /2 removed when the name is longer than two characters.  Bases go through bwa's table: ACGT and acgt
@@ -40,6 +47,7 @@
 #include <thread>
 #include "driver_common.h"
 #include "fmi_index_io.h"
+#include "ref_files.h"
 
 namespace {
 
@@ -250,6 +258,7 @@ int usage()
 {
     fprintf(stderr,
             "Usage: mem [options] <idxprefix> <in1.fq> [in2.fq]\n"
+            "       mem index [-p prefix] [--parse-only] <in.fa>   writes <prefix>.bwt.2bit.64 .ann .amb .pac .0123 (prefix: in.fa)\n"
             "  -k INT -w INT -d INT -r FLOAT -c INT -A INT -B INT -O INT[,INT] -E INT[,INT] -L INT[,INT] -U INT -T INT\n"
             "  -P  no pairing    -S  no mate rescue    -Y  soft clipping for supplementary records    -p  interleaved pairs\n"
             "  -I FLOAT[,FLOAT[,INT[,INT]]]  FR insert size: mean[,std[,max[,min]]] (std 0.1 mean, max/min mean +/- 4 std)\n"
@@ -259,10 +268,65 @@ int usage()
     return 1;
 }
 
+// mem index [-p prefix] [--parse-only] <in.fa>
+int index_main(int argc, char **argv)
+{
+    const char *prefix_arg = nullptr, *fasta = nullptr;
+    bool parse_only = false;
+    for (int i = 1; i < argc; ++i) {
+        const char *s = argv[i];
+        if (!strcmp(s, "--parse-only")) { parse_only = true; continue; }
+        if (s[0] != '-' || s[1] == 0) {
+            if (fasta) { fprintf(stderr, "mem index: one FASTA file\n"); return usage(); }
+            fasta = s;
+            continue;
+        }
+        if (s[1] != 'p') { fprintf(stderr, "mem index: option %s is not supported\n", s); return usage(); }
+        prefix_arg = s[2] ? s + 2 : (i + 1 < argc ? argv[++i] : nullptr);
+        if (!prefix_arg) { fprintf(stderr, "mem index: option -p needs a value\n"); return usage(); }
+    }
+    if (!fasta) return usage();
+    const std::string prefix = prefix_arg ? prefix_arg : fasta;
+    std::vector<char> raw;
+    if (!ref_files::read_file(fasta, raw)) { fprintf(stderr, "mem index: cannot read %s\n", fasta); return 1; }
+    ref_files::Reference R;
+    std::string err;
+    if (!ref_files::parse_fasta(raw.data(), raw.size(), R, err)) { fprintf(stderr, "mem index: %s: %s\n", fasta, err.c_str()); return 1; }
+    std::vector<char>().swap(raw);
+    if (!ref_files::write_reference(prefix, R, err)) { fprintf(stderr, "mem index: %s\n", err.c_str()); return 1; }
+    if (parse_only) {
+        const std::vector<uint8_t> text = ref_files::text_of(R);
+        printf("l_pac=%lld contigs=%d holes=%lld text_checksum=%016llx\n", (long long)R.l_pac, (int)R.contigs.size(), (long long)R.holes.size(),
+               (unsigned long long)ref_files::fnv1a(text.data(), text.size()));
+        for (size_t c = 0; c < R.contigs.size(); ++c)
+            printf("contig %d %s %lld %lld %d\n", (int)c, R.contigs[c].name.c_str(), (long long)R.contigs[c].off, (long long)R.contigs[c].len, R.contigs[c].n_ambs);
+        return 0;
+    }
+    const double t0 = now_s();
+    const int64_t n1 = 2 * R.l_pac + 1, n_sa = (n1 >> 3) + 1;
+    std::vector<gbx_fmi_cp_occ> cp((size_t)(n1 >> 6) + 1);
+    std::vector<int8_t> ms((size_t)n_sa);
+    std::vector<uint32_t> ls((size_t)n_sa);
+    gbx_fmi_index idx;
+    int64_t info[8];
+    char dev_name[256];
+    if (gbx_device_name(dev_name, sizeof dev_name) == GBX_OK) fprintf(stderr, "gbx device: %s\n", dev_name);
+    const int rc = gbx_fmi_build_host(R.codes.data(), R.l_pac, 3, &idx, cp.data(), ms.data(), ls.data(), info);
+    if (rc != GBX_OK) { fprintf(stderr, "mem index: gbx_fmi_build_host failed (%d): %s\n", rc, gbx_last_error()); return 1; }
+    if (!ref_files::write_bwt(prefix, idx.ref_seq_len, idx.count, idx.sentinel_index, cp.data(), ms.data(), ls.data(), n_sa)) {
+        fprintf(stderr, "mem index: cannot write %s.bwt.2bit.64\n", prefix.c_str());
+        return 1;
+    }
+    fprintf(stderr, "mem index: l_pac %lld, %d contigs, %lld holes, %lld doubling rounds, %.3f s\n", (long long)R.l_pac, (int)R.contigs.size(),
+            (long long)R.holes.size(), (long long)info[6], now_s() - t0);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
 {
+    if (argc > 1 && !strcmp(argv[1], "index")) return index_main(argc - 1, argv + 1);
     gbx_mem_align_params P;
     gbx_mem_align_default_params(&P);
     int32_t a = 1, b = 4, o_del = 6, o_ins = 6, e_del = 1, e_ins = 1, clip5 = 5, clip3 = 5, unpaired = 17, w = 100, zdrop = 100, k = 19, T = 30;

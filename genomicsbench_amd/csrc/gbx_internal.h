@@ -177,6 +177,16 @@ int fmi_sal_launch(const gbx_fmi_index *idx, const void *d_index, const gbx_fmi_
                    int64_t *d_n_pos, void *d_work, size_t work_bytes, hipStream_t s);
 int fmi_sal_read_steps(const void *d_work, int64_t *steps, int64_t *max_steps, hipStream_t s);
 
+// ---- FM index construction (mem_index_kernels.hip): suffix array by prefix doubling on radix sorts, BWT, checkpoints, samples
+bool fmi_build_fits(int64_t l_pac);              // 1 <= l_pac and 2 l_pac + 1 <= 2^32 - 1 (32-bit positions and ranks)
+size_t fmi_build_workspace_bytes(int64_t l_pac); // 0 when it does not fit
+// d_info: int64[8] = count[0..4], sentinel_index, doubling rounds run, slots the first round sorted.  Synchronises s once a round.
+int fmi_build_launch(const uint8_t *d_genome, int64_t l_pac, int32_t sa_compx, gbx_fmi_cp_occ *d_cp, int8_t *d_ms, uint32_t *d_ls, uint8_t *d_text,
+                     int64_t *d_info, void *d_work, size_t work_bytes, hipStream_t s);
+int fmi_build_rounds(int64_t *slots, int32_t cap, int32_t *n_rounds);     // of the calling thread's last fmi_build_launch
+// the host checks of every build entry (capi_mem_index.hip); genome: host codes to check, or null when they are on the device
+int fmi_build_check(const uint8_t *genome, int64_t l_pac, int32_t sa_compx, const char *who);
+
 // ---- what the bwa-mem stages share (mem_scan.hip; the device helpers: mem_common.h)
 // One exclusive scan over per-unit counts.  cnt holds nq quantities of n counts, n + 1 entries apart; each becomes its offsets
 // (entry n: the total) in place.  Three launches: a block scan, one block per quantity over the block sums, an offset pass.

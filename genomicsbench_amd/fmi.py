@@ -140,6 +140,68 @@ def build_index(ref, device=None, sa_compx=None):
     return idx.host() if dev.type == "cpu" else idx
 
 
+INFO_FIELDS = ("count0", "count1", "count2", "count3", "count4", "sentinel_index", "rounds", "first_round_slots")
+
+
+@N.declare_once
+def _build_lib(L):
+    """libgbx.so with the index-construction entries declared (raises if the library or the entries are missing)."""
+    vp, i64, i32, sz = C.c_void_p, C.c_int64, C.c_int32, C.c_size_t
+    L.gbx_fmi_build_workspace_bytes.argtypes = [i64]
+    L.gbx_fmi_build_workspace_bytes.restype = sz
+    L.gbx_fmi_build_device.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.gbx_fmi_build_host.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp]
+    L.gbx_fmi_build_rounds.argtypes = [vp, i32, C.POINTER(i32)]
+
+
+def build_workspace_bytes(l_pac):
+    """gbx_fmi_build_workspace_bytes: the device workspace of a native build (0 above the 32-bit limit)."""
+    return int(_build_lib().gbx_fmi_build_workspace_bytes(int(l_pac)))
+
+
+def build_index_native(ref, device=None, sa_compx=None, info=False):
+    """``build_index`` by the HIP builder (gbx_fmi_build_*: suffix array by prefix doubling on radix sorts, BWT, checkpoints and
+    samples on the device) - the same return values, byte for byte: an FmiIndex, or (FmiIndex, FmiSa) with sa_compx.  With a
+    device: torch tensors there, through gbx_fmi_build_device; without: numpy arrays, through gbx_fmi_build_host.  info=True
+    appends the dict of the entry's eight words (INFO_FIELDS)."""
+    L = _build_lib()
+    compx = 3 if sa_compx is None else int(sa_compx)
+    if device is None or str(device) == "cpu":
+        g = np.ascontiguousarray(ref.cpu().numpy() if hasattr(ref, "cpu") else ref, dtype=np.uint8)
+        n1 = 2 * len(g) + 1
+        cp = np.zeros((n1 >> 6) + 1, dtype=CP_OCC_DTYPE)
+        n_sa = FmiSa.n_sa_for(n1, compx) if compx in (0, 3) else 1
+        ms, ls = np.zeros(n_sa, dtype=np.int8), np.zeros(n_sa, dtype=np.uint32)
+        st, words = FmiIndexStruct(), np.zeros(8, dtype=np.int64)
+        N.check(L.gbx_fmi_build_host(N.ptr(g), len(g), compx, C.addressof(st), N.ptr(cp), N.ptr(ms), N.ptr(ls), N.ptr(words)))
+        idx, smp = FmiIndex(st.ref_seq_len, list(st.count), st.sentinel_index, cp), FmiSa(compx, ms, ls)
+    else:
+        import torch
+        dev = torch.device(device)
+        g = (ref if isinstance(ref, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(ref, dtype=np.uint8))).to(dev).contiguous()
+        if g.numel() and int(g.max().item()) > 3:
+            raise ValueError("base codes must be 0..3")
+        n1 = 2 * g.numel() + 1
+        n_sa = FmiSa.n_sa_for(n1, compx) if compx in (0, 3) else 1
+        cp = torch.empty(((n1 >> 6) + 1) * 64, dtype=torch.uint8, device=dev)
+        ms = torch.empty(n_sa, dtype=torch.uint8, device=dev)
+        ls = torch.empty(n_sa, dtype=torch.int32, device=dev)
+        words = torch.zeros(8, dtype=torch.int64, device=dev)
+        wb = build_workspace_bytes(g.numel())
+        work = torch.empty(max(wb, 1), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            N.check(L.gbx_fmi_build_device(g.data_ptr(), g.numel(), compx, cp.data_ptr(), ms.data_ptr(), ls.data_ptr(), None, words.data_ptr(),
+                                           work.data_ptr(), wb, torch.cuda.current_stream().cuda_stream))
+            torch.cuda.current_stream().synchronize()
+        del work
+        words = words.cpu().numpy()
+        idx, smp = FmiIndex(n1, words[:5], words[5], cp), FmiSa(compx, ms, ls)
+    out = (idx, smp) if sa_compx is not None else (idx,)
+    if info:
+        out += (dict(zip(INFO_FIELDS, (int(x) for x in words))),)
+    return out if len(out) > 1 else out[0]
+
+
 class FmiSaStruct(C.Structure):          # gbx_fmi_sa
     _fields_ = [("sa_compx", C.c_int32), ("n_sa", C.c_int64), ("ms_byte", C.c_void_p), ("ls_word", C.c_void_p)]
 

@@ -72,6 +72,7 @@ def lib(L):
     L.gbx_mem_align_check_params.argtypes = [PP]
     L.gbx_mem_align_plan.argtypes = [PP, i64, i64, i32, i64, PN, i64, PC]
     L.gbx_mem_index_create.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, C.POINTER(vp)]
+    L.gbx_mem_index_build.argtypes = [vp, i64, i32, vp, vp, vp, C.POINTER(vp)]
     L.gbx_mem_index_destroy.argtypes = [vp]
     L.gbx_mem_index_destroy.restype = None
     L.gbx_mem_sam_header.argtypes = [vp, vp, i64, C.POINTER(i64)]
@@ -173,6 +174,22 @@ class MemIndex:
         N.check(lib().gbx_mem_index_create(C.addressof(st), C.addressof(sst), N.ptr(text), self.l_pac, len(co) - 1, N.ptr(co),
                                            N.ptr(cn) if len(cn) else None, N.ptr(cno), C.byref(h)))
         self.handle = h
+
+    @classmethod
+    def build(cls, genome, contig_off, contig_names):
+        """gbx_mem_index_build: the same index from the genome alone, built on the device (sa_compx 3); nothing of it comes back to
+        the host."""
+        g = np.ascontiguousarray(genome, dtype=np.uint8)
+        co = np.ascontiguousarray(contig_off, dtype=np.int64)
+        cn, cno = SM.arena(contig_names)
+        self = cls.__new__(cls)
+        self.handle = None
+        self.l_pac, self.contig_off, self.contig_names = len(g), co, [x.decode() if isinstance(x, bytes) else str(x) for x in contig_names]
+        h = C.c_void_p()
+        N.check(lib().gbx_mem_index_build(N.ptr(g) if len(g) else None, len(g), len(co) - 1, N.ptr(co), N.ptr(cn) if len(cn) else None, N.ptr(cno),
+                                          C.byref(h)))
+        self.handle = h
+        return self
 
     def header(self):
         """gbx_mem_sam_header: the @SQ lines as bytes."""

@@ -654,6 +654,28 @@ int gbx_fmi_sal_device(const gbx_fmi_index *idx, const void *d_index, const gbx_
 /* LF steps of the last gbx_fmi_sal_device call on this workspace: their total and the longest walk of one hit. */
 int gbx_fmi_sal_steps(const void *d_work, int64_t *steps, int64_t *max_steps, void *stream);
 
+/* ---- building the index on the device (the job of `bwa-mem2 index`).  genome: l_pac base codes 0..3 of one strand.
+ * The text is the strand and its reverse complement, n = 2 l_pac symbols; its n + 1 suffixes include the empty one, which sorts
+ * first.  Suffix array by prefix doubling on radix sorts, then the BWT, the checkpoints and the samples: count[], sentinel_index,
+ * the (ref_seq_len >> 6) + 1 CP_OCC records (rows past the end match no base) and SA[i << sa_compx] split into ms_byte / ls_word
+ * (rows past the end: 0), n_sa as in gbx_fmi_sa.  Positions and ranks are 32-bit: 2 l_pac + 1 <= 2^32 - 1, i.e. l_pac <=
+ * 2147483647; above it every entry returns GBX_ERR_UNSUPPORTED (gbx_fmi_build_workspace_bytes: 0).  Checked on the host before
+ * any device work, GBX_ERR_ARG naming the lowest offender: null pointers, l_pac < 1, sa_compx other than 3 or 0, a base code
+ * above 3 (host entries; the device entry's contract), a workspace below gbx_fmi_build_workspace_bytes(l_pac).
+ * The workspace is about 38.7 bytes per text symbol (DESIGN 3.17 has the formula).
+ * info: int64[8] = count[0..4], sentinel_index, doubling rounds run, slots the first round had to sort.
+ * The device entry reads one count per doubling round, so it synchronises the stream; it returns with all work queued. */
+size_t gbx_fmi_build_workspace_bytes(int64_t l_pac);
+int gbx_fmi_build_device(const uint8_t *d_genome, int64_t l_pac, int32_t sa_compx, void *d_cp_occ, int8_t *d_ms, uint32_t *d_ls,
+                         uint8_t *d_text /* 2 l_pac bytes out, may be null */, int64_t *d_info, void *d_work, size_t work_bytes, void *stream);
+/* The slots each doubling round of the calling thread's last build (any entry) sorted: *n_rounds of them, the first cap into
+ * slots.  For measurements (scripts/time_mem_index.py). */
+int gbx_fmi_build_rounds(int64_t *slots, int32_t cap, int32_t *n_rounds);
+/* Host buffers in and out; fills idx->ref_seq_len, count, sentinel_index, idx->cp_occ = cp_occ and the caller's cp_occ / ms / ls
+ * arrays.  info: the eight words, may be null.  Safe under concurrent host threads. */
+int gbx_fmi_build_host(const uint8_t *genome, int64_t l_pac, int32_t sa_compx, gbx_fmi_index *idx, gbx_fmi_cp_occ *cp_occ,
+                       int8_t *ms, uint32_t *ls, int64_t *info);
+
 /* ---- seed chaining (bwa-mem's mem_chain, mem_chain_flt and the window of mem_chain2aln: the step between the suffix-array
  * lookup and gbx_bsw_extend_seeds_*).  UNPINNED by a compiled reference (bwa's source is not part of the reference tree):
  * the rules are restated in full in DESIGN 3.10 and tests/mem_chain_ref.py, and pinned by that restatement.
@@ -1344,6 +1366,11 @@ int gbx_mem_align_plan(const gbx_mem_align_params *p, int64_t n_reads, int64_t b
  * the contig table and names.  idx->cp_occ, sa->ms_byte, sa->ls_word, text, contig_off, cnames, cname_off: HOST pointers. */
 int gbx_mem_index_create(const gbx_fmi_index *idx, const gbx_fmi_sa *sa, const uint8_t *text, int64_t l_pac, int32_t n_contigs,
                          const int64_t *contig_off, const uint8_t *cnames, const int64_t *cname_off, gbx_mem_index **out);
+/* The same index from the genome alone (host pointers): built on the device with sa_compx 3 (gbx_fmi_build_device) and handed to
+ * the same layout passes, so nothing of the index crosses to the host.  Limits and checks as gbx_fmi_build_host and
+ * gbx_mem_index_create. */
+int gbx_mem_index_build(const uint8_t *genome, int64_t l_pac, int32_t n_contigs, const int64_t *contig_off,
+                        const uint8_t *cnames, const int64_t *cname_off, gbx_mem_index **out);
 void gbx_mem_index_destroy(gbx_mem_index *index);
 /* The @SQ lines, one per contig.  *need = their bytes; GBX_ERR_ARG when cap is less (nothing is written). */
 int gbx_mem_sam_header(const gbx_mem_index *index, uint8_t *buf, int64_t cap, int64_t *need);
