@@ -13,6 +13,7 @@ import numpy as np
 from . import _native as N
 from .bsw_seeds import SEED_DTYPE
 from .fmi import SMEM_DTYPE
+from .mem_stage import Batch, CigarList, Seeds
 
 CHAIN_DTYPE = np.dtype([("pos", "<i8"), ("seed_off", "<i8"), ("rmax0", "<i8"), ("rmax1", "<i8"), ("read", "<i4"),
                         ("contig", "<i4"), ("n_seeds", "<i4"), ("weight", "<i4"), ("kept", "<i4"), ("pad_", "<i4")])
@@ -140,7 +141,9 @@ class DeviceMemChain:
 
 
 class DeviceSeedExtension:
-    """gbx_bsw_extend_seeds_device on a DeviceMemChain's seed tensor: run(seed_params, stream), results()."""
+    """gbx_bsw_extend_seeds_device on a DeviceMemChain's seed tensor: run(seed_params, stream), results().  It owns the padded
+    arenas, so it makes the ``mem_stage.Batch`` the later stages carry on; ``seeds`` and ``cigar_input`` are the chaining's
+    seed records, the latter with this object's results."""
 
     def __init__(self, chain, text, n):
         import torch
@@ -158,6 +161,11 @@ class DeviceSeedExtension:
         self.out = torch.empty((max(self.n, 1), 8), dtype=torch.int32, device=dev)
         self.work_bytes = BS.lib().gbx_bsw_seeds_workspace_bytes(self.n, self.ref_bytes, self.qer_bytes)
         self.work = torch.empty(max(self.work_bytes, 1), dtype=torch.uint8, device=dev)
+        f = chain.fmi
+        self.batch = Batch(dev, chain.n_reads, self.qer, self.qer_bytes, f.read_off, f.read_len, self.ref, self.ref_bytes, chain.l_pac,
+                           chain.n_contigs, chain.contig_off)
+        self.seeds = Seeds(chain.seeds, chain.seed_cap, chain.l_rep)
+        self.cigar_input = CigarList(self.batch, chain.seeds, self.out, self.n)
 
     def run(self, seed_params, stream=None):
         N.check(self._bs.lib().gbx_bsw_extend_seeds_device(C.byref(seed_params), self.n, self.ref.data_ptr(), self.ref_bytes,

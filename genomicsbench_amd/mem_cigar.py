@@ -12,6 +12,7 @@ import numpy as np
 from . import _native as N
 from .bsw_seeds import SEED_DTYPE
 from .mem_chain import one_contig
+from .mem_stage import CigarList
 
 ALN_DTYPE = np.dtype([("pos", "<i8"), ("cigar_off", "<i8"), ("rid", "<i4"), ("is_rev", "<i4"), ("n_cigar", "<i4"), ("nm", "<i4"),
                       ("score", "<i4"), ("w", "<i4"), ("tries", "<i4"), ("pad_", "<i4")])
@@ -93,20 +94,19 @@ def cigar_host(params, seeds, res, text, qer, l_pac, contig_off=None, cigar_cap=
 
 
 class DeviceMemCigar:
-    """gbx_mem_cigar_device behind a ``mem_chain.DeviceSeedExtension``: its seed tensor, result tensor and arenas are used as
-    they are (no copy).  run(stream) can be queued behind the extension's run() on the same stream; n defaults to the
-    extension's n, so no count is needed.  z_bytes: the direction room (default: n records of the longest read against a
-    window as long)."""
+    """gbx_mem_cigar_device on a ``mem_stage.CigarList`` (a stage's ``cigar_input``) or behind a
+    ``mem_chain.DeviceSeedExtension``, which stands for its own: the seed tensor, result tensor and arenas are used as they are
+    (no copy).  run(stream) can be queued behind that stage's run() on the same stream; n defaults to the list's n, so no
+    count is needed.  z_bytes: the direction room (default: n records of the longest read against a window as long)."""
 
     def __init__(self, ext, params=None, n=None, cigar_cap=None, z_bytes=None, max_read_len=151):
         import torch
-        self.ext = ext
+        lst = self.list = ext if isinstance(ext, CigarList) else ext.cigar_input
+        self.batch = lst.batch
         self.params = params or make_params()
-        ch = ext.chain
-        dev = ch.device
-        self.device = dev
-        self.n = int(ext.n if n is None else n)
-        assert 0 <= self.n <= ext.n
+        dev = self.device = lst.batch.device
+        self.n = int(lst.n if n is None else n)
+        assert 0 <= self.n <= lst.n
         self.cigar_cap = int(cigar_cap if cigar_cap is not None else 8 * max(self.n, 1))
         if z_bytes is None:
             z_bytes = self.n * lib().gbx_mem_cigar_record_z_bytes(C.byref(self.params), max_read_len, 2 * max_read_len)
@@ -119,10 +119,10 @@ class DeviceMemCigar:
 
     def run(self, stream=None):
         """Asynchronous on `stream` (a raw hipStream_t handle or None)."""
-        e, ch = self.ext, self.ext.chain
+        lst, b = self.list, self.batch
         N.check(lib().gbx_mem_cigar_device(
-            C.byref(self.params), self.n, ch.seeds.data_ptr(), e.out.data_ptr(), e.ref.data_ptr(), e.ref_bytes, e.qer.data_ptr(),
-            e.qer_bytes, ch.l_pac, ch.n_contigs, ch.contig_off.data_ptr(), self.alns.data_ptr(), self.cigar.data_ptr(),
+            C.byref(self.params), self.n, lst.seeds.data_ptr(), lst.res.data_ptr(), b.ref.data_ptr(), b.ref_bytes, b.qer.data_ptr(),
+            b.qer_bytes, b.l_pac, b.n_contigs, b.contig_off.data_ptr(), self.alns.data_ptr(), self.cigar.data_ptr(),
             self.cigar_cap, self.n_cigar.data_ptr(), self.work.data_ptr(), self.work_bytes, stream))
 
     def results(self):

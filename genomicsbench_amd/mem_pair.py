@@ -13,7 +13,8 @@ import numpy as np
 from . import _native as N
 from .bsw_seeds import SEED_DTYPE
 from .mem_cigar import cigar_string
-from .mem_regs import FLAG_REPORTED, FLAG_SUPPLEMENTARY, REG_DTYPE, _SelExtension, _results
+from .mem_regs import FLAG_REPORTED, FLAG_SUPPLEMENTARY, REG_DTYPE, _results
+from .mem_stage import CigarList, Regions
 
 PESTAT_DTYPE = np.dtype([("low", "<i4"), ("high", "<i4"), ("failed", "<i4"), ("pad_", "<i4"), ("avg", "<f8"), ("std", "<f8")])
 PAIR_DTYPE = np.dtype([("dist", "<i8"), ("score", "<i4"), ("sub", "<i4"), ("n_sub", "<i4"), ("n_cand", "<i4"), ("z0", "<i4"), ("z1", "<i4"),
@@ -94,40 +95,40 @@ def pair_host(params, regs, reg_off, sel_seeds, sel_res, seeds, l_rep, l_pac, co
 
 
 class DeviceMemPair:
-    """gbx_mem_pair_device behind a ``mem_regs.DeviceMemRegs`` that was made with read_id0 = 2 * pair_id0 for interleaved reads:
-    its regions, reg_off, counts and CIGAR list and the chaining's seeds and l_rep are used where they are.  run(stream) can be
-    queued behind the regs stage's run() on the same stream; no count is read on the host.  ``cigar_input`` has the attributes
-    ``mem_cigar.DeviceMemCigar`` reads of an extension, so ``DeviceMemCigar(pair.cigar_input)`` aligns the new list (psel_cap
-    records, the tail being no records)."""
+    """gbx_mem_pair_device behind a ``mem_regs.DeviceMemRegs`` or a ``mem_rescue.DeviceMemRescue`` that was made with read_id0 =
+    2 * pair_id0 for interleaved reads: that stage's ``regions``, ``cigar_input`` and ``seeds`` records are used where they are.
+    run(stream) can be queued behind that stage's run() on the same stream; no count is read on the host.  Its outputs as
+    ``mem_stage`` records: ``regions`` (the same list with the decision's changes), ``pairs``, ``cigar_input``
+    (``DeviceMemCigar(pair.cigar_input)`` aligns the new list: psel_cap records, the tail being no records), ``batch``."""
 
     def __init__(self, regs_stage, params=None, pes_in=None, psel_cap=None):
         import torch
-        rg = self.regs_stage = regs_stage
-        ch = rg.ext.chain
-        assert rg.n_reads % 2 == 0 and rg.read_id0 % 2 == 0, "interleaved pairs, read_id0 = 2 * pair_id0"
+        b, rg, sel = regs_stage.batch, regs_stage.regions, regs_stage.cigar_input
+        self.batch, self.input, self.sel, self.seeds = b, rg, sel, regs_stage.seeds
+        assert b.n_reads % 2 == 0 and rg.read_id0 % 2 == 0, "interleaved pairs, read_id0 = 2 * pair_id0"
         self.params = params or make_params()
         self.pes_in = pestat_records(pes_in)
-        self.n_pairs, self.pair_id0 = rg.n_reads // 2, rg.read_id0 // 2
-        dev = self.device = rg.device
-        self.psel_cap = int(rg.sel_cap if psel_cap is None else psel_cap)
+        self.n_pairs, self.pair_id0 = b.n_reads // 2, rg.read_id0 // 2
+        dev = self.device = b.device
+        self.psel_cap = int(sel.n if psel_cap is None else psel_cap)
         self.pes = torch.zeros(4 * PESTAT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         self.pairs = torch.zeros(max(self.n_pairs, 1) * PAIR_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        self.pregs = torch.zeros(max(rg.reg_cap, 1) * REG_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self.pregs = torch.zeros(max(rg.cap, 1) * REG_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         self.psel_seeds = torch.zeros(max(self.psel_cap, 1) * SEED_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         self.psel_res = torch.full((max(self.psel_cap, 1), 8), -1, dtype=torch.int32, device=dev)
         self.count = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.work_bytes = lib().gbx_mem_pair_workspace_bytes(self.n_pairs, rg.reg_cap, self.params.max_ins)
+        self.work_bytes = lib().gbx_mem_pair_workspace_bytes(self.n_pairs, rg.cap, self.params.max_ins)
         self.work = torch.empty(max(self.work_bytes, 1), dtype=torch.uint8, device=dev)
-        self.cigar_input = _SelExtension(rg.ext, self.psel_seeds, self.psel_res, self.psel_cap)
-        self._chain = ch
+        self.regions = Regions(self.pregs, rg.reg_off, rg.count, rg.cap, rg.read_id0)
+        self.cigar_input = CigarList(b, self.psel_seeds, self.psel_res, self.psel_cap)
 
     def run(self, stream=None):
         """Asynchronous on `stream` (a raw hipStream_t handle or None)."""
-        rg, ch = self.regs_stage, self._chain
+        b, rg, sel, sd = self.batch, self.input, self.sel, self.seeds
         N.check(lib().gbx_mem_pair_device(
-            C.byref(self.params), self.n_pairs, self.pair_id0, rg.regs.data_ptr(), rg.reg_off.data_ptr(), rg.counts.data_ptr(), rg.reg_cap,
-            rg.sel_seeds.data_ptr(), rg.sel_res.data_ptr(), rg.sel_cap, ch.seeds.data_ptr(), ch.seed_cap, ch.l_rep.data_ptr(),
-            ch.l_pac, ch.n_contigs, ch.contig_off.data_ptr(), N.ptr(self.pes_in), self.pes.data_ptr(), self.pairs.data_ptr(),
+            C.byref(self.params), self.n_pairs, self.pair_id0, rg.regs.data_ptr(), rg.reg_off.data_ptr(), rg.count.data_ptr(), rg.cap,
+            sel.seeds.data_ptr(), sel.res.data_ptr(), sel.n, sd.seeds.data_ptr(), sd.cap, sd.l_rep.data_ptr(),
+            b.l_pac, b.n_contigs, b.contig_off.data_ptr(), N.ptr(self.pes_in), self.pes.data_ptr(), self.pairs.data_ptr(),
             self.pregs.data_ptr(), self.psel_seeds.data_ptr(), self.psel_res.data_ptr(), self.psel_cap, self.count.data_ptr(),
             self.work.data_ptr(), self.work_bytes, stream))
 
@@ -139,7 +140,7 @@ class DeviceMemPair:
             raise RuntimeError("mem pair: a stage before it overflowed its capacities")
         if n > self.psel_cap:
             raise RuntimeError("mem pair: %d reported regions do not fit psel_cap = %d" % (n, self.psel_cap))
-        nr = int(self.regs_stage.counts[0].item())
+        nr = int(self.input.count.item())
         return dict(pes=self.pes.cpu().numpy().view(PESTAT_DTYPE).copy(),
                     pairs=self.pairs[:self.n_pairs * PAIR_DTYPE.itemsize].cpu().numpy().view(PAIR_DTYPE).copy(),
                     pregs=self.pregs[:nr * REG_DTYPE.itemsize].cpu().numpy().view(REG_DTYPE).copy(),

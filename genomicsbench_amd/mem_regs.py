@@ -14,6 +14,7 @@ from . import _native as N
 from .bsw_seeds import SEED_DTYPE
 from .mem_chain import CHAIN_DTYPE
 from .mem_cigar import cigar_string
+from .mem_stage import CigarList, Regions
 
 REG_DTYPE = np.dtype([("rb", "<i8"), ("re", "<i8"), ("seed", "<i8"), ("qb", "<i4"), ("qe", "<i4"), ("read", "<i4"), ("rid", "<i4"),
                       ("score", "<i4"), ("truesc", "<i4"), ("sub", "<i4"), ("sub_n", "<i4"), ("w", "<i4"), ("seedcov", "<i4"),
@@ -81,38 +82,21 @@ def regs_host(params, chains, chain_off, seeds, res, l_rep, read_id0=0, reg_cap=
                 n_sel=int(ns.value))
 
 
-class _SelChain:
-    """What DeviceMemCigar reads of a DeviceMemChain, with the CIGAR list's seed tensor in the place of all seeds."""
-
-    def __init__(self, chain, seeds, cap):
-        self.seeds, self.seed_cap = seeds, cap
-        self.device, self.l_pac, self.n_contigs, self.contig_off, self.fmi = chain.device, chain.l_pac, chain.n_contigs, chain.contig_off, chain.fmi
-
-
-class _SelExtension:
-    """What DeviceMemCigar reads of a DeviceSeedExtension: chain.seeds, out, n and the arenas (shared, no copy)."""
-
-    def __init__(self, ext, seeds, out, n):
-        self.chain = _SelChain(ext.chain, seeds, n)
-        self.out, self.n = out, n
-        self.ref, self.ref_bytes, self.qer, self.qer_bytes = ext.ref, ext.ref_bytes, ext.qer, ext.qer_bytes
-
-
 class DeviceMemRegs:
     """gbx_mem_regs_device behind a ``mem_chain.DeviceSeedExtension``: the chaining's chains, seeds, counts and l_rep and the
     extension's results are used where they are.  run(stream) can be queued behind the extension's run() on the same stream; no
-    count is read on the host.  ``cigar_input`` has the attributes ``mem_cigar.DeviceMemCigar`` reads of an extension, so
-    ``DeviceMemCigar(regs.cigar_input)`` aligns the reported regions (sel_cap records, the tail being no records)."""
+    count is read on the host.  Its outputs as ``mem_stage`` records: ``regions``, ``seeds`` (the chaining's, carried on),
+    ``cigar_input`` (``DeviceMemCigar(regs.cigar_input)`` aligns the reported regions: sel_cap records, the tail being no
+    records), ``batch``; ``pairs`` is None: the reads are single."""
+    pairs = None
 
     def __init__(self, ext, params=None, read_id0=0, reg_cap=None, sel_cap=None):
         import torch
-        self.ext = ext
-        ch = ext.chain
+        self.ext, self.chain, self.batch, self.seeds = ext, ext.chain, ext.batch, ext.seeds
         self.params = params or make_params()
         self.read_id0 = int(read_id0)
-        dev = ch.device
-        self.device = dev
-        self.n_reads = ch.n_reads
+        dev = self.device = self.batch.device
+        self.n_reads = self.batch.n_reads
         self.seed_cap = int(ext.n)                   # the seeds the extension answered for
         self.reg_cap = int(self.seed_cap if reg_cap is None else reg_cap)
         self.sel_cap = int(self.seed_cap if sel_cap is None else sel_cap)
@@ -123,11 +107,12 @@ class DeviceMemRegs:
         self.counts = torch.zeros(2, dtype=torch.int64, device=dev)
         self.work_bytes = lib().gbx_mem_regs_workspace_bytes(self.n_reads, self.seed_cap)
         self.work = torch.empty(max(self.work_bytes, 1), dtype=torch.uint8, device=dev)
-        self.cigar_input = _SelExtension(ext, self.sel_seeds, self.sel_res, self.sel_cap)
+        self.regions = Regions(self.regs, self.reg_off, self.counts[:1], self.reg_cap, self.read_id0)
+        self.cigar_input = CigarList(self.batch, self.sel_seeds, self.sel_res, self.sel_cap)
 
     def run(self, stream=None):
         """Asynchronous on `stream` (a raw hipStream_t handle or None)."""
-        e, ch = self.ext, self.ext.chain
+        e, ch = self.ext, self.chain
         N.check(lib().gbx_mem_regs_device(
             C.byref(self.params), self.n_reads, self.read_id0, ch.chains.data_ptr(), ch.counts.data_ptr(), ch.chain_cap,
             ch.chain_off.data_ptr(), ch.seeds.data_ptr(), ch.counts.data_ptr() + 8, self.seed_cap, e.out.data_ptr(),

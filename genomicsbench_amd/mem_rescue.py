@@ -5,8 +5,8 @@ regions before the rescue.
 Input: the regs stage's output for 2 n_pairs interleaved reads, made with read_id0 = 2 pair_id0, and four PESTAT_DTYPE records.
 Output: the same region lists in the regs stage's shape with the rescued regions added (REG_DTYPE: the regs stage's record with
 its last field named csub), the seed records with one more per surviving rescued region, the new CIGAR list, and a STAT_DTYPE
-record per pair.  ``DeviceMemRescue`` stands where a ``DeviceMemRegs`` stands for ``mem_pair.DeviceMemPair``; ``pipeline`` queues
-regs -> pestat -> rescue -> pair -> cigar on one stream.
+record per pair.  ``DeviceMemRescue`` hands ``mem_pair.DeviceMemPair`` the records a ``DeviceMemRegs`` hands it; ``pipeline``
+queues regs -> pestat -> rescue -> pair -> cigar on one stream.
 """
 import ctypes as C
 
@@ -17,7 +17,8 @@ from . import mem_pair as MP
 from . import mem_regs as MR
 from .bsw_seeds import SEED_DTYPE
 from .mem_pair import PESTAT_DTYPE, pestat_records
-from .mem_regs import _SelExtension, _results
+from .mem_regs import _results
+from .mem_stage import CigarList, Regions, Seeds
 
 REG_DTYPE = np.dtype([(n if n != "pad_" else "csub", t) for n, t in MR.REG_DTYPE.descr])
 STAT_DTYPE = np.dtype([("n_sw", "<i4"), ("n_added", "<i4"), ("n_kept", "<i4"), ("pad_", "<i4")])
@@ -111,75 +112,59 @@ def rescue_host(params, regs, reg_off, seeds, l_rep, read_off, read_len, text, q
                 xsel_seeds=xsel_seeds[:scap], xsel_res=xsel_res[:scap], n_xsel=int(ns.value), stats=stats[:n_pairs])
 
 
-class _XChain:
-    """What DeviceMemPair and DeviceMemCigar read of a DeviceMemChain, with the rescue stage's seed records in the place of the
-    chaining's."""
-
-    def __init__(self, chain, seeds, cap):
-        self.seeds, self.seed_cap = seeds, cap
-        self.device, self.l_pac, self.n_contigs, self.contig_off, self.fmi = chain.device, chain.l_pac, chain.n_contigs, chain.contig_off, chain.fmi
-        self.l_rep = chain.l_rep
-
-
-class _XExtension:
-    def __init__(self, ext, chain):
-        self.chain = chain
-        self.ref, self.ref_bytes, self.qer, self.qer_bytes = ext.ref, ext.ref_bytes, ext.qer, ext.qer_bytes
-
-
 class DeviceMemRescue:
     """gbx_mem_pestat_device and gbx_mem_rescue_device behind a ``mem_regs.DeviceMemRegs`` that was made with read_id0 =
-    2 * pair_id0 for interleaved reads.  run(stream) queues both behind the regs stage's run(); no count is read on the host.  The
-    object has the attributes ``mem_pair.DeviceMemPair`` reads of a regs stage (regs, reg_off, counts, reg_cap, the CIGAR list,
-    ext.chain with the new seed records), so ``DeviceMemPair(rescue, pes_in=rescue.pes_host(stream))`` follows; that is the one
-    128-byte copy and synchronisation the paired stage's host pointer costs."""
+    2 * pair_id0 for interleaved reads.  run(stream) queues both behind the regs stage's run(); no count is read on the host.  Its
+    outputs as ``mem_stage`` records are a regs stage's: ``regions``, ``seeds`` (with the new seed records), ``cigar_input``,
+    ``batch``, and ``pairs`` None, so ``DeviceMemPair(rescue, pes_in=rescue.pes_host(stream))`` follows; that is the one 128-byte
+    copy and synchronisation the paired stage's host pointer costs."""
+    pairs = None
 
     def __init__(self, regs_stage, params=None, pair_params=None, pes=None, xreg_cap=None, xseed_cap=None, xsel_cap=None):
         import torch
-        rg = self.regs_stage = regs_stage
-        ch = rg.ext.chain
-        assert rg.n_reads % 2 == 0 and rg.read_id0 % 2 == 0, "interleaved pairs, read_id0 = 2 * pair_id0"
+        b, rg, sd = self.batch, self.input, self.input_seeds = regs_stage.batch, regs_stage.regions, regs_stage.seeds
+        assert b.n_reads % 2 == 0 and rg.read_id0 % 2 == 0, "interleaved pairs, read_id0 = 2 * pair_id0"
         self.params = params or make_params()
         self.pair_params = pair_params or MP.make_params()
-        self.n_reads, self.read_id0 = rg.n_reads, rg.read_id0
-        self.n_pairs, self.pair_id0 = rg.n_reads // 2, rg.read_id0 // 2
-        dev = self.device = rg.device
-        extra = most_added(self.n_pairs, rg.reg_cap, self.params.max_matesw)
-        self.reg_cap = int(rg.reg_cap + extra if xreg_cap is None else xreg_cap)
-        self.seed_cap = int(ch.seed_cap + extra if xseed_cap is None else xseed_cap)
-        self.sel_cap = int(rg.reg_cap + extra if xsel_cap is None else xsel_cap)
+        self.n_reads, self.read_id0 = b.n_reads, rg.read_id0
+        self.n_pairs, self.pair_id0 = b.n_reads // 2, rg.read_id0 // 2
+        dev = self.device = b.device
+        extra = most_added(self.n_pairs, rg.cap, self.params.max_matesw)
+        self.reg_cap = int(rg.cap + extra if xreg_cap is None else xreg_cap)
+        self.seed_cap = int(sd.cap + extra if xseed_cap is None else xseed_cap)
+        self.sel_cap = int(rg.cap + extra if xsel_cap is None else xsel_cap)
         self.given = pestat_records(pes)
         self.pes = torch.zeros(4 * PESTAT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         if self.given is not None:
             self.pes.copy_(torch.from_numpy(self.given.view(np.uint8).copy()))
         self.regs = torch.zeros(max(self.reg_cap, 1) * REG_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         self.reg_off = torch.zeros(self.n_reads + 1, dtype=torch.int64, device=dev)
-        self.seeds = torch.zeros(max(self.seed_cap, 1) * SEED_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self.seed_recs = torch.zeros(max(self.seed_cap, 1) * SEED_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         self.sel_seeds = torch.zeros(max(self.sel_cap, 1) * SEED_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         self.sel_res = torch.full((max(self.sel_cap, 1), 8), -1, dtype=torch.int32, device=dev)
         self.stats = torch.zeros(max(self.n_pairs, 1) * STAT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         self.counts = torch.zeros(3, dtype=torch.int64, device=dev)          # regions, reported regions, seed records
-        self.work_bytes = lib().gbx_mem_rescue_workspace_bytes(self.n_pairs, rg.reg_cap, self.params.max_matesw)
+        self.work_bytes = lib().gbx_mem_rescue_workspace_bytes(self.n_pairs, rg.cap, self.params.max_matesw)
         self.work = torch.empty(max(self.work_bytes, 1), dtype=torch.uint8, device=dev)
         self.pes_work_bytes = lib().gbx_mem_pestat_workspace_bytes(self.pair_params.max_ins)
         self.pes_work = torch.empty(max(self.pes_work_bytes, 1), dtype=torch.uint8, device=dev)
-        self.ext = _XExtension(rg.ext, _XChain(ch, self.seeds, self.seed_cap))
-        self.cigar_input = _SelExtension(self.ext, self.sel_seeds, self.sel_res, self.sel_cap)
+        self.regions = Regions(self.regs, self.reg_off, self.counts[:1], self.reg_cap, self.read_id0)
+        self.seeds = Seeds(self.seed_recs, self.seed_cap, sd.l_rep)
+        self.cigar_input = CigarList(b, self.sel_seeds, self.sel_res, self.sel_cap)
 
     def run(self, stream=None):
         """Asynchronous on `stream` (a raw hipStream_t handle or None)."""
-        rg, e = self.regs_stage, self.regs_stage.ext
-        ch, f = e.chain, e.chain.fmi
+        b, rg, sd = self.batch, self.input, self.input_seeds
         if self.given is None:
             N.check(lib().gbx_mem_pestat_device(C.byref(self.pair_params), self.n_pairs, rg.regs.data_ptr(), rg.reg_off.data_ptr(),
-                                                rg.counts.data_ptr(), rg.reg_cap, ch.l_pac, self.pes.data_ptr(), self.pes_work.data_ptr(),
+                                                rg.count.data_ptr(), rg.cap, b.l_pac, self.pes.data_ptr(), self.pes_work.data_ptr(),
                                                 self.pes_work_bytes, stream))
         c = self.counts.data_ptr()
         N.check(lib().gbx_mem_rescue_device(
-            C.byref(self.params), self.n_pairs, self.pair_id0, rg.regs.data_ptr(), rg.reg_off.data_ptr(), rg.counts.data_ptr(), rg.reg_cap,
-            ch.seeds.data_ptr(), ch.seed_cap, ch.l_rep.data_ptr(), f.read_off.data_ptr(), f.read_len.data_ptr(), e.ref.data_ptr(),
-            e.ref_bytes, e.qer.data_ptr(), e.qer_bytes, ch.l_pac, ch.n_contigs, ch.contig_off.data_ptr(), self.pes.data_ptr(),
-            self.regs.data_ptr(), self.reg_cap, self.reg_off.data_ptr(), c, self.seeds.data_ptr(), self.seed_cap, c + 16,
+            C.byref(self.params), self.n_pairs, self.pair_id0, rg.regs.data_ptr(), rg.reg_off.data_ptr(), rg.count.data_ptr(), rg.cap,
+            sd.seeds.data_ptr(), sd.cap, sd.l_rep.data_ptr(), b.read_off.data_ptr(), b.read_len.data_ptr(), b.ref.data_ptr(),
+            b.ref_bytes, b.qer.data_ptr(), b.qer_bytes, b.l_pac, b.n_contigs, b.contig_off.data_ptr(), self.pes.data_ptr(),
+            self.regs.data_ptr(), self.reg_cap, self.reg_off.data_ptr(), c, self.seed_recs.data_ptr(), self.seed_cap, c + 16,
             self.sel_seeds.data_ptr(), self.sel_res.data_ptr(), self.sel_cap, c + 8, self.stats.data_ptr(), self.work.data_ptr(),
             self.work_bytes, stream))
 
@@ -203,7 +188,7 @@ class DeviceMemRescue:
                                (nr, ns, nk, self.reg_cap, self.sel_cap, self.seed_cap))
         return dict(pes=self.pes.cpu().numpy().view(PESTAT_DTYPE).copy(), xregs=self.regs[:nr * REG_DTYPE.itemsize].cpu().numpy().view(REG_DTYPE).copy(),
                     xreg_off=self.reg_off.cpu().numpy(), n_xregs=nr,
-                    xseeds=self.seeds[:self.seed_cap * SEED_DTYPE.itemsize].cpu().numpy().view(SEED_DTYPE).copy(), n_xseeds=nk,
+                    xseeds=self.seed_recs[:self.seed_cap * SEED_DTYPE.itemsize].cpu().numpy().view(SEED_DTYPE).copy(), n_xseeds=nk,
                     xsel_seeds=self.sel_seeds[:self.sel_cap * SEED_DTYPE.itemsize].cpu().numpy().view(SEED_DTYPE).copy(),
                     xsel_res=self.sel_res[:self.sel_cap].cpu().numpy(), n_xsel=ns,
                     stats=self.stats[:self.n_pairs * STAT_DTYPE.itemsize].cpu().numpy().view(STAT_DTYPE).copy())
@@ -212,20 +197,11 @@ class DeviceMemRescue:
 def pipeline(ext, stream=None, pair_id0=0, regs_params=None, rescue_params=None, pair_params=None, cigar_params=None, cigar_cap=None,
              z_bytes=None):
     """regs -> pestat -> rescue -> pair -> cigar on one stream behind a ``mem_chain.DeviceSeedExtension`` that has been queued on
-    it.  The estimate is read back once between the rescue and the paired stage (128 bytes, one synchronisation): the paired
-    stage takes it as a host pointer.  -> (regs, rescue, pair, cigar) stages, all queued; synchronise before results()."""
-    from . import mem_cigar as MG
-    rg = MR.DeviceMemRegs(ext, regs_params, read_id0=2 * int(pair_id0))
-    rg.run(stream)
-    rs = DeviceMemRescue(rg, rescue_params, pair_params)
-    rs.run(stream)
-    pe = MP.DeviceMemPair(rs, pair_params, pes_in=rs.pes_host(stream))
-    pe.run(stream)
-    kw = {}
-    if cigar_cap is not None:
-        kw["cigar_cap"] = cigar_cap
-    if z_bytes is not None:
-        kw["z_bytes"] = z_bytes
-    cg = MG.DeviceMemCigar(pe.cigar_input, cigar_params or MG.make_params(), **kw)
-    cg.run(stream)
-    return rg, rs, pe, cg
+    it (``mem_pipeline.Stages`` from "regs" to "cigar").  The estimate is read back once between the rescue and the paired stage
+    (128 bytes, one synchronisation): the paired stage takes it as a host pointer.  -> (regs, rescue, pair, cigar) stages, all
+    queued; synchronise before results()."""
+    from .mem_pipeline import Stages
+    caps = {k: v for k, v in (("cigar_cap", cigar_cap), ("z_bytes", z_bytes)) if v is not None}
+    st = Stages(ext=ext, id0=pair_id0, params=dict(regs=regs_params, rescue=rescue_params, pair=pair_params, cigar=cigar_params), caps=caps)
+    st.queue(stream, "regs", "cigar")
+    return st.regs, st.rescue, st.pair, st.cigar

@@ -118,7 +118,8 @@ def sam_host(params, mode, regs, reg_off, pairs, alns, cigar, qer, read_off, rea
 
 class DeviceMemSam:
     """gbx_mem_sam_device behind a ``mem_cigar.DeviceMemCigar`` that aligned the list of `stage`: a ``mem_pair.DeviceMemPair``
-    (mode 1) or a ``mem_regs.DeviceMemRegs`` / ``mem_rescue.DeviceMemRescue`` (mode 0).  names: one byte string per read; qual: a
+    (mode 1) or a ``mem_regs.DeviceMemRegs`` / ``mem_rescue.DeviceMemRescue`` (mode 0); the mode is whether the stage has
+    ``pairs``, and its ``regions`` and ``batch`` records are what is read of it.  names: one byte string per read; qual: a
     uint8 array at the reads' offsets in the read arena, or None; contig_names: one byte string per contig.  run(stream) can be
     queued behind the CIGAR stage's run() on the same stream; no count is read on the host.  The capacities default to
     gbx_mem_sam_text_cap for reads with at most max_recs records and deletions of at most max_del bases."""
@@ -126,30 +127,26 @@ class DeviceMemSam:
     def __init__(self, stage, cigar_stage, names, qual, contig_names, params=None, rec_cap=None, md_cap=None, text_cap=None, max_recs=8,
                  max_del=1024):
         import torch
-        self.stage, self.cigar_stage = stage, cigar_stage
-        self.mode = 1 if hasattr(stage, "pregs") else 0
-        self.regs_stage = stage.regs_stage if self.mode else stage
-        rg = self.regs_stage
-        self.regs = stage.pregs if self.mode else stage.regs
-        self.pairs = stage.pairs if self.mode else None
+        self.cigar_stage = cigar_stage
+        b, rg = self.batch, self.regions = stage.batch, stage.regions
+        self.pairs = stage.pairs
+        self.mode = 0 if self.pairs is None else 1
         self.params = params or make_params()
-        ch = rg.ext.chain
-        self.chain, self.ext = ch, rg.ext
-        dev = self.device = rg.device
-        self.n_reads = rg.n_reads
+        dev = self.device = b.device
+        self.n_reads = b.n_reads
         nm, no = arena(names)
         cn, cno = arena(contig_names)
-        assert len(no) == self.n_reads + 1 and len(cno) == ch.n_contigs + 1
+        assert len(no) == self.n_reads + 1 and len(cno) == b.n_contigs + 1
         t = lambda a: torch.from_numpy(a if len(a) else np.zeros(1, a.dtype)).to(dev)
         self.names, self.name_off, self.name_bytes = t(nm), t(no), len(nm)
         self.cnames, self.cname_off, self.cname_bytes = t(cn), t(cno), len(cn)
         self.qual = None
         if qual is not None:
             qual = np.ascontiguousarray(qual, dtype=np.uint8)
-            assert len(qual) == self.ext.qer_bytes
+            assert len(qual) == b.qer_bytes
             self.qual = t(qual)
-        self.rec_cap = int(self.n_reads + min(rg.reg_cap, cigar_stage.n) if rec_cap is None else rec_cap)
-        cap = lib().gbx_mem_sam_text_cap(self.rec_cap, cigar_stage.cigar_cap, self.ext.qer_bytes, len(nm), int(np.diff(cno).max()), max_recs, max_del)
+        self.rec_cap = int(self.n_reads + min(rg.cap, cigar_stage.n) if rec_cap is None else rec_cap)
+        cap = lib().gbx_mem_sam_text_cap(self.rec_cap, cigar_stage.cigar_cap, b.qer_bytes, len(nm), int(np.diff(cno).max()), max_recs, max_del)
         self.text_cap = int(cap if text_cap is None else text_cap)
         self.md_cap = int(self.text_cap if md_cap is None else md_cap)
         self.recs = torch.zeros(max(self.rec_cap, 1) * SAM_DTYPE.itemsize, dtype=torch.uint8, device=dev)
@@ -157,19 +154,19 @@ class DeviceMemSam:
         self.md = torch.zeros(max(self.md_cap, 1), dtype=torch.uint8, device=dev)
         self.lines = torch.zeros(max(self.text_cap, 1), dtype=torch.uint8, device=dev)
         self.counts = torch.zeros(3, dtype=torch.int64, device=dev)           # records, md bytes, text bytes
-        self.work_bytes = lib().gbx_mem_sam_workspace_bytes(self.n_reads, rg.reg_cap, cigar_stage.n)
+        self.work_bytes = lib().gbx_mem_sam_workspace_bytes(self.n_reads, rg.cap, cigar_stage.n)
         self.work = torch.empty(max(self.work_bytes, 1), dtype=torch.uint8, device=dev)
 
     def run(self, stream=None):
         """Asynchronous on `stream` (a raw hipStream_t handle or None)."""
-        rg, cg, ch, e, f = self.regs_stage, self.cigar_stage, self.chain, self.ext, self.chain.fmi
+        b, rg, cg = self.batch, self.regions, self.cigar_stage
         c = self.counts.data_ptr()
         N.check(lib().gbx_mem_sam_device(
-            C.byref(self.params), self.n_reads, self.mode, self.regs.data_ptr(), rg.reg_off.data_ptr(), rg.counts.data_ptr(), rg.reg_cap,
+            C.byref(self.params), self.n_reads, self.mode, rg.regs.data_ptr(), rg.reg_off.data_ptr(), rg.count.data_ptr(), rg.cap,
             self.pairs.data_ptr() if self.mode else None, cg.alns.data_ptr(), cg.n, cg.cigar.data_ptr(), cg.n_cigar.data_ptr(), cg.cigar_cap,
-            e.qer.data_ptr(), e.qer_bytes, f.read_off.data_ptr(), f.read_len.data_ptr(), self.qual.data_ptr() if self.qual is not None else None,
+            b.qer.data_ptr(), b.qer_bytes, b.read_off.data_ptr(), b.read_len.data_ptr(), self.qual.data_ptr() if self.qual is not None else None,
             self.names.data_ptr(), self.name_off.data_ptr(), self.name_bytes, self.cnames.data_ptr(), self.cname_off.data_ptr(),
-            self.cname_bytes, e.ref.data_ptr(), e.ref_bytes, ch.l_pac, ch.n_contigs, ch.contig_off.data_ptr(), self.recs.data_ptr(),
+            self.cname_bytes, b.ref.data_ptr(), b.ref_bytes, b.l_pac, b.n_contigs, b.contig_off.data_ptr(), self.recs.data_ptr(),
             self.rec_cap, self.rec_off.data_ptr(), c, self.md.data_ptr(), self.md_cap, c + 8, self.lines.data_ptr(), self.text_cap, c + 16,
             self.work.data_ptr(), self.work_bytes, stream))
 
@@ -190,15 +187,18 @@ class DeviceMemSam:
         return self.results()["lines"].tobytes()
 
 
-def pipeline(ext, names, qual, contig_names, stream=None, pair_id0=0, sam_params=None, with_header=True, sam_caps=None, **kw):
-    """``mem_rescue.pipeline`` (regs -> pestat -> rescue -> pair -> cigar) and this stage behind it on one stream, behind a
-    ``mem_chain.DeviceSeedExtension`` that has been queued on it; `kw` goes to mem_rescue.pipeline, sam_caps to DeviceMemSam.  The
-    stream is synchronised and the text read back.  -> (SAM text as bytes, (regs, rescue, pair, cigar, sam) stages)."""
-    from . import mem_rescue as MS
-    rg, rs, pe, cg = MS.pipeline(ext, stream, pair_id0, **kw)
-    sm = DeviceMemSam(pe, cg, names, qual, contig_names, sam_params, **(sam_caps or {}))
-    sm.run(stream)
+def pipeline(ext, names, qual, contig_names, stream=None, pair_id0=0, sam_params=None, with_header=True, sam_caps=None, regs_params=None,
+             rescue_params=None, pair_params=None, cigar_params=None, cigar_cap=None, z_bytes=None):
+    """regs -> pestat -> rescue -> pair -> cigar -> sam on one stream behind a ``mem_chain.DeviceSeedExtension`` that has been
+    queued on it (``mem_pipeline.Stages`` from "regs" on); the arguments are ``mem_rescue.pipeline``'s, and sam_caps goes to
+    DeviceMemSam.  The stream is synchronised and the text read back.  -> (SAM text as bytes, (regs, rescue, pair, cigar, sam)
+    stages)."""
+    from .mem_pipeline import Stages
+    caps = {k: v for k, v in dict(sam_caps or {}, cigar_cap=cigar_cap, z_bytes=z_bytes).items() if v is not None}
+    st = Stages(ext=ext, id0=pair_id0, params=dict(regs=regs_params, rescue=rescue_params, pair=pair_params, cigar=cigar_params, sam=sam_params),
+                caps=caps, sam_input=(names, qual, contig_names))
+    st.queue(stream, "regs")
     N.check(N.lib().gbx_stream_synchronize(stream))
-    ch = rg.ext.chain
-    head = header(contig_names, ch.contig_off.cpu().numpy(), ch.l_pac).encode() if with_header else b""
-    return head + sm.text(), (rg, rs, pe, cg, sm)
+    b = ext.batch
+    head = header(contig_names, b.contig_off.cpu().numpy(), b.l_pac).encode() if with_header else b""
+    return head + st.sam.text(), (st.regs, st.rescue, st.pair, st.cigar, st.sam)

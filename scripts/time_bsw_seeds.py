@@ -14,16 +14,16 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for d in (ROOT, os.path.join(ROOT, "tests")):
+for d in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "scripts")):
     if d not in sys.path:
         sys.path.insert(0, d)
 
 import numpy as np  # noqa: E402
 
-from genomicsbench_amd import _native as N  # noqa: E402
 from genomicsbench_amd.bsw import DeviceBswBatch, make_params  # noqa: E402
 from genomicsbench_amd.bsw_seeds import DeviceSeedBatch, gen_seeds, make_seed_params  # noqa: E402
 import seedext_ref as R  # noqa: E402
+from _mem_timing import median_ms  # noqa: E402
 
 
 def composed(p, b, device, stream=None, stats=None):
@@ -43,19 +43,6 @@ def composed(p, b, device, stream=None, stats=None):
         d.run(params, stream if stream is not None else torch.cuda.current_stream().cuda_stream)
         return d.results()
     return R.extend_seeds_ref(p, b, ksw=ksw, stats=stats), stats
-
-
-def median_ms(fn, reps, warmup, stream):
-    for _ in range(warmup):
-        fn()
-    tm = N.StreamTimer()
-    xs = []
-    for _ in range(reps):
-        tm.start(stream)
-        fn()
-        tm.stop(stream)
-        xs.append(tm.elapsed_ms())
-    return float(np.median(xs)), xs
 
 
 def main():

@@ -13,27 +13,14 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for d in (ROOT, os.path.join(ROOT, "tests")):
+for d in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "scripts")):
     if d not in sys.path:
         sys.path.insert(0, d)
 
 import numpy as np  # noqa: E402
 
-from genomicsbench_amd import _native as N  # noqa: E402
 from genomicsbench_amd import fmi as FM  # noqa: E402
-
-
-def median_ms(fn, reps, warmup, stream):
-    for _ in range(warmup):
-        fn()
-    tm = N.StreamTimer()
-    xs = []
-    for _ in range(reps):
-        tm.start(stream)
-        fn()
-        tm.stop(stream)
-        xs.append(tm.elapsed_ms())
-    return float(np.median(xs)), xs
+from _mem_timing import median_ms  # noqa: E402
 
 
 def main():

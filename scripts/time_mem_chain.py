@@ -7,94 +7,31 @@ host synchronisation inside.  A sample of reads is checked against tests/mem_cha
 
     python scripts/time_mem_chain.py [--reads 200000] [--reps 10] [--out profiles/mem_chain_time.json]
 """
-import argparse
-import json
-import os
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for d in (ROOT, os.path.join(ROOT, "tests")):
-    if d not in sys.path:
-        sys.path.insert(0, d)
+import numpy as np
 
-import numpy as np  # noqa: E402
-
-from genomicsbench_amd import _native as N  # noqa: E402
-from genomicsbench_amd import bsw_seeds as BS  # noqa: E402
-from genomicsbench_amd import fmi as FM  # noqa: E402
-from genomicsbench_amd import mem_chain as MC  # noqa: E402
+import _mem_timing as T
 
 HBM_GBS = 8000.0            # MI355X peak HBM3E bandwidth, GB/s
 
 
-def median_ms(fn, reps, warmup, stream):
-    for _ in range(warmup):
-        fn()
-    tm = N.StreamTimer()
-    xs = []
-    for _ in range(reps):
-        tm.start(stream)
-        fn()
-        tm.stop(stream)
-        xs.append(tm.elapsed_ms())
-    return float(np.median(xs)), [round(x, 3) for x in xs]
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reads", type=int, default=200_000)
-    ap.add_argument("--genome", type=int, default=512 << 20)
-    ap.add_argument("--seed", type=int, default=6001)
-    ap.add_argument("--max-occ", type=int, default=500)
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
+    ap = T.parser("mem_chain_time.json")
     ap.add_argument("--check", type=int, default=300, help="reads checked against the restated rules")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mem_chain_time.json"))
     args = ap.parse_args()
     import torch
-    from genomicsbench_amd.datagen import gen_fmi_genome, gen_fmi_reads
+    from genomicsbench_amd.datagen import gen_fmi_reads
+    from genomicsbench_amd.mem_chain import text_of
     import mem_chain_ref as R
-    assert torch.cuda.is_available(), "needs a GPU"
-    dev = torch.device("cuda:0")
-    s = torch.cuda.current_stream().cuda_stream
-    t0 = time.perf_counter()
-    g = gen_fmi_genome(args.genome, args.seed)
-    idx, smp = FM.build_index(g, device=dev, sa_compx=3)
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    build_s = time.perf_counter() - t0
+    dev, s, g, idx, smp, build_s = T.setup(args)
     rs = gen_fmi_reads(g, args.reads, args.seed + 1)
     L = len(g)
-    # sizing pass: the counts of every stage, then tight capacities
-    d = FM.DeviceFmi(idx, rs, dev)
-    d.set_sa(smp)
-    d.run(s)
-    d.sal(args.max_occ, stream=s)
-    torch.cuda.synchronize()
-    n_smem, n_pos = int(d.n_out.item()), int(d.n_pos.item())
-    assert n_smem <= d.out_cap and not d.overflow() and n_pos <= d.pos_cap, "seeding output truncated"
-    d.sal(args.max_occ, pos_cap=n_pos + 64, stream=s)
-    params = MC.make_params(max_occ=args.max_occ)
-    mc = MC.DeviceMemChain(d, L, params=params)
-    mc.run(s)
-    torch.cuda.synchronize()
-    n_chains, n_seeds = (int(x) for x in mc.counts.cpu().numpy())
-    mc = MC.DeviceMemChain(d, L, params=params, chain_cap=n_chains + 64, seed_cap=n_seeds + 64)
-    text = torch.from_numpy(MC.text_of(g)).to(dev)
-    ext = mc.extension(text)
-    sp = BS.make_seed_params()
-
-    def whole():
-        d.run(s)
-        d.sal(args.max_occ, pos_cap=n_pos + 64, stream=s)
-        mc.run(s)
-        ext.run(sp, s)
-    t_all, all_xs = median_ms(whole, args.reps, args.warmup, s)
-    t_smem, _ = median_ms(lambda: d.run(s), args.reps, 1, s)
-    t_sal, _ = median_ms(lambda: d.sal(args.max_occ, pos_cap=n_pos + 64, stream=s), args.reps, 1, s)
-    t_chain, chain_xs = median_ms(lambda: mc.run(s), args.reps, 1, s)
-    t_ext, _ = median_ms(lambda: ext.run(sp, s), args.reps, 1, s)
+    st, n = T.sized_stages(idx, smp, rs, torch.from_numpy(text_of(g)).to(dev), L, dev, s, args, last="extend")
+    d, mc, ext = st.fmi, st.chain, st.extend
+    n_smem, n_pos, n_chains, n_seeds = n["n_smem"], n["n_pos"], n["n_chains"], n["n_seeds"]
+    t_all, all_xs, times = T.time_steps(st, s, args, last="extend")
+    (t_smem, _), (t_sal, _), (t_chain, chain_xs), (t_ext, _) = (times[k] for k in ("smem", "sal", "chain", "extend"))
     torch.cuda.synchronize()
     got = mc.results()
     assert len(got["chains"]) == n_chains and len(got["seeds"]) == n_seeds
@@ -122,12 +59,7 @@ def main():
            "chain_hbm_roofline_frac": round(floor_ms / t_chain, 4), "chain_workspace_bytes": int(mc.work_bytes),
            "extended_with_score": int((res[:, 0] > 0).sum()), "checked_reads": k, "checked_equal": ok,
            "device": torch.cuda.get_device_name(0)}
-    line = json.dumps(out)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
-    return 0 if ok else 1
+    return T.emit(out, args.out, ok)
 
 
 if __name__ == "__main__":

@@ -7,111 +7,33 @@ tests/mem_cigar_ref.py.
 
     python scripts/time_mem_cigar.py [--reads 200000] [--reps 10] [--out profiles/mem_cigar_time.json]
 """
-import argparse
-import ctypes as C
-import json
-import os
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for d in (ROOT, os.path.join(ROOT, "tests")):
-    if d not in sys.path:
-        sys.path.insert(0, d)
+import numpy as np
 
-import numpy as np  # noqa: E402
-
-from genomicsbench_amd import _native as N  # noqa: E402
-from genomicsbench_amd import bsw_seeds as BS  # noqa: E402
-from genomicsbench_amd import fmi as FM  # noqa: E402
-from genomicsbench_amd import mem_chain as MC  # noqa: E402
-from genomicsbench_amd import mem_cigar as MG  # noqa: E402
-
-
-def median_ms(fn, reps, warmup, stream):
-    for _ in range(warmup):
-        fn()
-    tm = N.StreamTimer()
-    xs = []
-    for _ in range(reps):
-        tm.start(stream)
-        fn()
-        tm.stop(stream)
-        xs.append(tm.elapsed_ms())
-    return float(np.median(xs)), [round(x, 3) for x in xs]
+import _mem_timing as T
+from genomicsbench_amd import bsw_seeds as BS
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reads", type=int, default=200_000)
-    ap.add_argument("--genome", type=int, default=512 << 20)
-    ap.add_argument("--seed", type=int, default=6001)
-    ap.add_argument("--max-occ", type=int, default=500)
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
+    ap = T.parser("mem_cigar_time.json")
     ap.add_argument("--check", type=int, default=2000, help="records checked against the restated rules")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mem_cigar_time.json"))
     args = ap.parse_args()
     import torch
-    from genomicsbench_amd.datagen import gen_fmi_genome, gen_fmi_reads
+    from genomicsbench_amd.datagen import gen_fmi_reads
+    from genomicsbench_amd.mem_chain import text_of
     import mem_cigar_ref as R
-    assert torch.cuda.is_available(), "needs a GPU"
-    dev = torch.device("cuda:0")
-    s = torch.cuda.current_stream().cuda_stream
-    t0 = time.perf_counter()
-    g = gen_fmi_genome(args.genome, args.seed)
-    idx, smp = FM.build_index(g, device=dev, sa_compx=3)
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    build_s = time.perf_counter() - t0
+    dev, s, g, idx, smp, build_s = T.setup(args)
     rs = gen_fmi_reads(g, args.reads, args.seed + 1)
     L = len(g)
-    # sizing pass: the counts of every stage, then tight capacities
-    d = FM.DeviceFmi(idx, rs, dev)
-    d.set_sa(smp)
-    d.run(s)
-    d.sal(args.max_occ, stream=s)
-    torch.cuda.synchronize()
-    n_smem, n_pos = int(d.n_out.item()), int(d.n_pos.item())
-    assert n_smem <= d.out_cap and not d.overflow() and n_pos <= d.pos_cap, "seeding output truncated"
-    d.sal(args.max_occ, pos_cap=n_pos + 64, stream=s)
-    params = MC.make_params(max_occ=args.max_occ)
-    mc = MC.DeviceMemChain(d, L, params=params)
-    mc.run(s)
-    torch.cuda.synchronize()
-    n_chains, n_seeds = (int(x) for x in mc.counts.cpu().numpy())
-    mc = MC.DeviceMemChain(d, L, params=params, chain_cap=n_chains + 64, seed_cap=n_seeds + 64)
-    text_h = MC.text_of(g)
-    text = torch.from_numpy(text_h).to(dev)
-    ext = mc.extension(text)
-    sp = BS.make_seed_params()
-    cp = MG.make_params()
-    mc.run(s)
-    ext.run(sp, s)
-    torch.cuda.synchronize()
+    text_h = text_of(g)
+    st, n = T.sized_stages(idx, smp, rs, torch.from_numpy(text_h).to(dev), L, dev, s, args, skip=("regs", "rescue", "pair"), last="cigar")
+    mc, ext, cg = st.chain, st.extend, st.cigar
+    n_smem, n_pos, n_chains, n_seeds, lq_max, lt_max = (n[k] for k in ("n_smem", "n_pos", "n_chains", "n_seeds", "lq_max", "lt_max"))
+    z_bytes, per_record = cg.z_bytes, n["z_per_record"]
     res = ext.results()
-    regions = res[res[:, 2] >= 0]
-    lq_max, lt_max = int((regions[:, 3] - regions[:, 2]).max()), int((regions[:, 5] - regions[:, 4]).max())
-    per_record = int(MG.lib().gbx_mem_cigar_record_z_bytes(C.byref(cp), lq_max, lt_max))
-    z_bytes = len(regions) * per_record
-    cg = MG.DeviceMemCigar(ext, cp, cigar_cap=8 * ext.n, z_bytes=z_bytes)
-    cg.run(s)
-    torch.cuda.synchronize()
-    alns, cigar = cg.results()
-    cg = MG.DeviceMemCigar(ext, cp, cigar_cap=len(cigar) + 64, z_bytes=z_bytes)
-
-    def whole():
-        d.run(s)
-        d.sal(args.max_occ, pos_cap=n_pos + 64, stream=s)
-        mc.run(s)
-        ext.run(sp, s)
-        cg.run(s)
-    t_all, all_xs = median_ms(whole, args.reps, args.warmup, s)
-    t_smem, _ = median_ms(lambda: d.run(s), args.reps, 1, s)
-    t_sal, _ = median_ms(lambda: d.sal(args.max_occ, pos_cap=n_pos + 64, stream=s), args.reps, 1, s)
-    t_chain, _ = median_ms(lambda: mc.run(s), args.reps, 1, s)
-    t_ext, _ = median_ms(lambda: ext.run(sp, s), args.reps, 1, s)
-    t_cg, cg_xs = median_ms(lambda: cg.run(s), args.reps, 1, s)
+    t_all, all_xs, times = T.time_steps(st, s, args, last="cigar")
+    (t_smem, _), (t_sal, _), (t_chain, _), (t_ext, _), (t_cg, cg_xs) = (times[k] for k in ("smem", "sal", "chain", "extend", "cigar"))
     torch.cuda.synchronize()
     alns, cigar = cg.results()
     # the first records against the restated rules (the C twin)
@@ -121,7 +43,7 @@ def main():
     ok = bool(alns[:k].tobytes() == want_a.tobytes() and np.array_equal(cigar[:len(want_c)], want_c))
     out = {"what": "smem -> sal -> chain -> extend -> cigar on one stream, fmi 'large' genome", "genome_bp": args.genome,
            "reads": rs.n_reads, "index_build_s": round(build_s, 1), "max_occ": args.max_occ, "smems": n_smem, "hits": n_pos,
-           "chains": n_chains, "seeds": n_seeds, "regions": int(len(regions)), "cigar_words": int(len(cigar)),
+           "chains": n_chains, "seeds": n_seeds, "regions": n["n_extended"], "cigar_words": int(len(cigar)),
            "records_without_room": int((alns["rid"] == -2).sum()), "records_through_the_dp": int((alns["w"] > 0).sum()),
            "tries_histogram": np.bincount(alns["tries"], minlength=4).tolist(), "longest_query": lq_max, "longest_text": lt_max,
            "z_bytes": z_bytes, "z_bytes_per_record": per_record,
@@ -129,12 +51,7 @@ def main():
            "cigar_ms": round(t_cg, 3), "cigar_ms_all": cg_xs, "whole_ms": round(t_all, 3), "whole_ms_all": all_xs,
            "cigar_over_extend": round(t_cg / t_ext, 4), "checked_records": k, "checked_equal": ok,
            "device": torch.cuda.get_device_name(0)}
-    line = json.dumps(out)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
-    return 0 if ok else 1
+    return T.emit(out, args.out, ok)
 
 
 if __name__ == "__main__":

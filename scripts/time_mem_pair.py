@@ -8,137 +8,29 @@ under the call's own estimate (given to the reference as pes_in: the estimate is
 
     python scripts/time_mem_pair.py [--reads 200000] [--reps 10] [--out profiles/mem_pair_time.json]
 """
-import argparse
-import ctypes as C
-import json
-import os
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for d in (ROOT, os.path.join(ROOT, "tests")):
-    if d not in sys.path:
-        sys.path.insert(0, d)
+import numpy as np
 
-import numpy as np  # noqa: E402
-
-from genomicsbench_amd import _native as N  # noqa: E402
-from genomicsbench_amd import bsw_seeds as BS  # noqa: E402
-from genomicsbench_amd import fmi as FM  # noqa: E402
-from genomicsbench_amd import mem_chain as MC  # noqa: E402
-from genomicsbench_amd import mem_cigar as MG  # noqa: E402
-from genomicsbench_amd import mem_pair as MP  # noqa: E402
-from genomicsbench_amd import mem_regs as MR  # noqa: E402
-
-
-def gen_pairs(g, n_pairs, seed, length=151, mean=350., sd=35.):
-    """n_pairs FR fragments of g as interleaved reads: the fragment's first `length` bases, then the reverse complement of its
-    last ones, each with about 1 % substitutions."""
-    rng = np.random.default_rng(seed)
-    frag = np.maximum(length + 20, np.rint(rng.normal(mean, sd, n_pairs)).astype(np.int64))
-    at = rng.integers(0, len(g) - frag.max(), n_pairs)
-    col = np.arange(length)
-    fwd = g[at[:, None] + col]
-    rev = 3 - g[(at + frag)[:, None] - 1 - col]
-    reads = np.empty((2 * n_pairs, length), dtype=np.uint8)
-    reads[0::2], reads[1::2] = fwd, rev
-    hit = rng.random(reads.shape) < 0.01
-    reads[hit] = (reads[hit] + rng.integers(1, 4, int(hit.sum()))) % 4
-    return FM.FmiReadSet.fixed(reads)
-
-
-def median_ms(fn, reps, warmup, stream):
-    for _ in range(warmup):
-        fn()
-    tm = N.StreamTimer()
-    xs = []
-    for _ in range(reps):
-        tm.start(stream)
-        fn()
-        tm.stop(stream)
-        xs.append(tm.elapsed_ms())
-    return float(np.median(xs)), [round(x, 3) for x in xs]
+import _mem_timing as T
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reads", type=int, default=200_000)
-    ap.add_argument("--genome", type=int, default=512 << 20)
-    ap.add_argument("--seed", type=int, default=6001)
-    ap.add_argument("--max-occ", type=int, default=500)
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
+    ap = T.parser("mem_pair_time.json")
     ap.add_argument("--check", type=int, default=2000, help="pairs that are checked against the restated rules")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mem_pair_time.json"))
     args = ap.parse_args()
     import torch
-    from genomicsbench_amd.datagen import gen_fmi_genome
+    from genomicsbench_amd.mem_chain import text_of
     import mem_pair_ref as R
-    assert torch.cuda.is_available(), "needs a GPU"
-    dev = torch.device("cuda:0")
-    s = torch.cuda.current_stream().cuda_stream
-    t0 = time.perf_counter()
-    g = gen_fmi_genome(args.genome, args.seed)
-    idx, smp = FM.build_index(g, device=dev, sa_compx=3)
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    build_s = time.perf_counter() - t0
-    rs = gen_pairs(g, args.reads // 2, args.seed + 1)
+    dev, s, g, idx, smp, build_s = T.setup(args)
+    rs, _ = T.gen_pairs(g, args.reads // 2, args.seed + 1)
     L = len(g)
-    # sizing pass: the counts of every stage, then tight capacities
-    d = FM.DeviceFmi(idx, rs, dev)
-    d.set_sa(smp)
-    d.run(s)
-    d.sal(args.max_occ, stream=s)
-    torch.cuda.synchronize()
-    n_smem, n_pos = int(d.n_out.item()), int(d.n_pos.item())
-    assert n_smem <= d.out_cap and not d.overflow() and n_pos <= d.pos_cap, "seeding output truncated"
-    d.sal(args.max_occ, pos_cap=n_pos + 64, stream=s)
-    params = MC.make_params(max_occ=args.max_occ)
-    mc = MC.DeviceMemChain(d, L, params=params)
-    mc.run(s)
-    torch.cuda.synchronize()
-    n_chains, n_seeds = (int(x) for x in mc.counts.cpu().numpy())
-    mc = MC.DeviceMemChain(d, L, params=params, chain_cap=n_chains + 64, seed_cap=n_seeds + 64)
-    text = torch.from_numpy(MC.text_of(g)).to(dev)
-    ext = mc.extension(text)
-    sp, rp, pp, cp = BS.make_seed_params(), MR.make_params(), MP.make_params(), MG.make_params()
-    mc.run(s)
-    ext.run(sp, s)
-    rg = MR.DeviceMemRegs(ext, rp)
-    rg.run(s)
-    torch.cuda.synchronize()
-    res = ext.results()
-    first = rg.results()
-    n_regs, n_sel = first["n_regs"], first["n_sel"]
-    rg = MR.DeviceMemRegs(ext, rp, reg_cap=n_regs + 64, sel_cap=n_sel + 64)
-    regions = res[res[:, 2] >= 0]
-    lq_max, lt_max = int((regions[:, 3] - regions[:, 2]).max()), int((regions[:, 5] - regions[:, 4]).max())
-    per_record = int(MG.lib().gbx_mem_cigar_record_z_bytes(C.byref(cp), lq_max, lt_max))
-    pe = MP.DeviceMemPair(rg, pp, psel_cap=n_regs + 64)
-    rg.run(s)
-    pe.run(s)
-    torch.cuda.synchronize()
-    n_psel = pe.results()["n_psel"]
-    pe = MP.DeviceMemPair(rg, pp, psel_cap=n_psel + 64)
-    cg = MG.DeviceMemCigar(pe.cigar_input, cp, cigar_cap=8 * pe.psel_cap, z_bytes=n_psel * per_record)
-
-    def whole():
-        d.run(s)
-        d.sal(args.max_occ, pos_cap=n_pos + 64, stream=s)
-        mc.run(s)
-        ext.run(sp, s)
-        rg.run(s)
-        pe.run(s)
-        cg.run(s)
-    t_all, all_xs = median_ms(whole, args.reps, args.warmup, s)
-    t_smem, _ = median_ms(lambda: d.run(s), args.reps, 1, s)
-    t_sal, _ = median_ms(lambda: d.sal(args.max_occ, pos_cap=n_pos + 64, stream=s), args.reps, 1, s)
-    t_chain, _ = median_ms(lambda: mc.run(s), args.reps, 1, s)
-    t_ext, _ = median_ms(lambda: ext.run(sp, s), args.reps, 1, s)
-    t_rg, rg_xs = median_ms(lambda: rg.run(s), args.reps, 1, s)
-    t_pe, pe_xs = median_ms(lambda: pe.run(s), args.reps, 1, s)
-    t_cg, cg_xs = median_ms(lambda: cg.run(s), args.reps, 1, s)
+    st, n = T.sized_stages(idx, smp, rs, torch.from_numpy(text_of(g)).to(dev), L, dev, s, args, skip=("rescue",), last="cigar")
+    mc, rg, pe, cg = st.chain, st.regs, st.pair, st.cigar
+    n_smem, n_pos, n_chains, n_seeds, n_regs, n_sel, n_psel = (n[k] for k in ("n_smem", "n_pos", "n_chains", "n_seeds", "n_regs", "n_sel", "n_psel"))
+    t_all, all_xs, times = T.time_steps(st, s, args, last="cigar")
+    (t_smem, _), (t_sal, _), (t_chain, _), (t_ext, _), (t_rg, rg_xs), (t_pe, pe_xs), (t_cg, cg_xs) = \
+        (times[k] for k in ("smem", "sal", "chain", "extend", "regs", "pair", "cigar"))
     torch.cuda.synchronize()
     regs_out = rg.results()
     got = pe.results()
@@ -165,12 +57,7 @@ def main():
            "regs_ms": round(t_rg, 3), "regs_ms_all": rg_xs, "pair_ms": round(t_pe, 3), "pair_ms_all": pe_xs, "cigar_ms": round(t_cg, 3),
            "cigar_ms_all": cg_xs, "whole_ms": round(t_all, 3), "whole_ms_all": all_xs, "pair_over_regs": round(t_pe / t_rg, 4),
            "checked_pairs": k, "checked_equal": ok, "device": torch.cuda.get_device_name(0)}
-    line = json.dumps(out)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
-    return 0 if ok else 1
+    return T.emit(out, args.out, ok)
 
 
 if __name__ == "__main__":

@@ -1,19 +1,16 @@
 """Inputs and expected outputs for the aligner's tests (tests/test_mem_align_cpu.py, tests/test_mem_align_gpu.py): generated
-reads, and the EXISTING composition of the stage classes (mem_sam.pipeline and its parts) with generous capacities, which is what
-the aligner has to equal byte for byte.  The composition asserts that none of its capacities overflowed."""
+reads, and the EXISTING composition of the stage classes (mem_pipeline.Stages, which mem_sam.pipeline queues through) with generous
+capacities, which is what the aligner has to equal byte for byte.  The composition asserts that none of its capacities overflowed."""
 import ctypes as C
 
 import numpy as np
 
-from genomicsbench_amd import _native as N
-from genomicsbench_amd import bsw_seeds as BS
 from genomicsbench_amd import fmi as FM
 from genomicsbench_amd import mem_chain as MC
 from genomicsbench_amd import mem_cigar as MG
 from genomicsbench_amd import mem_pair as MP
-from genomicsbench_amd import mem_regs as MR
-from genomicsbench_amd import mem_rescue as MS
 from genomicsbench_amd import mem_sam as SM
+from genomicsbench_amd.mem_pipeline import Stages
 import mem_rescue_cases as KR
 
 CONTIG_OFF = np.array([0, 14_000, 30_000], dtype=np.int64)
@@ -94,105 +91,56 @@ def letters_of(rs):
     return ["".join(LETTERS[c] for c in rs.enc[int(o):int(o) + int(l)]) for o, l in zip(rs.read_off, rs.read_len)]
 
 
-class Composed:
-    """The stages up to the seed extension, queued as tests/test_mem_sam_gpu.py::test_whole_pipeline_on_one_stream queues them."""
-
-    def __init__(self, g, rs, cap=8000):
-        import torch
-        self.g, self.rs, self.cap = g, rs, cap
-        self.idx, self.smp = FM.build_index(g, sa_compx=3)
-        self.text = MC.text_of(g)
-        self.stream = torch.cuda.Stream()
-        s = self.stream.cuda_stream
-        with torch.cuda.stream(self.stream):
-            d = self.fmi = FM.DeviceFmi(self.idx, rs, torch.device("cuda:0"))
-            d.set_sa(self.smp)
-            d.run(s)
-            d.sal(500, pos_cap=cap, stream=s)
-            self.chain = MC.DeviceMemChain(d, len(g), CONTIG_OFF)
-            self.chain.run(s)
-            self.ext = self.chain.extension(self.text)
-            self.ext.run(BS.make_seed_params(), s)
-
-    def check_front(self):
-        d = self.fmi
-        assert int(d.n_out.item()) <= d.out_cap and int(d.n_pos.item()) <= self.cap and not d.overflow()
-        self.chain.results()
+def compose(g, rs, names, qual, id0, cap=8000, **options):
+    """The composition on its own stream, from the index to the SAM stage -> (Stages, the torch stream); `options` go to
+    mem_pipeline.Stages (skip, pes, params)."""
+    import torch
+    idx, smp = FM.build_index(g, sa_compx=3)
+    p = MG.make_params()
+    z = 8 * rs.n_reads * MG.lib().gbx_mem_cigar_record_z_bytes(C.byref(p), 151, 302)
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        d = FM.DeviceFmi(idx, rs, torch.device("cuda:0"))
+        d.set_sa(smp)
+        params = dict(options.pop("params", {}), cigar=p)
+        st = Stages(d, MC.text_of(g), len(g), CONTIG_OFF, id0=id0, params=params, caps=dict(pos_cap=cap, cigar_cap=8 * cap, z_bytes=z),
+                    sam_input=(names, qual, CONTIG_NAMES), **options)
+        st.queue(stream.cuda_stream)
+    return st, stream
 
 
-def _finish(c, sm, cg, stages, pe=None):
-    c.stream.synchronize()
-    c.check_front()
-    for st in stages:
-        st.results()                                     # each raises when one of its capacities overflowed
-    alns, _ = cg.results()
-    assert not (alns["rid"] == -2).any()
-    got = sm.results()
-    pes = pe.results()["pes"] if pe is not None else None
+def finish(st, stream):
+    stream.synchronize()
+    res = st.check()                                     # each stage raises when one of its capacities overflowed
+    assert not (res["cigar"][0]["rid"] == -2).any()
+    got = res["sam"]
+    pes = res["pair"]["pes"] if "pair" in res else None
+    stages = [st.st[n] for n in st.names[3:]]             # from the regs stage on
     return dict(sam=got["lines"].tobytes(), recs=got["recs"], rec_off=got["rec_off"], pes=pes, stages=stages)
 
 
-def _cigar_room(n_reads):
-    p = MG.make_params()
-    return p, 8 * n_reads * MG.lib().gbx_mem_cigar_record_z_bytes(C.byref(p), 151, 302)
-
-
 def compose_paired(g, rs, names, qual, id0):
-    """mem_sam.pipeline (regs -> pestat -> rescue -> pair -> cigar -> sam), no header."""
+    """regs -> pestat -> rescue -> pair -> cigar -> sam, which is mem_sam.pipeline (no header) behind the same extension."""
     import torch
-    c = Composed(g, rs)
-    p, z = _cigar_room(rs.n_reads)
-    with torch.cuda.stream(c.stream):
-        sam, (rg, rsc, pe, cg, sm) = SM.pipeline(c.ext, names, qual, CONTIG_NAMES, c.stream.cuda_stream, id0, with_header=False, cigar_params=p,
-                                                 cigar_cap=8 * c.cap, z_bytes=z)
-    out = _finish(c, sm, cg, [rg, rsc, pe, cg, sm], pe)
+    st, stream = compose(g, rs, names, qual, id0)
+    out = finish(st, stream)
+    with torch.cuda.stream(stream):
+        sam, _ = SM.pipeline(st.extend, names, qual, CONTIG_NAMES, stream.cuda_stream, id0, with_header=False, cigar_params=st.params["cigar"],
+                             cigar_cap=st.caps["cigar_cap"], z_bytes=st.caps["z_bytes"])
     assert out["sam"] == sam
-    out["rescue_stats"] = rsc.results()["stats"]
+    out["rescue_stats"] = st.rescue.results()["stats"]
     return out
 
 
 def compose_variant(g, rs, names, qual, id0, pes=None, no_rescue=False, no_pairing=False):
-    """The same classes queued by hand for what mem_sam.pipeline has no argument for: a given estimate, no rescue (bwa -S),
-    no pairing (bwa -P)."""
-    import torch
-    c = Composed(g, rs)
-    p, z = _cigar_room(rs.n_reads)
-    s = c.stream.cuda_stream
+    """What mem_sam.pipeline has no argument for: a given estimate, no rescue (bwa -S), no pairing (bwa -P)."""
     pp = MP.make_params(no_pairing=1 if no_pairing else 0)
-    with torch.cuda.stream(c.stream):
-        rg = MR.DeviceMemRegs(c.ext, None, read_id0=2 * int(id0))
-        rg.run(s)
-        stages = [rg]
-        before = rg
-        if not no_rescue:
-            before = MS.DeviceMemRescue(rg, None, pp, pes=pes)
-            before.run(s)
-            stages.append(before)
-            pe = MP.DeviceMemPair(before, pp, pes_in=before.pes_host(s))
-        else:
-            pe = MP.DeviceMemPair(rg, pp, pes_in=pes)
-        pe.run(s)
-        cg = MG.DeviceMemCigar(pe.cigar_input, p, cigar_cap=8 * c.cap, z_bytes=z)
-        cg.run(s)
-        sm = SM.DeviceMemSam(pe, cg, names, qual, CONTIG_NAMES)
-        sm.run(s)
-    return _finish(c, sm, cg, stages + [pe, cg, sm], pe)
+    return finish(*compose(g, rs, names, qual, id0, pes=pes, skip=("rescue",) if no_rescue else (), params=dict(pair=pp)))
 
 
 def compose_single(g, rs, names, qual, id0):
     """regs -> cigar on the regs stage's list -> DeviceMemSam mode 0."""
-    import torch
-    c = Composed(g, rs)
-    p, z = _cigar_room(rs.n_reads)
-    s = c.stream.cuda_stream
-    with torch.cuda.stream(c.stream):
-        rg = MR.DeviceMemRegs(c.ext, None, read_id0=int(id0))
-        rg.run(s)
-        cg = MG.DeviceMemCigar(rg.cigar_input, p, cigar_cap=8 * c.cap, z_bytes=z)
-        cg.run(s)
-        sm = SM.DeviceMemSam(rg, cg, names, qual, CONTIG_NAMES)
-        sm.run(s)
-    return _finish(c, sm, cg, [rg, cg, sm])
+    return finish(*compose(g, rs, names, qual, id0, skip=("rescue", "pair")))
 
 
 def same_output(got, want, pes=True):

@@ -161,10 +161,10 @@ def run_pair(entry, rsc, pes_arg):
     """One of the two paired entries behind the rescue stage `rsc`, into fresh outputs -> the DeviceMemPair that holds them."""
     import torch
     pe = MP.DeviceMemPair(rsc, MP.make_params())
-    ch = rsc.ext.chain
+    sd, b = rsc.seeds, rsc.batch
     N.check(entry(C.byref(pe.params), pe.n_pairs, pe.pair_id0, rsc.regs.data_ptr(), rsc.reg_off.data_ptr(), rsc.counts.data_ptr(), rsc.reg_cap,
-                  rsc.sel_seeds.data_ptr(), rsc.sel_res.data_ptr(), rsc.sel_cap, ch.seeds.data_ptr(), ch.seed_cap, ch.l_rep.data_ptr(),
-                  ch.l_pac, ch.n_contigs, ch.contig_off.data_ptr(), pes_arg, pe.pes.data_ptr(), pe.pairs.data_ptr(), pe.pregs.data_ptr(),
+                  rsc.sel_seeds.data_ptr(), rsc.sel_res.data_ptr(), rsc.sel_cap, sd.seeds.data_ptr(), sd.cap, sd.l_rep.data_ptr(),
+                  b.l_pac, b.n_contigs, b.contig_off.data_ptr(), pes_arg, pe.pes.data_ptr(), pe.pairs.data_ptr(), pe.pregs.data_ptr(),
                   pe.psel_seeds.data_ptr(), pe.psel_res.data_ptr(), pe.psel_cap, pe.count.data_ptr(), pe.work.data_ptr(), pe.work_bytes, None))
     torch.cuda.synchronize()
     return pe.results()

@@ -8,12 +8,12 @@ import numpy as np
 import pytest
 
 from genomicsbench_amd import _native as N
-from genomicsbench_amd import bsw_seeds as BS
 from genomicsbench_amd import fmi as FM
 from genomicsbench_amd import mem_chain as MC
 from genomicsbench_amd import mem_cigar as MG
 from genomicsbench_amd import mem_pair as MP
 from genomicsbench_amd import mem_sam as SM
+from genomicsbench_amd.mem_pipeline import Stages
 import mem_cigar_cases as KG
 import mem_rescue_cases as KR
 import mem_sam_cases as K
@@ -227,21 +227,15 @@ def test_whole_pipeline_on_one_stream():
     qual = np.random.default_rng(8313).integers(33, 74, len(rs.enc)).astype(np.uint8)
     idx, smp = FM.build_index(g, sa_compx=3)
     text = MC.text_of(g)
-    sp = BS.make_seed_params()
     cap = 8000
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):
         d = FM.DeviceFmi(idx, rs, torch.device("cuda:0"))
         d.set_sa(smp)
-        d.run(s.cuda_stream)
-        d.sal(500, pos_cap=cap, stream=s.cuda_stream)
-        mc = MC.DeviceMemChain(d, len(g), co)
-        mc.run(s.cuda_stream)
-        ext = mc.extension(text)
-        ext.run(sp, s.cuda_stream)
+        front = Stages(d, text, len(g), co, caps=dict(pos_cap=cap)).queue(s.cuda_stream, last="extend")
         p = MG.make_params()
         z_bytes = 1000 * MG.lib().gbx_mem_cigar_record_z_bytes(C.byref(p), 101, 200)
-        sam, (rg, rsc, pe, cg, sm) = SM.pipeline(ext, names, qual, cnames, s.cuda_stream, pair_id0, cigar_params=p, cigar_cap=8 * cap,
+        sam, (rg, rsc, pe, cg, sm) = SM.pipeline(front.extend, names, qual, cnames, s.cuda_stream, pair_id0, cigar_params=p, cigar_cap=8 * cap,
                                                  z_bytes=z_bytes)
     s.synchronize()
     assert int(d.n_pos.item()) <= cap and not d.overflow()
