@@ -132,7 +132,8 @@ class AbeaMethReadSet:
 
 class DeviceAbeaMethJobSet:
     """An AbeaMethJobSet resident in HBM (torch tensors) with its plan and the scores.  `reads` may hand over device tensors
-    (event_off, event_mean, scale, shift) that already live there, as DeviceAbeaSignalSet / DeviceAbeaReadSet hold them."""
+    (event_off, event_mean, scale, shift, and optionally var, log_var) that already live there, as DeviceAbeaSignalSet /
+    DeviceAbeaReadSet / DeviceAbeaCalib hold them."""
 
     def __init__(self, js, device, reads=None):
         import torch
@@ -147,6 +148,7 @@ class DeviceAbeaMethJobSet:
             reads = dict(event_off=t(js.event_off), event_mean=t(np.concatenate([js.event_mean, np.zeros(4, np.float32)])),
                          scale=t(js.scale), shift=t(js.shift))
         d.update({k: reads[k] for k in ("event_off", "event_mean", "scale", "shift")})
+        d.update({k: reads[k] for k in ("var", "log_var") if k in reads})          # DeviceAbeaCalib.reads() holds these too
         self.d = d
         self.scores = torch.zeros(max(self.n_jobs, 1), dtype=torch.float32, device=device)
 

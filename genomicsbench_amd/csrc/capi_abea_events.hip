@@ -8,14 +8,14 @@ static int abea_signal_host(const char *who, bool align, int64_t n_reads, const 
                             const float *digitisation, const float *offset, const int64_t *seq_off, const int32_t *seq_len, const char *seq_arena,
                             int64_t seq_bytes, const gbx_abea_model *models, int64_t *n_events, int64_t *event_off, gbx_abea_event *events,
                             int64_t event_cap, int64_t *n_events_total, float *scale, float *shift, int32_t *status, gbx_abea_pair *out,
-                            int32_t *n_pairs)
+                            int32_t *n_pairs, abea_tail_fn tail = nullptr, void *tail_ctx = nullptr)
 {
     RoctxRange range_(who);
     if (n_reads < 0 || event_cap < 0 || (align && seq_bytes < 0)) { set_error("%s: bad argument", who); return GBX_ERR_ARG; }
     if (n_events_total) *n_events_total = 0;
     if (n_reads == 0) { if (event_off) event_off[0] = 0; return GBX_OK; }
     if (!raw || !raw_off || !range || !digitisation || !offset || !event_off || (!events && event_cap > 0) || !n_events_total || !status ||
-        (align && (!seq_off || !seq_len || !seq_arena || !models || !scale || !shift || !out || !n_pairs))) {
+        (align && (!seq_off || !seq_len || !seq_arena || !models || !scale || !shift || (!out && !tail) || !n_pairs))) {
         set_error("%s: null pointer", who);
         return GBX_ERR_ARG;
     }
@@ -71,7 +71,7 @@ static int abea_signal_host(const char *who, bool align, int64_t n_reads, const 
     for (int64_t r = 0; r < n_reads; ++r) event_off[r + 1] = event_off[r] + n_events[r];
     const int64_t total = event_off[n_reads];
     *n_events_total = total;
-    if (total > event_cap) {
+    if (total > event_cap && !tail) {                                         // with a tail the records stay on the device
         set_error("%s: %lld events, room for %lld", who, (long long)total, (long long)event_cap);
         return pipe.finish(GBX_ERR_ARG);
     }
@@ -79,7 +79,7 @@ static int abea_signal_host(const char *who, bool align, int64_t n_reads, const 
     if ((rc = abea_events_launch(GBX_ABEA_EVENTS_FILL, n_reads, draw.as<int16_t>(), dro.as<int64_t>(), drg.as<float>(), ddg.as<float>(), dof.as<float>(),
                                  dne.as<int64_t>(), deo.as<int64_t>(), dev.as<gbx_abea_event>(), dem.as<float>(), total, dst.as<int32_t>(), cs)))
         return pipe.finish(rc);
-    if (total) EV_HIP(hipMemcpyAsync(events, dev.p, (size_t)total * sizeof(gbx_abea_event), hipMemcpyDeviceToHost, cs));
+    if (total && !tail) EV_HIP(hipMemcpyAsync(events, dev.p, (size_t)total * sizeof(gbx_abea_event), hipMemcpyDeviceToHost, cs));
     if (!align) {
         EV_HIP(hipStreamSynchronize(cs));
         return pipe.finish();
@@ -129,6 +129,12 @@ static int abea_signal_host(const char *who, bool align, int64_t n_reads, const 
         return pipe.finish(rc);
     EV_HIP(hipMemcpyAsync(cnp.data(), dnp.p, (size_t)m * 4, hipMemcpyDeviceToHost, cs));
     EV_HIP(hipStreamSynchronize(cs));
+    if (tail) {
+        for (int64_t k = 0; k < m; ++k) n_pairs[keep[(size_t)k]] = cnp[(size_t)k];
+        const AbeaAligned a{L, n_reads, seq_bytes, event_off, n_pairs, dso.as<int64_t>(), dsl.as<int32_t>(), dsq.as<char>(), deo.as<int64_t>(),
+                            dem.as<float>(), dmo.as<gbx_abea_model>(), dsc.as<float>(), dsh.as<float>(), dout.as<gbx_abea_pair>()};
+        return pipe.finish(tail(tail_ctx, a));
+    }
     // half of the 2 x n_events slots are slack: the pairs are packed on the device, come back in one piece and go to
     // the reads' places from there
     int64_t tot = 0;
@@ -152,6 +158,19 @@ static int abea_signal_host(const char *who, bool align, int64_t n_reads, const 
     return pipe.finish();
 #undef EV_HIP
 }
+
+namespace gbx {
+int abea_signal_align_tail(const char *who, int64_t n_reads, const int16_t *raw, const int64_t *raw_off, const float *range, const float *digitisation,
+                           const float *offset, const int64_t *seq_off, const int32_t *seq_len, const char *seq_arena, int64_t seq_bytes,
+                           const gbx_abea_model *models, int32_t *status, float *scale, float *shift, abea_tail_fn tail, void *ctx)
+{
+    std::vector<int64_t> event_off((size_t)(n_reads > 0 ? n_reads : 0) + 1);
+    std::vector<int32_t> n_pairs((size_t)(n_reads > 0 ? n_reads : 0) + 1);
+    int64_t total = 0;
+    return abea_signal_host(who, true, n_reads, raw, raw_off, range, digitisation, offset, seq_off, seq_len, seq_arena, seq_bytes, models, nullptr,
+                            event_off.data(), nullptr, 0, &total, scale, shift, status, nullptr, n_pairs.data(), tail, ctx);
+}
+}  // namespace gbx
 
 extern "C" {
 

@@ -382,6 +382,15 @@ int abea_meth_launch(int64_t n_jobs, const gbx_abea_meth_job *d_jobs, const char
                      const float *d_flogsum, const float *d_trans, const float *d_pre, const float *d_post, const int32_t *d_order,
                      const int64_t *class_off, float *d_scores, hipStream_t s);
 
+// ---- abea calibration and event-alignment record (abea_calib_kernels.hip)
+int abea_calib_launch(int64_t n_reads, const int64_t *d_seq_off, const int32_t *d_seq_len, const char *d_seq, const int64_t *d_event_off,
+                      const float *d_event_mean, const gbx_abea_model *d_models, const gbx_abea_pair *d_pairs, const int32_t *d_n_pairs,
+                      float *d_scale, float *d_shift, float *d_var, double *d_var64, int32_t *d_map, double *d_events_per_base,
+                      int32_t *d_n_event_alignment, int32_t *d_n_m_state, int32_t *d_flags, hipStream_t s);
+int abea_record_launch(int pass, int64_t n_reads, const int64_t *d_cigar_off, const uint32_t *d_cigar, const int32_t *d_pos, const uint8_t *d_rc,
+                       const int64_t *d_seq_off, const int32_t *d_seq_len, const int32_t *d_map, const int32_t *d_flags, int32_t *d_near,
+                       int64_t *d_rec_off, gbx_abea_pair *d_rec, int64_t rec_cap, hipStream_t s);
+
 // ---- poa (poa_kernels.hip)
 constexpr int POA_PIPE_MAXLEN = 512;     // longest sequence of the pipelined DP (two-plane slots)
 size_t poa_slot_bytes(int ncap, int deg, int lmax, bool long_slot);

@@ -274,6 +274,71 @@ def gen_abea_meth(n_reads, seed, first=0):
     return ms
 
 
+def bam_cigar(ops):
+    """[(length, op letter)] -> the BAM encoding, len << 4 | code with MIDNSHP=X as 0..8"""
+    return np.array([(int(n) << 4) | "MIDNSHP=X".index(o) for n, o in ops], dtype=np.uint32)
+
+
+def gen_abea_cigars(ss, seed, first=0):
+    """Alignments for the reads of gen_abea_raw / gen_abea(n_reads, seed, first), as call-methylation reads them from a BAM: per
+    read a CIGAR (hard and soft clips at either end, between them blocks of M or = separated by an insertion, a deletion
+    or a run of X), pos, rc (one read in four; the CIGAR then describes the reverse complement of the bases) and the
+    reference segment derived from the read through the CIGAR: = and M copy the read's bases (one M base in 50 is changed),
+    X changes them, D draws reference bases, I, S and H leave none.  -> dict(cigar_off, cigar, pos, rc, ref_off, ref_len,
+    ref_arena, cpg_model)."""
+    n_reads = ss.n_reads
+    ridx = np.arange(first, first + n_reads)
+    rc = (_unif(seed, 0x5C, ridx) < 0.25).astype(np.uint8)
+    pos = (1000 + 100000 * _unif(seed, 0x57A, ridx)).astype(np.int32)
+    comp = np.zeros(256, np.uint8); comp[:] = ord("T")
+    for a, b in zip(b"ACGT", b"TGCA"):
+        comp[a] = b
+    other = np.zeros(256, np.uint8); other[:] = ord("C")               # a base that differs from the read's
+    for a, b in zip(b"ACGT", b"CGTA"):
+        other[a] = b
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    cigars, refs = [], []
+    for r in range(n_reads):
+        rng = np.random.default_rng([int(seed), 0xC16A, int(first) + r])
+        n = int(ss.seq_len[r])
+        q = ss.seq_arena[ss.seq_off[r]:ss.seq_off[r] + n]
+        q = comp[q[::-1]] if rc[r] else q
+        s0, s1 = (int(rng.integers(0, min(24, n // 8) + 1)) for _ in range(2))
+        ops, ref, i, end = [], [], s0, n - s1
+        if rng.random() < 0.5:
+            ops.append((int(rng.integers(1, 30)), "H"))
+        if s0:
+            ops.append((s0, "S"))
+        while i < end:
+            m = min(int(rng.integers(8, 90)), end - i)
+            kind = "=" if rng.random() < 0.4 else "M"
+            seg = q[i:i + m].copy()
+            if kind == "M":
+                hit = rng.random(m) < 0.02
+                seg[hit] = other[seg[hit]]
+            ops.append((m, kind)); ref.append(seg); i += m
+            if i >= end:
+                break
+            e, k = rng.random(), min(int(rng.integers(1, 4)), end - i)
+            if e < 0.35:
+                ops.append((k, "I")); i += k
+            elif e < 0.7:
+                ops.append((k, "D")); ref.append(acgt[rng.integers(0, 4, k)])
+            else:
+                ops.append((k, "X")); ref.append(other[q[i:i + k]]); i += k
+        if s1:
+            ops.append((s1, "S"))
+        if rng.random() < 0.5:
+            ops.append((int(rng.integers(1, 30)), "H"))
+        cigars.append(bam_cigar(ops))
+        refs.append(np.concatenate(ref) if ref else np.zeros(0, np.uint8))
+    cigar_off = np.zeros(n_reads + 1, np.int64); np.cumsum([len(c) for c in cigars], out=cigar_off[1:])
+    ref_len = np.array([len(x) for x in refs], np.int32)
+    ref_off = np.zeros(n_reads, np.int64); ref_off[1:] = np.cumsum(ref_len[:-1])
+    return dict(cigar_off=cigar_off, cigar=np.concatenate(cigars + [np.zeros(0, np.uint32)]), pos=pos, rc=rc, ref_off=ref_off, ref_len=ref_len,
+                ref_arena=np.concatenate(refs + [np.zeros(8, np.uint8)]), cpg_model=gen_abea_cpg_model(ss.model, seed))
+
+
 def gen_fmi_genome(length, seed):
     """Synthetic genome (one strand, base codes 0..3) with repeat families and low-complexity runs."""
     L = _L()

@@ -540,6 +540,100 @@ int gbx_abea_meth_sites_host(int64_t n_reads, const int64_t *ref_off, const int3
                              int64_t site_cap, gbx_abea_meth_site *sites, gbx_abea_meth_job *jobs, int64_t *n_sites,
                              int64_t seq_cap, char *seq_arena, int64_t *seq_bytes);
 
+/* abea, calibration and the event-alignment record: what f5c runs per read between align() and the methylation score.
+ * Replaces  int32_t postalign(alignment, base_to_event_map, events_per_base, sequence, n_kmers, event_alignment, n_events)
+ *                                                                                              align.c:550-650
+ *           bool recalibrate_model(pore_model, et, scallings, alignment_output, num_alignments, scale_var = 1)
+ *                                                                                              align.c:655-762
+ *           with the three QC rules of scaling_single                                          f5c.c:1262-1330
+ *           int32_t get_event_alignment_record(record, read_length, base_to_event_map, &aligned_events)   meth.c:15-185
+ * Bit for bit the reference's order of operations: the five sums of the normal equations and the residual sum are double
+ * accumulations in k-mer order, division and square root are the correctly rounded double ones.  The event_alignment_t
+ * array is not materialised: a k-mer with events gives stop - start + 1 records, the first of them 'M' (its event:
+ * start) when its rank differs from the rank of the previous k-mer with events, every other one 'E' and in no sum.
+ * The one assumption: the pairs of a read never decrease in either field, as align() writes them (align.c:476-487); the
+ * host entry checks it.
+ * Per read r: flags[r] = GBX_ABEA_FAILED_ALIGNMENT when n_pairs[r] == 0 (map all -1, events_per_base 0, scalings
+ * untouched); GBX_ABEA_FAILED_CALIBRATION with fewer than 200 M states (scale, shift unchanged; var, which the reference
+ * leaves uninitialised there, is 0) or when the recalibrated var is above 2.5 (scale, shift and var are overwritten
+ * all the same); GBX_ABEA_FAILED_QUALITY_CHK when events_per_base > 5.0, tested only when calibration did not fail.
+ * The map: int32 (start, stop) per k-mer, (-1, -1) for a k-mer without events; read r's seq_len[r] - 5 entries at
+ * map + 2 * seq_off[r] (ints), the slots behind them unspecified.  events_per_base = (double)(max_event - min_event) /
+ * n_kmers with min_event starting at INT32_MAX and max_event at 0, as written. */
+#define GBX_ABEA_FAILED_CALIBRATION 1   /* FAILED_CALIBRATION, f5c.h:49 */
+#define GBX_ABEA_FAILED_ALIGNMENT   2   /* FAILED_ALIGNMENT,   f5c.h:50 */
+#define GBX_ABEA_FAILED_QUALITY_CHK 4   /* FAILED_QUALITY_CHK, f5c.h:51 */
+#define GBX_ABEA_RECORD_COUNT 1         /* pass: the record lengths and rec_off */
+#define GBX_ABEA_RECORD_FILL  2         /* pass: the records at the rec_off of a count pass */
+
+/* Device entry, on what gbx_abea_align_device leaves: d_event_off ABSOLUTE as there, read r's pairs at d_pairs +
+ * 2 * d_event_off[r], d_n_pairs[r] of them.  d_scale / d_shift are never read; for a recalibrated read they are overwritten,
+ * for every other read they are left as they were.
+ * d_var64 is the double that var was stored from (its logarithm is taken on the host, below).  d_map holds 2 ints per
+ * base of the arena.  Nothing is synchronised. */
+int gbx_abea_calib_device(int64_t n_reads, const int64_t *d_seq_off, const int32_t *d_seq_len, const char *d_seq_arena,
+                          const int64_t *d_event_off, const float *d_event_mean, const gbx_abea_model *d_models,
+                          const gbx_abea_pair *d_pairs, const int32_t *d_n_pairs, float *d_scale, float *d_shift,
+                          float *d_var, double *d_var64, int32_t *d_map, double *d_events_per_base,
+                          int32_t *d_n_event_alignment, int32_t *d_n_m_state, int32_t *d_flags, void *stream);
+/* log_var[r] = (float)log(var64[r]) (scallings->log_var, align.c:749: a double logarithm, taken with the host C library
+ * so that it carries the reference's bits) for the reads recalibration ran on (n_m_state[r] >= 200), 0 for the others. */
+int gbx_abea_calib_logvar_host(int64_t n_reads, const double *var64, const int32_t *n_m_state, float *log_var);
+/* Host-buffer entry (one device).  events: the 24-byte records; pairs as gbx_abea_align_host returns them (2 *
+ * event_off[n_reads] slots); map: 2 * seq_bytes ints.  Checked before the device is touched, GBX_ERR_ARG naming the
+ * lowest offender: reads inside the arena with at least KMER bases, 0 <= n_pairs <= 2 * n_events, every pair inside
+ * the read's k-mers and events, and no pair below the one before it in either field. */
+int gbx_abea_calib_host(int64_t n_reads, const int64_t *seq_off, const int32_t *seq_len, const char *seq_arena,
+                        int64_t seq_bytes, const int64_t *event_off, const gbx_abea_event *events,
+                        const gbx_abea_model *models, const gbx_abea_pair *pairs, const int32_t *n_pairs, float *scale,
+                        float *shift, float *var, float *log_var, double *var64, int32_t *map, double *events_per_base,
+                        int32_t *n_event_alignment, int32_t *n_m_state, int32_t *flags);
+
+/* The event-alignment record of read r from its BAM-encoded CIGAR (len << 4 | op; cigar[cigar_off[r] .. cigar_off[r+1])),
+ * pos[r], rc[r], seq_len[r] and its map: get_aligned_segments (M, = and X advance both positions and emit a pair, D the
+ * reference, I and S the read, H nothing), the boundary skip (read_pos < 6 or read_pos + 6 >= read_length), the strand
+ * flip (read_length - read_pos - 6), get_closest_event_to (backwards over k_idx .. max(0, k_idx - 1000) + 1, else forwards
+ * over k_idx .. min(k_idx + 1000, n_kmers - 1) - 1; -1 is a legal result) and the degenerate rule (first event == last
+ * event: length 0).  Output: the compact record gbx_abea_meth_sites_host consumes, rec_off[n_reads + 1] and (ref_pos,
+ * event index) pairs.
+ * Device entry.  pass = COUNT writes d_rec_off[n_reads + 1] and the workspace d_near (2 ints per base of the arena, like
+ * the map); pass = FILL writes the records of a count pass over the same input; a read whose record would end past
+ * rec_cap is left unwritten.  COUNT | FILL does both (a record never has more than seq_len - 12 pairs).  d_flags may be
+ * NULL; a read with a non-zero flag gets an empty record (meth_single, f5c.c:1376).  An operation the reference refuses
+ * (N, P, a code above 8) advances nothing here.  Nothing is synchronised. */
+int gbx_abea_event_record_device(int pass, int64_t n_reads, const int64_t *d_cigar_off, const uint32_t *d_cigar,
+                                 const int32_t *d_pos, const uint8_t *d_rc, const int64_t *d_seq_off, const int32_t *d_seq_len,
+                                 const int32_t *d_map, const int32_t *d_flags, int32_t *d_near, int64_t *d_rec_off,
+                                 gbx_abea_pair *d_rec, int64_t rec_cap, void *stream);
+/* Host-buffer entry (one device).  map: 2 * seq_bytes ints; flags may be NULL.  *n_rec = the pairs of all records; more
+ * than rec_cap gives GBX_ERR_ARG with the needed count there and in gbx_last_error() (rec_off is valid then; call with
+ * 0 / NULL to size).  Refused with GBX_ERR_ARG where the reference exits or asserts: operation N (meth.c:54-58), P or a
+ * code above 8 (meth.c:65-68), more aligned bases than seq_len (meth.c:135). */
+int gbx_abea_event_record_host(int64_t n_reads, const int64_t *cigar_off, const uint32_t *cigar, const int32_t *pos,
+                               const uint8_t *rc, const int64_t *seq_off, const int32_t *seq_len, int64_t seq_bytes,
+                               const int32_t *map, const int32_t *flags, int64_t *rec_off, int64_t rec_cap,
+                               gbx_abea_pair *rec, int64_t *n_rec);
+
+/* call-methylation from raw signal in one call (one device): events -> scalings -> align -> calibration -> record ->
+ * site planner -> score, what f5c runs per batch between reading its input and writing its TSV (process_db,
+ * f5c.c:1219-1400, mode 0).  Signal, reads and model as gbx_abea_signal_align_host; the CpG model as
+ * gbx_abea_meth_score_host; CIGARs, pos and rc as gbx_abea_event_record_host; the reference segments as
+ * gbx_abea_meth_sites_host with ref_start_pos = pos.  The events, their means and the scalings stay on the device: what
+ * comes down is the event counts, the per-read calibration (log_var is taken on the host) and the record of the
+ * unflagged reads; the site planner runs on the host and its jobs go back up.
+ * Per read: flags (a read without events: GBX_ABEA_FAILED_ALIGNMENT), scale, shift, var, events_per_base, status (the
+ * event stage's).  Sites of all unflagged reads in read order, scores[2 s] the unmethylated and scores[2 s + 1] the
+ * methylated score of site s; ctx_off refers to the read's reference segment.  More sites than site_cap: GBX_ERR_ARG
+ * with the needed count in *n_sites (the per-read outputs are valid then; call with 0 / NULL to size). */
+int gbx_abea_call_methylation_host(int64_t n_reads, const int16_t *raw, const int64_t *raw_off, const float *range,
+                                   const float *digitisation, const float *offset, const int64_t *seq_off,
+                                   const int32_t *seq_len, const char *seq_arena, int64_t seq_bytes,
+                                   const gbx_abea_model *models, const gbx_abea_model *cpg_model, const int64_t *cigar_off,
+                                   const uint32_t *cigar, const int32_t *pos, const uint8_t *rc, const int64_t *ref_off,
+                                   const int32_t *ref_len, const char *ref_arena, int32_t *flags, int32_t *status,
+                                   float *scale, float *shift, float *var, double *events_per_base, int64_t site_cap,
+                                   gbx_abea_meth_site *sites, float *scores, int64_t *n_sites);
+
 /* --------------------------------------------------------------------- fmi
  * SMEM seeding on the FM-index of reference + reverse complement (second half): the three
  * seeding rounds bwa-mem2 runs per batch of reads and the driver times,
