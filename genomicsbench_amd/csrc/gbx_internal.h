@@ -292,6 +292,27 @@ int64_t mem_sam_rec_max(int64_t n_reads, int64_t reg_cap, int64_t n_alns);      
 size_t mem_sam_workspace_bytes(int64_t n_reads, int64_t reg_cap, int64_t n_alns);
 int mem_sam_launch(const gbx_mem_sam_params *p, int64_t n_reads, int mode, const MemSamIo &io, void *d_work, size_t work_bytes, hipStream_t s);
 
+// ---- minimizer seeding in front of chain (mm_kernels.hip; the machine: mm_machine.h)
+struct MmIndexView { int64_t *hdr; uint64_t *keys; int64_t *koff; uint64_t *vals; };      // hdr: n_vals, n_keys, mid_occ, k, w, is_hpc
+MmIndexView mm_index_view(void *d_index, int64_t mini_cap);
+size_t mm_index_bytes(int64_t mini_cap);
+size_t mm_sketch_workspace_bytes(const gbx_mm_params *p, int64_t n_seqs, int64_t total_len);
+int mm_sketch_launch(const gbx_mm_params *p, int64_t n_seqs, const uint8_t *d_seq, const int64_t *d_seq_off, int64_t total_len, int rid_ordinal,
+                     uint64_t *d_mx, uint64_t *d_my, int64_t mini_cap, int64_t *d_mini_off, int64_t *d_n_mini, void *d_work, size_t work_bytes,
+                     hipStream_t s);
+size_t mm_index_workspace_bytes(const gbx_mm_params *p, int64_t n_seqs, int64_t total_len, int64_t mini_cap);
+int mm_index_launch(const gbx_mm_params *p, int64_t n_seqs, const uint8_t *d_seq, const int64_t *d_seq_off, int64_t total_len, void *d_index,
+                    int64_t mini_cap, void *d_work, size_t work_bytes, hipStream_t s);
+struct MmSeedIo {                    // the device arguments of gbx_mm_seed_device
+    const void *index; int64_t index_mini_cap, ref_n_seqs, ref_max_len;
+    int64_t n_reads; const uint8_t *seq; const int64_t *seq_off; int64_t total_len;
+    uint64_t *mini_x, *mini_y; int64_t mini_cap; int64_t *mini_off;
+    uint64_t *ax, *ay; int64_t anchor_cap; int64_t *off; gbx_chain_call *hdr;
+    int32_t *rep_len, *n_mini; int64_t *counts;
+};
+size_t mm_seed_workspace_bytes(const gbx_mm_params *p, int64_t n_reads, int64_t total_len, int64_t mini_cap, int64_t anchor_cap);
+int mm_seed_launch(const gbx_mm_params *p, const MmSeedIo &io, void *d_work, size_t work_bytes, hipStream_t s);
+
 // ---- the aligner's gather behind the chain (mem_align_kernels.hip): every stage's count into one record
 struct MemAlignGather {              // a null pointer: the stage does not run, its count is 0
     const unsigned long long *fmi_counters;         // the fmi workspace: [2] is the slot overflow word fmi_read_overflow reads

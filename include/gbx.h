@@ -1734,6 +1734,97 @@ int gbx_dbg_graph_device(const gbx_dbg_params *p, const gbx_dbg_reads *reads, co
                          const int64_t *d_node_off, const int64_t *d_edge_off, gbx_dbg_node *d_nodes, gbx_dbg_edge *d_edges,
                          void *d_work, size_t work_bytes, void *stream);
 
+/* ------------------------------------------------------------------- mm: minimizer seeding in front of chain
+ * minimap2's seeding stage: the minimizer sketch (mm_sketch), the minimizer index (mm_idx_*) and seed collection with the
+ * occurrence filter (collect_matches + collect_seed_hits): what fmi + fmi_sal are for bsw, this is for chain.  UNPINNED by a
+ * compiled reference (minimap2's source is not part of the reference tree): the rules are restated in full in DESIGN 3.18 and
+ * tests/mm_ref.py, and pinned by that restatement.
+ * Sequences are text, one byte per base: A C G T in either case are codes 0..3, every other byte is ambiguous.  Sequence s =
+ * seq[seq_off[s] .. seq_off[s + 1]); seq_off[0] = 0, never decreasing.
+ *   sketch   the (x, y) pairs of minimap2's sequential machine, bit for bit and in its order: x = hash64(k-mer) << 8 | span,
+ *            y = rid << 32 | last base << 1 | strand.  A sequence is taken in pieces of GBX_MM_SKETCH_CHUNK bases, each
+ *            warm-started w + k steps ahead (exact for odd k; for even k a sequence is one piece, one lane).
+ *   index    the minimizers of every reference sequence (rid = its ordinal) grouped by x >> 8: sorted distinct keys, a CSR of
+ *            their values y in ascending order (minimap2's order inside a key comes from an unstable sort), and mid_occ
+ *   seeding  per read (rid 0): every minimizer whose key occurs fewer than mid_occ times gives one anchor per occurrence,
+ *            the others feed rep_len; a read's anchors ascending by x, ties by the whole of y (minimap2 sorts by x alone,
+ *            unstably); the output is a chain batch: off, ax, ay and one gbx_chain_call per read.
+ * Not modelled: multi-segment reads, index batches and .mmi files, the self / dual filters, re-seeding. */
+#define GBX_MM_SKETCH_CHUNK 256
+#define GBX_MM_SEED_TANDEM  (1ull << 42)   /* MM_SEED_TANDEM in ay */
+#define GBX_MM_MAX_READS    (1 << 21)      /* reads of one seeding call (the sort key holds the read in 21 bits) */
+typedef struct gbx_mm_params {
+    int32_t k;             /* 15; 1..28 */
+    int32_t w;             /* 10; 1..255 */
+    int32_t is_hpc;        /* 0; homopolymer-compressed k-mers */
+    int32_t mid_occ;       /* 0: from mid_occ_frac; > 0: the threshold itself */
+    float   mid_occ_frac;  /* 2e-4; <= 0: INT32_MAX; below 1 */
+    int32_t max_gap;       /* 5000: max_dist_x = max_dist_y of the calls */
+    int32_t bw;            /* 500 */
+} gbx_mm_params;
+typedef struct gbx_mm_index_info {
+    int64_t n_keys, n_vals;    /* distinct keys, minimizers */
+    int32_t mid_occ;
+    int32_t k, w, is_hpc;      /* what it was built with */
+} gbx_mm_index_info;
+
+void gbx_mm_default_params(gbx_mm_params *p);
+/* GBX_ERR_ARG naming the field: k outside 1..28, w outside 1..255, a negative mid_occ, max_gap or bw, a mid_occ_frac that is not
+ * a number or is 1 or more.  Needs no device. */
+int gbx_mm_check_params(const gbx_mm_params *p);
+
+/* Sketch of n_seqs sequences (total_len = seq_off[n_seqs] bytes).  rid_ordinal != 0: sequence s has rid s, else every rid is 0.
+ * Sequence s owns minimizers [mini_off[s], mini_off[s + 1]); *n_mini = their number, which may exceed mini_cap: then only the
+ * first mini_cap are written and the offsets stay true.  The device entry does no host synchronisation. */
+size_t gbx_mm_sketch_workspace_bytes(const gbx_mm_params *p, int64_t n_seqs, int64_t total_len);
+int gbx_mm_sketch_device(const gbx_mm_params *p, int64_t n_seqs, const uint8_t *d_seq, const int64_t *d_seq_off, int64_t total_len,
+                         int32_t rid_ordinal, uint64_t *d_mini_x, uint64_t *d_mini_y, int64_t mini_cap, int64_t *d_mini_off,
+                         int64_t *d_n_mini, void *d_work, size_t work_bytes, void *stream);
+/* Checked before the device is touched, GBX_ERR_ARG naming the lowest offender: null pointers, seq_off[0] != 0, offsets that
+ * decrease; GBX_ERR_UNSUPPORTED: a sequence of 2^31 bases or more, 2^31 sequences or more.  More minimizers than mini_cap:
+ * GBX_ERR_ARG with the needed count in *n_mini and gbx_last_error() (mini_off is written; call with 0 / NULL to size). */
+int gbx_mm_sketch_host(const gbx_mm_params *p, int64_t n_seqs, const uint8_t *seq, const int64_t *seq_off, int32_t rid_ordinal,
+                       uint64_t *mini_x, uint64_t *mini_y, int64_t mini_cap, int64_t *mini_off, int64_t *n_mini);
+
+/* The index on the device: one allocation of gbx_mm_index_bytes(mini_cap) bytes for up to mini_cap minimizers (total_len is
+ * always enough).  gbx_mm_index_build_device queues the whole build on `stream` without synchronising; gbx_mm_index_stats
+ * synchronises it and reads the counts: GBX_ERR_ARG with the need in gbx_last_error() when the reference has more than mini_cap
+ * minimizers (such an index must not be used). */
+size_t gbx_mm_index_bytes(int64_t mini_cap);
+size_t gbx_mm_index_workspace_bytes(const gbx_mm_params *p, int64_t n_seqs, int64_t total_len, int64_t mini_cap);
+int gbx_mm_index_build_device(const gbx_mm_params *p, int64_t n_seqs, const uint8_t *d_seq, const int64_t *d_seq_off, int64_t total_len,
+                              void *d_index, int64_t mini_cap, void *d_work, size_t work_bytes, void *stream);
+int gbx_mm_index_stats(const void *d_index, int64_t mini_cap, gbx_mm_index_info *st, void *stream);
+/* Host buffers in and out: keys[key_cap], key_off[key_cap + 1] (key j owns vals[key_off[j] .. key_off[j + 1])), vals[val_cap].
+ * The checks of gbx_mm_sketch_host; counts above the capacities: GBX_ERR_ARG with the need in *st and gbx_last_error() (call
+ * with 0 / NULL to size). */
+int gbx_mm_index_build_host(const gbx_mm_params *p, int64_t n_seqs, const uint8_t *seq, const int64_t *seq_off,
+                            uint64_t *keys, int64_t *key_off, int64_t key_cap, uint64_t *vals, int64_t val_cap, gbx_mm_index_info *st);
+
+/* Seeding of n_reads reads (at most GBX_MM_MAX_READS, total_len bytes) against an index built with the same k, w and is_hpc;
+ * the index's mid_occ applies.  ref_n_seqs / ref_max_len: the reference's sequence count and longest sequence (they bound the
+ * digits the anchor sort visits; larger values are safe).  Output: the chain batch off[n_reads + 1], ax, ay, hdr[n_reads]
+ * (avg_qspan = (float)sum of the anchors' spans / their number, 0 without anchors; max_dist_x = max_dist_y = max_gap; bw;
+ * n_segs = 1), rep_len[n_reads], n_mini[n_reads], the reads' minimizers (mini_off, mini_x, mini_y) and counts[2] = minimizers,
+ * anchors.  A count above its capacity reports the need, nothing is written past a capacity, off and mini_off stay true (with
+ * more minimizers than mini_cap the anchors are not made: counts[1] = -1).  The device entry does no host synchronisation. */
+size_t gbx_mm_seed_workspace_bytes(const gbx_mm_params *p, int64_t n_reads, int64_t total_len, int64_t mini_cap, int64_t anchor_cap);
+int gbx_mm_seed_device(const gbx_mm_params *p, const void *d_index, int64_t index_mini_cap, int64_t ref_n_seqs, int64_t ref_max_len,
+                       int64_t n_reads, const uint8_t *d_seq, const int64_t *d_seq_off, int64_t total_len,
+                       uint64_t *d_mini_x, uint64_t *d_mini_y, int64_t mini_cap, int64_t *d_mini_off,
+                       uint64_t *d_ax, uint64_t *d_ay, int64_t anchor_cap, int64_t *d_off, gbx_chain_call *d_hdr,
+                       int32_t *d_rep_len, int32_t *d_n_mini, int64_t *d_counts, void *d_work, size_t work_bytes, void *stream);
+/* Host buffers in and out; the index as gbx_mm_index_build_host left it (n_keys keys, mid_occ the threshold to apply).  The
+ * checks of gbx_mm_sketch_host on the reads, and on the index: key_off from 0, never decreasing.  mini_x / mini_y / mini_off may
+ * be NULL (mini_cap 0).  Counts above the capacities: GBX_ERR_ARG with the needed counts in counts[2] and gbx_last_error() (off,
+ * hdr, rep_len and n_mini are written). */
+int gbx_mm_seed_host(const gbx_mm_params *p, const uint64_t *keys, const int64_t *key_off, int64_t n_keys, const uint64_t *vals,
+                     int32_t mid_occ, int64_t ref_n_seqs, int64_t ref_max_len,
+                     int64_t n_reads, const uint8_t *seq, const int64_t *seq_off,
+                     uint64_t *mini_x, uint64_t *mini_y, int64_t mini_cap, int64_t *mini_off,
+                     uint64_t *ax, uint64_t *ay, int64_t anchor_cap, int64_t *off, gbx_chain_call *hdr,
+                     int32_t *rep_len, int32_t *n_mini, int64_t *counts);
+
 #ifdef __cplusplus
 }
 #endif

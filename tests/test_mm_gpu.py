@@ -1,0 +1,221 @@
+"""Minimizer seeding on the GPU (gbx_mm_sketch_*, gbx_mm_index_*, gbx_mm_seed_*), compared exactly, order included, with the
+restatement tests/mm_ref.py; then reads -> anchors -> chain scores on one stream against the chain oracle, and the mmseed driver."""
+import os
+import random
+import subprocess
+
+import numpy as np
+import pytest
+
+from genomicsbench_amd import _native as N
+from genomicsbench_amd import io as gio
+from genomicsbench_amd import mm_seed as MS
+from genomicsbench_amd.chain import DeviceChainBatch
+from oracle import oracle_py as O
+import mm_cases as K
+import mm_ref as R
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "genomicsbench_amd", "bin")
+GUARD = 0x5a5a5a5a5a5a5a5a
+FIELDS = ("off", "ax", "ay", "hdr", "rep_len", "n_mini", "mini_off", "mini_x", "mini_y")
+
+
+def dev():
+    import torch
+    return torch.device("cuda:0")
+
+
+def stream():
+    import torch
+    return torch.cuda.current_stream().cuda_stream
+
+
+@pytest.mark.parametrize("w,k,hpc", K.SKETCH_PARAMS)
+def test_sketch_batch(w, k, hpc):
+    """Every edge length, alphabet and hand case of mm_cases.sketch_batch in one call, with reads of 5 000 and 70 000 bases: pieces of
+    GBX_MM_SKETCH_CHUNK = 256 bases, so the long reads cross some 20 and 270 piece borders."""
+    assert MS.SKETCH_CHUNK == K.CHUNK
+    seqs = K.sketch_batch(w, k, hpc)
+    x, y, off = MS.sketch_host(MS.make_params(w=w, k=k, is_hpc=hpc), seqs)
+    wx, wy, woff = K.sketch_expected(w, k, hpc)
+    assert np.array_equal(off, woff)
+    assert np.array_equal(x, wx) and np.array_equal(y, wy)
+
+
+def test_sketch_hand_cases():
+    p = MS.make_params(w=3, k=3)
+    x, y, off = MS.sketch_host(p, [K.SEVENTEEN, b"", b"AC"], rid_ordinal=False)
+    assert [R.unpack(m) for m in zip(x.tolist(), y.tolist())] == [(23, 3, 4, 1), (26, 3, 6, 1), (33, 3, 7, 0), (15, 3, 10, 0), (12, 3, 12, 1),
+                                                                  (5, 3, 15, 0), (5, 3, 16, 1)]
+    assert off.tolist() == [0, 7, 7, 7]
+    x, y, off = MS.sketch_host(MS.make_params(w=2, k=4), [b"AT" * 40, b"ATATATGCGCATTAATCGAT"])
+    assert off.tolist() == [0, 0, 11] and (y >> np.uint64(32) == 1).all()
+    x, y, off = MS.sketch_host(MS.make_params(w=10, k=19, is_hpc=1), [K.rand_seq(random.Random(6), 60) + b"A" * 300 + K.rand_seq(random.Random(7), 60)])
+    assert len(x) and ((x & np.uint64(0xff)) < 256).all()
+
+
+@pytest.mark.parametrize("short", [0, 1, 5000])
+def test_sketch_device_capacity(short):
+    """mini_cap at, one below and far below the need: the count is the need, the offsets stay true, nothing behind the capacity is
+    touched and what is in front of it is the head of the list."""
+    import torch
+    w, k, hpc = 10, 15, 0
+    p = MS.make_params(w=w, k=k, is_hpc=hpc)
+    text, off = MS.pack_seqs(K.sketch_batch(w, k, hpc))
+    wx, wy, woff = K.sketch_expected(w, k, hpc)
+    cap = len(wx) - short
+    d = dev()
+    t = lambda a: torch.from_numpy(a).to(d)
+    d_text, d_off = t(text), t(off)
+    mx, my = (t(np.full(cap + 16, GUARD, np.uint64).view(np.int64)) for _ in range(2))
+    moff, cnt = torch.zeros(len(off), dtype=torch.int64, device=d), torch.zeros(1, dtype=torch.int64, device=d)
+    L = MS.lib()
+    wb = L.gbx_mm_sketch_workspace_bytes(p, len(off) - 1, len(text))
+    work = torch.empty(wb, dtype=torch.uint8, device=d)
+    N.check(L.gbx_mm_sketch_device(p, len(off) - 1, d_text.data_ptr(), d_off.data_ptr(), len(text), 1, mx.data_ptr(), my.data_ptr(), cap,
+                                   moff.data_ptr(), cnt.data_ptr(), work.data_ptr(), wb, stream()))
+    torch.cuda.synchronize()
+    assert int(cnt.item()) == len(wx) and np.array_equal(moff.cpu().numpy(), woff)
+    gx, gy = mx.cpu().numpy().view(np.uint64), my.cpu().numpy().view(np.uint64)
+    assert np.array_equal(gx[:cap], wx[:cap]) and np.array_equal(gy[:cap], wy[:cap])
+    assert (gx[cap:] == GUARD).all() and (gy[cap:] == GUARD).all()
+
+
+@pytest.mark.parametrize("variant", K.INDEX_VARIANTS, ids=lambda v: "-".join("%s=%g" % kv for kv in v.items()))
+def test_index(variant):
+    seqs = K.index_case()
+    want = R.Index(seqs, 10, 15, False, mid_occ=variant.get("mid_occ", 0), mid_occ_frac=variant.get("mid_occ_frac", 2e-4))
+    assert len(seqs[0]) < 15 and max(len(v) for v in want.vals.values()) >= 40
+    ix = MS.DeviceMmIndex(MS.make_params(**variant), seqs, dev(), stream())
+    wk, wo, wv = want.flat()
+    assert (ix.info.n_keys, ix.info.n_vals, ix.info.mid_occ) == (len(wk), len(wv), want.mid_occ)
+    assert (ix.info.k, ix.info.w, ix.info.is_hpc) == (15, 10, 0)
+    keys, koff, vals = ix.flat()
+    assert np.array_equal(keys, wk) and np.array_equal(koff, wo) and np.array_equal(vals, wv)
+
+
+def test_index_host_and_capacity():
+    seqs = K.index_case()
+    want = R.Index(seqs, 10, 15, False)
+    wk, wo, wv = want.flat()
+    keys, koff, vals, st = MS.index_host(MS.make_params(), seqs)
+    assert st.mid_occ == want.mid_occ and np.array_equal(keys, wk) and np.array_equal(koff, wo) and np.array_equal(vals, wv)
+    with pytest.raises(N.GbxError) as e:                                     # a device index too small for the reference reports the need
+        MS.DeviceMmIndex(MS.make_params(), seqs, dev(), stream(), mini_cap=len(wv) - 1)
+    assert e.value.code == N.GBX_ERR_ARG and str(len(wv)) in str(e.value)
+
+
+@pytest.fixture(scope="module")
+def seed_index():
+    refs, _, _ = K.seed_case()
+    return MS.DeviceMmIndex(MS.make_params(**K.SEED_PARAMS), refs, dev(), stream())
+
+
+def same(got, want, fields=FIELDS):
+    for f in fields:
+        assert np.array_equal(got[f], want[f]), f
+
+
+def test_seed_batch(seed_index):
+    _, reads, want = K.seed_case()
+    sd = MS.DeviceMmSeeder(seed_index, reads)
+    sd.run(stream())
+    assert sd.counts() == (len(want["mini_x"]), len(want["ax"])) and sd.fits()
+    same(sd.results(), want)
+
+
+@pytest.mark.parametrize("what", ["anchor", "mini"])
+@pytest.mark.parametrize("short", [0, 1, 600])
+def test_seed_capacity(seed_index, what, short):
+    """A capacity exactly at, one below and far below the need: the counts are the need, off and mini_off stay true, nothing is
+    written behind a capacity; with too few minimizer slots the anchors are not made (-1)."""
+    import torch
+    _, reads, want = K.seed_case()
+    n_m, n_a = len(want["mini_x"]), len(want["ax"])
+    mcap, acap = (n_m - short, n_a) if what == "mini" else (n_m, n_a - short)
+    sd = MS.DeviceMmSeeder(seed_index, reads, mini_cap=mcap, anchor_cap=acap)
+    g = lambda n: torch.from_numpy(np.full(n + 16, GUARD, np.uint64).view(np.int64)).to(sd.device)
+    sd.mini_x, sd.mini_y, sd.ax, sd.ay = g(mcap), g(mcap), g(acap), g(acap)
+    sd.run(stream())
+    m, a = sd.counts()
+    assert m == n_m and a == (n_a if mcap >= n_m else -1) and sd.fits() == (short == 0)
+    u = lambda t: t.cpu().numpy().view(np.uint64)
+    for t, cap in ((sd.mini_x, mcap), (sd.mini_y, mcap), (sd.ax, acap), (sd.ay, acap)):
+        assert (u(t)[cap:] == GUARD).all()
+    got = sd.results()
+    same(got, want, ("mini_off", "n_mini"))
+    assert np.array_equal(got["mini_x"], want["mini_x"][:mcap]) and np.array_equal(got["mini_y"], want["mini_y"][:mcap])
+    if mcap >= n_m:
+        same(got, want, ("off", "hdr", "rep_len"))
+        if short == 0:
+            same(got, want)
+        else:
+            with pytest.raises(N.GbxError):
+                sd.chain_batch()
+
+
+def test_seed_host(seed_index):
+    refs, reads, want = K.seed_case()
+    flat = seed_index.flat()
+    p = MS.make_params(**K.SEED_PARAMS)
+    got = MS.seed_host(p, flat, seed_index.mid_occ, len(refs), max(len(r) for r in refs), reads, len(want["ax"]))
+    same(got, want)
+    with pytest.raises(N.GbxError) as e:
+        MS.seed_host(p, flat, seed_index.mid_occ, len(refs), max(len(r) for r in refs), reads, len(want["ax"]) - 1)
+    assert e.value.code == N.GBX_ERR_ARG and str(len(want["ax"])) in str(e.value)
+
+
+def test_seed_then_chain_on_one_stream(seed_index):
+    """reads -> anchors -> chain scores without a host copy of the anchors: DeviceMmSeeder.chain_batch() is a DeviceChainBatch over the
+    seeder's tensors; score, parent, target and peak equal the chain oracle on the restatement's anchors."""
+    _, reads, want = K.seed_case()
+    s = stream()
+    sd = MS.DeviceMmSeeder(seed_index, reads)
+    sd.run(s)
+    cb = sd.chain_batch()
+    assert isinstance(cb, DeviceChainBatch) and cb.ax.data_ptr() == sd.ax.data_ptr() and cb.n_anchors == len(want["ax"])
+    cb.run(s)
+    import torch
+    torch.cuda.synchronize()
+    exp = O.chain_oracle(want["off"], want["ax"], want["ay"], want["hdr"])
+    for g, w_, name in zip(cb.results(), exp, ("score", "parent", "target", "peak")):
+        assert np.array_equal(g, w_), name
+    assert exp[0].max() > 100                                               # the reads do chain
+
+
+def test_mmseed_driver(tmp_path):
+    """mmseed on a generated 20 kb reference and 50 reads: its file, parsed back, is the restatement's; bin/chain on it is the oracle's."""
+    rng = random.Random(99)
+    refs = [K.rand_seq(rng, 12000), K.rand_seq(rng, 8000)]
+    reads = []
+    for i in range(50):
+        r = refs[i & 1]
+        o, ln = rng.randrange(0, len(r) - 900), rng.randrange(300, 900)
+        s = K.mutate(rng, r[o:o + ln])
+        reads.append(K.revcomp(s) if i % 3 == 0 else s)
+    fa, fq, out = tmp_path / "ref.fa", tmp_path / "reads.fq", tmp_path / "calls.txt"
+    with open(fa, "w") as f:
+        for i, r in enumerate(refs):
+            f.write(">ref%d some text\n" % i)
+            f.write("\n".join(r[o:o + 70].decode() for o in range(0, len(r), 70)) + "\n")
+    with open(fq, "w") as f:
+        for i, r in enumerate(reads):
+            f.write("@read%d\n%s\n+\n%s\n" % (i, r.decode(), "I" * len(r)))
+    r = subprocess.run([os.path.join(BIN, "mmseed"), "-k", "13", "-w", "8", "-g", "4000", "-r", "400", "-o", str(out), str(fa), str(fq)],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    assert "Seeding: 50 reads" in r.stderr
+    want = R.seed_batch(R.Index(refs, 8, 13), reads, max_gap=4000, bw=400)
+    off, ax, ay, hdr = gio.read_chain_calls(str(out))
+    assert np.array_equal(off, want["off"]) and np.array_equal(ax, want["ax"]) and np.array_equal(ay, want["ay"])
+    assert np.array_equal(hdr, want["hdr"]) and len(ax) > 2000
+    cout = tmp_path / "chain.out"
+    r = subprocess.run([os.path.join(BIN, "chain"), "-i", str(out), "-o", str(cout), "--print"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    s, p, _, _ = O.chain_oracle(off, ax, ay, hdr)
+    import io
+    buf = io.StringIO()
+    gio.write_chain_returns(buf, off, s, p)
+    assert open(cout).read() == buf.getvalue()
