@@ -313,6 +313,24 @@ struct MmSeedIo {                    // the device arguments of gbx_mm_seed_devi
 size_t mm_seed_workspace_bytes(const gbx_mm_params *p, int64_t n_reads, int64_t total_len, int64_t mini_cap, int64_t anchor_cap);
 int mm_seed_launch(const gbx_mm_params *p, const MmSeedIo &io, void *d_work, size_t work_bytes, hipStream_t s);
 
+// ---- minimap2 behind the chain scores (mm_map_kernels.hip; the rules: mm_map_rules.h)
+struct MmMapIo {                     // the device arguments of gbx_mm_map_device
+    int64_t n_reads; const int64_t *off; const uint64_t *ax, *ay; int64_t anchor_cap;
+    const int32_t *f, *p, *v; const int64_t *seq_off; const int32_t *rep_len; const uint32_t *hash;
+    int64_t *chain_off; uint64_t *u; int64_t chain_cap; uint64_t *cax, *cay; int32_t *n_chained;
+    int64_t *reg_off; gbx_mm_reg *regs; int64_t reg_cap; int64_t *counts;
+};
+size_t mm_map_workspace_bytes(int64_t n_reads, int64_t anchor_cap, int64_t chain_cap);
+int mm_map_launch(const gbx_mm_map_params *p, const MmMapIo &io, void *d_work, size_t work_bytes, hipStream_t s);
+struct MmPafIo {                     // the device arguments of gbx_mm_paf_device
+    int64_t n_reads; const gbx_mm_reg *regs; const int64_t *reg_off; const int64_t *n_regs; int64_t reg_cap;
+    const uint8_t *qnames; const int64_t *qname_off, *seq_off; const int32_t *rep_len;
+    int64_t n_targets; const uint8_t *tnames; const int64_t *tname_off, *tseq_off;
+    uint8_t *lines; int64_t text_cap; int64_t *line_off; int64_t *n_text;
+};
+size_t mm_paf_workspace_bytes(int64_t n_reads, int64_t reg_cap);
+int mm_paf_launch(const MmPafIo &io, void *d_work, size_t work_bytes, hipStream_t s);
+
 // ---- the aligner's gather behind the chain (mem_align_kernels.hip): every stage's count into one record
 struct MemAlignGather {              // a null pointer: the stage does not run, its count is 0
     const unsigned long long *fmi_counters;         // the fmi workspace: [2] is the slot overflow word fmi_read_overflow reads

@@ -1825,6 +1825,82 @@ int gbx_mm_seed_host(const gbx_mm_params *p, const uint64_t *keys, const int64_t
                      uint64_t *ax, uint64_t *ay, int64_t anchor_cap, int64_t *off, gbx_chain_call *hdr,
                      int32_t *rep_len, int32_t *n_mini, int64_t *counts);
 
+/* ------------------------------------------------------------------- mm map: from chain scores to PAF records
+ * minimap2 behind the chain DP, as `minimap2 -x map-ont` runs it without -c: the chain ends and the backtrack (second half of
+ * mm_chain_dp), mm_gen_regs, mm_set_parent, mm_select_sub, mm_set_mapq and the PAF line.  UNPINNED by a compiled reference, as
+ * the seeding stage is: the rules are restated in DESIGN 3.19 and tests/mm_map_ref.py and pinned by that restatement; where
+ * minimap2 leaves an order to an unstable sort the rule fixes it.
+ * Input: the chain batch of gbx_mm_seed_* (off, ax, ay), chain's score, parent and peak over it (parent local to the call, -1:
+ * none; chain leaves parent[i] < i, any other value counts as none), and per read its length, rep_len and a 32-bit hash.
+ * Not modelled: mm_join_long, mm_squeeze_a, re-chaining with max_occ, mm_filter_regs, mm_split_reg, inversions, dv:f,
+ * mm_set_sam_pri, multi-segment reads, CIGAR. */
+typedef struct gbx_mm_map_params {
+    int32_t min_cnt;           /* 3; >= 1 */
+    int32_t min_chain_score;   /* 40; >= 0 */
+    float   mask_level;        /* 0.5 */
+    float   pri_ratio;         /* 0.8; <= 0: no selection */
+    int32_t best_n;            /* 5; >= 0 */
+    int32_t min_diff;          /* 30 = 2k */
+} gbx_mm_map_params;
+/* One mapping: 72 bytes, 18 words of 4. */
+typedef struct gbx_mm_reg {
+    int32_t id, parent;        /* within the read; parent == id: a primary */
+    int32_t score, subsc;
+    int32_t cnt, as;           /* its anchors: cnt from `as` of the read's chained anchors */
+    int32_t rid, rev;
+    int32_t rs, re, qs, qe;
+    int32_t mlen, blen;
+    int32_t n_sub, mapq;
+    uint32_t hash;
+    int32_t read;
+} gbx_mm_reg;
+
+void gbx_mm_map_default_params(gbx_mm_map_params *p);
+/* GBX_ERR_ARG naming the field: min_cnt < 1, min_chain_score < 0, best_n < 0, a mask_level or pri_ratio that is not a number. */
+int gbx_mm_map_check_params(const gbx_mm_map_params *p);
+
+/* Chains and regions of n_reads reads whose anchors fill [0, anchor_cap) at most (anchor_cap >= off[n_reads]).  Output:
+ *   chain_off[n_reads + 1], u[chain_cap]   read r's chains [chain_off[r], chain_off[r + 1]), u = score << 32 | anchors, ascending
+ *                                          by the x of their first anchor
+ *   cax, cay [anchor_cap], n_chained[n_reads]   read r's chained anchors at off[r], n_chained[r] of them, chain after chain
+ *   reg_off[n_reads + 1], regs[reg_cap]    read r's regions, in order
+ *   counts[2]                              chains, regions
+ * A count above its capacity reports the need, nothing is written past a capacity and chain_off stays true; with more chains
+ * than chain_cap the regions are not made (counts[1] = -1, reg_off all 0).  The device entry does no host synchronisation. */
+size_t gbx_mm_map_workspace_bytes(int64_t n_reads, int64_t anchor_cap, int64_t chain_cap);
+int gbx_mm_map_device(const gbx_mm_map_params *p, int64_t n_reads, const int64_t *d_off, const uint64_t *d_ax, const uint64_t *d_ay,
+                      int64_t anchor_cap, const int32_t *d_score, const int32_t *d_parent, const int32_t *d_peak,
+                      const int64_t *d_seq_off, const int32_t *d_rep_len, const uint32_t *d_hash,
+                      int64_t *d_chain_off, uint64_t *d_u, int64_t chain_cap, uint64_t *d_cax, uint64_t *d_cay, int32_t *d_n_chained,
+                      int64_t *d_reg_off, gbx_mm_reg *d_regs, int64_t reg_cap, int64_t *d_counts, void *d_work, size_t work_bytes, void *stream);
+/* Host buffers in and out; seq_off[n_reads + 1]: the reads' lengths as offsets.  Checked before the device is touched,
+ * GBX_ERR_ARG naming the lowest offender: null pointers, off[0] or seq_off[0] != 0, offsets that decrease, negative
+ * capacities, a parent outside -1 .. i - 1; GBX_ERR_UNSUPPORTED: more than GBX_MM_MAX_READS reads, a read of 2^31 anchors or
+ * bases.  Counts above the capacities: GBX_ERR_ARG with the needed counts in counts[2] and gbx_last_error() (chain_off is
+ * written; call with 0 / NULL to size). */
+int gbx_mm_map_host(const gbx_mm_map_params *p, int64_t n_reads, const int64_t *off, const uint64_t *ax, const uint64_t *ay,
+                    const int32_t *score, const int32_t *parent, const int32_t *peak,
+                    const int64_t *seq_off, const int32_t *rep_len, const uint32_t *hash,
+                    int64_t *chain_off, uint64_t *u, int64_t chain_cap, uint64_t *cax, uint64_t *cay, int32_t *n_chained,
+                    int64_t *reg_off, gbx_mm_reg *regs, int64_t reg_cap, int64_t *counts);
+
+/* PAF text of the regions: one line a region, read after read (a read's lines are lines[line_off[r] .. line_off[r + 1])):
+ * qname qlen qs qe +/- tname tlen rs re mlen blen mapq tp:A:P|S cm:i: s1:i: s2:i: (primaries) rl:i:.  Names are byte arenas
+ * with offsets; a region whose rid is outside 0 .. n_targets - 1 prints `*` and length 0.  *n_text = the bytes needed, which
+ * may exceed text_cap: then nothing is written past it and line_off stays true.  d_n_regs: the region count on the device
+ * (counts + 1 of gbx_mm_map_device); regions at and past reg_cap do not exist.  No host synchronisation. */
+size_t gbx_mm_paf_workspace_bytes(int64_t n_reads, int64_t reg_cap);
+int gbx_mm_paf_device(int64_t n_reads, const gbx_mm_reg *d_regs, const int64_t *d_reg_off, const int64_t *d_n_regs, int64_t reg_cap,
+                      const uint8_t *d_qnames, const int64_t *d_qname_off, const int64_t *d_seq_off, const int32_t *d_rep_len,
+                      int64_t n_targets, const uint8_t *d_tnames, const int64_t *d_tname_off, const int64_t *d_tseq_off,
+                      uint8_t *d_lines, int64_t text_cap, int64_t *d_line_off, int64_t *d_n_text, void *d_work, size_t work_bytes, void *stream);
+/* The checks of gbx_mm_map_host on every offset array, and a region's read inside 0 .. n_reads - 1.  More text than text_cap:
+ * GBX_ERR_ARG with the need in *n_text and gbx_last_error() (line_off is written; call with 0 / NULL to size). */
+int gbx_mm_paf_host(int64_t n_reads, const gbx_mm_reg *regs, const int64_t *reg_off,
+                    const uint8_t *qnames, const int64_t *qname_off, const int64_t *seq_off, const int32_t *rep_len,
+                    int64_t n_targets, const uint8_t *tnames, const int64_t *tname_off, const int64_t *tseq_off,
+                    uint8_t *lines, int64_t text_cap, int64_t *line_off, int64_t *n_text);
+
 #ifdef __cplusplus
 }
 #endif
