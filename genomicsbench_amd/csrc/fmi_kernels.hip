@@ -28,7 +28,7 @@
 //     per read, a second kernel sorts each read's few records by (m ascending, n descending) and packs them behind a
 //     prefix sum of the counts.
 #include <algorithm>
-#include "mem_common.h"
+#include "dev_prims.h"
 
 namespace gbx {
 namespace {
@@ -507,13 +507,12 @@ static FmiLayout fmi_layout(int64_t n_reads, int32_t max_len, int RAW_CAP)
     L.chunk = n_reads < cap_chunk ? (n_reads > 0 ? n_reads : 1) : cap_chunk;
     const long long want = (L.chunk + 15) / 16;
     L.blocks = want < FMI_MAX_BLOCKS ? want : FMI_MAX_BLOCKS;
-    size_t at = 64;                                                        // counters: 8 x u64
-    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 255) & ~(size_t)255; return o; };
+    Carver take{64};                                                       // counters: 8 x u64
     L.o_raw = take((size_t)L.chunk * RAW_CAP * 40);
     L.o_cnt = take((size_t)L.chunk * 4);
     L.o_prev = take((size_t)L.blocks * 16 * (size_t)(max_len + 1) * 32);
     L.o_bsum = take((size_t)((L.chunk + SCAN_BLOCK - 1) / SCAN_BLOCK) * 8);
-    L.total = at;
+    L.total = take.at;
     return L;
 }
 

@@ -20,7 +20,7 @@
 //   * per-SMEM hit counts and their exclusive scan (pos_off) are computed on the device from the device SMEM count, so
 //     the lookup chains behind gbx_fmi_smem_device on one stream.
 #include <algorithm>
-#include "mem_common.h"
+#include "dev_prims.h"
 
 namespace gbx {
 namespace {

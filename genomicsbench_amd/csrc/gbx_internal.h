@@ -187,7 +187,8 @@ int fmi_build_rounds(int64_t *slots, int32_t cap, int32_t *n_rounds);     // of 
 // the host checks of every build entry (capi_mem_index.hip); genome: host codes to check, or null when they are on the device
 int fmi_build_check(const uint8_t *genome, int64_t l_pac, int32_t sa_compx, const char *who);
 
-// ---- what the bwa-mem stages share (mem_scan.hip; the device helpers: mem_common.h)
+// ---- what the device pipelines share: the scan (mem_scan.hip; its pieces and the other device helpers: dev_prims.h) and the
+// radix sort built on it (dev_sort.hip).  What only the bwa-mem stages share on the device is in mem_common.h.
 // One exclusive scan over per-unit counts.  cnt holds nq quantities of n counts, n + 1 entries apart; each becomes its offsets
 // (entry n: the total) in place.  Three launches: a block scan, one block per quantity over the block sums, an offset pass.
 struct MemScanGuard { const int64_t *n; int64_t lo, hi; };      // n == nullptr: no guard; else the stage before it fits iff lo <= *n <= hi
@@ -199,6 +200,20 @@ struct MemScanJob {
     MemScanGuard guard[2];
 };
 void mem_scan_launch(const MemScanJob &job, hipStream_t s);
+// Stable LSD radix sort of items (uint64_t a, V b), V = uint32_t or uint64_t, a digit of up to 8 bits a pass; a pass is three
+// launches: block histograms, mem_scan_launch over 256 * blocks entries, scatter.  The items start in buffer 0.
+constexpr int SORT_THREADS = 256, SORT_ITEMS = 16, SORT_TILE = SORT_THREADS * SORT_ITEMS;      // a thread's and a block's elements
+inline long long sort_blocks(long long n) { const long long b = (n + SORT_TILE - 1) / SORT_TILE; return b > 0 ? b : 1; }
+struct SortPass { int word, shift; uint32_t mask; };           // the digit: (word 0: a, 1: b, V = uint64_t only) >> shift & mask, mask <= 255
+struct SortCount { const int64_t *dev; long long n; };         // dev null: n items; else *dev clipped to n.  The grid covers n
+template <class V>
+struct SortBufs { uint64_t *a[2]; V *b[2]; long long *hist, *hsum; };      // hist: 256 sort_blocks(n) + 1, hsum: mem_scan_blocks of that
+template <class V>
+int radix_sort(const SortBufs<V> &bufs, const SortCount &count, const SortPass *pass, int n_pass, hipStream_t s);      // -> the buffer with the result
+struct Carver;                                                  // dev_prims.h
+struct SortLayout { size_t o_a[2], o_b[2], o_hist, o_hsum; };   // of (uint64_t, uint64_t) items
+SortLayout sort_layout(int64_t cap, Carver &carve);
+SortBufs<uint64_t> sort_bufs(char *wb, const SortLayout &L);
 // the CIGAR list past *n (below 0: 0), up to cap: zeroed seeds (len = 0 is no seed) with results of all -1
 void mem_sel_tail_launch(gbx_bsw_seed *seeds, gbx_bsw_seed_result *res, int64_t cap, const int64_t *n, hipStream_t s);
 

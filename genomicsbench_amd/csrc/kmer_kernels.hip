@@ -20,7 +20,7 @@
 // Every loop is counted: the unit loop by the unit total, the base loop by (KC_CHUNK + k - 1) / 16 + 2 words, the sweeps
 // by the slice size.  Base codes are masked with & 3, so a table index never leaves the slice whatever the input bytes.
 #include <algorithm>
-#include "gbx_internal.h"
+#include "dev_prims.h"
 
 namespace gbx {
 namespace {
@@ -37,8 +37,6 @@ struct KmerLayout {
     long long slice_n, n_slices;
     size_t o_blk, o_base, o_table, total;
 };
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 KmerLayout kmer_layout(int k, long long n_reads)
 {

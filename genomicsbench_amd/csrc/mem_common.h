@@ -1,15 +1,11 @@
-// mem_common.h — what the bwa-mem stage files (mem_chain / mem_cigar / mem_regs / mem_pair / mem_rescue / mem_sam _kernels.hip) share on the device:
-// the small helpers, the mapq formula, the one-wave key sort, the CIGAR-list record and the pieces of the exclusive scan over
-// per-unit counts.  fmi_kernels.hip and fmi_sal_kernels.hip use the scan's pieces inside their fused kernels.  The scan's own
-// kernels and the CIGAR list's tail kernel are in mem_scan.hip (mem_scan_launch, mem_sel_tail_launch: gbx_internal.h).
+// mem_common.h — what the bwa-mem stage files (mem_chain / mem_cigar / mem_regs / mem_pair / mem_rescue / mem_sam _kernels.hip) share on the device
+// and nobody else uses: the small helpers, the mapq formula, the one-wave key sort, the wave-wide steps on a read's regions and
+// the CIGAR-list record.  The helpers that are not bwa-mem's (align256, the pieces of the exclusive scan) are in dev_prims.h,
+// which this includes; the CIGAR list's tail kernel is in mem_scan.hip (mem_sel_tail_launch: gbx_internal.h).
 #pragma once
-#include "gbx_internal.h"
+#include "dev_prims.h"
 
 namespace gbx {
-
-constexpr int MEM_SCAN = 1024;                      // entries a block of the scan takes
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-inline int mem_scan_blocks(int64_t n) { return (int)((n + 1 + MEM_SCAN - 1) / MEM_SCAN); }     // n counts make n + 1 offsets
 
 __device__ inline long long clampll(long long v, long long lo, long long hi) { return v < lo ? lo : v > hi ? hi : v; }
 
@@ -320,55 +316,6 @@ __device__ inline gbx_bsw_seed_result reg_result(const gbx_mem_reg &R, const gbx
     e.score = R.score; e.truesc = R.truesc; e.qb = R.qb; e.qe = R.qe;
     e.rb = (int32_t)(R.rb - s.roff); e.re = (int32_t)(R.re - s.roff); e.w = R.w; e.sc0 = 0;
     return e;
-}
-
-// ---- exclusive scan, the pieces.  A block scans its entries (block_scan_excl) and leaves its sum; one block scans the sums
-// (scan_block_sums); an offset pass adds a block's scanned sum to its entries.
-template <class T>
-__device__ inline T wave_scan_incl(T v, int lane)
-{
-    for (int d = 1; d < 64; d <<= 1) { const T u = __shfl_up(v, d); if (lane >= d) v += u; }
-    return v;
-}
-
-// every thread of the block calls it with its count c; -> the sum of the counts of the threads before it.  sh: a long long per
-// wavefront of the block.  *block_total: the sum up to and including this thread - in the block's last thread, the block's sum.
-__device__ inline long long block_scan_excl(long long c, long long *sh, long long *block_total)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const long long v = wave_scan_incl(c, lane);
-    if (lane == 63) sh[wv] = v;
-    __syncthreads();
-    long long before = 0;
-    for (int w = 0; w < wv; ++w) before += sh[w];
-    *block_total = before + v;
-    return before + v - c;
-}
-
-// one block of 1024 threads: bsum[0 .. blocks) becomes its exclusive scan; -> the total (in every thread)
-__device__ inline long long scan_block_sums(long long *bsum, int blocks)
-{
-    __shared__ long long sh[1024];
-    __shared__ long long carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < blocks; b0 += 1024) {
-        const int i = b0 + threadIdx.x;
-        const long long v = i < blocks ? bsum[i] : 0;
-        sh[threadIdx.x] = v;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {
-            const long long u = threadIdx.x >= d ? sh[threadIdx.x - d] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += u;
-            __syncthreads();
-        }
-        if (i < blocks) bsum[i] = carry + sh[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry += sh[1023];
-        __syncthreads();
-    }
-    return carry;
 }
 
 }  // namespace gbx

@@ -5,9 +5,7 @@
 //
 // Suffix array by prefix doubling on radix sorts (Larsson-Sadakane numbering: a suffix's rank is the slot of its group's head):
 //   keys      the first 16 symbols of a suffix in 32 bits, zero-padded past the end, then min(16, n - i) in 5 bits
-//   sort      LSD radix sort of (key, position), 8 bits a pass, three plain kernels a pass: per-block digit histograms, the
-//             shared exclusive scan (mem_scan_launch) and a stable scatter (ranks inside a wavefront from ballots over the
-//             digit's bits, across the waves of a block from LDS counters).  No block waits for another inside a kernel.
+//   sort      LSD radix sort of (key, position), 8 bits a pass: radix_sort of dev_sort.hip, with the count the host knows
 //   groups    a head flag per slot whose key differs from the slot before it; rank[sa[j]] = the slot of j's group head
 //   rounds    h = 16, 32, ..: the slots of groups with more than one member are compacted (flags, scan; the host reads the
 //             count), keyed by (group head << 32 | rank[pos + h] + 1, 0 past the end), sorted, written back in order to the
@@ -16,20 +14,16 @@
 //             mem_scan_launch turns the counts into cp_count and the totals into count[].
 // Positions and ranks are 32-bit: N <= 2^32 - 1.  Every device loop here has a trip count the host fixed (a constant or a
 // function of the launch's sizes); the one data-dependent loop is the host's round loop, bounded by ceil(log2 N) + 1.
-#include "mem_common.h"
+#include "dev_prims.h"
 
 namespace gbx {
 namespace {
 
-constexpr int SORT_THREADS = 256, SORT_WAVES = SORT_THREADS / 64;
-constexpr int SORT_ITEMS = 16;                                   // elements a thread takes
-constexpr int SORT_TILE = SORT_THREADS * SORT_ITEMS;             // elements a block takes
 constexpr int EL = 1024;                                         // the element-wise kernels' block
 
-using u32 = unsigned;
-using u64 = unsigned long long;
+using u32 = uint32_t;
+using u64 = uint64_t;
 
-inline long long sort_blocks(long long m) { return (m + SORT_TILE - 1) / SORT_TILE; }
 inline long long el_blocks(long long m) { return (m + EL - 1) / EL; }
 
 struct Layout {
@@ -43,8 +37,7 @@ Layout layout_of(int64_t l_pac)
     Layout L;
     const size_t N = (size_t)(2 * l_pac + 1);
     L.N = (long long)N;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += align256(bytes); return o; };
+    Carver take;
     L.o_text = take(N + 16);                                     // n symbols and zeros behind them (the key kernel reads 16 past any start)
     L.o_sa = take(N * 4);
     L.o_rank = take(N * 4);
@@ -60,7 +53,7 @@ Layout layout_of(int64_t l_pac)
     L.o_csum = take((size_t)mem_scan_blocks(L.cnt_blocks) * 8);
     L.o_bmax = take((size_t)L.cnt_blocks * 4);
     L.o_misc = take(256);
-    L.total = at;
+    L.total = take.at;
     return L;
 }
 
@@ -88,72 +81,6 @@ __global__ void __launch_bounds__(EL) first_key_kernel(const uint8_t *text, long
     const long long left = N - 1 - i;
     key[i] = (u64)k << 5 | (u64)(left < 16 ? left : 16);
     val[i] = (u32)i;
-}
-
-// ---- radix sort, one pass = hist, scan, scatter.  hist[d * blocks + b]: elements of block b with digit d
-__global__ void __launch_bounds__(SORT_THREADS) sort_hist_kernel(const u64 *key, long long m, int shift, long long *hist, long long blocks)
-{
-    __shared__ u32 h[256];
-    h[threadIdx.x] = 0;
-    __syncthreads();
-    const long long base = (long long)blockIdx.x * SORT_TILE;
-#pragma unroll 4
-    for (int r = 0; r < SORT_ITEMS; ++r) {
-        const long long i = base + (long long)r * SORT_THREADS + threadIdx.x;
-        if (i < m) atomicAdd(&h[(u32)(key[i] >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    hist[(long long)threadIdx.x * blocks + blockIdx.x] = h[threadIdx.x];
-}
-
-// hist has become its exclusive scan: where block b's elements of digit d start.  A wave takes SORT_ITEMS * 64 consecutive
-// elements, 64 a trip, so the order inside a block is wave, trip, lane.
-__global__ void __launch_bounds__(SORT_THREADS) sort_scatter_kernel(const u64 *key, const u32 *val, long long m, int shift, const long long *hist,
-                                                                   long long blocks, u64 *key_out, u32 *val_out)
-{
-    __shared__ long long wcount[SORT_WAVES][256];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const u64 below = (1ull << lane) - 1;
-    for (int w = 0; w < SORT_WAVES; ++w) wcount[w][threadIdx.x] = 0;
-    __syncthreads();
-    const long long base = (long long)blockIdx.x * SORT_TILE + (long long)wv * SORT_ITEMS * 64;
-    u64 k[SORT_ITEMS];
-    u32 v[SORT_ITEMS], at[SORT_ITEMS];
-#pragma unroll
-    for (int r = 0; r < SORT_ITEMS; ++r) {
-        const long long i = base + r * 64 + lane;
-        const bool act = i < m;
-        k[r] = act ? key[i] : 0;
-        v[r] = act ? val[i] : 0;
-        const u32 d = (u32)(k[r] >> shift) & 255u;
-        u64 same = __ballot(act);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const bool bit = (d >> b) & 1u;
-            const u64 bal = __ballot(bit);
-            same &= bit ? bal : ~bal;
-        }
-        const u32 before = (u32)wcount[wv][d];                              // every lane of a digit reads before its first lane adds
-        at[r] = before + (u32)__builtin_popcountll(same & below);
-        __builtin_amdgcn_wave_barrier();
-        if (act && (same & below) == 0) wcount[wv][d] = before + (u32)__builtin_popcountll(same);
-        __builtin_amdgcn_wave_barrier();
-    }
-    __syncthreads();
-    {
-        long long o = hist[(long long)threadIdx.x * blocks + blockIdx.x];
-        for (int w = 0; w < SORT_WAVES; ++w) { const long long c = wcount[w][threadIdx.x]; wcount[w][threadIdx.x] = o; o += c; }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < SORT_ITEMS; ++r) {
-        const long long i = base + r * 64 + lane;
-        if (i < m) {
-            const long long dst = wcount[wv][(u32)(k[r] >> shift) & 255u] + at[r];
-            key_out[dst] = k[r];
-            val_out[dst] = v[r];
-        }
-    }
 }
 
 // ---- after a sort of m elements: element k belongs in slot cslot[k] (null: k).  Writes the position there, the slot's head
@@ -312,27 +239,13 @@ __global__ void __launch_bounds__(EL) sample_kernel(const u32 *sa, long long N, 
 
 thread_local std::vector<long long> last_rounds;      // the slots each round of this thread's last build sorted
 
-void scan(long long *cnt, long long n, int nq, long long *bsum, int64_t *t0, int64_t *t1, hipStream_t s)
+// two quantities of n counts in one scan, their totals to t[0] and t[1]
+void scan2(long long *cnt, long long n, long long *bsum, int64_t *t, hipStream_t s)
 {
     MemScanJob J{};
-    J.cnt = cnt; J.n = n; J.nq = nq; J.bsum = bsum; J.blocks = mem_scan_blocks(n);
-    J.total[0] = t0; J.total[1] = t1; J.off0 = nullptr;
+    J.cnt = cnt; J.n = n; J.nq = 2; J.bsum = bsum; J.blocks = mem_scan_blocks(n);
+    J.total[0] = t; J.total[1] = t + 1;
     mem_scan_launch(J, s);
-}
-
-// LSD radix sort of m (key, val) pairs from buffer 0 on the digits at the given shifts -> the buffer that holds the result
-int radix_sort(u64 *key[2], u32 *val[2], long long m, const int *shifts, int n_shifts, long long *hist, long long *hsum, hipStream_t s)
-{
-    const long long blocks = sort_blocks(m);
-    int cur = 0;
-    for (int p = 0; p < n_shifts; ++p) {
-        hipLaunchKernelGGL(sort_hist_kernel, dim3((unsigned)blocks), dim3(SORT_THREADS), 0, s, key[cur], m, shifts[p], hist, blocks);
-        scan(hist, 256 * blocks, 1, hsum, nullptr, nullptr, s);
-        hipLaunchKernelGGL(sort_scatter_kernel, dim3((unsigned)blocks), dim3(SORT_THREADS), 0, s, key[cur], val[cur], m, shifts[p], hist, blocks,
-                           key[cur ^ 1], val[cur ^ 1]);
-        cur ^= 1;
-    }
-    return cur;
 }
 
 }  // namespace
@@ -361,9 +274,10 @@ int fmi_build_launch(const uint8_t *d_genome, int64_t l_pac, int32_t sa_compx, g
     const long long N = L.N;
     uint8_t *const text = (uint8_t *)(wb + L.o_text), *const flags = (uint8_t *)(wb + L.o_flags);
     u32 *const sa = (u32 *)(wb + L.o_sa), *const rank = (u32 *)(wb + L.o_rank), *const cslot = (u32 *)(wb + L.o_cslot), *const bmax = (u32 *)(wb + L.o_bmax);
-    u64 *key[2] = {(u64 *)(wb + L.o_key[0]), (u64 *)(wb + L.o_key[1])};
-    u32 *val[2] = {(u32 *)(wb + L.o_val[0]), (u32 *)(wb + L.o_val[1])};
-    long long *const hist = (long long *)(wb + L.o_hist), *const hsum = (long long *)(wb + L.o_hsum);
+    const SortBufs<u32> B{{(u64 *)(wb + L.o_key[0]), (u64 *)(wb + L.o_key[1])}, {(u32 *)(wb + L.o_val[0]), (u32 *)(wb + L.o_val[1])},
+                          (long long *)(wb + L.o_hist), (long long *)(wb + L.o_hsum)};
+    u64 *const *const key = B.a;
+    u32 *const *const val = B.b;
     long long *const cnt = (long long *)(wb + L.o_cnt), *const csum = (long long *)(wb + L.o_csum);
     int64_t *const misc = (int64_t *)(wb + L.o_misc);                       // [0]: a round's open slots; [1 .. 4]: the BWT's totals
     const dim3 gN((unsigned)el_blocks(N)), tb(EL);
@@ -382,16 +296,17 @@ int fmi_build_launch(const uint8_t *d_genome, int64_t l_pac, int32_t sa_compx, g
     };
     {
         Stage st("mem_index_sort0", s);
-        const int shifts[5] = {0, 8, 16, 24, 32};                            // 37 key bits
-        const int cur = radix_sort(key, val, N, shifts, 5, hist, hsum, s);
+        const SortPass first[5] = {{0, 0, 255u}, {0, 8, 255u}, {0, 16, 255u}, {0, 24, 255u}, {0, 32, 255u}};      // 37 key bits
+        const int cur = radix_sort(B, SortCount{nullptr, N}, first, 5, s);
         place(cur, N, nullptr);
     }
     GBX_HIP(hipGetLastError());
     int bits = 1;
     while (bits < 33 && (1ll << bits) <= N) ++bits;                          // N < 2^bits: ranks and ranks + 1 (at most N) fit
-    int shifts[8], n_shifts = 0;
-    for (int b = 0; b < bits; b += 8) shifts[n_shifts++] = b;
-    for (int b = 0; b < bits; b += 8) shifts[n_shifts++] = 32 + b;
+    SortPass pass[8];
+    int n_pass = 0;
+    for (int b = 0; b < bits; b += 8) pass[n_pass++] = SortPass{0, b, 255u};
+    for (int b = 0; b < bits; b += 8) pass[n_pass++] = SortPass{0, 32 + b, 255u};
     const int max_rounds = bits + 1;                                        // ceil(log2 N) rounds can be needed; one more is an error
     long long rounds = 0, first_open = 0;
     last_rounds.clear();
@@ -399,7 +314,7 @@ int fmi_build_launch(const uint8_t *d_genome, int64_t l_pac, int32_t sa_compx, g
         {
             Stage st("mem_index_open", s);
             hipLaunchKernelGGL(open_count_kernel, gN, tb, 0, s, (const uint8_t *)flags, N, cnt);
-            scan(cnt, L.cnt_blocks, 1, csum, misc, nullptr, s);
+            scan_launch1(cnt, L.cnt_blocks, csum, misc, MemScanGuard{}, s);
         }
         long long m = -1;
         GBX_HIP(hipMemcpyAsync(&m, misc, 8, hipMemcpyDeviceToHost, s));
@@ -416,7 +331,7 @@ int fmi_build_launch(const uint8_t *d_genome, int64_t l_pac, int32_t sa_compx, g
         Stage st("mem_index_round", s);
         hipLaunchKernelGGL(open_list_kernel, gN, tb, 0, s, (const uint8_t *)flags, N, (const long long *)cnt, cslot);
         hipLaunchKernelGGL(round_key_kernel, dim3((unsigned)el_blocks(m)), tb, 0, s, (const u32 *)cslot, m, (const u32 *)sa, (const u32 *)rank, N, h, key[0], val[0]);
-        const int cur = radix_sort(key, val, m, shifts, n_shifts, hist, hsum, s);
+        const int cur = radix_sort(B, SortCount{nullptr, m}, pass, n_pass, s);
         place(cur, m, cslot);
         GBX_HIP(hipGetLastError());
     }
@@ -427,8 +342,8 @@ int fmi_build_launch(const uint8_t *d_genome, int64_t l_pac, int32_t sa_compx, g
         long long *const bs = (long long *)key[1];
         GBX_HIP(hipMemsetAsync(d_info, 0, 64, s));
         hipLaunchKernelGGL(bwt_kernel, dim3((unsigned)((ncp + 3) / 4)), dim3(256), 0, s, (const u32 *)sa, (const uint8_t *)text, N, ncp, d_cp, bc, d_info);
-        scan(bc, ncp, 2, bs, misc + 1, misc + 2, s);
-        scan(bc + 2 * (ncp + 1), ncp, 2, bs, misc + 3, misc + 4, s);
+        scan2(bc, ncp, bs, misc + 1, s);
+        scan2(bc + 2 * (ncp + 1), ncp, bs, misc + 3, s);
         hipLaunchKernelGGL(cp_count_kernel, dim3((unsigned)((ncp * 4 + 255) / 256)), dim3(256), 0, s, (const long long *)bc, (const int64_t *)(misc + 1), ncp, d_cp,
                            d_info, rounds, first_open);
         const long long n_sa = sa_compx ? (N >> 3) + 1 : N;

@@ -1,6 +1,6 @@
-// mem_scan.hip — the kernels the bwa-mem stages share: the exclusive scan that turns per-unit counts into offsets (chain, cigar,
-// regs, pair) and the tail fill of a CIGAR list (regs, pair).  The pieces of the scan are in mem_common.h.
-#include "mem_common.h"
+// mem_scan.hip — the exclusive scan that turns per-unit counts into offsets (the bwa-mem stages, the index builder, the mm stages
+// and the radix sort of dev_sort.hip) and the tail fill of a CIGAR list (regs, pair).  The pieces of the scan are in dev_prims.h.
+#include "dev_prims.h"
 
 namespace gbx {
 namespace {

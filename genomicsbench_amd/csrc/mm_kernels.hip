@@ -6,15 +6,14 @@
 //            fall in it), warm-started w + k steps ahead; a count pass, the shared scan (mem_scan_launch), a fill pass.  The ring
 //            of w slots and the HPC queue are per lane, lane-interleaved: in LDS up to w = 16 (sized by w), in the workspace above.  Even k:
 //            a lane takes a whole sequence.
-//   sort     LSD radix sort of 128-bit items (hi, lo) on a list of 8-bit digits, the scheme of mem_index_kernels.hip (block
-//            histograms, the shared scan, a stable scatter by ballots) with the element count read on the device: the grid
-//            covers the capacity.  Stable, so equal keys keep their order.
+//   sort     LSD radix sort of 128-bit items (hi, lo) on a list of 8-bit digits: radix_sort of dev_sort.hip with the element
+//            count read on the device, the grid covering the capacity.  Stable, so equal keys keep their order.
 //   index    sketch (rid = ordinal) -> sort on the digits of x >> 8 (the values keep their ascending y) -> head flags, scan ->
 //            sorted distinct keys + CSR; the keys' counts are sorted for mid_occ.  Lookup: binary search over the keys.
 //   seeding  sketch (rid 0) -> lookup (read, key range, count per minimizer) -> scan -> per-read record (one wavefront a read)
 //            -> fill -> sort on the significant digits of (read, x, y) -> unpack.
 // No kernel here waits for another block, and no entry synchronises with the host.
-#include "mem_common.h"
+#include "dev_prims.h"
 #include "mm_machine.h"
 
 namespace gbx {
@@ -24,22 +23,12 @@ using u32 = unsigned;
 using u64 = uint64_t;
 
 constexpr int LDS_W = 16;                                        // the widest ring kept in LDS
-constexpr int SORT_THREADS = 256, SORT_WAVES = SORT_THREADS / 64;
-constexpr int SORT_ITEMS = 16;
-constexpr int SORT_TILE = SORT_THREADS * SORT_ITEMS;
 constexpr int EL = 256;                                          // the element-wise kernels' block
 constexpr int READ_SHIFT = 43;                                   // the read's place in an anchor's sort word
 constexpr u64 Y_MASK = (1ull << READ_SHIFT) - 1;
 
-inline long long sort_blocks(long long cap) { const long long b = (cap + SORT_TILE - 1) / SORT_TILE; return b > 0 ? b : 1; }
 inline unsigned el_blocks(long long n) { const long long b = (n + EL - 1) / EL; return (unsigned)(b > 0 ? b : 1); }
 inline int bits_of(long long v) { int b = 0; while (v > 0) { ++b; v >>= 1; } return b; }
-
-__device__ inline long long clip_count(const int64_t *n, long long cap)
-{
-    const long long v = *n;
-    return v < 0 ? 0 : v > cap ? cap : v;
-}
 
 // ------------------------------------------------------------------------------------------------ sketch
 struct SketchJob {
@@ -117,135 +106,12 @@ SketchLayout sketch_layout(const gbx_mm_params *p, int64_t n_seqs, int64_t total
     SketchLayout L;
     L.n_units = (p->k & 1) ? total_len / MM_CHUNK + 1 : (n_seqs > 0 ? n_seqs : 1);
     L.blocks = (L.n_units + 63) / 64;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += align256(bytes); return o; };
+    Carver take;
     L.o_cnt = take((size_t)(L.n_units + 1) * 8);
     L.o_bsum = take((size_t)mem_scan_blocks(L.n_units) * 8);
     L.o_ring = take(p->w > LDS_W ? (size_t)L.blocks * 64 * (2 * (size_t)p->w + MM_TQ / 2) * 8 : 0);
-    L.total = at;
+    L.total = take.at;
     return L;
-}
-
-// ------------------------------------------------------------------------------------------------ sort
-struct SortPass { int word, shift; u32 mask; };          // word 0: hi, 1: lo
-struct SortBufs { u64 *hi[2], *lo[2]; long long *hist, *hsum; long long cap; };
-
-__global__ void __launch_bounds__(SORT_THREADS) mm_sort_hist_kernel(const u64 *word, const int64_t *d_m, long long cap, int shift, u32 mask,
-                                                                   long long *hist, long long blocks)
-{
-    __shared__ u32 h[256];
-    const long long m = clip_count(d_m, cap);
-    h[threadIdx.x] = 0;
-    __syncthreads();
-    const long long base = (long long)blockIdx.x * SORT_TILE;
-    if (base < m) {
-#pragma unroll 4
-        for (int r = 0; r < SORT_ITEMS; ++r) {
-            const long long i = base + (long long)r * SORT_THREADS + threadIdx.x;
-            if (i < m) atomicAdd(&h[(u32)(word[i] >> shift) & mask], 1u);
-        }
-    }
-    __syncthreads();
-    hist[(long long)threadIdx.x * blocks + blockIdx.x] = h[threadIdx.x];
-}
-
-// hist has become its exclusive scan.  A wave takes SORT_ITEMS * 64 consecutive elements, 64 a trip: the order inside a block
-// is wave, trip, lane.
-__global__ void __launch_bounds__(SORT_THREADS) mm_sort_scatter_kernel(const u64 *hi, const u64 *lo, int word, const int64_t *d_m, long long cap,
-                                                                      int shift, u32 mask, const long long *hist, long long blocks,
-                                                                      u64 *hi_out, u64 *lo_out)
-{
-    __shared__ long long wcount[SORT_WAVES][256];
-    const long long m = clip_count(d_m, cap);
-    if ((long long)blockIdx.x * SORT_TILE >= m) return;                      // (the whole block leaves)
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const u64 below = (1ull << lane) - 1;
-    for (int w = 0; w < SORT_WAVES; ++w) wcount[w][threadIdx.x] = 0;
-    __syncthreads();
-    const long long base = (long long)blockIdx.x * SORT_TILE + (long long)wv * SORT_ITEMS * 64;
-    u64 kh[SORT_ITEMS], kl[SORT_ITEMS];
-    u32 at[SORT_ITEMS];
-#pragma unroll
-    for (int r = 0; r < SORT_ITEMS; ++r) {
-        const long long i = base + r * 64 + lane;
-        const bool act = i < m;
-        kh[r] = act ? hi[i] : 0;
-        kl[r] = act ? lo[i] : 0;
-        const u32 d = (u32)((word ? kl[r] : kh[r]) >> shift) & mask;
-        u64 same = __ballot(act);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const bool bit = (d >> b) & 1u;
-            const u64 bal = __ballot(bit);
-            same &= bit ? bal : ~bal;
-        }
-        const u32 before = (u32)wcount[wv][d];                               // every lane of a digit reads before its first lane adds
-        at[r] = before + (u32)__builtin_popcountll(same & below);
-        __builtin_amdgcn_wave_barrier();
-        if (act && (same & below) == 0) wcount[wv][d] = before + (u32)__builtin_popcountll(same);
-        __builtin_amdgcn_wave_barrier();
-    }
-    __syncthreads();
-    {
-        long long o = hist[(long long)threadIdx.x * blocks + blockIdx.x];
-        for (int w = 0; w < SORT_WAVES; ++w) { const long long c = wcount[w][threadIdx.x]; wcount[w][threadIdx.x] = o; o += c; }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < SORT_ITEMS; ++r) {
-        const long long i = base + r * 64 + lane;
-        if (i < m) {
-            const long long dst = wcount[wv][(u32)((word ? kl[r] : kh[r]) >> shift) & mask] + at[r];
-            hi_out[dst] = kh[r];
-            lo_out[dst] = kl[r];
-        }
-    }
-}
-
-void scan1(long long *cnt, long long n, long long *bsum, int64_t *total, const MemScanGuard &guard, hipStream_t s)
-{
-    MemScanJob J{};
-    J.cnt = cnt; J.n = n; J.nq = 1; J.bsum = bsum; J.blocks = mem_scan_blocks(n);
-    J.total[0] = total; J.guard[0] = guard;
-    mem_scan_launch(J, s);
-}
-
-// -> the buffer that holds the result
-int radix_sort(const SortBufs &B, const int64_t *d_m, const SortPass *pass, int n_pass, hipStream_t s)
-{
-    const long long blocks = sort_blocks(B.cap);
-    int cur = 0;
-    for (int p = 0; p < n_pass; ++p) {
-        hipLaunchKernelGGL(mm_sort_hist_kernel, dim3((unsigned)blocks), dim3(SORT_THREADS), 0, s, pass[p].word ? B.lo[cur] : B.hi[cur], d_m, B.cap,
-                           pass[p].shift, pass[p].mask, B.hist, blocks);
-        scan1(B.hist, 256 * blocks, B.hsum, nullptr, MemScanGuard{}, s);
-        hipLaunchKernelGGL(mm_sort_scatter_kernel, dim3((unsigned)blocks), dim3(SORT_THREADS), 0, s, B.hi[cur], B.lo[cur], pass[p].word, d_m, B.cap,
-                           pass[p].shift, pass[p].mask, B.hist, blocks, B.hi[cur ^ 1], B.lo[cur ^ 1]);
-        cur ^= 1;
-    }
-    return cur;
-}
-
-struct SortLayout { size_t o_hi[2], o_lo[2], o_hist, o_hsum; };
-
-template <class Take>
-SortLayout sort_layout(int64_t cap, Take &take)
-{
-    SortLayout L;
-    const size_t c = (size_t)(cap > 0 ? cap : 1);
-    for (int b = 0; b < 2; ++b) { L.o_hi[b] = take(c * 8); L.o_lo[b] = take(c * 8); }
-    const long long he = 256 * sort_blocks(cap);
-    L.o_hist = take((size_t)(he + 1) * 8);
-    L.o_hsum = take((size_t)mem_scan_blocks(he) * 8);
-    return L;
-}
-
-SortBufs sort_bufs(char *wb, const SortLayout &L, int64_t cap)
-{
-    SortBufs B;
-    for (int b = 0; b < 2; ++b) { B.hi[b] = (u64 *)(wb + L.o_hi[b]); B.lo[b] = (u64 *)(wb + L.o_lo[b]); }
-    B.hist = (long long *)(wb + L.o_hist); B.hsum = (long long *)(wb + L.o_hsum); B.cap = cap > 0 ? cap : 1;
-    return B;
 }
 
 // ------------------------------------------------------------------------------------------------ index
@@ -302,14 +168,13 @@ struct IndexLayout { size_t o_sketch, o_moff, o_cnt, o_bsum, total; SortLayout s
 IndexLayout index_layout(const gbx_mm_params *p, int64_t n_seqs, int64_t total_len, int64_t cap)
 {
     IndexLayout L;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += align256(bytes); return o; };
+    Carver take;
     L.o_sketch = take(sketch_layout(p, n_seqs, total_len).total);
     L.o_moff = take((size_t)(n_seqs + 1) * 8);
     L.sort = sort_layout(cap, take);
     L.o_cnt = take((size_t)(cap + 2) * 8);
     L.o_bsum = take((size_t)mem_scan_blocks(cap > 0 ? cap : 1) * 8);
-    L.total = at;
+    L.total = take.at;
     return L;
 }
 
@@ -431,8 +296,7 @@ struct SeedLayout { size_t o_sketch, o_mread, o_kst, o_mt, o_acnt, o_bsum, total
 SeedLayout seed_layout(const gbx_mm_params *p, int64_t n_reads, int64_t total_len, int64_t mini_cap, int64_t anchor_cap)
 {
     SeedLayout L;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += align256(bytes); return o; };
+    Carver take;
     const size_t mc = (size_t)(mini_cap > 0 ? mini_cap : 1);
     L.o_sketch = take(sketch_layout(p, n_reads, total_len).total);
     L.o_mread = take(mc * 4);
@@ -441,7 +305,7 @@ SeedLayout seed_layout(const gbx_mm_params *p, int64_t n_reads, int64_t total_le
     L.o_acnt = take((mc + 1) * 8);
     L.o_bsum = take((size_t)mem_scan_blocks((long long)mc) * 8);
     L.sort = sort_layout(anchor_cap, take);
-    L.total = at;
+    L.total = take.at;
     return L;
 }
 
@@ -490,7 +354,7 @@ int mm_sketch_launch(const gbx_mm_params *p, int64_t n_seqs, const uint8_t *d_se
     }
     {
         Stage st("mm_sketch_scan", s);
-        scan1(J.cnt, J.n_units, (long long *)(wb + L.o_bsum), d_n_mini, MemScanGuard{}, s);
+        scan_launch1(J.cnt, J.n_units, (long long *)(wb + L.o_bsum), d_n_mini, MemScanGuard{}, s);
     }
     {
         Stage st("mm_sketch_fill", s);
@@ -512,13 +376,13 @@ int mm_index_launch(const gbx_mm_params *p, int64_t n_seqs, const uint8_t *d_seq
     const IndexLayout L = index_layout(p, n_seqs, total_len, mini_cap);
     if (work_bytes < L.total) { set_error("mm index: workspace too small (%zu bytes, %zu needed)", work_bytes, L.total); return GBX_ERR_ARG; }
     char *wb = (char *)d_work;
-    const SortBufs B = sort_bufs(wb, L.sort, mini_cap);
+    const SortBufs<u64> B = sort_bufs(wb, L.sort);
     IndexJob J;
-    J.v = mm_index_view(d_index, mini_cap); J.cap = B.cap;
+    J.v = mm_index_view(d_index, mini_cap); J.cap = mini_cap > 0 ? mini_cap : 1;
     J.cnt = (long long *)(wb + L.o_cnt);
     J.frac = p->mid_occ_frac; J.mid_occ = p->mid_occ; J.k = p->k; J.w = p->w; J.hpc = p->is_hpc;
     // the minimizers land in sort buffer 0; their offsets per sequence are not kept
-    int rc = mm_sketch_launch(p, n_seqs, d_seq, d_seq_off, total_len, 1, B.hi[0], B.lo[0], mini_cap, (int64_t *)(wb + L.o_moff), J.v.hdr, wb + L.o_sketch,
+    int rc = mm_sketch_launch(p, n_seqs, d_seq, d_seq_off, total_len, 1, B.a[0], B.b[0], mini_cap, (int64_t *)(wb + L.o_moff), J.v.hdr, wb + L.o_sketch,
                               sketch_layout(p, n_seqs, total_len).total, s);
     if (rc) return rc;
     SortPass pass[8];
@@ -527,25 +391,25 @@ int mm_index_launch(const gbx_mm_params *p, int64_t n_seqs, const uint8_t *d_seq
     int cur;
     {
         Stage st("mm_index_sort", s);
-        cur = radix_sort(B, J.v.hdr, pass, np, s);
+        cur = radix_sort(B, SortCount{J.v.hdr, J.cap}, pass, np, s);
     }
-    J.hi = B.hi[cur]; J.lo = B.lo[cur]; J.chi = B.hi[cur ^ 1];
+    J.hi = B.a[cur]; J.lo = B.b[cur]; J.chi = B.a[cur ^ 1];
     {
         Stage st("mm_index_group", s);
         hipLaunchKernelGGL(mm_idx_head_kernel, dim3(el_blocks(J.cap)), dim3(EL), 0, s, J);
-        scan1(J.cnt, J.cap, (long long *)(wb + L.o_bsum), J.v.hdr + 1, MemScanGuard{}, s);
+        scan_launch1(J.cnt, J.cap, (long long *)(wb + L.o_bsum), J.v.hdr + 1, MemScanGuard{}, s);
         hipLaunchKernelGGL(mm_idx_write_kernel, dim3(el_blocks(J.cap)), dim3(EL), 0, s, J);
         hipLaunchKernelGGL(mm_idx_count_kernel, dim3(el_blocks(J.cap)), dim3(EL), 0, s, J);
     }
     {
         Stage st("mm_index_mid_occ", s);
         // the counts sit in the buffer the sorted minimizers do not use; the sort starts from buffer 0
-        SortBufs C = B;
-        if (cur == 0) { std::swap(C.hi[0], C.hi[1]); std::swap(C.lo[0], C.lo[1]); }
+        SortBufs<u64> C = B;
+        if (cur == 0) { std::swap(C.a[0], C.a[1]); std::swap(C.b[0], C.b[1]); }
         np = 0;
         for (int sh = 0; sh < bits_of(J.cap) && sh < 32; sh += 8) pass[np++] = SortPass{0, sh, 255u};
-        const int c2 = radix_sort(C, J.v.hdr + 1, pass, np, s);
-        J.hi = C.hi[c2];
+        const int c2 = radix_sort(C, SortCount{J.v.hdr + 1, J.cap}, pass, np, s);
+        J.hi = C.a[c2];
         hipLaunchKernelGGL(mm_idx_mid_occ_kernel, dim3(1), dim3(1), 0, s, J);
     }
     GBX_HIP(hipGetLastError());
@@ -571,21 +435,22 @@ int mm_seed_launch(const gbx_mm_params *p, const MmSeedIo &io, void *d_work, siz
     int rc = mm_sketch_launch(p, io.n_reads, io.seq, io.seq_off, io.total_len, 0, io.mini_x, io.mini_y, io.mini_cap, io.mini_off, io.counts,
                               wb + L.o_sketch, sketch_layout(p, io.n_reads, io.total_len).total, s);
     if (rc) return rc;
-    const SortBufs B = sort_bufs(wb, L.sort, io.anchor_cap);
+    const SortBufs<u64> B = sort_bufs(wb, L.sort);
+    const long long sort_cap = io.anchor_cap > 0 ? io.anchor_cap : 1;
     SeedJob J;
     J.v = mm_index_view(const_cast<void *>(io.index), io.index_mini_cap); J.idx_cap = io.index_mini_cap > 0 ? io.index_mini_cap : 1;
     J.seq = io.seq; J.seq_off = io.seq_off; J.n_reads = io.n_reads;
     J.mx = (const u64 *)io.mini_x; J.my = (const u64 *)io.mini_y; J.mini_cap = io.mini_cap; J.mini_off = io.mini_off;
     J.mread = (int32_t *)(wb + L.o_mread); J.kst = (long long *)(wb + L.o_kst); J.mt = (int32_t *)(wb + L.o_mt);
     J.acnt = (long long *)(wb + L.o_acnt);
-    J.hi = B.hi[0]; J.lo = B.lo[0]; J.anchor_cap = io.anchor_cap;
+    J.hi = B.a[0]; J.lo = B.b[0]; J.anchor_cap = io.anchor_cap;
     J.off = io.off; J.hdr = io.hdr; J.rep_len = io.rep_len; J.n_mini = io.n_mini; J.counts = io.counts;
     J.ax = (u64 *)io.ax; J.ay = (u64 *)io.ay; J.max_gap = p->max_gap; J.bw = p->bw;
     {
         Stage st("mm_seed_lookup", s);
         if (io.mini_cap > 0) hipLaunchKernelGGL(mm_seed_lookup_kernel, dim3(el_blocks(io.mini_cap)), dim3(EL), 0, s, J);
         else GBX_HIP(hipMemsetAsync(J.acnt, 0, 16, s));
-        scan1(J.acnt, io.mini_cap, (long long *)(wb + L.o_bsum), io.counts + 1, MemScanGuard{io.counts, 0, io.mini_cap}, s);
+        scan_launch1(J.acnt, io.mini_cap, (long long *)(wb + L.o_bsum), io.counts + 1, MemScanGuard{io.counts, 0, io.mini_cap}, s);
         hipLaunchKernelGGL(mm_seed_read_kernel, dim3((unsigned)io.n_reads), dim3(64), 0, s, J);
     }
     {
@@ -603,8 +468,8 @@ int mm_seed_launch(const gbx_mm_params *p, const MmSeedIo &io, void *d_work, siz
     for (int sh = READ_SHIFT; sh < READ_SHIFT + bits_of(io.n_reads - 1); sh += 8) pass[np++] = SortPass{1, sh, 255u};      // the read
     {
         Stage st("mm_seed_sort", s);
-        const int cur = radix_sort(B, io.counts + 1, pass, np, s);
-        hipLaunchKernelGGL(mm_seed_unpack_kernel, dim3(el_blocks(B.cap)), dim3(EL), 0, s, B.hi[cur], B.lo[cur], io.counts + 1, (long long)io.anchor_cap,
+        const int cur = radix_sort(B, SortCount{io.counts + 1, sort_cap}, pass, np, s);
+        hipLaunchKernelGGL(mm_seed_unpack_kernel, dim3(el_blocks(sort_cap)), dim3(EL), 0, s, B.a[cur], B.b[cur], io.counts + 1, (long long)io.anchor_cap,
                            J.ax, J.ay);
     }
     GBX_HIP(hipGetLastError());

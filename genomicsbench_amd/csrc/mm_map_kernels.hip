@@ -10,7 +10,7 @@
 //   PAF       a lane per region measures its line, scan, a lane per region writes it
 // Counts live on the device, nothing is written past a capacity, no kernel waits for another block and no entry synchronises
 // with the host.
-#include "gbx_internal.h"
+#include "dev_prims.h"
 #include "mm_map_rules.h"
 
 namespace gbx {
@@ -18,7 +18,6 @@ namespace {
 
 constexpr int EL = 256, SCAN_T = 1024;
 inline unsigned el_blocks(long long n) { const long long b = (n + EL - 1) / EL; return (unsigned)(b > 0 ? b : 1); }
-inline size_t a256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct MmWave {
     __device__ int lane() const { return (int)threadIdx.x; }
@@ -33,20 +32,12 @@ MapLayout map_layout(int64_t n_reads, int64_t anchor_cap, int64_t chain_cap)
 {
     const size_t A = (size_t)(anchor_cap > 0 ? anchor_cap : 1), R = (size_t)(n_reads > 0 ? n_reads : 1), Cc = (size_t)(chain_cap > 0 ? chain_cap : 1);
     MapLayout L;
-    size_t o = 0;
-    L.o_own = o; o += a256(A * 4);
-    L.o_top = o; o += a256(A * 4);
-    L.o_perm = o; o += a256(A * 4);
-    L.o_key = o; o += a256(A * 8);
-    L.o_urank = o; o += a256(A * 8);
-    L.o_uws = o; o += a256(A * 8);
-    L.o_nkeys = o; o += a256(R * 4);
-    L.o_nch = o; o += a256(R * 4);
-    L.o_nreg = o; o += a256(R * 4);
-    L.o_z = o; o += a256(Cc * sizeof(MmZ));
-    L.o_w = o; o += a256(Cc * 4);
-    L.o_stage = o; o += a256(Cc * sizeof(gbx_mm_reg));
-    L.total = o;
+    Carver take;
+    L.o_own = take(A * 4); L.o_top = take(A * 4); L.o_perm = take(A * 4);
+    L.o_key = take(A * 8); L.o_urank = take(A * 8); L.o_uws = take(A * 8);
+    L.o_nkeys = take(R * 4); L.o_nch = take(R * 4); L.o_nreg = take(R * 4);
+    L.o_z = take(Cc * sizeof(MmZ)); L.o_w = take(Cc * 4); L.o_stage = take(Cc * sizeof(gbx_mm_reg));
+    L.total = take.at;
     return L;
 }
 
@@ -93,8 +84,7 @@ __global__ void __launch_bounds__(SCAN_T) mm_map_scan_kernel(int64_t *a, const i
                                                              long long guard_cap)
 {
     __shared__ long long part[SCAN_T];
-    long long n = n_cap;
-    if (n_dev) { const long long v = *n_dev; n = v < 0 ? 0 : v > n_cap ? n_cap : v; }
+    const long long n = n_dev ? clip_count(n_dev, n_cap) : n_cap;
     const long long chunk = (n + SCAN_T - 1) / SCAN_T, lo = (long long)threadIdx.x * chunk, hi = lo + chunk < n ? lo + chunk : n;
     long long sum = 0;
     for (long long i = lo; i < hi; ++i) sum += a[i];
@@ -159,23 +149,17 @@ __device__ inline long long paf_line(const PafJob &J, long long g, uint8_t *out,
                        tok ? J.io.tnames + t0 : nullptr, t1 > t0 ? t1 - t0 : 0, tlen, J.io.rep_len[r]);
 }
 
-__device__ inline long long paf_regs(const PafJob &J)
-{
-    const long long v = *J.io.n_regs;
-    return v < 0 ? 0 : v > J.io.reg_cap ? J.io.reg_cap : v;
-}
-
 __global__ void __launch_bounds__(EL) mm_paf_measure_kernel(PafJob J)
 {
     const long long g = (long long)blockIdx.x * EL + threadIdx.x;
     if (g >= J.io.reg_cap) return;
-    J.at[g] = g < paf_regs(J) ? paf_line(J, g, nullptr, 0) : 0;
+    J.at[g] = g < clip_count(J.io.n_regs, J.io.reg_cap) ? paf_line(J, g, nullptr, 0) : 0;
 }
 
 __global__ void __launch_bounds__(EL) mm_paf_write_kernel(PafJob J)
 {
     const long long g = (long long)blockIdx.x * EL + threadIdx.x;
-    if (g < paf_regs(J)) paf_line(J, g, J.io.lines, J.at[g]);
+    if (g < clip_count(J.io.n_regs, J.io.reg_cap)) paf_line(J, g, J.io.lines, J.at[g]);
     if (g <= J.io.n_reads) {
         const long long ro = J.io.reg_off[g];
         J.io.line_off[g] = J.at[ro < 0 ? 0 : ro > J.io.reg_cap ? J.io.reg_cap : ro];
@@ -221,7 +205,7 @@ int mm_map_launch(const gbx_mm_map_params *p, const MmMapIo &io, void *d_work, s
     return GBX_OK;
 }
 
-size_t mm_paf_workspace_bytes(int64_t n_reads, int64_t reg_cap) { (void)n_reads; return a256((size_t)((reg_cap > 0 ? reg_cap : 0) + 1) * 8); }
+size_t mm_paf_workspace_bytes(int64_t n_reads, int64_t reg_cap) { (void)n_reads; return align256((size_t)((reg_cap > 0 ? reg_cap : 0) + 1) * 8); }
 
 int mm_paf_launch(const MmPafIo &io, void *d_work, size_t work_bytes, hipStream_t s)
 {

@@ -24,7 +24,7 @@
 // GBX_LOOP_GUARD build the op walks count down from the read's op count as well.  Query positions outside [0, l_seq) and
 // unknown ops are skipped on the device; the host entries refuse such reads before uploading them.
 #include <algorithm>
-#include "gbx_internal.h"
+#include "dev_prims.h"
 
 namespace gbx {
 namespace {
@@ -44,8 +44,6 @@ __host__ __device__ inline bool op_query(int op) { return op == OP_M || op == OP
 // nt16 (+16 on the reverse strand) -> index in "acgtACGTdD", -1 for IUPAC codes (medaka_counts.h: num2countbase)
 __constant__ int8_t c_countbase[32] = {-1, 4, 5, -1, 6, -1, -1, -1, 7, -1, -1, -1, -1, -1, -1, -1,
                                        -1, 0, 1, -1, 2, -1, -1, -1, 3, -1, -1, -1, -1, -1, -1, -1};
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct PlpOp {                                     // per CIGAR op: reference and query position of its start, the indel of its
     int32_t r, q, ind;                             // last position

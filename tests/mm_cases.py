@@ -132,3 +132,28 @@ def seed_case():
     assert per_read[-3] == 0 and exp["n_mini"][-3] > 0 and per_read[-2] == 0, "the random and the empty read have anchors"
     assert (per_read > 0).sum() >= 10
     return refs, tuple(reads), exp
+
+
+SORT_TILE = 4096                           # items a block of the radix sort takes (csrc/gbx_internal.h)
+
+
+@functools.lru_cache(maxsize=None)
+def tile_case():
+    """-> (reference sequences, reads, expected dict of the restatement) with enough minimizers and anchors for the (u64, u64)
+    radix sort to run over several tiles with a ragged last one: index values, keys and anchors each above two tiles."""
+    rng = random.Random(9091)
+    refs = (rand_seq(rng, 30000), rand_seq(rng, 20000), rand_seq(rng, 7))
+    reads = []
+    for i in range(24):
+        src = refs[i % 2]
+        o = rng.randrange(0, len(src) - 4000)
+        s = mutate(rng, src[o:o + 4000], 0.01)
+        reads.append(revcomp(s) if i % 3 == 0 else s)
+    reads.append(b"")
+    idx = R.Index(refs, SEED_PARAMS["w"], SEED_PARAMS["k"], False, mid_occ=SEED_PARAMS["mid_occ"])
+    exp = R.seed_batch(idx, reads)
+    keys, _, vals = idx.flat()
+    for n in (len(vals), len(keys), len(exp["ax"])):
+        assert n > 2 * SORT_TILE and n % SORT_TILE != 0, n
+    assert (exp["ax"] >> np.uint64(63)).any(), "no reverse-strand anchor"
+    return refs, tuple(reads), exp

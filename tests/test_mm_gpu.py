@@ -126,16 +126,14 @@ def test_seed_batch(seed_index):
     same(sd.results(), want)
 
 
-@pytest.mark.parametrize("what", ["anchor", "mini"])
-@pytest.mark.parametrize("short", [0, 1, 600])
-def test_seed_capacity(seed_index, what, short):
-    """A capacity exactly at, one below and far below the need: the counts are the need, off and mini_off stay true, nothing is
-    written behind a capacity; with too few minimizer slots the anchors are not made (-1)."""
+def check_seed_capacity(index, case, what, short):
+    """The capacity of `what` is `short` below the need: the counts are the need, off and mini_off stay true, nothing is written
+    behind a capacity; with too few minimizer slots the anchors are not made (-1)."""
     import torch
-    _, reads, want = K.seed_case()
+    _, reads, want = case
     n_m, n_a = len(want["mini_x"]), len(want["ax"])
     mcap, acap = (n_m - short, n_a) if what == "mini" else (n_m, n_a - short)
-    sd = MS.DeviceMmSeeder(seed_index, reads, mini_cap=mcap, anchor_cap=acap)
+    sd = MS.DeviceMmSeeder(index, reads, mini_cap=mcap, anchor_cap=acap)
     g = lambda n: torch.from_numpy(np.full(n + 16, GUARD, np.uint64).view(np.int64)).to(sd.device)
     sd.mini_x, sd.mini_y, sd.ax, sd.ay = g(mcap), g(mcap), g(acap), g(acap)
     sd.run(stream())
@@ -154,6 +152,50 @@ def test_seed_capacity(seed_index, what, short):
         else:
             with pytest.raises(N.GbxError):
                 sd.chain_batch()
+
+
+@pytest.mark.parametrize("what", ["anchor", "mini"])
+@pytest.mark.parametrize("short", [0, 1, 600])
+def test_seed_capacity(seed_index, what, short):
+    """A capacity exactly at, one below and far below the need."""
+    check_seed_capacity(seed_index, K.seed_case(), what, short)
+
+
+@pytest.mark.parametrize("variant", [dict(mid_occ=20), dict(mid_occ_frac=0.1)], ids=["mid_occ=20", "mid_occ_frac=0.1"])
+def test_index_across_sort_tiles(variant):
+    """mm_cases.tile_case: the minimizers fill more than two tiles of the radix sort and end inside one; under mid_occ_frac the
+    ascending sort of the keys' counts, over two tiles itself, decides mid_occ."""
+    refs, _, _ = K.tile_case()
+    want = R.Index(refs, K.SEED_PARAMS["w"], K.SEED_PARAMS["k"], False, mid_occ=variant.get("mid_occ", 0), mid_occ_frac=variant.get("mid_occ_frac", 2e-4))
+    ix = MS.DeviceMmIndex(MS.make_params(k=K.SEED_PARAMS["k"], w=K.SEED_PARAMS["w"], is_hpc=0, **variant), refs, dev(), stream())
+    wk, wo, wv = want.flat()
+    assert (ix.info.n_keys, ix.info.n_vals, ix.info.mid_occ) == (len(wk), len(wv), want.mid_occ)
+    keys, koff, vals = ix.flat()
+    assert np.array_equal(keys, wk) and np.array_equal(koff, wo) and np.array_equal(vals, wv)
+
+
+@pytest.fixture(scope="module")
+def tile_index():
+    refs, _, _ = K.tile_case()
+    return MS.DeviceMmIndex(MS.make_params(**K.SEED_PARAMS), refs, dev(), stream())
+
+
+def test_seed_across_sort_tiles(tile_index):
+    """The anchors of mm_cases.tile_case fill three tiles of the sort and part of a fourth: under the default capacities, under an
+    anchor capacity that is the need, and under one a tile and 17 items above it (blocks wholly past the count)."""
+    _, reads, want = K.tile_case()
+    n_a = len(want["ax"])
+    for caps in (dict(), dict(anchor_cap=n_a), dict(anchor_cap=n_a + K.SORT_TILE + 17)):
+        sd = MS.DeviceMmSeeder(tile_index, reads, **caps)
+        sd.run(stream())
+        assert sd.counts() == (len(want["mini_x"]), n_a) and sd.fits(), caps
+        same(sd.results(), want)
+
+
+@pytest.mark.parametrize("short", [1, 4097])
+def test_seed_capacity_across_sort_tiles(tile_index, short):
+    """An anchor capacity one item and a tile and an item below the need, on the case whose sort runs over several tiles."""
+    check_seed_capacity(tile_index, K.tile_case(), "anchor", short)
 
 
 def test_seed_host(seed_index):
