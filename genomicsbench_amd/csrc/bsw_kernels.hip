@@ -49,6 +49,7 @@ struct BswDev {
     uint8_t remap[24];     // query class -> the class whose kernel runs it (identity, or a wider class for small jobs)
     uint32_t lrow[5];      // lane path: lrow[t] = mat[t][q] as five signed 6-bit fields at bit 6q (read with one v_bfe_i32)
     int lane_on;           // 1: pairs that qualify (lane_ok) run on bsw_lane_kernel, one pair per lane
+    int lane_prio;         // 1: the lane wavefronts that hold the most LDS issue first (lane_wave_prio)
 };
 
 struct BswPairs {
@@ -721,9 +722,28 @@ __device__ __forceinline__ uint32_t lane_pair_step(uint32_t w, uint32_t qq, uint
 #ifdef GBX_BSW_LANE_STATS
 // development aid (scripts/dbg_bsw_lanes.py): how full the lock-step rows are.  Per launch slot: [0] cells the lanes
 // computed, [1] 64 x the widest window of every row (what the wavefront paid), [2] rows the lanes ran, [3] 64 x rows the
-// wavefront ran; units of 256.
-__device__ unsigned long long g_bsw_lane_stats[16][4];
+// wavefront ran; units of 256.  [4] chunks the launch's wavefronts took, [5] the sum of their times from the claim to the
+// result store, in wall_clock64 ticks (100 MHz): the mean chunk time says how long a wavefront holds its LDS per chunk (both
+// lane kernels; the register kernel fills these two only).
+constexpr int LANE_NSTAT = 6;
+__device__ unsigned long long g_bsw_lane_stats[16][LANE_NSTAT];
 #endif
+// Dynamic LDS of a bsw_lane_kernel wavefront (launch_lanes allocates it, the kernel ranks itself by it).  Compact: cols / 2
+// dword rows of cells, cols / 2 rows of query codes (halfwords, or bytes: CODE4), and what the look-ahead of the query plane
+// reads past its end (the cells' look-ahead lands in the query plane); wide: a dword row per column and 2 columns of look-ahead.
+__host__ __device__ constexpr int lane_lds_bytes(bool compact, bool code4, int cols)
+{
+    return compact ? (cols / 2) * (code4 ? 320 : 384) + 640 : (cols + 2) * 256;
+}
+// Issue priority of the lane wavefronts.  A wavefront of bsw_lane_kernel holds 10-27 KB of LDS for as long as
+// its chunk takes, and the CU's LDS is what keeps the next one out; a wavefront of bsw_lane_reg_kernel on the same SIMD holds
+// none and fills whatever issue slots are left.  The launches of 20 KB and more per wavefront (queries from 100 on, the long
+// wide classes: six or seven wavefronts per CU, the job's last to finish) issue first, at priority 3; all others stay at 0:
+// raising the middle classes as well (3 / 2 / 1 by footprint, or all at 2) starved the register kernel and lost.
+__host__ __device__ constexpr int lane_wave_prio(int on, int lds_bytes)
+{
+    return on && lds_bytes >= 20 * 1024 ? 3 : 0;
+}
 // PACKED: P.ref / P.qer are the packed images of the arenas (two base codes per byte, host_pipeline.h: pack4; code k of an
 // arena is nibble k & 1 of byte k >> 1) - the pipelined host call's chunks whose pairs all run here are never expanded.
 template <bool SYM, bool COMPACT, bool CODE4 = false, bool PACKED = false>
@@ -733,7 +753,7 @@ __global__ void __launch_bounds__(64) bsw_lane_kernel(BswDev prm, BswPairs P, Bs
 #ifdef GBX_BSW_LANE_STATS
     __shared__ int st_rowmax[2048];
     for (int k = threadIdx.x; k < 2048; k += 64) st_rowmax[k] = 0;
-    unsigned long long st_cells = 0, st_rows = 0, st_wcells = 0, st_wrows = 0;
+    unsigned long long st_cells = 0, st_rows = 0, st_wcells = 0, st_wrows = 0, st_chunks = 0, st_ticks = 0;
 #endif
 #define LCELL(byte_addr) (*(uint32_t *)((char *)lcell + (byte_addr)))
 #define LCELL16(byte_addr) (*(uint16_t *)((char *)lcell + (byte_addr)))
@@ -768,11 +788,18 @@ __global__ void __launch_bounds__(64) bsw_lane_kernel(BswDev prm, BswPairs P, Bs
 #define LTAB(base_code) (*(const uint4 *)((const char *)lcell + tab + min((int)(base_code), 4) * 16))
     int rel0 = 0, rel1 = 2, rel2 = 256, rel3 = 258, rel4 = 512, rel5 = 514, rel6 = 768, rel7 = 770;      // cell offsets within a trip of the main loop
     asm volatile("" : "+v"(rel0), "+v"(rel1), "+v"(rel2), "+v"(rel3), "+v"(rel4), "+v"(rel5), "+v"(rel6), "+v"(rel7));
+    // The wavefront's issue priority, once, from kernel arguments only: the condition is uniform, one s_setprio behind a scalar
+    // branch (the instruction takes an immediate and ignores EXEC).  Behind the loads of the list's bounds: ahead of them the
+    // compiler takes the instruction for a store and reads the bounds per lane.
+    if (lane_wave_prio(prm.lane_prio, lane_lds_bytes(COMPACT, CODE4, cols)) == 3) __builtin_amdgcn_s_setprio(3);
     for (;;) {
         int c = 0;
         if (lane == 0) c = atomicAdd(&W.lchunk[slot], 1);
         c = __builtin_amdgcn_readfirstlane(c);
         if (c >= nchunks) break;
+#ifdef GBX_BSW_LANE_STATS
+        const unsigned long long st_t0 = wall_clock64();
+#endif
         // the sorted list ascends in query length: chunks are taken from its end, so the kernel's tail is short pairs
         const int hi_ = count - (c << 6), idx = hi_ - 64 + lane;
         const bool have = idx >= 0;                     // only the last chunk of a launch is ragged: its spare lanes repeat entry 0
@@ -1003,12 +1030,14 @@ __global__ void __launch_bounds__(64) bsw_lane_kernel(BswDev prm, BswPairs P, Bs
         if (have) P.out[pair] = r;
 #ifdef GBX_BSW_LANE_STATS
         __builtin_amdgcn_s_waitcnt(0);
+        st_chunks += 1; st_ticks += wall_clock64() - st_t0;
         for (int k = threadIdx.x; k < 2048; k += 64) { const int m = st_rowmax[k]; if (m) { st_wcells += 64ull * (unsigned)(m - 1); st_wrows += 64; } st_rowmax[k] = 0; }
 #endif
     }
 #ifdef GBX_BSW_LANE_STATS
     atomicAdd(&g_bsw_lane_stats[slot][0], st_cells); atomicAdd(&g_bsw_lane_stats[slot][1], st_wcells);
     atomicAdd(&g_bsw_lane_stats[slot][2], st_rows); atomicAdd(&g_bsw_lane_stats[slot][3], st_wrows);
+    if (lane == 0) { atomicAdd(&g_bsw_lane_stats[slot][4], st_chunks); atomicAdd(&g_bsw_lane_stats[slot][5], st_ticks); }
 #endif
 #undef LCELL
 #undef LCELL16
@@ -1181,11 +1210,20 @@ __global__ void __launch_bounds__(64, 3) bsw_lane_reg_kernel(BswDev prm, BswPair
     const int nchunks = (count + 63) >> 6;
     const int32_t *order = W.lorder + first;
     const int e_ins = prm.e_ins, e_del = prm.e_del, oe_ins = prm.oe_ins, oe_del = prm.oe_del;
+#ifdef GBX_BSW_LANE_STATS
+    unsigned long long st_chunks = 0, st_ticks = 0;
+#endif
+    // holds no LDS to speak of: behind every bsw_lane_kernel wavefront (lane_wave_prio).  Placed behind the loads of the list's
+    // bounds: ahead of them the compiler takes the instruction for a store and reads the bounds per lane.
+    __builtin_amdgcn_s_setprio(0);
     for (;;) {
         int c = 0;
         if (lane == 0) c = atomicAdd(&W.lchunk[slot], 1);
         c = __builtin_amdgcn_readfirstlane(c);
         if (c >= nchunks) break;
+#ifdef GBX_BSW_LANE_STATS
+        const unsigned long long st_t0 = wall_clock64();
+#endif
         const int hi_ = count - (c << 6), idx = hi_ - 64 + lane;
         const bool have = idx >= 0;                    // the ragged last chunk's spare lanes repeat entry 0
         const int pair = order[have ? idx : 0];
@@ -1366,7 +1404,14 @@ __global__ void __launch_bounds__(64, 3) bsw_lane_reg_kernel(BswDev prm, BswPair
         gbx_bsw_result r;
         r.score = best; r.tle = best_i + 1; r.gtle = g_i + 1; r.qle = best_j + 1; r.gscore = g_score; r.max_off = off;
         if (have) P.out[pair] = r;
+#ifdef GBX_BSW_LANE_STATS
+        __builtin_amdgcn_s_waitcnt(0);
+        st_chunks += 1; st_ticks += wall_clock64() - st_t0;
+#endif
     }
+#ifdef GBX_BSW_LANE_STATS
+    if (lane == 0) { atomicAdd(&g_bsw_lane_stats[slot][4], st_chunks); atomicAdd(&g_bsw_lane_stats[slot][5], st_ticks); }
+#endif
 }
 
 // ---- kernel shapes ----------------------------------------------------------
@@ -1465,6 +1510,7 @@ int make_dev_params(const gbx_bsw_params *p, BswDev *d)
     }
     // lane path: the matrix row as five signed 6-bit fields; scorings outside [-32, 31] keep every pair on the row kernels
     d->lane_on = 0;
+    d->lane_prio = 0;      // bsw_launch sets it
     bool fits6 = true;
     for (int k = 0; k < 25; ++k) fits6 = fits6 && p->mat[k] >= -32 && p->mat[k] <= 31;
     for (int t = 0; t < 5; ++t) {
@@ -1727,14 +1773,41 @@ static void launch_row_classes(BswCall &c)
     }
 }
 
-// The compact 80..99 class with its cells in registers (bsw_lane_reg_kernel), as many wavefronts as its registers allow
+// VGPRs a wavefront of `fn` is allocated (the compiler's count in the allocation's steps of eight); 0 if the query fails
+static int wave_vgprs(const void *fn)
+{
+    hipFuncAttributes a;
+    if (hipFuncGetAttributes(&a, fn) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    return a.numRegs >= 1 && a.numRegs <= 512 ? (a.numRegs + 7) & ~7 : 0;
+}
+
+// wavefronts per CU of the last bsw_lane_reg_kernel launch (gbx_debug_bsw_lane_reg_waves)
+static std::atomic<int> g_lane_reg_waves{0};
+
+// The compact 80..99 class with its cells in registers (bsw_lane_reg_kernel).  Its persistent grid is not what fits when it has the
+// chip to itself (the occupancy query: three wavefronts per SIMD at 149 VGPRs, which leave 56 of a SIMD's 512 registers, so that
+// no wavefront of bsw_lane_kernel joins them until the whole 80..99 list is done) but the most wavefronts per SIMD that leave
+// room for two of the 100..135 launch: two, eight per CU, with today's 152 and 88 registers.  Each then loops over more chunks.
+// Measured beside the priorities: DESIGN.md §3.1.  GBX_BSW_LANE_REG_WAVES = wavefronts per CU (read per call: the tests vary it),
+// at most what is resident.
 static void launch_lane_reg(const BswCall &c, hipStream_t sc, int64_t want, int rlo, int rhi, int slot)
 {
     static_assert(LANE_RANGE_HI[0][2] == 99, "bsw_lane_reg_kernel instance");
     typedef void (*LaneRegFn)(BswDev, BswPairs, BswWork, int, int, int);
     static const LaneRegFn reg_fn[2] = {bsw_lane_reg_kernel<false, 99>, bsw_lane_reg_kernel<true, 99>};
-    static std::atomic<int> reg_bpc[2];
-    const int64_t cap = (int64_t)c.cus * resident_blocks(reg_bpc[c.sym], (const void *)reg_fn[c.sym], 64, 8, INT_MAX);
+    static std::atomic<int> reg_bpc[2], reg_plan[2];
+    const int resident = resident_blocks(reg_bpc[c.sym], (const void *)reg_fn[c.sym], 64, 8, INT_MAX);
+    int plan = reg_plan[c.sym].load(std::memory_order_relaxed);
+    if (!plan) {
+        const int rv = wave_vgprs((const void *)reg_fn[c.sym]), lv = wave_vgprs((const void *)lane_kernels[0][LANE_COMPACT4][c.sym]);
+        plan = rv && lv && 512 - 2 * lv >= rv ? 4 * ((512 - 2 * lv) / rv) : resident;       // four SIMDs per CU, 512 VGPRs each
+        reg_plan[c.sym].store(plan, std::memory_order_relaxed);
+    }
+    int per_cu = plan;
+    if (const char *e = getenv("GBX_BSW_LANE_REG_WAVES")) { const int v = atoi(e); if (v >= 1) per_cu = v; }
+    per_cu = per_cu < resident ? per_cu : resident;
+    g_lane_reg_waves.store(per_cu, std::memory_order_relaxed);
+    const int64_t cap = (int64_t)c.cus * per_cu;
     hipLaunchKernelGGL(reg_fn[c.sym], dim3((unsigned)(want < cap ? want : cap)), dim3(64), 0, sc, c.dev, c.P, c.W, rlo, rhi, slot);
     g_lane_reg_launches.fetch_add(1, std::memory_order_relaxed);
 }
@@ -1752,11 +1825,9 @@ static void launch_lanes(const BswCall &c)
         for (int r = LANE_NRANGE - 1; r >= 0; --r) {
             const int qlo = r ? LANE_RANGE_HI[fmt][r - 1] + 1 : 1, qhi = LANE_RANGE_HI[fmt][r];
             const int cols = (qhi + 3) & ~1;                   // columns 0..qlen, and even
-            // compact: cols / 2 dword rows of cells, cols / 2 halfword rows of query codes, and what the look-ahead of the
-            // query plane reads past its end (the cells' look-ahead lands in the query plane); wide: 2 columns of look-ahead
             // (four-bit query codes for the two longest compact classes: see bsw_lane_kernel)
             const int kind = fmt ? LANE_WIDE : qhi > 99 ? LANE_COMPACT4 : LANE_COMPACT;
-            const size_t lds = fmt ? (size_t)(cols + 2) * 256 : (size_t)(cols / 2) * (kind == LANE_COMPACT4 ? 320 : 384) + 640;
+            const size_t lds = (size_t)lane_lds_bytes(!fmt, kind == LANE_COMPACT4, cols);
             const int fit = (int)((size_t)160 * 1024 / lds), per_cu = fit > 16 ? 16 : fit;
             const int sk = (LANE_NRANGE - 1 - r) & 3;          // the launch's ordinal in its format, longest first
             hipStream_t sc = sk == 0 ? c.s : c.ss->side[sk - 1];
@@ -1809,6 +1880,7 @@ int bsw_launch(const gbx_bsw_params *p, int64_t n,
     int32_t *wi = (int32_t *)d_work, *wl = wi + WS_HDR + 4 * n;
     c.W = {wi, wi + HDR, wi + 2 * HDR, wi + 3 * HDR, wi + WS_HDR, wi + WS_HDR + n, wl, wi + WS_HDR + 3 * n, wi + WS_HDR + 2 * n, wl + LANE_BINS + 64};
     c.dev.lane_on = c.dev.lane_on && lane_wanted(n) ? 1 : 0;
+    c.dev.lane_prio = switched_off("GBX_BSW_LANE_PRIO") ? 0 : 1;         // read per call: the tests vary it
     c.sym = c.dev.oe_ins == c.dev.oe_del;
     c.s = s; c.join_events = join_events; c.prep = prep;
     if ((rc = side_streams(&c.ss))) return rc;
@@ -1856,11 +1928,17 @@ extern "C" long long gbx_debug_bsw_lane_reg_launches(void)
     return gbx::g_lane_reg_launches.load(std::memory_order_relaxed);
 }
 
+extern "C" int gbx_debug_bsw_lane_reg_waves(void)
+{
+    return gbx::g_lane_reg_waves.load(std::memory_order_relaxed);
+}
+
 #ifdef GBX_BSW_LANE_STATS
 extern "C" int gbx_debug_bsw_lane_stats(unsigned long long *out, int reset)
 {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(gbx::g_bsw_lane_stats), sizeof(unsigned long long) * 64) != hipSuccess) return -1;
-    if (reset) { unsigned long long z[64] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(gbx::g_bsw_lane_stats), z, sizeof(z)) != hipSuccess) return -1; }
+    // out: 16 slots x LANE_NSTAT values
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(gbx::g_bsw_lane_stats), sizeof(gbx::g_bsw_lane_stats)) != hipSuccess) return -1;
+    if (reset) { unsigned long long z[16 * gbx::LANE_NSTAT] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(gbx::g_bsw_lane_stats), z, sizeof(z)) != hipSuccess) return -1; }
     return 0;
 }
 #endif
