@@ -125,10 +125,12 @@ def poa_oracle(params, ws, nthreads=1, stride=None, return_cells=False):
     return (out, cells.value) if return_cells else out
 
 
-def abea_oracle(rs, nthreads=1, return_cells=False):
-    """oracle_abea_align over an AbeaReadSet -> (pairs flat structured array, n_pairs)."""
+def abea_oracle(rs, nthreads=1, return_cells=False, room=0):
+    """oracle_abea_align over an AbeaReadSet -> (pairs flat structured array, n_pairs).  The pair array holds 2 x events
+    as the reference's does; `room` asks for more entries, which the last read's walk may then run into (a read with more
+    k-mers than 2 x its events walks past its own share: only safe as the last read, with room >= events + k-mers)."""
     from genomicsbench_amd.abea import PAIR_DTYPE
-    out = np.zeros(2 * max(int(rs.event_off[-1]), 1), dtype=PAIR_DTYPE)
+    out = np.zeros(max(2 * max(int(rs.event_off[-1]), 1), room), dtype=PAIR_DTYPE)
     n_pairs = np.zeros(max(rs.n_reads, 1), dtype=np.int32)
     cells = C.c_int64(0)
     f = oracle_lib().oracle_abea_align
