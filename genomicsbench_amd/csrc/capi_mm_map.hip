@@ -1,5 +1,5 @@
 // capi_mm_map.hip — the entries of the C-ABI (include/gbx.h) behind the chain scores: chains and regions, PAF text.
-#include "capi_common.h"
+#include "host_mm.h"
 
 using namespace gbx;
 
@@ -13,26 +13,6 @@ int params_check(const gbx_mm_map_params *p, const char *who)
     if (p->best_n < 0) { set_error("%s: best_n = %d is negative", who, p->best_n); return GBX_ERR_ARG; }
     if (!(p->mask_level == p->mask_level)) { set_error("%s: mask_level is not a number", who); return GBX_ERR_ARG; }
     if (!(p->pri_ratio == p->pri_ratio)) { set_error("%s: pri_ratio is not a number", who); return GBX_ERR_ARG; }
-    return GBX_OK;
-}
-
-// off[0 .. n]: from 0, never decreasing, steps below 2^31
-int offsets_check(const int64_t *off, int64_t n, const char *name, const char *what, const char *who)
-{
-    if (!off) { set_error("%s: null pointer", who); return GBX_ERR_ARG; }
-    if (off[0] != 0) { set_error("%s: %s[0] must be 0", who, name); return GBX_ERR_ARG; }
-    for (int64_t r = 0; r < n; ++r) {
-        const int64_t len = off[r + 1] - off[r];
-        if (len < 0) { set_error("%s: %s is not monotone at %s %lld", who, name, what, (long long)r); return GBX_ERR_ARG; }
-        if (len >= (1ll << 31)) { set_error("%s: %s %lld spans %lld in %s (fewer than 2^31)", who, what, (long long)r, (long long)len, name); return GBX_ERR_UNSUPPORTED; }
-    }
-    return GBX_OK;
-}
-
-int reads_check(int64_t n_reads, const char *who)
-{
-    if (n_reads < 0) { set_error("%s: bad argument", who); return GBX_ERR_ARG; }
-    if (n_reads > GBX_MM_MAX_READS) { set_error("%s: %lld reads (at most %d a call)", who, (long long)n_reads, GBX_MM_MAX_READS); return GBX_ERR_UNSUPPORTED; }
     return GBX_OK;
 }
 
@@ -64,7 +44,7 @@ int gbx_mm_map_device(const gbx_mm_map_params *p, int64_t n_reads, const int64_t
     const char *who = "gbx_mm_map_device";
     int rc = params_check(p, who);
     if (rc) return rc;
-    if ((rc = reads_check(n_reads, who))) return rc;
+    if ((rc = mm_reads_check(n_reads, who))) return rc;
     if (anchor_cap < 0 || chain_cap < 0 || reg_cap < 0) { set_error("%s: bad argument", who); return GBX_ERR_ARG; }
     if (!d_off || !d_seq_off || !d_chain_off || !d_reg_off || !d_counts || !d_work || (n_reads > 0 && (!d_rep_len || !d_hash || !d_n_chained)) ||
         (anchor_cap > 0 && (!d_ax || !d_ay || !d_score || !d_parent || !d_peak || !d_cax || !d_cay)) || (chain_cap > 0 && !d_u) || (reg_cap > 0 && !d_regs)) {
@@ -87,13 +67,13 @@ int gbx_mm_map_host(const gbx_mm_map_params *p, int64_t n_reads, const int64_t *
     const char *who = "gbx_mm_map_host";
     int rc = params_check(p, who);
     if (rc) return rc;
-    if ((rc = reads_check(n_reads, who))) return rc;
+    if ((rc = mm_reads_check(n_reads, who))) return rc;
     if (chain_cap < 0 || reg_cap < 0) { set_error("%s: bad argument", who); return GBX_ERR_ARG; }
     if (!chain_off || !reg_off || !counts || (n_reads > 0 && (!rep_len || !hash || !n_chained)) || (chain_cap > 0 && !u) || (reg_cap > 0 && !regs)) {
         set_error("%s: null pointer", who);
         return GBX_ERR_ARG;
     }
-    if ((rc = offsets_check(off, n_reads, "off", "read", who)) || (rc = offsets_check(seq_off, n_reads, "seq_off", "read", who))) return rc;
+    if ((rc = mm_offsets_check(off, n_reads, "off", "read", who)) || (rc = mm_offsets_check(seq_off, n_reads, "seq_off", "read", who))) return rc;
     const int64_t na = off[n_reads];
     if (na > 0 && (!ax || !ay || !score || !parent || !peak || !cax || !cay)) { set_error("%s: null pointer", who); return GBX_ERR_ARG; }
     for (int64_t r = 0; r < n_reads; ++r)
@@ -161,7 +141,7 @@ int gbx_mm_paf_device(int64_t n_reads, const gbx_mm_reg *d_regs, const int64_t *
                       uint8_t *d_lines, int64_t text_cap, int64_t *d_line_off, int64_t *d_n_text, void *d_work, size_t work_bytes, void *stream)
 {
     const char *who = "gbx_mm_paf_device";
-    int rc = reads_check(n_reads, who);
+    int rc = mm_reads_check(n_reads, who);
     if (rc) return rc;
     if (reg_cap < 0 || n_targets < 0 || text_cap < 0) { set_error("%s: bad argument", who); return GBX_ERR_ARG; }
     if (!d_reg_off || !d_n_regs || !d_qname_off || !d_seq_off || !d_line_off || !d_n_text || !d_work || (reg_cap > 0 && !d_regs) ||
@@ -182,20 +162,18 @@ int gbx_mm_paf_host(int64_t n_reads, const gbx_mm_reg *regs, const int64_t *reg_
 {
     RoctxRange range_("gbx_mm_paf_host");
     const char *who = "gbx_mm_paf_host";
-    int rc = reads_check(n_reads, who);
+    int rc = mm_reads_check(n_reads, who);
     if (rc) return rc;
     if (n_targets < 0 || n_targets >= (1ll << 31) || text_cap < 0) { set_error("%s: bad argument", who); return GBX_ERR_ARG; }
     if (!line_off || !n_text || (n_reads > 0 && !rep_len) || (text_cap > 0 && !lines)) { set_error("%s: null pointer", who); return GBX_ERR_ARG; }
-    if ((rc = offsets_check(reg_off, n_reads, "reg_off", "read", who)) || (rc = offsets_check(qname_off, n_reads, "qname_off", "read", who)) ||
-        (rc = offsets_check(seq_off, n_reads, "seq_off", "read", who)))
+    if ((rc = mm_offsets_check(reg_off, n_reads, "reg_off", "read", who)) || (rc = mm_offsets_check(qname_off, n_reads, "qname_off", "read", who)) ||
+        (rc = mm_offsets_check(seq_off, n_reads, "seq_off", "read", who)))
         return rc;
-    if (n_targets > 0 && ((rc = offsets_check(tname_off, n_targets, "tname_off", "target", who)) || (rc = offsets_check(tseq_off, n_targets, "tseq_off", "target", who))))
+    if (n_targets > 0 && ((rc = mm_offsets_check(tname_off, n_targets, "tname_off", "target", who)) || (rc = mm_offsets_check(tseq_off, n_targets, "tseq_off", "target", who))))
         return rc;
     const int64_t nr = reg_off[n_reads], qb = qname_off[n_reads], tb = n_targets > 0 ? tname_off[n_targets] : 0;
     if ((nr > 0 && !regs) || (qb > 0 && !qnames) || (tb > 0 && !tnames)) { set_error("%s: null pointer", who); return GBX_ERR_ARG; }
-    for (int64_t r = 0; r < n_reads; ++r)
-        for (int64_t g = reg_off[r]; g < reg_off[r + 1]; ++g)
-            if (regs[g].read != r) { set_error("%s: region %lld names read %d, it lies in read %lld", who, (long long)g, regs[g].read, (long long)r); return GBX_ERR_ARG; }
+    if ((rc = mm_regions_check(regs, reg_off, n_reads, who))) return rc;
     *n_text = 0;
     line_off[0] = 0;
     if (n_reads == 0) return GBX_OK;

@@ -1,13 +1,18 @@
-// mmpaf — long reads to PAF, as `minimap2 -x map-ont` prints without -c (approximate mappings, no base-level alignment): a
-// reference FASTA and reads (FASTA / FASTQ) in, one PAF line per mapping out.
+// mmpaf — long reads to PAF, as `minimap2 -x map-ont` prints it: without -c approximate mappings, with -c the base-level alignment
+// of every mapping (CIGAR in cg:Z:, NM, ms, AS, nn).  A reference FASTA and reads (FASTA / FASTQ) in, one PAF line per mapping out.
 //   mmpaf [options] <ref.fa> <reads.fa|fq> > out.paf
 //     -k INT  k-mer size (15)            -w INT  window (10)               -H  homopolymer-compressed k-mers
 //     -f FLOAT  mid_occ_frac (2e-4)      --mid-occ INT  the threshold itself (0: from -f)
 //     -g INT  max_gap (5000)             -r INT  bandwidth (500)
 //     -n INT  min_cnt (3)                -m INT  min_chain_score (40)      -M FLOAT  mask_level (0.5)
 //     -p FLOAT  pri_ratio (0.8)          -N INT  best_n (5)                -o FILE  output (stdout)
-// Index, seeds, chain scores, chains, regions, mapq and the text are all made on the device (gbx_mm_index_build_host,
-// gbx_mm_seed_host, gbx_chain_host, gbx_mm_map_host, gbx_mm_paf_host); this file parses, hashes the read names and prints.
+//     -c  base-level alignment; with it: -A INT match (2)  -B INT mismatch (4)  -O INT,INT gap open (4,24)  -E INT,INT gap
+//         extension (2,1)  -z INT z-drop (400)  --end-bonus INT (0)  --min-ksw-len INT (200)  --max-ext INT (5000); -r is its band too
+//         all reads are aligned in one call, which takes about 2 (r + 1) bytes of device memory a read base: split a read file
+//         that does not fit
+// Index, seeds, chain scores, chains, regions, mapq, alignments and the text are all made on the device (gbx_mm_index_build_host,
+// gbx_mm_seed_host, gbx_chain_host, gbx_mm_map_host, gbx_mm_align_host, gbx_mm_paf_host / gbx_mm_paf_cigar_host); this file
+// parses, hashes the read names and prints.
 #include "driver_common.h"
 #include <algorithm>
 #include "seq_reader.h"
@@ -17,6 +22,7 @@ namespace {
 int usage(FILE *f, int rc)
 {
     fprintf(f, "usage: mmpaf [-k INT] [-w INT] [-H] [-f FLOAT] [--mid-occ INT] [-g INT] [-r INT] [-n INT] [-m INT] [-M FLOAT] [-p FLOAT] [-N INT]\n"
+               "             [-c [-A INT] [-B INT] [-O INT,INT] [-E INT,INT] [-z INT] [--end-bonus INT] [--min-ksw-len INT] [--max-ext INT]]\n"
                "             [-o out.paf] <ref.fa> <reads.fa|fq>\n");
     return rc;
 }
@@ -57,6 +63,15 @@ bool int_arg(const char *s, int32_t *v)
     return true;
 }
 
+// "INT,INT"
+bool pair_arg(const char *s, int32_t *a, int32_t *b)
+{
+    const char *c = strchr(s, ',');
+    if (!c) return false;
+    const std::string first(s, c);
+    return int_arg(first.c_str(), a) && int_arg(c + 1, b);
+}
+
 uint32_t wang(uint32_t key)
 {
     key += ~(key << 15); key ^= key >> 10; key += key << 3; key ^= key >> 6; key += ~(key << 11); key ^= key >> 16;
@@ -81,6 +96,10 @@ int main(int argc, char **argv)
     gbx_mm_map_params mp;
     gbx_mm_default_params(&p);
     gbx_mm_map_default_params(&mp);
+    gbx_mm_align_params ap;
+    gbx_mm_align_default_params(&ap);
+    bool cigar = false;
+    const char *align_opt = nullptr;                                   // the first option that only means something with -c
     const char *out_path = nullptr;
     std::vector<const char *> files;
     for (int i = 1; i < argc; ++i) {
@@ -101,9 +120,23 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "-f")) fp = &p.mid_occ_frac;
         else if (!strcmp(a, "-M")) fp = &mp.mask_level;
         else if (!strcmp(a, "-p")) fp = &mp.pri_ratio;
+        else if (!strcmp(a, "-c")) cigar = true;
+        else if (!strcmp(a, "-A")) ip = &ap.a;
+        else if (!strcmp(a, "-B")) ip = &ap.b;
+        else if (!strcmp(a, "-z")) ip = &ap.zdrop;
+        else if (!strcmp(a, "--end-bonus")) ip = &ap.end_bonus;
+        else if (!strcmp(a, "--min-ksw-len")) ip = &ap.min_ksw_len;
+        else if (!strcmp(a, "--max-ext")) ip = &ap.max_ext;
+        else if (!strcmp(a, "-O") || !strcmp(a, "-E")) {
+            const char *v = value();
+            const bool open = a[1] == 'O';
+            if (!v || !pair_arg(v, open ? &ap.q : &ap.e, open ? &ap.q2 : &ap.e2)) { fprintf(stderr, "mmpaf: %s takes two integers (INT,INT)\n", a); return usage(stderr, 1); }
+            if (!align_opt) align_opt = a;
+        }
         else if (!strcmp(a, "-o")) { if (!(out_path = value())) { fprintf(stderr, "mmpaf: -o takes a file\n"); return usage(stderr, 1); } }
         else if (a[0] == '-' && a[1]) { fprintf(stderr, "mmpaf: unknown option %s\n", a); return usage(stderr, 1); }
         else files.push_back(a);
+        if (ip && !align_opt && (const char *)ip >= (const char *)&ap && (const char *)ip < (const char *)(&ap + 1)) align_opt = a;
         if (ip) {
             const char *v = value();
             if (!v || !int_arg(v, ip)) { fprintf(stderr, "mmpaf: %s takes an integer\n", a); return usage(stderr, 1); }
@@ -115,7 +148,9 @@ int main(int argc, char **argv)
         }
     }
     if (files.size() != 2) { fprintf(stderr, "mmpaf: a reference and a read file\n"); return usage(stderr, 1); }
-    if (gbx_mm_check_params(&p) || gbx_mm_map_check_params(&mp)) return fail();
+    if (align_opt && !cigar) { fprintf(stderr, "mmpaf: %s needs -c\n", align_opt); return usage(stderr, 1); }
+    ap.bw = p.bw;
+    if (gbx_mm_check_params(&p) || gbx_mm_map_check_params(&mp) || (cigar && gbx_mm_align_check_params(&ap))) return fail();
     mp.min_diff = 2 * p.k;
 
     Seqs ref, rd;
@@ -169,17 +204,42 @@ int main(int argc, char **argv)
     const double t4 = now_s();
     std::vector<uint8_t> text;
     int64_t n_text = 0;
-    rc = gbx_mm_paf_host(n_reads, regs.data(), reg_off.data(), rd.names.data(), rd.name_off.data(), rd.off.data(), rep.data(), n_ref, ref.names.data(),
-                         ref.name_off.data(), ref.off.data(), nullptr, 0, line_off.data(), &n_text);
+    std::vector<gbx_mm_aln> alns((size_t)std::max<int64_t>(mc[1], 1));
+    std::vector<uint32_t> cig;
+    int64_t ac[3] = {0, 0, 0};
+    if (cigar) {
+        // z is sized by a call without room, which plans and reports the need but runs no job; the words by their bound: a
+        // region's CIGAR has at most 2 qlen + 1 (every M or I run takes a query base, D runs lie between them).  One call aligns
+        // every read: the z room (about 2 (bw + 1) bytes a read base) has to fit the device.
+        auto align = [&](int64_t cigar_cap, int64_t z_bytes) {
+            return gbx_mm_align_host(&ap, n_reads, regs.data(), reg_off.data(), off.data(), cax.data(), cay.data(), n_chained.data(), rd.text.data(),
+                                     rd.off.data(), n_ref, ref.text.data(), ref.off.data(), alns.data(), cig.data(), cigar_cap, z_bytes, ac);
+        };
+        int64_t wcap = 0;
+        for (int64_t r = 0; r < n_reads; ++r) wcap += (reg_off[(size_t)r + 1] - reg_off[(size_t)r]) * (2 * (rd.off[(size_t)r + 1] - rd.off[(size_t)r]) + 1);
+        rc = align(0, 0);
+        if (rc == GBX_ERR_ARG && ac[2] > 0) { cig.resize((size_t)wcap); rc = align(wcap, ac[2]); }
+        if (rc) return fail();
+    }
+    const double t4a = now_s();
+    auto paf = [&](uint8_t *lines, int64_t cap) {
+        return cigar ? gbx_mm_paf_cigar_host(n_reads, regs.data(), reg_off.data(), alns.data(), cig.data(), ac[1], rd.names.data(), rd.name_off.data(),
+                                             rd.off.data(), rep.data(), n_ref, ref.names.data(), ref.name_off.data(), ref.off.data(), lines, cap,
+                                             line_off.data(), &n_text)
+                     : gbx_mm_paf_host(n_reads, regs.data(), reg_off.data(), rd.names.data(), rd.name_off.data(), rd.off.data(), rep.data(), n_ref,
+                                       ref.names.data(), ref.name_off.data(), ref.off.data(), lines, cap, line_off.data(), &n_text);
+    };
+    rc = paf(nullptr, 0);
     if (rc == GBX_ERR_ARG && n_text > 0) {
         text.resize((size_t)n_text);
-        rc = gbx_mm_paf_host(n_reads, regs.data(), reg_off.data(), rd.names.data(), rd.name_off.data(), rd.off.data(), rep.data(), n_ref, ref.names.data(),
-                             ref.name_off.data(), ref.off.data(), text.data(), n_text, line_off.data(), &n_text);
+        rc = paf(text.data(), n_text);
     }
     if (rc) return fail();
     const double t5 = now_s();
+    if (cigar)
+        fprintf(stderr, "Alignment: %lld jobs, %lld CIGAR words, %lld bytes of DP room (%.2f sec)\n", (long long)ac[0], (long long)ac[1], (long long)ac[2], t4a - t4);
     fprintf(stderr, "Mapping: %lld reads, %lld anchors, %lld chains, %lld mappings, %lld bytes (seeding %.2f, chain %.2f, map %.2f, text %.2f sec)\n",
-            (long long)n_reads, (long long)na, (long long)mc[0], (long long)mc[1], (long long)n_text, t2 - t1, t3 - t2, t4 - t3, t5 - t4);
+            (long long)n_reads, (long long)na, (long long)mc[0], (long long)mc[1], (long long)n_text, t2 - t1, t3 - t2, t4 - t3, t5 - t4a);
 
     FILE *fo = out_path ? fopen(out_path, "w") : stdout;
     if (!fo) { fprintf(stderr, "mmpaf: cannot write %s\n", out_path); return 1; }

@@ -346,6 +346,19 @@ struct MmPafIo {                     // the device arguments of gbx_mm_paf_devic
 size_t mm_paf_workspace_bytes(int64_t n_reads, int64_t reg_cap);
 int mm_paf_launch(const MmPafIo &io, void *d_work, size_t work_bytes, hipStream_t s);
 
+// ---- base-level alignment of the regions (mm_align_kernels.hip; the rules: mm_align_rules.h)
+struct MmAlignIo {                   // the device arguments of gbx_mm_align_device
+    int64_t n_reads; const gbx_mm_reg *regs; const int64_t *n_regs; int64_t reg_cap;
+    const int64_t *off; const uint64_t *cax, *cay; const int32_t *n_chained; int64_t anchor_cap;
+    const uint8_t *seq; const int64_t *seq_off; int64_t n_targets; const uint8_t *tseq; const int64_t *tseq_off;
+    gbx_mm_aln *alns; uint32_t *cigar; int64_t cigar_cap; int64_t *counts; uint8_t *z; int64_t z_bytes;
+};
+size_t mm_align_workspace_bytes(int64_t n_reads, int64_t reg_cap, int64_t anchor_cap);
+int mm_align_launch(const gbx_mm_align_params *p, const MmAlignIo &io, void *d_work, size_t work_bytes, hipStream_t s);
+struct MmPafCigarIo { MmPafIo paf; const gbx_mm_aln *alns; const uint32_t *cigar; int64_t cigar_cap; };
+size_t mm_paf_cigar_workspace_bytes(int64_t reg_cap);
+int mm_paf_cigar_launch(const MmPafCigarIo &io, void *d_work, size_t work_bytes, hipStream_t s);
+
 // ---- the aligner's gather behind the chain (mem_align_kernels.hip): every stage's count into one record
 struct MemAlignGather {              // a null pointer: the stage does not run, its count is 0
     const unsigned long long *fmi_counters;         // the fmi workspace: [2] is the slot overflow word fmi_read_overflow reads

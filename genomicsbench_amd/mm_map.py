@@ -137,9 +137,11 @@ def paf_host(regs, reg_off, qnames, seq_off, rep_len, tnames, tseq_off, text_cap
 class DeviceMmMapper:
     """Reads -> PAF on one stream.  seeder: a DeviceMmSeeder (its index names the targets); read_names / ref_names default to
     read<i> / ref<i>.  chain_cap / reg_cap / text_cap None: sized from the anchor count (a kept chain has min_cnt anchors of its
-    own), which run() reads for gbx_chain_device anyway; counts() reports the need when a given capacity was too small."""
+    own), which run() reads for gbx_chain_device anyway; counts() reports the need when a given capacity was too small.
+    align: True or a gbx_mm_align_params (mm_align.make_params) - run() then queues seed -> chain -> map -> align -> PAF with
+    CIGAR (`minimap2 -c`), results() also gives alns and cigar, and self.aligner is the DeviceMmAligner with its own counts()."""
 
-    def __init__(self, seeder, p=None, read_names=None, ref_names=None, chain_cap=None, reg_cap=None, text_cap=None):
+    def __init__(self, seeder, p=None, read_names=None, ref_names=None, chain_cap=None, reg_cap=None, text_cap=None, align=None):
         import torch
         self.seeder, self.device = seeder, seeder.device
         self.p = make_params() if p is None else p
@@ -164,6 +166,10 @@ class DeviceMmMapper:
         self.cnt = torch.zeros(3, dtype=torch.int64, device=self.device)          # chains, regions, bytes of text
         self.cb = None
         self.sized_for = None
+        self.aligner = None
+        if align is not None and align is not False:
+            from . import mm_align as MA
+            self.aligner = MA.DeviceMmAligner(self, None if align is True else align, text_cap=text_cap)
 
     def _size(self, n_anchors):
         import torch
@@ -211,7 +217,10 @@ class DeviceMmMapper:
         """seed -> chain -> map -> PAF, all queued on `stream`"""
         self.run_seed_chain(stream)
         self.run_map(stream)
-        self.run_paf(stream)
+        if self.aligner is not None:
+            self.aligner.run(stream)
+        else:
+            self.run_paf(stream)
 
     def counts(self):
         """(chains, regions, bytes of text) of the last run(); regions -1 when the chains did not fit.  Synchronises."""
@@ -233,11 +242,17 @@ class DeviceMmMapper:
         c, r, _ = self._need_fit()
         a = self.cb.n_anchors
         u64 = lambda t, n: t[:n].cpu().numpy().view(np.uint64)
-        return dict(chain_off=self.chain_off.cpu().numpy(), u=u64(self.u, c), cax=u64(self.cax, a), cay=u64(self.cay, a),
-                    n_chained=self.n_chained[:self.seeder.n_reads].cpu().numpy(), reg_off=self.reg_off.cpu().numpy(),
-                    regs=self.regs[:r * REG_DTYPE.itemsize].cpu().numpy().view(REG_DTYPE), line_off=self.line_off.cpu().numpy())
+        out = dict(chain_off=self.chain_off.cpu().numpy(), u=u64(self.u, c), cax=u64(self.cax, a), cay=u64(self.cay, a),
+                   n_chained=self.n_chained[:self.seeder.n_reads].cpu().numpy(), reg_off=self.reg_off.cpu().numpy(),
+                   regs=self.regs[:r * REG_DTYPE.itemsize].cpu().numpy().view(REG_DTYPE), line_off=self.line_off.cpu().numpy())
+        if self.aligner is not None:
+            out.update(self.aligner.results())
+        return out
 
     def paf(self):
         """the PAF text of the last run()"""
+        if self.aligner is not None:
+            self._need_fit()
+            return self.aligner.paf()
         _, _, t = self._need_fit()
         return self.lines[:t].cpu().numpy().tobytes().decode()

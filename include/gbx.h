@@ -1901,6 +1901,105 @@ int gbx_mm_paf_host(int64_t n_reads, const gbx_mm_reg *regs, const int64_t *reg_
                     int64_t n_targets, const uint8_t *tnames, const int64_t *tname_off, const int64_t *tseq_off,
                     uint8_t *lines, int64_t text_cap, int64_t *line_off, int64_t *n_text);
 
+/* ------------------------------------------------------------------- mm align: base-level alignment of the regions (`-c`)
+ * The dynamic programme between a region's anchors and beyond its ends, after minimap2's mm_align1 and ksw2's ksw_extd2:
+ * two-piece affine gaps gap(l) = min(q + e l, q2 + e2 l), a band, z-drop on the extensions, gaps left-aligned on the forward
+ * strand.  UNPINNED by a compiled reference; the rules are DESIGN 3.20, restated in tests/mm_align_ref.py.  In short:
+ *   codes     A C G T in either case 0..3, anything else 4; s(t, c) = -sc_ambi if a code is above 3, a if equal, else -b
+ *   a job     target T[0..tl) x query Q[0..ql), band w, ties LEFT or RIGHT, global or extension.  Cell (t, j) of antidiagonal
+ *             r = t + j is in the band iff (r - w + 1) >> 1 <= t <= (r + w) >> 1; outside it everything is minus infinity.
+ *             H(-1,-1) = 0, H(-1,j) = -gap(j + 1), H(t,-1) = -gap(t + 1), gap states on a border are minus infinity.
+ *             E = max(H(t-1,j) - q, E(t-1,j)) - e (deletion), F likewise from (t,j-1) (insertion), E2 F2 with q2 e2; a state's
+ *             continuation flag is set iff it extends (LEFT: E(t-1,j) > H(t-1,j) - q, RIGHT: >=; clear on a border).
+ *             H = the diagonal plus s, then E F E2 F2 in that order, taken iff larger (LEFT) or not smaller (RIGHT).
+ *             Extension: per antidiagonal the first largest H; z-drop when max - best > zdrop + l e2 beyond the maximum's cell;
+ *             the end is the query-end cell when mqe + end_bonus > max and nothing dropped, else the maximum's cell, else empty.
+ *             The walk back follows the cell's choice, a gap state while its flag at the cell it leaves is set.
+ *   a region  breakpoints from its anchors: from (x0 + 1 - span0, y0 + 1 - span0), each next anchor gives re = max(x - (span >> 1),
+ *             rs), qe likewise; a fill closes at the last anchor or once both sides reach min_ksw_len.  Fills are global LEFT jobs
+ *             with w = max(bw, |tl - ql| + 1) (an empty side: one D or I), never z-dropped, so a region is never split.  Left
+ *             extension: lq = min(qs, max_ext), lt = min(rs, lq + bw), both sequences reversed, RIGHT; right extension forward, LEFT.
+ *   output    CIGAR words len << 4 | op (M 0, I 1, D 2) left + fills + right, equal neighbours merged; mlen, blen, n_ambi,
+ *             nm = blen - mlen + n_ambi, dp_max and dp_score from the final CIGAR and the jobs' scores.
+ * Bounds: penalties and the match score at most 255 each, reads and contigs shorter than 2^28 bases, so no CIGAR run reaches
+ * 2^28.  Scores are 32-bit and anything at or below -2^29 counts as minus infinity: a job is exact while its largest penalty
+ * times (tl + ql) stays below 2^29 (with the defaults: tl + ql below 2^26); beyond that it is not.
+ * A region's CIGAR has at most 2 qlen + 1 words (every M or I run takes a query base, D runs lie between them), which sizes
+ * cigar_cap without a counting call.  z takes about 2 (bw + 1) bytes a read base (a direction byte a band cell, and the rows):
+ * about 1 000 at the default band, so one call aligns what its z room holds - the entries do not batch; a caller with more
+ * reads than that calls once a batch.
+ * Not modelled: splitting at a z-drop inside a fill, inversions, mm_fix_bad_ends, mm_filter_bad_seeds, long-join bands,
+ * limiting an extension by the neighbouring region, the re-run of parents / selection / mapq on DP scores. */
+typedef struct gbx_mm_align_params {
+    int32_t a, b, sc_ambi;     /* 2, 4, 1 */
+    int32_t q, e, q2, e2;      /* 4, 2, 24, 1 */
+    int32_t bw;                /* 500 */
+    int32_t zdrop;             /* 400; < 0: off */
+    int32_t end_bonus;         /* 0 */
+    int32_t min_ksw_len;       /* 200 */
+    int32_t max_ext;           /* 5000 */
+} gbx_mm_align_params;
+#define GBX_MM_ALN_ALIGNED   1   /* flags of gbx_mm_aln */
+#define GBX_MM_ALN_ZDROP_L   2
+#define GBX_MM_ALN_ZDROP_R   4
+#define GBX_MM_ALN_END_L     8
+#define GBX_MM_ALN_END_R     16
+#define GBX_MM_ALN_NO_ROOM   32  /* its jobs' direction bytes did not fit z_bytes: not aligned */
+#define GBX_MM_ALN_INVALID   64  /* not aligned */
+/* One per region, parallel to the regions: 56 bytes.  A region that is not aligned copies rs re qs qe mlen blen from its
+ * gbx_mm_reg and has n_cigar = 0 and the rest 0. */
+typedef struct gbx_mm_aln {
+    int32_t rs, re, qs, qe;    /* qs, qe mirrored in qlen on the reverse strand, as gbx_mm_reg's */
+    int32_t mlen, blen, n_ambi, nm;
+    int32_t dp_score, dp_max;
+    int32_t n_cigar, flags;
+    int64_t cigar_off;         /* its words: cigar[cigar_off .. cigar_off + n_cigar) */
+} gbx_mm_aln;
+
+void gbx_mm_align_default_params(gbx_mm_align_params *p);
+/* GBX_ERR_ARG naming the field: a < 1, a negative b / sc_ambi / q / q2 / end_bonus, e < 1, e2 < 1, bw < 1, min_ksw_len < 1,
+ * max_ext < 0, a score or penalty above 255. */
+int gbx_mm_align_check_params(const gbx_mm_align_params *p);
+
+/* Alignment of the regions of gbx_mm_map_device (regs, its counts + 1 as d_n_regs, off / cax / cay / n_chained as it left
+ * them) over the reads' text (seq, seq_off) and the contigs' (tseq, tseq_off[n_targets + 1]).  Output:
+ *   alns[reg_cap]       one record a region
+ *   cigar[cigar_cap]    the regions' words, region after region
+ *   counts[3]           jobs (left, fills, right of every valid region), CIGAR words, bytes of z needed
+ * d_z: z_bytes of room for the jobs' direction bytes and DP rows, 16-aligned, handed out in region order: a region whose jobs
+ * end past z_bytes is not aligned (flag 32) and counts[2] reports what all of them need.  More words than cigar_cap: nothing is
+ * written past it, counts[1] reports the need, and the statistics of a region whose words do not all fit are 0.  The device
+ * entry does no host synchronisation. */
+size_t gbx_mm_align_workspace_bytes(int64_t n_reads, int64_t reg_cap, int64_t anchor_cap);
+int gbx_mm_align_device(const gbx_mm_align_params *p, int64_t n_reads, const gbx_mm_reg *d_regs, const int64_t *d_reg_off, const int64_t *d_n_regs,
+                        int64_t reg_cap, const int64_t *d_off, const uint64_t *d_cax, const uint64_t *d_cay, const int32_t *d_n_chained,
+                        int64_t anchor_cap, const uint8_t *d_seq, const int64_t *d_seq_off, int64_t n_targets, const uint8_t *d_tseq,
+                        const int64_t *d_tseq_off, gbx_mm_aln *d_alns, uint32_t *d_cigar, int64_t cigar_cap, int64_t *d_counts,
+                        void *d_z, int64_t z_bytes, void *d_work, size_t work_bytes, void *stream);
+/* Host buffers in and out.  Checked before the device is touched, GBX_ERR_ARG naming the lowest offender: null pointers, offsets
+ * that do not start at 0 or decrease, negative capacities, a region whose read is not the one reg_off puts it in, n_chained
+ * outside its read's anchors; GBX_ERR_UNSUPPORTED: more than GBX_MM_MAX_READS reads, a read or contig of 2^28 bases or more.
+ * More words than cigar_cap, or a region left with flag 32: GBX_ERR_ARG with the needs in counts[3] (call with cigar_cap 0 /
+ * z_bytes 0 / NULL to size; alns is written). */
+int gbx_mm_align_host(const gbx_mm_align_params *p, int64_t n_reads, const gbx_mm_reg *regs, const int64_t *reg_off,
+                      const int64_t *off, const uint64_t *cax, const uint64_t *cay, const int32_t *n_chained,
+                      const uint8_t *seq, const int64_t *seq_off, int64_t n_targets, const uint8_t *tseq, const int64_t *tseq_off,
+                      gbx_mm_aln *alns, uint32_t *cigar, int64_t cigar_cap, int64_t z_bytes, int64_t *counts);
+
+/* PAF text with CIGAR: an aligned region prints qname qlen qs qe +/- tname tlen rs re mlen blen mapq NM:i: ms:i: AS:i: nn:i:
+ * tp:A: cm:i: s1:i: s2:i: (primaries) rl:i: cg:Z: with the coordinates and lengths of its gbx_mm_aln; one that is not aligned
+ * prints the line of gbx_mm_paf_*.  Otherwise the contract of gbx_mm_paf_*, with a workspace size of its own. */
+size_t gbx_mm_paf_cigar_workspace_bytes(int64_t n_reads, int64_t reg_cap);
+int gbx_mm_paf_cigar_device(int64_t n_reads, const gbx_mm_reg *d_regs, const int64_t *d_reg_off, const int64_t *d_n_regs, int64_t reg_cap,
+                            const gbx_mm_aln *d_alns, const uint32_t *d_cigar, int64_t cigar_cap,
+                            const uint8_t *d_qnames, const int64_t *d_qname_off, const int64_t *d_seq_off, const int32_t *d_rep_len,
+                            int64_t n_targets, const uint8_t *d_tnames, const int64_t *d_tname_off, const int64_t *d_tseq_off,
+                            uint8_t *d_lines, int64_t text_cap, int64_t *d_line_off, int64_t *d_n_text, void *d_work, size_t work_bytes, void *stream);
+int gbx_mm_paf_cigar_host(int64_t n_reads, const gbx_mm_reg *regs, const int64_t *reg_off, const gbx_mm_aln *alns, const uint32_t *cigar,
+                          int64_t n_cigar, const uint8_t *qnames, const int64_t *qname_off, const int64_t *seq_off, const int32_t *rep_len,
+                          int64_t n_targets, const uint8_t *tnames, const int64_t *tname_off, const int64_t *tseq_off,
+                          uint8_t *lines, int64_t text_cap, int64_t *line_off, int64_t *n_text);
+
 #ifdef __cplusplus
 }
 #endif
