@@ -134,6 +134,17 @@ def _declare(L):
         L.gbx_abea_meth_score_host.argtypes = [i64, vp, vp, i64, i64] + [vp] * 9
         L.gbx_abea_meth_cells.argtypes = [i64, vp, vp]
         L.gbx_abea_meth_sites_host.argtypes = [i64] + [vp] * 7 + [i64, vp, vp, vp, i64, vp, vp]
+    if hasattr(L, "gbx_abea_eventalign_host"):
+        f32 = C.c_float
+        L.gbx_abea_eventalign_trans_host.argtypes = [i64, vp, vp]
+        L.gbx_abea_eventalign_workspace_bytes.argtypes = [i64, i64, i64]
+        L.gbx_abea_eventalign_workspace_bytes.restype = sz
+        L.gbx_abea_eventalign_device.argtypes = [i64] + [vp] * 20 + [i32, i32] + [vp] * 5 + [i64, i64, vp, sz, vp]
+        L.gbx_abea_eventalign_host.argtypes = [i64, vp, vp, i64] + [vp] * 17 + [i32, i32, vp, vp, vp]
+        L.gbx_abea_eventalign_summary_host.argtypes = [i64] + [vp] * 14
+        L.gbx_abea_eventalign_tsv_host.argtypes = [vp, i64, vp, f32, f32, f32, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, i64, C.c_char_p,
+                                                   C.c_char_p, f32, vp, i64, vp]
+        L.gbx_abea_eventalign_from_signal_host.argtypes = [i64] + [vp] * 8 + [i64] + [vp] * 8 + [i32, i32] + [vp] * 9 + [i64] + [vp] * 4
     if hasattr(L, "gbx_fmi_smem_host"):
         L.gbx_fmi_default_params.argtypes = [vp, C.c_int32]
         L.gbx_fmi_default_params.restype = None

@@ -1,14 +1,16 @@
 // abea_calib_kernels.hip — what f5c runs per read between align() and the methylation score: postalign (align.c:550-650),
 // recalibrate_model (align.c:655-762) with the QC rules of scaling_single (f5c.c:1262-1330), and get_event_alignment_record
 // (meth.c:15-185).  A wavefront per read; every loop is counted from seq_len, n_pairs or n_cigar.
-#include "gbx_internal.h"
+#include "abea_dev.h"
 
 namespace gbx {
 
 namespace {
 
+using abea_dev::rec_scan_incl;
+using abea_dev::rec_closest;
+
 constexpr int CAL_MIN_M_STATES = 200;      // minNumEventsToRescale, align.c:679
-constexpr int REC_WINDOW = 1000;           // get_closest_event_to, meth.c:107-108
 
 __device__ inline unsigned cal_rank(char b) { return b == 'C' ? 1u : b == 'G' ? 2u : b == 'T' ? 3u : 0u; }   // align.c:10-23
 
@@ -186,16 +188,6 @@ __global__ void __launch_bounds__(64) abea_calib_kernel(long long n_reads, const
 
 // ---- get_event_alignment_record
 
-__device__ inline long long rec_scan_incl(long long v, int lane)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long u = __shfl_up(v, d);
-        if (lane >= d) v += u;
-    }
-    return v;
-}
-
 // near[k] = (the largest k' <= k whose k-mer has events or -1, the smallest k' >= k or n_kmers): get_next_event's two walks
 // (meth.c:92-102) as a max-scan and a min-scan over the map
 __device__ inline void rec_near_scan(const int2 *mp, int2 *nr, int n_kmers, int lane)
@@ -216,17 +208,6 @@ __device__ inline void rec_near_scan(const int2 *mp, int2 *nr, int n_kmers, int 
         if (k < n_kmers) nr[k].y = from ? b + __ffsll((long long)from) - 1 : carry;
         if (hm) carry = b + __ffsll((long long)hm) - 1;
     }
-}
-
-// get_closest_event_to, meth.c:105-117: backwards over k_idx .. max(0, k_idx - 1000) + 1, forwards over k_idx ..
-// min(k_idx + 1000, n_kmers - 1) - 1; -1 is a legal result
-__device__ inline int rec_closest(const int2 *mp, const int2 *nr, int k_idx, int n_kmers)
-{
-    const int stop_before = max(0, k_idx - REC_WINDOW), stop_after = min(k_idx + REC_WINDOW, n_kmers - 1);
-    const int2 nn = nr[k_idx];
-    const int before = nn.x > stop_before ? mp[nn.x].x : -1;
-    const int after = nn.y < stop_after ? mp[nn.y].x : -1;
-    return before == -1 ? after : before;
 }
 
 // One chunk of 64 CIGAR operations of get_aligned_segments (meth.c:36-85), lane l: operation c + l.  The pairs an operation

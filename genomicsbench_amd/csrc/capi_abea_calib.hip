@@ -8,43 +8,6 @@ namespace {
 
 #define CAL_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_fail(e_, #call); } while (0)
 
-// Several small arrays out of one device block: a lane keeps at most 48 idle blocks between calls (host_pipeline.h), and the one
-// call would hold more than that with a block per array.
-struct Carve {
-    DevBuf buf;
-    size_t need = 0, used = 0;
-    explicit Carve(Lane *l) : buf(l) {}
-    void want(size_t bytes) { need += (bytes + 255) & ~(size_t)255; }
-    int alloc() { return buf.alloc(need); }
-    template <class T> T *take(size_t bytes) { T *p = (T *)((char *)buf.p + used); used += (bytes + 255) & ~(size_t)255; return p; }
-};
-
-// where the reference exits or asserts (meth.c:54-58, 65-68, 135), before any device work
-int check_cigars(const char *who, int64_t n_reads, const int64_t *cigar_off, const uint32_t *cigar, const int32_t *seq_len)
-{
-    if (cigar_off[0] < 0) { set_error("%s: cigar_off below 0", who); return GBX_ERR_ARG; }
-    for (int64_t r = 0; r < n_reads; ++r) {
-        if (cigar_off[r + 1] < cigar_off[r]) { set_error("%s: cigar_off not monotone at read %lld", who, (long long)r); return GBX_ERR_ARG; }
-        if (cigar_off[r + 1] > cigar_off[r] && !cigar) { set_error("%s: null pointer", who); return GBX_ERR_ARG; }
-        if (seq_len[r] < GBX_ABEA_KMER) { set_error("%s: read %lld needs at least %d bases", who, (long long)r, GBX_ABEA_KMER); return GBX_ERR_ARG; }
-        int64_t aligned = 0, advance = 0;
-        for (int64_t c = cigar_off[r]; c < cigar_off[r + 1]; ++c) {
-            const int op = (int)(cigar[c] & 0xf);
-            const int64_t len = cigar[c] >> 4;
-            if (op == 3) { set_error("%s: read %lld: a spliced alignment (operation N)", who, (long long)r); return GBX_ERR_ARG; }
-            if (op == 6 || op > 8) { set_error("%s: read %lld: unhandled CIGAR operation %d", who, (long long)r, op); return GBX_ERR_ARG; }
-            if (op == 0 || op == 7 || op == 8) aligned += len;
-            if (op != 5) advance += len;
-        }
-        if (aligned > seq_len[r]) {
-            set_error("%s: read %lld: %lld aligned bases, the read has %d", who, (long long)r, (long long)aligned, seq_len[r]);
-            return GBX_ERR_ARG;
-        }
-        if (advance > 0x3fffffffLL) { set_error("%s: read %lld: its CIGAR spans more than 2^30 positions", who, (long long)r); return GBX_ERR_UNSUPPORTED; }
-    }
-    return GBX_OK;
-}
-
 // COUNT, the total to the host, FILL, the record to the host.  Everything else is on the device already.
 int record_to_host(const char *who, Lane *L, int64_t n_reads, const int64_t *d_cigar_off, const uint32_t *d_cigar, const int32_t *d_pos,
                    const uint8_t *d_rc, const int64_t *d_seq_off, const int32_t *d_seq_len, const int32_t *d_map, const int32_t *d_flags,

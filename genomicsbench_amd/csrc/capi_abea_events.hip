@@ -132,7 +132,7 @@ static int abea_signal_host(const char *who, bool align, int64_t n_reads, const 
     if (tail) {
         for (int64_t k = 0; k < m; ++k) n_pairs[keep[(size_t)k]] = cnp[(size_t)k];
         const AbeaAligned a{L, n_reads, seq_bytes, event_off, n_pairs, dso.as<int64_t>(), dsl.as<int32_t>(), dsq.as<char>(), deo.as<int64_t>(),
-                            dem.as<float>(), dmo.as<gbx_abea_model>(), dsc.as<float>(), dsh.as<float>(), dout.as<gbx_abea_pair>()};
+                            dem.as<float>(), dmo.as<gbx_abea_model>(), dsc.as<float>(), dsh.as<float>(), dout.as<gbx_abea_pair>(), dev.as<gbx_abea_event>()};
         return pipe.finish(tail(tail_ctx, a));
     }
     // half of the 2 x n_events slots are slack: the pairs are packed on the device, come back in one piece and go to

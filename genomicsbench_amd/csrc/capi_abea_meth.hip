@@ -163,18 +163,7 @@ int gbx_abea_meth_plan_host(int64_t n_jobs, const gbx_abea_meth_job *jobs, int64
     for (int i = 0; i < GBX_ABEA_FLOGSUM_TBL; i++) flogsum[i] = log(1. + exp((double)-i / 1000.f));           /* logsum.h:44-46 */
     for (int64_t r = 0; r < n_reads; ++r) {                                                  /* hmm.c:247-295 */
         if (event_off[r + 1] < event_off[r]) { set_error("gbx_abea_meth_plan_host: event_off not monotone at read %lld", (long long)r); return GBX_ERR_ARG; }
-        float p_stay = 1 - (1 / events_per_base[r]);
-        float p_skip = 0.0025, p_bad = 0.001, p_bad_self = p_bad, p_skip_self = 0.3;
-        float p_mk = p_skip, p_mb = p_bad, p_mm_self = p_stay;
-        float p_mm_next = 1.0f - p_mm_self - p_mk - p_mb;
-        float p_bb = p_bad_self, p_bk, p_bm_next, p_bm_self;
-        p_bk = p_bm_next = p_bm_self = (1.0f - p_bb) / 3;
-        float p_kk = p_skip_self, p_km = 1.0f - p_kk;
-        float *t = trans + r * GBX_ABEA_METH_NTRANS;
-        /* the reference's `log` has a float argument in C++: the float overload */
-        t[0] = logf(p_mk); t[1] = logf(p_mb); t[2] = logf(p_mm_self); t[3] = logf(p_mm_next);
-        t[4] = logf(p_bb); t[5] = logf(p_bk); t[6] = logf(p_bm_next); t[7] = logf(p_bm_self);
-        t[8] = logf(p_kk); t[9] = logf(p_km);
+        abea_transitions(events_per_base[r], trans + r * GBX_ABEA_METH_NTRANS);
     }
     /* pre_flank[i] depends on i alone (hmm.c:172-205), post_flank on the distance to the last event (hmm.c:132-168); the sums
        are double, stored to float */

@@ -449,6 +449,24 @@ int abea_meth_launch(int64_t n_jobs, const gbx_abea_meth_job *d_jobs, const char
                      const float *d_flogsum, const float *d_trans, const float *d_pre, const float *d_post, const int32_t *d_order,
                      const int64_t *class_off, float *d_scores, hipStream_t s);
 
+// ---- abea eventalign (abea_eventalign_kernels.hip)
+struct AbeaEventalignArgs {                   // the device entry's arguments, by value to the kernel
+    long long n_reads;
+    const int64_t *seq_off; const int32_t *seq_len; const int64_t *event_off; const float *event_mean; const gbx_abea_model *models;
+    const float *scale, *shift, *var, *log_var, *trans;
+    const int32_t *map, *near, *flags;
+    const int64_t *cigar_off; const uint32_t *cigar; const int32_t *pos; const uint8_t *rc;
+    const int64_t *ref_off; const int32_t *ref_len; const char *ref;
+    int32_t region_start, region_end;
+    const int32_t *order;
+    gbx_abea_eventalign_rec *rec; int32_t *n_rec; int32_t *status; int64_t *counts;
+    long long n_cigar_total, rows_cap;
+    void *work;
+    float pre0;                               // pre_flank[0] = (float)log(1 - TRANS_START_TO_CLIP), eventalign.c:124
+};
+size_t abea_eventalign_workspace_bytes(int64_t n_reads, int64_t n_cigar_total, int64_t rows_cap);
+int abea_eventalign_launch(AbeaEventalignArgs a, size_t work_bytes, hipStream_t s);
+
 // ---- abea calibration and event-alignment record (abea_calib_kernels.hip)
 int abea_calib_launch(int64_t n_reads, const int64_t *d_seq_off, const int32_t *d_seq_len, const char *d_seq, const int64_t *d_event_off,
                       const float *d_event_mean, const gbx_abea_model *d_models, const gbx_abea_pair *d_pairs, const int32_t *d_n_pairs,

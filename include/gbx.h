@@ -634,6 +634,105 @@ int gbx_abea_call_methylation_host(int64_t n_reads, const int16_t *raw, const in
                                    float *scale, float *shift, float *var, double *events_per_base, int64_t site_cap,
                                    gbx_abea_meth_site *sites, float *scores, int64_t *n_sites);
 
+/* abea, eventalign: what f5c eventalign runs per read behind the calibration in place of the methylation score
+ * (meth_single, f5c.c:1381-1387, mode 1).
+ * Replaces  std::vector<event_alignment_t> align_read_to_ref(params, ref)        eventalign.c:1263-1540 (realign_read)
+ *           profile_hmm_align, the Viterbi fill and its traceback                 eventalign.c:345-911
+ *           EventalignSummary summarize_alignment(...)                            eventalign.c:1580-1642
+ *           void emit_event_alignment_tsv(...) and its header                     eventalign.c:1651-1662, 1853-1938
+ * A read is realigned in segments of about 100 reference bases: the aligned pairs of its CIGAR (M, = and X; no 6-base
+ * boundary skip; trimmed to [region_start, region_end] when neither is -1, then to read_pos <= seq_len - 6) give the
+ * segment's reference bases and, through get_closest_event_to, its events; a three-state profile HMM (M, B, K per k-mer) is
+ * filled with float max in place of the log-sum, on the NUCLEOTIDE model (4096 k-mers, N and every other byte rank as A);
+ * `from` of a cell is the LAST of its six candidates that equals their maximum (six -inf: HMT_FROM_SOFT); the traceback
+ * starts at M of the last k-mer in the last row; the first 50 states that are not K and not on the segment's first event are
+ * emitted (all of them when the segment reaches the last pair) and the next segment starts at the last one emitted.
+ * Bit for bit the reference's paths: the emission is the float one of eventalign.c:293-338 with its division, the transition
+ * logarithms and log(1 - TRANS_START_TO_CLIP) are taken with the host C library.
+ * A record: ref_pos = curr_start_ref + kmer_idx, event_idx (the read's own index), state 'M' or 'B'.  ref_kmer is the six
+ * disambiguated upper-case bases at ref_pos; model_kmer is NNNNNN for B, else ref_kmer, reverse-complemented on an rc read.
+ * A read has at most n_events records, read r's at rec + event_off[r] (ABSOLUTE on the device entry), n_rec[r] of them.
+ * Status bits of a read; with any of them the read keeps the records of the segments before:
+ *   ROWS       a segment has more events than the workspace holds rows for (rows_cap; the host entries use
+ *              GBX_ABEA_EVENTALIGN_ROWS and the caller of the device entry sizes the workspace)
+ *   UNDEFINED  the reference would assert or read out of range: the traceback's start cell is -inf (or not a number),
+ *              get_closest_event_to gives -1 for the first or the last event, an event index outside the read, a segment
+ *              outside the reference segment, events that run against rc (eventalign.c:363), a path that leaves the matrix
+ *   BOUND      a loop hit its bound (segments <= n_events + 1, traceback steps <= rows + k-mers + 1)
+ * One deviation: a segment of length <= 0 (curr_start_ref inside a deletion of more than 100 bases; the reference calls
+ * substr with a negative length) ends the read like a segment of fewer than 12 bases. */
+#define GBX_ABEA_EVENTALIGN_ROWS       1024   /* rows_cap of the host entries */
+#define GBX_ABEA_EVENTALIGN_SLABS      3072   /* wavefronts (and backtrack slabs) of a launch, at most */
+#define GBX_ABEA_EVENTALIGN_MAX_KMERS  96     /* align_stride 100 + 1 bases */
+#define GBX_ABEA_EVENTALIGN_ST_ROWS      1
+#define GBX_ABEA_EVENTALIGN_ST_UNDEFINED 2
+#define GBX_ABEA_EVENTALIGN_ST_BOUND     4
+typedef struct gbx_abea_eventalign_rec { int32_t ref_pos, event_idx, state; } gbx_abea_eventalign_rec;
+typedef struct gbx_abea_eventalign_summary {   /* EventalignSummary, f5c.h:222-245, without the NM tag (the caller's) */
+    int32_t num_events, num_steps, num_stays, num_skips;
+    double sum_duration, sum_z_score;
+    int32_t reference_span, pad_;
+} gbx_abea_eventalign_summary;
+
+/* trans[r][GBX_ABEA_METH_NTRANS] as gbx_abea_meth_plan_host lays them out (calculate_transitions, eventalign.c:171-240: the
+ * same float arithmetic and float logarithms), from events_per_base; host C library. */
+int gbx_abea_eventalign_trans_host(int64_t n_reads, const double *events_per_base, float *trans);
+/* 256 bytes of header, 16 bytes per CIGAR operation and min(n_reads, GBX_ABEA_EVENTALIGN_SLABS) slabs of rows_cap x 192 bytes */
+size_t gbx_abea_eventalign_workspace_bytes(int64_t n_reads, int64_t n_cigar_total, int64_t rows_cap);
+/* Device entry, on what gbx_abea_calib_device (map, scalings, var, flags), gbx_abea_calib_logvar_host (log_var) and the count
+ * pass of gbx_abea_event_record_device (near) leave.  d_event_off ABSOLUTE; d_cigar_off[0] = 0 .. d_cigar_off[n_reads] =
+ * n_cigar_total; d_ref_off / d_ref_len: the reference segment of read r starts at pos[r].  d_order: the reads in the order
+ * they are to be drawn (longest first), or NULL for 0, 1, ...  Reads with a non-zero flag, without events or without pairs
+ * get n_rec 0, status 0.  An operation the reference refuses (N, P, a code above 8) advances nothing.  Nothing is synchronised. */
+int gbx_abea_eventalign_device(int64_t n_reads, const int64_t *d_seq_off, const int32_t *d_seq_len, const int64_t *d_event_off,
+                               const float *d_event_mean, const gbx_abea_model *d_models, const float *d_scale, const float *d_shift,
+                               const float *d_var, const float *d_log_var, const float *d_trans, const int32_t *d_map,
+                               const int32_t *d_near, const int32_t *d_flags, const int64_t *d_cigar_off, const uint32_t *d_cigar,
+                               const int32_t *d_pos, const uint8_t *d_rc, const int64_t *d_ref_off, const int32_t *d_ref_len,
+                               const char *d_ref_arena, int32_t region_start, int32_t region_end, const int32_t *d_order,
+                               gbx_abea_eventalign_rec *d_rec, int32_t *d_n_rec, int32_t *d_status, int64_t *d_counts /* [3] or NULL: segments, cells, traceback steps */,
+                               int64_t n_cigar_total, int64_t rows_cap, void *d_work, size_t work_bytes, void *stream);
+/* Host-buffer entry (one device), on what gbx_abea_calib_host returned: events (24-byte records), scale, shift, var, log_var,
+ * events_per_base, map (2 * seq_bytes ints), flags.  rec holds event_off[n_reads] - event_off[0] records, read r's at rec +
+ * event_off[r] - event_off[0].  Checked before the device is touched, GBX_ERR_ARG naming the lowest offender: reads inside
+ * the arena, CIGARs as gbx_abea_event_record_host checks them (operation N is refused), reference bases outside the IUPAC
+ * alphabet (the reference asserts), region_start > region_end. */
+int gbx_abea_eventalign_host(int64_t n_reads, const int64_t *seq_off, const int32_t *seq_len, int64_t seq_bytes,
+                             const int64_t *event_off, const gbx_abea_event *events, const gbx_abea_model *models, const float *scale,
+                             const float *shift, const float *var, const float *log_var, const double *events_per_base,
+                             const int32_t *map, const int32_t *flags, const int64_t *cigar_off, const uint32_t *cigar,
+                             const int32_t *pos, const uint8_t *rc, const int64_t *ref_off, const int32_t *ref_len,
+                             const char *ref_arena, int32_t region_start, int32_t region_end, gbx_abea_eventalign_rec *rec,
+                             int32_t *n_rec, int32_t *status);
+/* summarize_alignment per read (host only, no device): event lengths in samples, z-scores of the M records. */
+int gbx_abea_eventalign_summary_host(int64_t n_reads, const int64_t *event_off, const gbx_abea_event *events,
+                                     const gbx_abea_model *models, const float *scale, const float *shift, const float *var,
+                                     const uint8_t *rc, const int32_t *pos, const int64_t *ref_off, const int32_t *ref_len,
+                                     const char *ref_arena, const gbx_abea_eventalign_rec *rec, const int32_t *n_rec,
+                                     gbx_abea_eventalign_summary *out);
+/* The TSV of one read (host only): emit_event_alignment_tsv's lines, behind the header line when `header` is set.  Formatted
+ * with the C library.  Returns through *need the bytes of the text (without a terminator); more than cap: GBX_ERR_ARG, call
+ * again with room.  write_samples != 0 is refused (the reference asserts). */
+int gbx_abea_eventalign_tsv_host(const gbx_abea_event *events, int64_t n_events, const gbx_abea_model *models, float scale, float shift,
+                                 float var, int rc, int32_t pos, const char *ref, int32_t ref_len,
+                                 const gbx_abea_eventalign_rec *rec, int32_t n_rec, int header, int print_read_names, int scale_events,
+                                 int write_samples, int64_t read_index, const char *read_name, const char *ref_name, float sample_rate,
+                                 char *text, int64_t cap, int64_t *need);
+/* eventalign from raw signal in one call (one device): events -> scalings -> align -> calibration -> near table -> eventalign.
+ * Inputs as gbx_abea_call_methylation_host without the CpG model.  The events, their means, the map and the scalings stay on
+ * the device; the per-read calibration comes down (log_var and the transitions are taken on the host) and, at the end, the
+ * event records (events: event_cap of them; read r's at events + event_off[r]) and the eventalign records beside them (rec:
+ * event_cap).  More events than event_cap: GBX_ERR_ARG with the count in *n_events_total, as gbx_abea_events_host. */
+int gbx_abea_eventalign_from_signal_host(int64_t n_reads, const int16_t *raw, const int64_t *raw_off, const float *range,
+                                         const float *digitisation, const float *offset, const int64_t *seq_off,
+                                         const int32_t *seq_len, const char *seq_arena, int64_t seq_bytes,
+                                         const gbx_abea_model *models, const int64_t *cigar_off, const uint32_t *cigar,
+                                         const int32_t *pos, const uint8_t *rc, const int64_t *ref_off, const int32_t *ref_len,
+                                         const char *ref_arena, int32_t region_start, int32_t region_end, int32_t *flags,
+                                         int32_t *status, float *scale, float *shift, float *var, float *log_var,
+                                         double *events_per_base, int64_t *event_off, gbx_abea_event *events, int64_t event_cap,
+                                         int64_t *n_events_total, gbx_abea_eventalign_rec *rec, int32_t *n_rec, int32_t *ea_status);
+
 /* --------------------------------------------------------------------- fmi
  * SMEM seeding on the FM-index of reference + reverse complement (second half): the three
  * seeding rounds bwa-mem2 runs per batch of reads and the driver times,
