@@ -345,8 +345,10 @@ __global__ void __launch_bounds__(64) chain_kernel(int n_calls, const int64_t *_
         unsigned long long visited = 0;
         // NARROW: one segment id and one upper x word in the whole call (and sorted x): `same` is always true and the
         // reference-position differences fit 32 unsigned bits, which takes a fifth of the instructions out of a chunk
-        auto run_call = [&](auto narrow_tag) {
+        // ROUND: the general path of an unsorted call, the one place where a gap cost can be negative (see the chunk)
+        auto run_call = [&](auto narrow_tag, auto round_tag) {
             constexpr bool NARROW = decltype(narrow_tag)::value;
+            constexpr bool ROUND = decltype(round_tag)::value;
             const gbx_chain_call h = hdr[call];
             const int max_dist_x = h.max_dist_x, max_dist_y = h.max_dist_y, bw = h.bw, n_segs = h.n_segs;
             const double avg_qspan = (double)h.avg_qspan;
@@ -504,8 +506,14 @@ __global__ void __launch_bounds__(64) chain_kernel(int n_calls, const int64_t *_
                                 gap_cost = c_lin + (log_dd >> 1);
                             }
                         }
-                        // (int)((double)gap_cost * gap_scale + .499) with gap_scale = 1.0f is gap_cost itself: gap_cost >= 0
-                        // for every lane that is not skipped (dd >= 0), and skipped lanes never use sc
+                        // (int)((double)gap_cost * gap_scale + .499) with gap_scale = 1.0f truncates toward zero: gap_cost itself
+                        // when gap_cost >= 0, gap_cost + 1 when it is negative.  In a sorted call every visited lane has
+                        // 0 <= dr <= max_dist_x (that is what st is), so dd = |dr - dq| >= 0 and gap_cost >= 0 for every lane
+                        // that is not skipped (skipped lanes never use sc): the rounding is the identity there, on the narrow
+                        // path and on the general one.  In an unsorted call dr is a wrapped 64-bit difference, dd =
+                        // (int32)(dq - dr) goes negative (and passes dd > bw) and c_lin with it: there the reference subtracts
+                        // gap_cost + 1.  The sorted calls' instance of the general path does not pay for that.
+                        if constexpr (ROUND) gap_cost += gap_cost < 0 ? 1 : 0;
                         sc -= gap_cost;
                         sc += fj;
     #ifdef GBX_CHAIN_STAMPS
@@ -666,7 +674,9 @@ __global__ void __launch_bounds__(64) chain_kernel(int n_calls, const int64_t *_
             }
     #endif
         };
-        if (flags == 0) run_call(std::true_type{}); else run_call(std::false_type{});
+        if (flags == 0) run_call(std::true_type{}, std::false_type{});
+        else if (sorted) run_call(std::false_type{}, std::false_type{});
+        else run_call(std::false_type{}, std::true_type{});
         (void)n_calls;
         if (lane == 0) atomicAdd(W.evaluated, visited);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
