@@ -67,7 +67,7 @@ struct BswWork {
     int32_t *counts, *cursors, *base, *bad, *order, *wband;
     // lane path (bsw_lane_kernel): pairs sorted by (query length, seed score): lbase[] = exclusive prefix of the key
     // histogram (LANE_BINS + 1 entries), lrank[] = a pair's rank in its bin, lorder[] = sorted pair indices, lchunk[] = per-launch
-    // chunk cursors
+    // chunk cursors.  Keys, and with them lorder[], hold the sort's group L first and group S behind it (lane_row).
     int32_t *lbase, *lrank, *lorder, *lchunk;
 };
 
@@ -83,7 +83,7 @@ __host__ __device__ inline int cls_of(int qlen, int bound)
 // the seed score far more than of the bases, so the 64 pairs of a wavefront taken from consecutive keys sweep nearly
 // the same columns in every row (measured on 'large': 97 % of the lane-iterations do live work).
 constexpr int LANE_QMAX = 159;                       // longest query on the lane path
-constexpr int LANE_ROWS = 2 * (LANE_QMAX + 1);       // key rows: format (0 = compact cells, 1 = wide) x query length
+constexpr int LANE_ROWS = 2 * (LANE_QMAX + 1);       // key rows: format (0 = compact cells, 1 = wide) x query length, in lane_row()'s order
 constexpr int LANE_BINS = LANE_ROWS * 256;
 constexpr int LANE_SCORE_LIMIT = 8192;               // wide cell word = h:14 | e:13 | query code x 6 : 5
 constexpr int LANE_COMPACT_LIMIT = 256;              // compact cell = h:8 | e:8, query code in a byte plane
@@ -95,10 +95,24 @@ __host__ __device__ inline bool lane_ok(int lane_on, int qlen, int tlen, int h0,
 {
     return lane_on && qlen >= 1 && qlen <= LANE_QMAX && tlen >= 1 && h0 >= 0 && h0 + qlen * (max_mat > 0 ? max_mat : 0) < LANE_SCORE_LIMIT;
 }
+// The sort can run in two groups (queue_prepare, GBX_BSW_SORT_SPLIT=1): group L, the queries from LANE_SPLIT_Q on in both formats - the launches that
+// hold the most LDS and run longest - and group S, the rest.  The key rows of L come first, so that L's stretch of lbase[] and
+// lorder[] is complete once L alone is counted, scanned and placed: rows [0, LANE_L_ROWS) = L compact, L wide; the rows
+// behind them = S compact, S wide.  lbase[LANE_L_BINS] is both L's total and the base of S's lists: L's scan writes it, S's
+// only reads it.  The cut is a class bound of both formats, so a launch's rows lie in one group.
+constexpr int LANE_SPLIT_Q = 80;
+constexpr int LANE_L_QROWS = LANE_QMAX + 1 - LANE_SPLIT_Q;   // key rows of group L per format
+constexpr int LANE_L_ROWS = 2 * LANE_L_QROWS;
+constexpr int LANE_L_BINS = LANE_L_ROWS * 256;
+static_assert(LANE_RANGE_HI[0][1] == LANE_SPLIT_Q - 1 && LANE_RANGE_HI[1][1] == LANE_SPLIT_Q - 1, "the group cut is a class bound");
+__host__ __device__ inline int lane_row(int wide, int qlen)
+{
+    return qlen >= LANE_SPLIT_Q ? wide * LANE_L_QROWS + qlen - LANE_SPLIT_Q : LANE_L_ROWS + wide * LANE_SPLIT_Q + qlen;
+}
 __host__ __device__ inline int lane_key(int qlen, int h0, int max_mat)
 {
     const int wide = h0 + qlen * (max_mat > 0 ? max_mat : 0) < LANE_COMPACT_LIMIT ? 0 : 1;
-    return ((wide * (LANE_QMAX + 1) + qlen) << 8) | (h0 < 255 ? h0 : 255);
+    return (lane_row(wide, qlen) << 8) | (h0 < 255 ? h0 : 255);
 }
 
 __host__ __device__ inline int bin_of(int cls, int tlen)
@@ -582,27 +596,31 @@ __global__ void __launch_bounds__(64) bsw_lds_kernel(BswDev prm, BswPairs P, Bsw
 // ([column][lane]: every access is bank-conflict free whatever column each lane is at).  The wavefront runs the rows
 // in lock-step (a row lasts as long as its widest window), which costs nothing when the lanes' windows agree: the
 // pairs are sorted by (query length, seed score) first (bsw_lane_sort_kernel).
-__global__ void __launch_bounds__(256) bsw_lane_sort_kernel(BswDev prm, BswPairs P, int64_t n, BswWork W, int pass)
+// grp: 0 = the pairs of group L only, 1 = of group S only (every pass reads every pair's lengths: 24 MB on 'large'), -1 = all
+__global__ void __launch_bounds__(256) bsw_lane_sort_kernel(BswDev prm, BswPairs P, int64_t n, BswWork W, int pass, int grp)
 {
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
     const int qlen = P.len2[k], tlen = P.len1[k], h0 = P.h0[k];
     if (!lane_ok(prm.lane_on, qlen, tlen, h0, prm.max_mat) || tlen > GBX_BSW_MAX_TLEN) return;
     const int key = lane_key(qlen, h0, prm.max_mat);
+    if (grp >= 0 && (key >= LANE_L_BINS ? 1 : 0) != grp) return;
     // one pass of atomics: the count's old value is the pair's rank in its bin, kept for the placement (2 M scattered atomics
     // cost 0.13 ms whether they return a value or not: the second pass used to pay that again for its cursors)
     if (pass == 0) W.lrank[k] = atomicAdd(&W.lbase[key + 1], 1);
     else W.lorder[W.lbase[key] + W.lrank[k]] = (int)k;
 }
-// exclusive prefix of the key histogram in place: lbase[k + 1] holds count(k) on entry, lbase[k] = pairs with a key below k
-// on exit (one block)
+// exclusive prefix of the key histogram over the bins [LO, LO + NB) in place: lbase[k + 1] holds count(k) on entry, lbase[k] =
+// pairs with a key below k on exit (one block).  lbase[LO] is read, never written: group L's total is the base of group S's lists.
+// (The range at compile time: with it as kernel arguments the scan of half the bins took 80 us, of all bins 67 us, against 34 us.)
+template <int LO, int NB>
 __global__ void __launch_bounds__(1024) bsw_lane_scan_kernel(BswWork W)
 {
-    constexpr int PER = (LANE_BINS + 1023) / 1024;
+    constexpr int PER = (NB + 1023) / 1024, HI = LO + NB;
     __shared__ int part[1024];
     const int tid = threadIdx.x;
     int sum = 0;
-    for (int k = 0; k < PER; ++k) { const int b = tid * PER + k; if (b < LANE_BINS) sum += W.lbase[b + 1]; }
+    for (int k = 0; k < PER; ++k) { const int b = LO + tid * PER + k; if (b < HI) sum += W.lbase[b + 1]; }
     part[tid] = sum;
     __syncthreads();
     for (int d = 1; d < 1024; d <<= 1) {
@@ -611,10 +629,10 @@ __global__ void __launch_bounds__(1024) bsw_lane_scan_kernel(BswWork W)
         part[tid] += add;
         __syncthreads();
     }
-    int run = part[tid] - sum;
+    int run = (LO ? W.lbase[LO] : 0) + part[tid] - sum;
     for (int k = 0; k < PER; ++k) {
-        const int b = tid * PER + k;
-        if (b < LANE_BINS) { const int c = W.lbase[b + 1]; run += c; W.lbase[b + 1] = run; }
+        const int b = LO + tid * PER + k;
+        if (b < HI) { const int c = W.lbase[b + 1]; run += c; W.lbase[b + 1] = run; }
     }
 }
 
@@ -1654,6 +1672,8 @@ struct BswCall {
     int phase;                                  // BswChunkPrep::phase
     hipStream_t s_cls;                          // classify's stream
     hipEvent_t ev_pre, ev_aux;                  // behind classify (recorded when `ahead`), behind the lane sort
+    bool split;                                 // the lane sort in two groups: group L's launches wait for ev_aux_first only
+    hipEvent_t ev_aux_first;                    // behind the sort of group L (recorded when `split`)
 };
 
 // The streams and events of this call.  Returns 1 for a phase-1 call that cannot be split (nothing is queued).
@@ -1684,6 +1704,12 @@ static int plan_call(BswCall &c)
     }
     c.ev_pre = c.phase ? prep->ev_pre : c.ss->ev_pre;
     c.ev_aux = c.phase ? prep->ev_aux : c.ss->ev_aux;
+    // The sort in two groups (GBX_BSW_SORT_SPLIT=1; unset or 0: one sort) starts group L's launches before group S is sorted.
+    // Measured slower on 'large' (DESIGN.md §8): S's sort then shares the chip with L's kernels.  Never for a pipelined chunk,
+    // whose sort runs beside the previous chunk's kernels anyway.
+    const char *split_env = getenv("GBX_BSW_SORT_SPLIT");                            /* read per call: the tests vary it */
+    c.split = c.dev.lane_on && !c.ahead && split_env && atoi(split_env) != 0;
+    c.ev_aux_first = c.ss->ev_aux_first;
     if (c.packed_lanes) { c.P.ref = prep->ref_packed; c.P.qer = prep->qer_packed; c.P.packed = 1; }
     return GBX_OK;
 }
@@ -1710,8 +1736,9 @@ static int queue_prepare(BswCall &c)
         if (prep->unp_q && prep->hi_q > *prep->unp_q) *prep->unp_q = prep->hi_q;
     }
     GBX_HIP(hipMemsetAsync(c.W.counts, 0, WS_HDR * sizeof(int32_t), c.s_cls));        // the workspace's header arrays
-    // The lane sort (0.3 ms on 'large': two passes of scattered atomics) runs on a side stream of its own, beside
-    // classify and the row-kernel classes on the caller's stream, which do not need it; the lane launches wait for it.
+    // The lane sort (0.2 ms on 'large': a pass of scattered atomics, a scan, a placement pass) runs on a side stream of its
+    // own, beside classify and the row-kernel classes on the caller's stream, which do not need it; the lane launches wait
+    // for it.  lbase[] and lchunk[] are zeroed once, also when the sort runs in two groups.
     if (c.dev.lane_on) {
         hipStream_t so;
         if (c.ahead) {
@@ -1722,11 +1749,25 @@ static int queue_prepare(BswCall &c)
             if ((rc = ss->fork(c.s))) return rc;
             so = ss->side[SideStreams::N - 1];
         }
-        Stage st("bsw_lane_sort", so);
         const int sblocks = (int)((n + 255) / 256);
-        hipLaunchKernelGGL(bsw_lane_sort_kernel, dim3(sblocks), dim3(256), 0, so, c.dev, c.P, n, c.W, 0);
-        hipLaunchKernelGGL(bsw_lane_scan_kernel, dim3(1), dim3(1024), 0, so, c.W);
-        hipLaunchKernelGGL(bsw_lane_sort_kernel, dim3(sblocks), dim3(256), 0, so, c.dev, c.P, n, c.W, 1);
+        // count, scan, place: the pairs of one group over its bins of the key space, or of both (grp = -1) over all bins
+        auto sort_group = [&](int grp) {
+            Stage st("bsw_lane_sort", so);                  // (the profile adds up the stages of one name)
+            hipLaunchKernelGGL(bsw_lane_sort_kernel, dim3(sblocks), dim3(256), 0, so, c.dev, c.P, n, c.W, 0, grp);
+            if (grp < 0) hipLaunchKernelGGL((bsw_lane_scan_kernel<0, LANE_BINS>), dim3(1), dim3(1024), 0, so, c.W);
+            else if (grp == 0) hipLaunchKernelGGL((bsw_lane_scan_kernel<0, LANE_L_BINS>), dim3(1), dim3(1024), 0, so, c.W);
+            else hipLaunchKernelGGL((bsw_lane_scan_kernel<LANE_L_BINS, LANE_BINS - LANE_L_BINS>), dim3(1), dim3(1024), 0, so, c.W);
+            hipLaunchKernelGGL(bsw_lane_sort_kernel, dim3(sblocks), dim3(256), 0, so, c.dev, c.P, n, c.W, 1, grp);
+        };
+        if (c.split) {
+            // Group L first, with an event of its own: its launches (bsw_launch) start while group S is still being sorted here.
+            // S writes lbase[] behind LANE_L_BINS and lorder[] from L's total on, nothing that L's kernels read.
+            sort_group(0);
+            GBX_HIP(hipEventRecord(c.ev_aux_first, so));
+            sort_group(1);
+        } else {
+            sort_group(-1);
+        }
         GBX_HIP(hipEventRecord(c.ev_aux, so));
     }
     const int cblocks = (int)((n + CLS_THREADS - 1) / CLS_THREADS);
@@ -1812,8 +1853,9 @@ static void launch_lane_reg(const BswCall &c, hipStream_t sc, int64_t want, int 
     g_lane_reg_launches.fetch_add(1, std::memory_order_relaxed);
 }
 
-// The lane launches: longest queries first, one launch per format and LDS class, spread over the streams; grids = resident wavefronts
-static void launch_lanes(const BswCall &c)
+// The lane launches: longest queries first, one launch per format and LDS class, spread over the streams; grids = resident wavefronts.
+// grp: 0 = the launches of the sort's group L only, 1 = of group S only, -1 = all
+static void launch_lanes(const BswCall &c, int grp)
 {
     static const char *names[2][LANE_NRANGE] = {{"bsw_lane_c47", "bsw_lane_c79", "bsw_lane_c99", "bsw_lane_c135", "bsw_lane_c159"},
                                                 {"bsw_lane_w39", "bsw_lane_w79", "bsw_lane_w103", "bsw_lane_w127", "bsw_lane_w159"}};
@@ -1824,15 +1866,18 @@ static void launch_lanes(const BswCall &c)
     for (int fmt = 1; fmt >= 0; --fmt) {
         for (int r = LANE_NRANGE - 1; r >= 0; --r) {
             const int qlo = r ? LANE_RANGE_HI[fmt][r - 1] + 1 : 1, qhi = LANE_RANGE_HI[fmt][r];
+            if (grp >= 0 && (qlo >= LANE_SPLIT_Q ? 0 : 1) != grp) continue;
             const int cols = (qhi + 3) & ~1;                   // columns 0..qlen, and even
             // (four-bit query codes for the two longest compact classes: see bsw_lane_kernel)
             const int kind = fmt ? LANE_WIDE : qhi > 99 ? LANE_COMPACT4 : LANE_COMPACT;
             const size_t lds = (size_t)lane_lds_bytes(!fmt, kind == LANE_COMPACT4, cols);
             const int fit = (int)((size_t)160 * 1024 / lds), per_cu = fit > 16 ? 16 : fit;
-            const int sk = (LANE_NRANGE - 1 - r) & 3;          // the launch's ordinal in its format, longest first
+            // the launch's ordinal in its format, longest first.  (The shortest class behind the second shortest on the last side
+            // stream, so that it need not wait for the row-kernel launches on the caller's stream: 5.54-5.63 against 5.17-5.26 ms.)
+            const int sk = (LANE_NRANGE - 1 - r) & 3;
             hipStream_t sc = sk == 0 ? c.s : c.ss->side[sk - 1];
             const int64_t cap = (int64_t)c.cus * per_cu;
-            const int rlo = fmt * (LANE_QMAX + 1) + qlo, rhi = fmt * (LANE_QMAX + 1) + qhi, slot = fmt * LANE_NRANGE + r;
+            const int rlo = lane_row(fmt, qlo), rhi = lane_row(fmt, qhi), slot = fmt * LANE_NRANGE + r;
             Stage st(names[fmt][r], sc);
             // unpacked bases: the compact 80..99 class runs on the register kernel; GBX_BSW_LANE_REG=0 keeps it on bsw_lane_kernel
             if (fmt == 0 && !c.P.packed && qhi == 99 && !switched_off("GBX_BSW_LANE_REG")) { launch_lane_reg(c, sc, want, rlo, rhi, slot); continue; }
@@ -1903,8 +1948,17 @@ int bsw_launch(const gbx_bsw_params *p, int64_t n,
     if (!c.no_rows) launch_row_classes(c);
     if (c.dev.lane_on) {
         // the lane launches need the sorted lists (the sort's own stream, the last side stream unless `ahead`, has them in order)
-        if ((rc = kernel_streams_wait(c, c.ev_aux, c.ahead ? SideStreams::N : SideStreams::N - 1))) return rc;
-        launch_lanes(c);
+        const int n_side = c.ahead ? SideStreams::N : SideStreams::N - 1;
+        if (c.split) {
+            // group L's launches behind L's sort alone, then group S's behind the whole sort; within a group the order is as before
+            if ((rc = kernel_streams_wait(c, c.ev_aux_first, n_side))) return rc;
+            launch_lanes(c, 0);
+            if ((rc = kernel_streams_wait(c, c.ev_aux, n_side))) return rc;
+            launch_lanes(c, 1);
+        } else {
+            if ((rc = kernel_streams_wait(c, c.ev_aux, n_side))) return rc;
+            launch_lanes(c, -1);
+        }
     }
     // join_events == nullptr: the caller's stream waits for the side streams (everything of this call is then
     // ordered on `s`).  Otherwise nothing waits: one event per stream is recorded (join_events[0] on `s`,
@@ -1912,6 +1966,7 @@ int bsw_launch(const gbx_bsw_params *p, int64_t n,
     // the host pipeline queues chunk after chunk like that, so that the single-wavefront tails of one chunk
     // overlap the next chunk's kernels, and its downloader waits for the events.
     if (!join_events && (rc = c.ss->join(s))) return rc;
+    // (bsw_lds queued with the row classes instead, ahead of the lane launches, measured no faster: DESIGN.md §8)
     if (!c.no_rows && (rc = launch_lds(c))) return rc;
     if (join_events) {
         GBX_HIP(hipEventRecord(join_events[0], s));

@@ -112,6 +112,7 @@ int side_streams(SideStreams **out)
     SideStreams *ss = new SideStreams();
     GBX_HIP(hipEventCreateWithFlags(&ss->ev_fork, hipEventDisableTiming));
     GBX_HIP(hipEventCreateWithFlags(&ss->ev_aux, hipEventDisableTiming));
+    GBX_HIP(hipEventCreateWithFlags(&ss->ev_aux_first, hipEventDisableTiming));
     // Stream priorities (GBX_SIDE_PRIO="-1,-1,0": one number per side stream, HIP's scale - lower = more urgent; default all
     // 0).  A tuning aid that stayed one: bsw puts its longest-query classes on side streams 0 and 1 - their wavefronts hold
     // the most LDS and run at the lowest occupancy, so they should finish first and leave the tail to the short-query

@@ -92,6 +92,7 @@ struct SideStreams {
     hipStream_t pre[2];                          // urgent streams for the passes that prepare a launch (bsw's pipelined chunks)
     hipEvent_t ev_fork, ev_join[N], ev_aux;      // ev_aux: a point on one side stream the others wait for (bsw: the lane sort)
     hipEvent_t ev_pre;                           // the other preparing pass (bsw: classify)
+    hipEvent_t ev_aux_first;                     // an earlier point on ev_aux's stream (bsw: the lane sort's first group)
     std::mutex mu;
     int fork(hipStream_t main);
     int join(hipStream_t main);
