@@ -233,6 +233,16 @@ def check(rc):
         raise GbxError(rc, lib().gbx_last_error().decode())
 
 
+def call_with_room(call, cap, need, fixed=False):
+    """``call(cap)`` -> (return code, its output arrays for `cap` entries).  An entry that found `cap` too small returns GBX_ERR_ARG with
+    the count in ``need[0]``: unless the caller `fixed` the room, once more with that count.  -> the arrays; other codes raise."""
+    rcode, out = call(cap)
+    if rcode == GBX_ERR_ARG and need[0] > cap and not fixed:
+        rcode, out = call(int(need[0]))
+    check(rcode)
+    return out
+
+
 def ptr(a):
     """Raw pointer of a C-contiguous numpy array (or None)."""
     if a is None:

@@ -25,6 +25,15 @@ def make_model(level_mean, level_stdv):
     return m
 
 
+def alignment_arrays(cg):
+    """The alignment dictionary of datagen.gen_abea_cigars as the C-ABI takes it -> (cigar_off, cigar, pos, rc, ref_off, ref_len,
+    ref_arena); an empty cigar or ref_arena is padded to one entry, so that its pointer is not null."""
+    cigar = np.ascontiguousarray(cg["cigar"], np.uint32) if len(cg["cigar"]) else np.zeros(1, np.uint32)
+    ref = np.ascontiguousarray(cg["ref_arena"], np.uint8) if len(cg["ref_arena"]) else np.zeros(1, np.uint8)
+    return (np.ascontiguousarray(cg["cigar_off"], np.int64), cigar, np.ascontiguousarray(cg["pos"], np.int32), np.ascontiguousarray(cg["rc"], np.uint8),
+            np.ascontiguousarray(cg["ref_off"], np.int64), np.ascontiguousarray(cg["ref_len"], np.int32), ref)
+
+
 class AbeaReadSet:
     """Reads (bases), their events (means are all align() reads), scalings and the pore model."""
 

@@ -5,7 +5,7 @@ meth.c:15-185), and call-methylation from raw signal in one call.  All arithmeti
 import numpy as np
 
 from . import _native as N
-from .abea import EVENT_DTYPE, MODEL_DTYPE, PAIR_DTYPE, KMER
+from .abea import EVENT_DTYPE, MODEL_DTYPE, PAIR_DTYPE, KMER, alignment_arrays
 from .abea_meth import SITE_DTYPE, NMODEL_CPG
 
 FAILED_CALIBRATION, FAILED_ALIGNMENT, FAILED_QUALITY_CHK = 1, 2, 4       # read_stat_flag bits (f5c.h:49-51)
@@ -61,16 +61,13 @@ def event_record_host(cigar_off, cigar, pos, rc, seq_off, seq_len, map_, flags=N
     rc, map_ = np.ascontiguousarray(rc, np.uint8), np.ascontiguousarray(map_, np.int32)
     flags = None if flags is None else np.ascontiguousarray(flags, np.int32)
     rec_off, total = np.zeros(n + 1, np.int64), np.zeros(1, np.int64)
-    call = lambda cap, rec: _lib().gbx_abea_event_record_host(n, N.ptr(cigar_off), N.ptr(cigar), N.ptr(pos), N.ptr(rc), N.ptr(seq_off), N.ptr(seq_len),
-                                                              map_.shape[0], N.ptr(map_), N.ptr(flags), N.ptr(rec_off), cap, N.ptr(rec), N.ptr(total))
-    rcode = call(0, None)                                    # sizes first
-    if rcode != 0 and not (rcode == N.GBX_ERR_ARG and total[0] > 0):
-        N.check(rcode)
-    cap = int(total[0])
-    rec = np.zeros(max(cap, 1), PAIR_DTYPE)
-    if cap:
-        N.check(call(cap, rec))
-    return rec_off, rec[:cap]
+
+    def call(cap):
+        rec = np.zeros(max(cap, 1), PAIR_DTYPE)
+        return _lib().gbx_abea_event_record_host(n, N.ptr(cigar_off), N.ptr(cigar), N.ptr(pos), N.ptr(rc), N.ptr(seq_off), N.ptr(seq_len), map_.shape[0],
+                                                 N.ptr(map_), N.ptr(flags), N.ptr(rec_off), cap, N.ptr(rec), N.ptr(total)), rec
+    rec = N.call_with_room(call, 0, total)                   # sizes first
+    return rec_off, rec[:int(total[0])]
 
 
 def call_methylation_host(ss, cg, site_cap=None):
@@ -80,26 +77,20 @@ def call_methylation_host(ss, cg, site_cap=None):
     n = ss.n_reads
     cpg = np.ascontiguousarray(cg["cpg_model"], MODEL_DTYPE)
     assert cpg.size == NMODEL_CPG
-    cigar_off, ref_off = np.ascontiguousarray(cg["cigar_off"], np.int64), np.ascontiguousarray(cg["ref_off"], np.int64)
-    cigar = np.ascontiguousarray(cg["cigar"], np.uint32) if len(cg["cigar"]) else np.zeros(1, np.uint32)
-    pos, ref_len = np.ascontiguousarray(cg["pos"], np.int32), np.ascontiguousarray(cg["ref_len"], np.int32)
-    rc, ref_arena = np.ascontiguousarray(cg["rc"], np.uint8), np.ascontiguousarray(cg["ref_arena"], np.uint8)
+    cigar_off, cigar, pos, rc, ref_off, ref_len, ref_arena = alignment_arrays(cg)
     z = lambda dt: np.zeros(max(n, 1), dt)
     o = dict(flags=z(np.int32), status=z(np.int32), scale=z(np.float32), shift=z(np.float32), var=z(np.float32), events_per_base=z(np.float64))
     ns = np.zeros(1, np.int64)
     cap = int(site_cap) if site_cap is not None else int(ref_len.sum()) // 12 + 64      # a CpG group per 16 bases of a uniform draw
-    for _ in range(2):
+
+    def call(cap):
         sites, scores = np.zeros(max(cap, 1), SITE_DTYPE), np.zeros(2 * max(cap, 1), np.float32)
-        rcode = _lib().gbx_abea_call_methylation_host(
+        return _lib().gbx_abea_call_methylation_host(
             n, N.ptr(ss.raw), N.ptr(ss.raw_off), N.ptr(ss.range), N.ptr(ss.digitisation), N.ptr(ss.offset), N.ptr(ss.seq_off), N.ptr(ss.seq_len),
             N.ptr(ss.seq_arena), ss.seq_arena.size, N.ptr(ss.model), N.ptr(cpg), N.ptr(cigar_off), N.ptr(cigar), N.ptr(pos), N.ptr(rc), N.ptr(ref_off),
             N.ptr(ref_len), N.ptr(ref_arena), N.ptr(o["flags"]), N.ptr(o["status"]), N.ptr(o["scale"]), N.ptr(o["shift"]), N.ptr(o["var"]),
-            N.ptr(o["events_per_base"]), cap, N.ptr(sites), N.ptr(scores), N.ptr(ns))
-        if rcode == N.GBX_ERR_ARG and ns[0] > cap and site_cap is None:
-            cap = int(ns[0])                          # the default bound was too small: once more with the count
-            continue
-        N.check(rcode)
-        break
+            N.ptr(o["events_per_base"]), cap, N.ptr(sites), N.ptr(scores), N.ptr(ns)), (sites, scores)
+    sites, scores = N.call_with_room(call, cap, ns, fixed=site_cap is not None)
     k = int(ns[0])
     o = {a: v[:n] for a, v in o.items()}
     o.update(sites=sites[:k], scores=scores[:2 * k].reshape(k, 2))

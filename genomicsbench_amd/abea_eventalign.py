@@ -6,7 +6,7 @@ GPU (one device); the summary and the TSV are host code of the library.
 import numpy as np
 
 from . import _native as N
-from .abea import EVENT_DTYPE, MODEL_DTYPE
+from .abea import EVENT_DTYPE, MODEL_DTYPE, alignment_arrays as _cg
 
 REC_DTYPE = np.dtype([("ref_pos", "<i4"), ("event_idx", "<i4"), ("state", "<i4")])          # gbx_abea_eventalign_rec
 SUMMARY_DTYPE = np.dtype([("num_events", "<i4"), ("num_steps", "<i4"), ("num_stays", "<i4"), ("num_skips", "<i4"), ("sum_duration", "<f8"),
@@ -24,13 +24,6 @@ def trans_host(events_per_base):
     out = np.zeros((max(len(epb), 1), NTRANS), np.float32)
     N.check(_lib().gbx_abea_eventalign_trans_host(len(epb), N.ptr(epb), N.ptr(out)))
     return out[:len(epb)]
-
-
-def _cg(cg):
-    cigar = np.ascontiguousarray(cg["cigar"], np.uint32) if len(cg["cigar"]) else np.zeros(1, np.uint32)
-    ref = np.ascontiguousarray(cg["ref_arena"], np.uint8) if len(cg["ref_arena"]) else np.zeros(1, np.uint8)
-    return (np.ascontiguousarray(cg["cigar_off"], np.int64), cigar, np.ascontiguousarray(cg["pos"], np.int32), np.ascontiguousarray(cg["rc"], np.uint8),
-            np.ascontiguousarray(cg["ref_off"], np.int64), np.ascontiguousarray(cg["ref_len"], np.int32), ref)
 
 
 def eventalign_host(seq_off, seq_len, event_off, events, model, calib, cg, region=(-1, -1)):
@@ -97,17 +90,14 @@ def tsv(events, model, scale, shift, var, rc, pos, ref, rec, header=False, print
         rec = np.zeros(1, REC_DTYPE)
     need = np.zeros(1, np.int64)
     cap = 160 + 128 * n_rec + (len(ref_name) + len(read_name)) * n_rec
-    for _ in range(2):
+
+    def call(cap):
         text = np.zeros(max(cap, 1), np.uint8)
-        rcode = _lib().gbx_abea_eventalign_tsv_host(N.ptr(events), n_events, N.ptr(model), float(scale), float(shift), float(var), int(rc), int(pos),
-                                                    N.ptr(ref), ref_len, N.ptr(rec), n_rec, int(header), int(print_read_names), int(scale_events),
-                                                    int(write_samples), int(read_index), bytes(read_name), bytes(ref_name), float(sample_rate),
-                                                    N.ptr(text), cap, N.ptr(need))
-        if rcode == N.GBX_ERR_ARG and need[0] > cap:
-            cap = int(need[0])
-            continue
-        N.check(rcode)
-        break
+        return _lib().gbx_abea_eventalign_tsv_host(N.ptr(events), n_events, N.ptr(model), float(scale), float(shift), float(var), int(rc), int(pos),
+                                                   N.ptr(ref), ref_len, N.ptr(rec), n_rec, int(header), int(print_read_names), int(scale_events),
+                                                   int(write_samples), int(read_index), bytes(read_name), bytes(ref_name), float(sample_rate),
+                                                   N.ptr(text), cap, N.ptr(need)), text
+    text = N.call_with_room(call, cap, need)
     return text[:int(need[0])].tobytes()
 
 
@@ -121,19 +111,16 @@ def eventalign_from_signal_host(ss, cg, region=(-1, -1), event_cap=None):
              events_per_base=z(np.float64), n_rec=z(np.int32), ea_status=z(np.int32))
     event_off, total = z(np.int64, 1), np.zeros(1, np.int64)
     cap = int(event_cap) if event_cap is not None else int(ss.raw_off[-1] - ss.raw_off[0]) // 4 + n + 16
-    for _ in range(2):
+
+    def call(cap):
         events, rec = np.zeros(max(cap, 1), EVENT_DTYPE), np.zeros(max(cap, 1), REC_DTYPE)
-        rcode = _lib().gbx_abea_eventalign_from_signal_host(
+        return _lib().gbx_abea_eventalign_from_signal_host(
             n, N.ptr(ss.raw), N.ptr(ss.raw_off), N.ptr(ss.range), N.ptr(ss.digitisation), N.ptr(ss.offset), N.ptr(ss.seq_off), N.ptr(ss.seq_len),
             N.ptr(ss.seq_arena), ss.seq_arena.size, N.ptr(ss.model), N.ptr(cigar_off), N.ptr(cigar), N.ptr(pos), N.ptr(rc), N.ptr(ref_off), N.ptr(ref_len),
             N.ptr(ref), int(region[0]), int(region[1]), N.ptr(o["flags"]), N.ptr(o["status"]), N.ptr(o["scale"]), N.ptr(o["shift"]), N.ptr(o["var"]),
             N.ptr(o["log_var"]), N.ptr(o["events_per_base"]), N.ptr(event_off), N.ptr(events), cap, N.ptr(total), N.ptr(rec), N.ptr(o["n_rec"]),
-            N.ptr(o["ea_status"]))
-        if rcode == N.GBX_ERR_ARG and total[0] > cap and event_cap is None:
-            cap = int(total[0])
-            continue
-        N.check(rcode)
-        break
+            N.ptr(o["ea_status"])), (events, rec)
+    events, rec = N.call_with_room(call, cap, total, fixed=event_cap is not None)
     k = int(total[0])
     o = {a: v[:n] for a, v in o.items()}
     o.update(event_off=event_off[:n + 1], events=events[:k], rec=rec[:k])

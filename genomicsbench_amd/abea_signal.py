@@ -59,16 +59,12 @@ def events_host(ss, event_cap=None):
     n = ss.n_reads
     n_ev, off, status = np.zeros(max(n, 1), np.int64), np.zeros(n + 1, np.int64), np.zeros(max(n, 1), np.int32)
     total = np.zeros(1, np.int64)
-    cap = _cap(ss, event_cap)
-    for _ in range(2):
+
+    def call(cap):
         ev = np.zeros(max(cap, 1), dtype=EVENT_DTYPE)
-        rc = N.lib().gbx_abea_events_host(n, N.ptr(ss.raw), N.ptr(ss.raw_off), N.ptr(ss.range), N.ptr(ss.digitisation), N.ptr(ss.offset),
-                                          N.ptr(n_ev), N.ptr(off), N.ptr(ev), cap, N.ptr(total), N.ptr(status))
-        if rc == N.GBX_ERR_ARG and total[0] > cap and event_cap is None:
-            cap = int(total[0])                       # the default bound was too small: once more with the count
-            continue
-        N.check(rc)
-        break
+        return N.lib().gbx_abea_events_host(n, N.ptr(ss.raw), N.ptr(ss.raw_off), N.ptr(ss.range), N.ptr(ss.digitisation), N.ptr(ss.offset),
+                                            N.ptr(n_ev), N.ptr(off), N.ptr(ev), cap, N.ptr(total), N.ptr(status)), ev
+    ev = N.call_with_room(call, _cap(ss, event_cap), total, fixed=event_cap is not None)
     return off, ev[:int(total[0])], status[:n]
 
 
@@ -79,19 +75,14 @@ def signal_align_host(ss, event_cap=None):
     off, status, n_pairs = np.zeros(n + 1, np.int64), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
     scale, shift = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float32)
     total = np.zeros(1, np.int64)
-    cap = _cap(ss, event_cap)
-    for _ in range(2):
-        ev = np.zeros(max(cap, 1), dtype=EVENT_DTYPE)
-        out = np.zeros(2 * max(cap, 1), dtype=PAIR_DTYPE)
-        rc = N.lib().gbx_abea_signal_align_host(n, N.ptr(ss.raw), N.ptr(ss.raw_off), N.ptr(ss.range), N.ptr(ss.digitisation), N.ptr(ss.offset),
-                                                N.ptr(ss.seq_off), N.ptr(ss.seq_len), N.ptr(ss.seq_arena), ss.seq_arena.size, N.ptr(ss.model),
-                                                N.ptr(off), N.ptr(ev), cap, N.ptr(total), N.ptr(scale), N.ptr(shift), N.ptr(status),
-                                                N.ptr(out), N.ptr(n_pairs))
-        if rc == N.GBX_ERR_ARG and total[0] > cap and event_cap is None:
-            cap = int(total[0])
-            continue
-        N.check(rc)
-        break
+
+    def call(cap):
+        ev, out = np.zeros(max(cap, 1), dtype=EVENT_DTYPE), np.zeros(2 * max(cap, 1), dtype=PAIR_DTYPE)
+        return N.lib().gbx_abea_signal_align_host(n, N.ptr(ss.raw), N.ptr(ss.raw_off), N.ptr(ss.range), N.ptr(ss.digitisation), N.ptr(ss.offset),
+                                                  N.ptr(ss.seq_off), N.ptr(ss.seq_len), N.ptr(ss.seq_arena), ss.seq_arena.size, N.ptr(ss.model),
+                                                  N.ptr(off), N.ptr(ev), cap, N.ptr(total), N.ptr(scale), N.ptr(shift), N.ptr(status),
+                                                  N.ptr(out), N.ptr(n_pairs)), (ev, out)
+    ev, out = N.call_with_room(call, _cap(ss, event_cap), total, fixed=event_cap is not None)
     t = int(total[0])
     return dict(event_off=off, events=ev[:t], scale=scale[:n], shift=shift[:n], status=status[:n], pairs=out[:2 * max(t, 1)], n_pairs=n_pairs[:n])
 

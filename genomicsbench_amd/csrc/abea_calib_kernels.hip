@@ -7,12 +7,11 @@ namespace gbx {
 
 namespace {
 
+using abea_dev::base_rank;
 using abea_dev::rec_scan_incl;
 using abea_dev::rec_closest;
 
 constexpr int CAL_MIN_M_STATES = 200;      // minNumEventsToRescale, align.c:679
-
-__device__ inline unsigned cal_rank(char b) { return b == 'C' ? 1u : b == 'G' ? 2u : b == 'T' ? 3u : 0u; }   // align.c:10-23
 
 __device__ inline double cal_lane(double v, int j)
 {
@@ -116,7 +115,7 @@ __global__ void __launch_bounds__(64) abea_calib_kernel(long long n_reads, const
                 if (f < i1) { start = p[f].read_pos; stop = p[i1 - 1].read_pos; }
             }
             mp[k] = make_int2(start, stop);
-            for (int q = 0; q < GBX_ABEA_KMER; ++q) kr = kr << 2 | cal_rank(s[k + q]);
+            for (int q = 0; q < GBX_ABEA_KMER; ++q) kr = kr << 2 | base_rank(s[k + q]);
         }
         const bool has = start != -1;
         const bool is_m = cal_m_state(has, kr, lane, prev_rank);
@@ -158,7 +157,7 @@ __global__ void __launch_bounds__(64) abea_calib_kernel(long long n_reads, const
             unsigned kr = 0;
             if (k < n_kmers) {
                 start = mp[k].x;
-                for (int q = 0; q < GBX_ABEA_KMER; ++q) kr = kr << 2 | cal_rank(s[k + q]);
+                for (int q = 0; q < GBX_ABEA_KMER; ++q) kr = kr << 2 | base_rank(s[k + q]);
             }
             const bool is_m = cal_m_state(start != -1, kr, lane, prev_rank);
             double t = 0.0;

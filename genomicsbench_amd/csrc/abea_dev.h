@@ -1,11 +1,13 @@
-// abea_dev.h — device functions that more than one abea kernel file uses: the wavefront scan over CIGAR operations and
-// get_closest_event_to over the base-to-event map and its nearest-k-mer table (abea_calib_kernels.hip writes that table in the
-// record's count pass; abea_eventalign_kernels.hip reads it).
+// abea_dev.h — device functions that more than one abea kernel file uses: the rank of a base (abea_events_kernels.hip,
+// abea_calib_kernels.hip), the wavefront scan over CIGAR operations and get_closest_event_to over the base-to-event map and its
+// nearest-k-mer table (abea_calib_kernels.hip writes that table in the record's count pass; abea_eventalign_kernels.hip reads it).
 #pragma once
 #include "gbx_internal.h"
 
 namespace gbx {
 namespace abea_dev {
+
+__device__ inline unsigned base_rank(char b) { return b == 'C' ? 1u : b == 'G' ? 2u : b == 'T' ? 3u : 0u; }   // align.c:10-23
 
 constexpr int REC_WINDOW = 1000;           // get_closest_event_to, meth.c:107-108
 

@@ -14,7 +14,7 @@
 //      already in flight.
 // The kernel runs twice: a count pass (events per read, status), and after an exclusive scan over the reads a fill
 // pass that writes the packed event records and means.
-#include "gbx_internal.h"
+#include "abea_dev.h"
 #include <cfloat>
 
 namespace gbx {
@@ -248,8 +248,6 @@ __device__ inline double ev_ordered_add(double acc, double v)
     return acc;
 }
 
-__device__ inline unsigned ev_rank(char b) { return b == 'C' ? 1u : b == 'G' ? 2u : b == 'T' ? 3u : 0u; }   // align.c:10-23
-
 // estimate_scalings_using_mom, align.c:49-97: a wavefront per read; the terms are formed 64 at a time, the double sums
 // run in index order.  A read without events or without a k-mer gets scale = shift = 0.
 __global__ void __launch_bounds__(64) abea_scalings_kernel(long long n_reads, const int64_t *__restrict__ seq_off, const int32_t *__restrict__ seq_len,
@@ -276,7 +274,7 @@ __global__ void __launch_bounds__(64) abea_scalings_kernel(long long n_reads, co
         double l = 0.0;
         if (b + lane < n_kmers) {
             unsigned kr = 0;
-            for (int q = 0; q < GBX_ABEA_KMER; ++q) kr = kr << 2 | ev_rank(s[b + lane + q]);
+            for (int q = 0; q < GBX_ABEA_KMER; ++q) kr = kr << 2 | abea_dev::base_rank(s[b + lane + q]);
             l = (double)models[kr].level_mean;
         }
         kmer_level_sum = ev_ordered_add(kmer_level_sum, l);

@@ -85,18 +85,14 @@ static int abea_host_one(int64_t n_reads, const int64_t *seq_off, const int32_t 
         set_error("gbx_abea_align_host: null pointer");
         return GBX_ERR_ARG;
     }
-    for (int64_t r = 0; r < n_reads; ++r) {
-        if (seq_off[r] < 0 || seq_len[r] < 0 || seq_off[r] + seq_len[r] > seq_bytes) {
-            set_error("gbx_abea_align_host: read %lld lies outside the arena", (long long)(base + r));
-            return GBX_ERR_ARG;
-        }
-        if (event_off[r + 1] < event_off[r] || event_off[r] < 0) { set_error("gbx_abea_align_host: event_off not monotone at read %lld", (long long)(base + r)); return GBX_ERR_ARG; }
-    }
+    int rc;
+    for (int64_t r = 0; r < n_reads; ++r)
+        if ((rc = read_check(seq_off, seq_len, seq_bytes, r, "gbx_abea_align_host", base)) || (rc = event_off_check(event_off, r, "gbx_abea_align_host", base)))
+            return rc;
     std::vector<int64_t> band_off((size_t)n_reads + 1);
     std::vector<int32_t> order((size_t)n_reads);
     std::vector<double> lp((size_t)n_reads * 2);
-    int rc = gbx_abea_plan_host(n_reads, seq_len, event_off, band_off.data(), order.data(), lp.data());
-    if (rc) return rc;
+    if ((rc = gbx_abea_plan_host(n_reads, seq_len, event_off, band_off.data(), order.data(), lp.data()))) return rc;
     if ((rc = require_device())) return rc;
     const int64_t e0 = event_off[0], n_ev = event_off[n_reads] - e0;
     int64_t n_kmers_total = 0;
@@ -104,8 +100,7 @@ static int abea_host_one(int64_t n_reads, const int64_t *seq_off, const int32_t 
     // only the means of the events are read (align.c:125): the upload workers gather them from the 24-byte records
     // straight into the pinned slabs (no compact host copy)
     mark("planned");
-    std::vector<int64_t> eoff((size_t)n_reads + 1);
-    for (int64_t r = 0; r <= n_reads; ++r) eoff[(size_t)r] = event_off[r] - e0;
+    const std::vector<int64_t> eoff = rebased0(event_off, n_reads);
     HostLane lane;
     if ((rc = lane.acquire())) return rc;
     Lane *L = lane.l;
@@ -189,9 +184,8 @@ int gbx_abea_align_host(int64_t n_reads, const int64_t *seq_off, const int32_t *
     if (!host_multi_wanted() || n_reads <= 0 || seq_bytes < 0 || !seq_off || !seq_len || !seq_arena || !event_off || !events || !models ||
         !scale || !shift || !out || !n_pairs)
         return one();
-    for (int64_t r = 0; r < n_reads; ++r)
-        if (seq_off[r] < 0 || seq_len[r] < 0 || seq_off[r] + seq_len[r] > seq_bytes || event_off[r + 1] < event_off[r] || event_off[r] < 0 ||
-            event_off[r + 1] - event_off[r] < 1 || seq_len[r] < GBX_ABEA_KMER)
+    for (int64_t r = 0; r < n_reads; ++r)                   // a batch the checks or the plan refuse: one() says why
+        if (read_check(seq_off, seq_len, seq_bytes, r, "") || event_off_check(event_off, r, "") || event_off[r + 1] - event_off[r] < 1 || seq_len[r] < GBX_ABEA_KMER)
             return one();
     return spread_over_devices("gbx_abea_align_host", n_reads, n_reads, 128,
         [&](int64_t r) { return (double)((event_off[r + 1] - event_off[r] + 1) + ((int64_t)seq_len[r] - GBX_ABEA_KMER + 2)); }, one,

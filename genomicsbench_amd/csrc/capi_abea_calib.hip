@@ -6,8 +6,6 @@ using namespace gbx;
 
 namespace {
 
-#define CAL_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_fail(e_, #call); } while (0)
-
 // COUNT, the total to the host, FILL, the record to the host.  Everything else is on the device already.
 int record_to_host(const char *who, Lane *L, int64_t n_reads, const int64_t *d_cigar_off, const uint32_t *d_cigar, const int32_t *d_pos,
                    const uint8_t *d_rc, const int64_t *d_seq_off, const int32_t *d_seq_len, const int32_t *d_map, const int32_t *d_flags,
@@ -20,8 +18,8 @@ int record_to_host(const char *who, Lane *L, int64_t n_reads, const int64_t *d_c
     if ((rc = abea_record_launch(GBX_ABEA_RECORD_COUNT, n_reads, d_cigar_off, d_cigar, d_pos, d_rc, d_seq_off, d_seq_len, d_map, d_flags,
                                  dnear.as<int32_t>(), droff.as<int64_t>(), nullptr, 0, cs)))
         return rc;
-    CAL_HIP(hipMemcpyAsync(rec_off, droff.p, (size_t)(n_reads + 1) * 8, hipMemcpyDeviceToHost, cs));
-    CAL_HIP(hipStreamSynchronize(cs));
+    GBX_HIP(hipMemcpyAsync(rec_off, droff.p, (size_t)(n_reads + 1) * 8, hipMemcpyDeviceToHost, cs));
+    GBX_HIP(hipStreamSynchronize(cs));
     const int64_t total = rec_off[n_reads];
     *n_rec = total;
     if (own) { own->resize((size_t)std::max<int64_t>(total, 1)); rec = own->data(); rec_cap = total; }
@@ -31,124 +29,8 @@ int record_to_host(const char *who, Lane *L, int64_t n_reads, const int64_t *d_c
     if ((rc = abea_record_launch(GBX_ABEA_RECORD_FILL, n_reads, d_cigar_off, d_cigar, d_pos, d_rc, d_seq_off, d_seq_len, d_map, d_flags,
                                  dnear.as<int32_t>(), droff.as<int64_t>(), drec.as<gbx_abea_pair>(), total, cs)))
         return rc;
-    CAL_HIP(hipMemcpyAsync(rec, drec.p, (size_t)total * sizeof(gbx_abea_pair), hipMemcpyDeviceToHost, cs));
-    CAL_HIP(hipStreamSynchronize(cs));
-    return GBX_OK;
-}
-
-struct CallMeth {                                            // the caller's side of gbx_abea_call_methylation_host
-    const gbx_abea_model *cpg_model;
-    const int64_t *cigar_off; const uint32_t *cigar; const int32_t *pos; const uint8_t *rc;
-    const int64_t *ref_off; const int32_t *ref_len; const char *ref_arena;
-    int32_t *flags; float *scale, *shift, *var; double *events_per_base;
-    int64_t site_cap; gbx_abea_meth_site *sites; float *scores; int64_t *n_sites;
-};
-
-// behind align(), on the buffers it left: calibration, record, the host planner and plan, the score
-int call_meth_tail(void *ctx, const AbeaAligned &a)
-{
-    const CallMeth &c = *(const CallMeth *)ctx;
-    Lane *L = a.L;
-    const hipStream_t cs = L->compute;
-    const int64_t n = a.n_reads;
-    int rc;
-    DevBuf dmap(L), dcg(L);
-    Carve per_read(L);
-    const int64_t n_cig = c.cigar_off[n] - c.cigar_off[0];
-    for (size_t b : {n * 4, n * 4, n * 8, n * 8, n * 4, n * 4, n * 4, n * 4, (n + 1) * 8, n * 4, n}) per_read.want(b);
-    if ((rc = per_read.alloc()) || (rc = dmap.alloc((size_t)a.seq_bytes * 8 + 16)) || (rc = dcg.alloc((size_t)n_cig * 4 + 16))) return rc;
-    int32_t *dnp = per_read.take<int32_t>(n * 4);
-    float *dvar = per_read.take<float>(n * 4);
-    double *dv64 = per_read.take<double>(n * 8), *depb = per_read.take<double>(n * 8);
-    int32_t *dnea = per_read.take<int32_t>(n * 4), *dnm = per_read.take<int32_t>(n * 4), *dfl = per_read.take<int32_t>(n * 4);
-    float *dlv = per_read.take<float>(n * 4);
-    int64_t *dco = per_read.take<int64_t>((n + 1) * 8);
-    int32_t *dpos = per_read.take<int32_t>(n * 4);
-    uint8_t *drc = per_read.take<uint8_t>(n);
-    std::vector<int64_t> coff((size_t)n + 1);
-    for (int64_t r = 0; r <= n; ++r) coff[(size_t)r] = c.cigar_off[r] - c.cigar_off[0];
-    CAL_HIP(hipMemcpyAsync(dnp, a.n_pairs, (size_t)n * 4, hipMemcpyHostToDevice, cs));
-    CAL_HIP(hipMemcpyAsync(dco, coff.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, cs));
-    if (n_cig) CAL_HIP(hipMemcpyAsync(dcg.p, c.cigar + c.cigar_off[0], (size_t)n_cig * 4, hipMemcpyHostToDevice, cs));
-    CAL_HIP(hipMemcpyAsync(dpos, c.pos, (size_t)n * 4, hipMemcpyHostToDevice, cs));
-    CAL_HIP(hipMemcpyAsync(drc, c.rc, (size_t)n, hipMemcpyHostToDevice, cs));
-    if ((rc = abea_calib_launch(n, a.d_seq_off, a.d_seq_len, a.d_seq, a.d_event_off, a.d_event_mean, a.d_models, a.d_pairs, dnp, a.d_scale, a.d_shift, dvar,
-                                dv64, dmap.as<int32_t>(), depb, dnea, dnm, dfl, cs)))
-        return rc;
-    // the per-read calibration comes down: the caller's outputs, and var64 for the host logarithm
-    std::vector<double> v64((size_t)n);
-    std::vector<int32_t> nm((size_t)n);
-    std::vector<float> lv((size_t)n), flogsum, trans, pre, post;
-    std::vector<int64_t> rec_off((size_t)n + 1), eoff0((size_t)n + 1);
-    std::vector<gbx_abea_pair> rec;
-    std::vector<gbx_abea_meth_job> jobs;
-    std::vector<char> arena;
-    std::vector<int32_t> order;
-    // every host array a queued copy uses is declared above: whichever way this function is left, the stream is drained first
-    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{cs};
-    CAL_HIP(hipMemcpyAsync(c.scale, a.d_scale, (size_t)n * 4, hipMemcpyDeviceToHost, cs));
-    CAL_HIP(hipMemcpyAsync(c.shift, a.d_shift, (size_t)n * 4, hipMemcpyDeviceToHost, cs));
-    CAL_HIP(hipMemcpyAsync(c.var, dvar, (size_t)n * 4, hipMemcpyDeviceToHost, cs));
-    CAL_HIP(hipMemcpyAsync(v64.data(), dv64, (size_t)n * 8, hipMemcpyDeviceToHost, cs));
-    CAL_HIP(hipMemcpyAsync(c.events_per_base, depb, (size_t)n * 8, hipMemcpyDeviceToHost, cs));
-    CAL_HIP(hipMemcpyAsync(nm.data(), dnm, (size_t)n * 4, hipMemcpyDeviceToHost, cs));
-    CAL_HIP(hipMemcpyAsync(c.flags, dfl, (size_t)n * 4, hipMemcpyDeviceToHost, cs));
-    // the record of the unflagged reads (the flags are on the device; the count pass is queued behind the calibration)
-    int64_t n_rec = 0;
-    if ((rc = record_to_host("gbx_abea_call_methylation_host", L, n, dco, dcg.as<uint32_t>(), dpos, drc, a.d_seq_off, a.d_seq_len,
-                             dmap.as<int32_t>(), dfl, a.seq_bytes, rec_off.data(), 0, nullptr, &n_rec, &rec)))
-        return rc;
-    if ((rc = gbx_abea_calib_logvar_host(n, v64.data(), nm.data(), lv.data()))) return rc;
-    CAL_HIP(hipMemcpyAsync(dlv, lv.data(), (size_t)n * 4, hipMemcpyHostToDevice, cs));
-    // the site planner and the plan, on the host as they are
-    int64_t ns = 0, nb = 0;
-    rc = gbx_abea_meth_sites_host(n, c.ref_off, c.ref_len, c.ref_arena, c.pos, c.rc, rec_off.data(), rec.data(), 0, nullptr, nullptr, &ns, 0, nullptr, &nb);
-    if (rc && !(rc == GBX_ERR_ARG && (ns > 0 || nb > 0))) return rc;
-    *c.n_sites = ns;
-    if (ns > c.site_cap) {
-        set_error("gbx_abea_call_methylation_host: %lld sites, room for %lld", (long long)ns, (long long)c.site_cap);
-        return GBX_ERR_ARG;
-    }
-    if (ns == 0) { CAL_HIP(hipStreamSynchronize(cs)); return GBX_OK; }
-    const int64_t n_jobs = 2 * ns;
-    jobs.resize((size_t)n_jobs);
-    arena.resize((size_t)nb);
-    if ((rc = gbx_abea_meth_sites_host(n, c.ref_off, c.ref_len, c.ref_arena, c.pos, c.rc, rec_off.data(), rec.data(), ns, c.sites, jobs.data(), &ns, nb,
-                                       arena.data(), &nb)))
-        return rc;
-    int64_t max_rows = 1;
-    for (const gbx_abea_meth_job &J : jobs) max_rows = std::max<int64_t>(max_rows, std::abs((int64_t)J.event_stop - J.event_start) + 1);
-    const int64_t flank_len = max_rows + 1;
-    flogsum.resize(GBX_ABEA_FLOGSUM_TBL); trans.resize((size_t)n * GBX_ABEA_METH_NTRANS); pre.resize((size_t)flank_len); post.resize((size_t)flank_len);
-    order.resize((size_t)n_jobs);
-    for (int64_t r = 0; r <= n; ++r) eoff0[(size_t)r] = a.event_off[r];
-    int64_t class_off[GBX_ABEA_METH_NCLASS + 1];
-    if ((rc = gbx_abea_meth_plan_host(n_jobs, jobs.data(), nb, n, eoff0.data(), c.events_per_base, flogsum.data(), trans.data(), flank_len, pre.data(),
-                                      post.data(), order.data(), class_off)))
-        return rc;
-    DevBuf djb(L), dsq(L), dor(L), dout(L);
-    Carve tables(L);
-    const size_t job_bytes = (size_t)n_jobs * sizeof(gbx_abea_meth_job), model_bytes = GBX_ABEA_NMODEL_CPG * sizeof(gbx_abea_model);
-    for (size_t b : {model_bytes, (size_t)GBX_ABEA_FLOGSUM_TBL * 4, trans.size() * 4, (size_t)flank_len * 4, (size_t)flank_len * 4}) tables.want(b);
-    if ((rc = djb.alloc(job_bytes)) || (rc = dsq.alloc((size_t)nb + 16)) || (rc = tables.alloc()) || (rc = dor.alloc((size_t)n_jobs * 4)) ||
-        (rc = dout.alloc((size_t)n_jobs * 4)))
-        return rc;
-    gbx_abea_model *dmo = tables.take<gbx_abea_model>(model_bytes);
-    float *dflg = tables.take<float>(GBX_ABEA_FLOGSUM_TBL * 4), *dtr = tables.take<float>(trans.size() * 4);
-    float *dpr = tables.take<float>((size_t)flank_len * 4), *dpo = tables.take<float>((size_t)flank_len * 4);
-    CAL_HIP(hipMemcpyAsync(djb.p, jobs.data(), job_bytes, hipMemcpyHostToDevice, cs));
-    CAL_HIP(hipMemcpyAsync(dsq.p, arena.data(), (size_t)nb, hipMemcpyHostToDevice, cs));
-    CAL_HIP(hipMemcpyAsync(dmo, c.cpg_model, model_bytes, hipMemcpyHostToDevice, cs));
-    CAL_HIP(hipMemcpyAsync(dflg, flogsum.data(), GBX_ABEA_FLOGSUM_TBL * 4, hipMemcpyHostToDevice, cs));
-    CAL_HIP(hipMemcpyAsync(dtr, trans.data(), trans.size() * 4, hipMemcpyHostToDevice, cs));
-    CAL_HIP(hipMemcpyAsync(dpr, pre.data(), (size_t)flank_len * 4, hipMemcpyHostToDevice, cs));
-    CAL_HIP(hipMemcpyAsync(dpo, post.data(), (size_t)flank_len * 4, hipMemcpyHostToDevice, cs));
-    CAL_HIP(hipMemcpyAsync(dor.p, order.data(), (size_t)n_jobs * 4, hipMemcpyHostToDevice, cs));
-    if ((rc = abea_meth_launch(n_jobs, djb.as<gbx_abea_meth_job>(), dsq.as<char>(), a.d_event_off, a.d_event_mean, a.d_scale, a.d_shift, dvar, dlv, dmo,
-                               dflg, dtr, dpr, dpo, dor.as<int32_t>(), class_off, dout.as<float>(), cs)))
-        return rc;
-    CAL_HIP(hipMemcpyAsync(c.scores, dout.p, (size_t)n_jobs * 4, hipMemcpyDeviceToHost, cs));
-    CAL_HIP(hipStreamSynchronize(cs));
+    GBX_HIP(hipMemcpyAsync(rec, drec.p, (size_t)total * sizeof(gbx_abea_pair), hipMemcpyDeviceToHost, cs));
+    GBX_HIP(hipStreamSynchronize(cs));
     return GBX_OK;
 }
 
@@ -197,12 +79,12 @@ int gbx_abea_calib_host(int64_t n_reads, const int64_t *seq_off, const int32_t *
     }
     if (event_off[0] < 0) { set_error("%s: event_off below 0", who); return GBX_ERR_ARG; }
     if (event_off[n_reads] > event_off[0] && !events) { set_error("%s: null pointer", who); return GBX_ERR_ARG; }
+    int rc;
     for (int64_t r = 0; r < n_reads; ++r) {
-        if (seq_off[r] < 0 || seq_len[r] < 0 || seq_off[r] + seq_len[r] > seq_bytes) { set_error("%s: read %lld lies outside the arena", who, (long long)r); return GBX_ERR_ARG; }
-        if (seq_len[r] < GBX_ABEA_KMER) { set_error("%s: read %lld needs at least %d bases", who, (long long)r, GBX_ABEA_KMER); return GBX_ERR_ARG; }
-        if (event_off[r + 1] < event_off[r]) { set_error("%s: event_off not monotone at read %lld", who, (long long)r); return GBX_ERR_ARG; }
+        if ((rc = read_check(seq_off, seq_len, seq_bytes, r, who)) || (rc = kmer_check(seq_len, r, who)) || (rc = event_off_check(event_off, r, who)) ||
+            (rc = event_count_check(event_off, r, who)))
+            return rc;
         const int64_t ne = event_off[r + 1] - event_off[r], nk = (int64_t)seq_len[r] - GBX_ABEA_KMER + 1;
-        if (ne > 0x3fffffffLL) { set_error("%s: read %lld has too many events", who, (long long)r); return GBX_ERR_UNSUPPORTED; }
         if (n_pairs[r] < 0 || n_pairs[r] > 2 * ne) { set_error("%s: read %lld: %d pairs, room for %lld", who, (long long)r, n_pairs[r], (long long)(2 * ne)); return GBX_ERR_ARG; }
         if (n_pairs[r] > 0 && !pairs) { set_error("%s: null pointer", who); return GBX_ERR_ARG; }
         const gbx_abea_pair *p = pairs + 2 * event_off[r];
@@ -217,13 +99,10 @@ int gbx_abea_calib_host(int64_t n_reads, const int64_t *seq_off, const int32_t *
             }
         }
     }
-    int rc = require_device();
-    if (rc) return rc;
+    if ((rc = require_device())) return rc;
     const int64_t e0 = event_off[0], n_ev = event_off[n_reads] - e0;
-    std::vector<int64_t> eoff((size_t)n_reads + 1);
-    for (int64_t r = 0; r <= n_reads; ++r) eoff[(size_t)r] = event_off[r] - e0;
-    std::vector<float> means((size_t)n_ev + 1);
-    for (int64_t i = 0; i < n_ev; ++i) means[(size_t)i] = events[e0 + i].mean;                                 // only the mean is read (align.c:697)
+    const std::vector<int64_t> eoff = rebased0(event_off, n_reads);
+    const std::vector<float> means = event_means(events, e0, n_ev);                                            // only the mean is read (align.c:697)
     HostLane lane;
     if ((rc = lane.acquire())) return rc;
     Lane *L = lane.l;
@@ -235,31 +114,31 @@ int gbx_abea_calib_host(int64_t n_reads, const int64_t *seq_off, const int32_t *
         (rc = dsh.alloc(n_reads * 4)) || (rc = dvar.alloc(n_reads * 4)) || (rc = dv64.alloc(n_reads * 8)) || (rc = dmap.alloc((size_t)seq_bytes * 8 + 16)) ||
         (rc = depb.alloc(n_reads * 8)) || (rc = dnea.alloc(n_reads * 4)) || (rc = dnm.alloc(n_reads * 4)) || (rc = dfl.alloc(n_reads * 4)))
         return rc;
-    CAL_HIP(hipMemcpyAsync(dso.p, seq_off, (size_t)n_reads * 8, hipMemcpyHostToDevice, cs));
-    CAL_HIP(hipMemcpyAsync(dsl.p, seq_len, (size_t)n_reads * 4, hipMemcpyHostToDevice, cs));
-    if (seq_bytes) CAL_HIP(hipMemcpyAsync(dsq.p, seq_arena, (size_t)seq_bytes, hipMemcpyHostToDevice, cs));
-    CAL_HIP(hipMemcpyAsync(deo.p, eoff.data(), (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, cs));
-    if (n_ev) CAL_HIP(hipMemcpyAsync(dem.p, means.data(), (size_t)n_ev * 4, hipMemcpyHostToDevice, cs));
-    CAL_HIP(hipMemcpyAsync(dmo.p, models, GBX_ABEA_NMODEL * sizeof(gbx_abea_model), hipMemcpyHostToDevice, cs));
-    if (n_ev && pairs) CAL_HIP(hipMemcpyAsync(dpr.p, pairs + 2 * e0, (size_t)n_ev * 2 * sizeof(gbx_abea_pair), hipMemcpyHostToDevice, cs));
-    CAL_HIP(hipMemcpyAsync(dnp.p, n_pairs, (size_t)n_reads * 4, hipMemcpyHostToDevice, cs));
-    CAL_HIP(hipMemcpyAsync(dsc.p, scale, (size_t)n_reads * 4, hipMemcpyHostToDevice, cs));
-    CAL_HIP(hipMemcpyAsync(dsh.p, shift, (size_t)n_reads * 4, hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(dso.p, seq_off, (size_t)n_reads * 8, hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(dsl.p, seq_len, (size_t)n_reads * 4, hipMemcpyHostToDevice, cs));
+    if (seq_bytes) GBX_HIP(hipMemcpyAsync(dsq.p, seq_arena, (size_t)seq_bytes, hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(deo.p, eoff.data(), (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, cs));
+    if (n_ev) GBX_HIP(hipMemcpyAsync(dem.p, means.data(), (size_t)n_ev * 4, hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(dmo.p, models, GBX_ABEA_NMODEL * sizeof(gbx_abea_model), hipMemcpyHostToDevice, cs));
+    if (n_ev && pairs) GBX_HIP(hipMemcpyAsync(dpr.p, pairs + 2 * e0, (size_t)n_ev * 2 * sizeof(gbx_abea_pair), hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(dnp.p, n_pairs, (size_t)n_reads * 4, hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(dsc.p, scale, (size_t)n_reads * 4, hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(dsh.p, shift, (size_t)n_reads * 4, hipMemcpyHostToDevice, cs));
     if ((rc = abea_calib_launch(n_reads, dso.as<int64_t>(), dsl.as<int32_t>(), dsq.as<char>(), deo.as<int64_t>(), dem.as<float>(), dmo.as<gbx_abea_model>(),
                                 dpr.as<gbx_abea_pair>(), dnp.as<int32_t>(), dsc.as<float>(), dsh.as<float>(), dvar.as<float>(), dv64.as<double>(),
                                 dmap.as<int32_t>(), depb.as<double>(), dnea.as<int32_t>(), dnm.as<int32_t>(), dfl.as<int32_t>(), cs)))
         return rc;
-    CAL_HIP(hipMemcpyAsync(scale, dsc.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, cs));
-    CAL_HIP(hipMemcpyAsync(shift, dsh.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, cs));
-    CAL_HIP(hipMemcpyAsync(var, dvar.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, cs));
-    CAL_HIP(hipMemcpyAsync(var64, dv64.p, (size_t)n_reads * 8, hipMemcpyDeviceToHost, cs));
-    CAL_HIP(hipMemcpyAsync(events_per_base, depb.p, (size_t)n_reads * 8, hipMemcpyDeviceToHost, cs));
-    CAL_HIP(hipMemcpyAsync(n_event_alignment, dnea.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, cs));
-    CAL_HIP(hipMemcpyAsync(n_m_state, dnm.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, cs));
-    CAL_HIP(hipMemcpyAsync(flags, dfl.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, cs));
+    GBX_HIP(hipMemcpyAsync(scale, dsc.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, cs));
+    GBX_HIP(hipMemcpyAsync(shift, dsh.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, cs));
+    GBX_HIP(hipMemcpyAsync(var, dvar.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, cs));
+    GBX_HIP(hipMemcpyAsync(var64, dv64.p, (size_t)n_reads * 8, hipMemcpyDeviceToHost, cs));
+    GBX_HIP(hipMemcpyAsync(events_per_base, depb.p, (size_t)n_reads * 8, hipMemcpyDeviceToHost, cs));
+    GBX_HIP(hipMemcpyAsync(n_event_alignment, dnea.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, cs));
+    GBX_HIP(hipMemcpyAsync(n_m_state, dnm.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, cs));
+    GBX_HIP(hipMemcpyAsync(flags, dfl.p, (size_t)n_reads * 4, hipMemcpyDeviceToHost, cs));
     std::vector<int32_t> whole((size_t)seq_bytes * 2);
-    if (seq_bytes) CAL_HIP(hipMemcpyAsync(whole.data(), dmap.p, (size_t)seq_bytes * 8, hipMemcpyDeviceToHost, cs));
-    CAL_HIP(hipStreamSynchronize(cs));
+    if (seq_bytes) GBX_HIP(hipMemcpyAsync(whole.data(), dmap.p, (size_t)seq_bytes * 8, hipMemcpyDeviceToHost, cs));
+    GBX_HIP(hipStreamSynchronize(cs));
     for (int64_t r = 0; r < n_reads; ++r)                                     // a read's entries only: the slots between reads are not written
         memcpy(map + 2 * seq_off[r], whole.data() + 2 * seq_off[r], ((size_t)seq_len[r] - GBX_ABEA_KMER + 1) * 8);
     return gbx_abea_calib_logvar_host(n_reads, var64, n_m_state, log_var);
@@ -295,14 +174,13 @@ int gbx_abea_event_record_host(int64_t n_reads, const int64_t *cigar_off, const 
     *n_rec = 0;
     if (n_reads == 0) { if (rec_off) rec_off[0] = 0; return GBX_OK; }
     if (!cigar_off || !pos || !rc_flag || !seq_off || !seq_len || !map || !rec_off || (rec_cap > 0 && !rec)) { set_error("%s: null pointer", who); return GBX_ERR_ARG; }
+    int rc;
     for (int64_t r = 0; r < n_reads; ++r)
-        if (seq_off[r] < 0 || seq_len[r] < 0 || seq_off[r] + seq_len[r] > seq_bytes) { set_error("%s: read %lld lies outside the arena", who, (long long)r); return GBX_ERR_ARG; }
-    int rc = check_cigars(who, n_reads, cigar_off, cigar, seq_len);
-    if (rc) return rc;
+        if ((rc = read_check(seq_off, seq_len, seq_bytes, r, who))) return rc;
+    if ((rc = check_cigars(who, n_reads, cigar_off, cigar, seq_len))) return rc;
     if ((rc = require_device())) return rc;
     const int64_t c0 = cigar_off[0], n_cig = cigar_off[n_reads] - c0;
-    std::vector<int64_t> coff((size_t)n_reads + 1);
-    for (int64_t r = 0; r <= n_reads; ++r) coff[(size_t)r] = cigar_off[r] - c0;
+    const std::vector<int64_t> coff = rebased0(cigar_off, n_reads);
     HostLane lane;
     if ((rc = lane.acquire())) return rc;
     Lane *L = lane.l;
@@ -311,14 +189,14 @@ int gbx_abea_event_record_host(int64_t n_reads, const int64_t *cigar_off, const 
     if ((rc = dco.alloc((n_reads + 1) * 8)) || (rc = dcg.alloc((size_t)n_cig * 4 + 16)) || (rc = dpos.alloc(n_reads * 4)) || (rc = drc.alloc(n_reads)) ||
         (rc = dso.alloc(n_reads * 8)) || (rc = dsl.alloc(n_reads * 4)) || (rc = dmap.alloc((size_t)seq_bytes * 8 + 16)) || (rc = dfl.alloc(n_reads * 4)))
         return rc;
-    CAL_HIP(hipMemcpyAsync(dco.p, coff.data(), (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, cs));
-    if (n_cig) CAL_HIP(hipMemcpyAsync(dcg.p, cigar + c0, (size_t)n_cig * 4, hipMemcpyHostToDevice, cs));
-    CAL_HIP(hipMemcpyAsync(dpos.p, pos, (size_t)n_reads * 4, hipMemcpyHostToDevice, cs));
-    CAL_HIP(hipMemcpyAsync(drc.p, rc_flag, (size_t)n_reads, hipMemcpyHostToDevice, cs));
-    CAL_HIP(hipMemcpyAsync(dso.p, seq_off, (size_t)n_reads * 8, hipMemcpyHostToDevice, cs));
-    CAL_HIP(hipMemcpyAsync(dsl.p, seq_len, (size_t)n_reads * 4, hipMemcpyHostToDevice, cs));
-    if (seq_bytes) CAL_HIP(hipMemcpyAsync(dmap.p, map, (size_t)seq_bytes * 8, hipMemcpyHostToDevice, cs));
-    if (flags) CAL_HIP(hipMemcpyAsync(dfl.p, flags, (size_t)n_reads * 4, hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(dco.p, coff.data(), (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, cs));
+    if (n_cig) GBX_HIP(hipMemcpyAsync(dcg.p, cigar + c0, (size_t)n_cig * 4, hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(dpos.p, pos, (size_t)n_reads * 4, hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(drc.p, rc_flag, (size_t)n_reads, hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(dso.p, seq_off, (size_t)n_reads * 8, hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(dsl.p, seq_len, (size_t)n_reads * 4, hipMemcpyHostToDevice, cs));
+    if (seq_bytes) GBX_HIP(hipMemcpyAsync(dmap.p, map, (size_t)seq_bytes * 8, hipMemcpyHostToDevice, cs));
+    if (flags) GBX_HIP(hipMemcpyAsync(dfl.p, flags, (size_t)n_reads * 4, hipMemcpyHostToDevice, cs));
     return record_to_host(who, L, n_reads, dco.as<int64_t>(), dcg.as<uint32_t>(), dpos.as<int32_t>(), drc.as<uint8_t>(), dso.as<int64_t>(),
                           dsl.as<int32_t>(), dmap.as<int32_t>(), flags ? dfl.as<int32_t>() : nullptr, seq_bytes, rec_off, rec_cap, rec, n_rec, nullptr);
 }
@@ -340,15 +218,72 @@ int gbx_abea_call_methylation_host(int64_t n_reads, const int16_t *raw, const in
         set_error("%s: null pointer", who);
         return GBX_ERR_ARG;
     }
+    int rc;
     for (int64_t r = 0; r < n_reads; ++r)
-        if (ref_off[r] < 0 || ref_len[r] < 0) { set_error("%s: bad reference segment at read %lld", who, (long long)r); return GBX_ERR_ARG; }
-    int rc = check_cigars(who, n_reads, cigar_off, cigar, seq_len);
-    if (rc) return rc;
+        if ((rc = ref_segment_check(ref_off, ref_len, r, who))) return rc;
+    if ((rc = check_cigars(who, n_reads, cigar_off, cigar, seq_len))) return rc;
     // a batch in which no read has events never reaches the tail
     for (int64_t r = 0; r < n_reads; ++r) { flags[r] = GBX_ABEA_FAILED_ALIGNMENT; var[r] = 0.0f; events_per_base[r] = 0.0; }
-    CallMeth c{cpg_model, cigar_off, cigar, pos, rc_flag, ref_off, ref_len, ref_arena, flags, scale, shift, var, events_per_base, site_cap, sites, scores, n_sites};
+    // behind align(), on the buffers it left: calibration, record, the host planner and plan, the score
+    const abea_tail_fn call_meth_tail = [&](const AbeaAligned &a) -> int {
+        Lane *L = a.L;
+        const hipStream_t cs = L->compute;
+        const int64_t n = a.n_reads;
+        std::vector<int64_t> rec_off((size_t)n + 1);
+        std::vector<gbx_abea_pair> rec;
+        std::vector<gbx_abea_meth_job> jobs;
+        std::vector<char> arena;
+        AbeaMethPlan plan;
+        AbeaCalibrated cal(L);                                   // behind every host array a queued copy uses: it drains the stream before they die
+        if ((rc = cal.queue(a, cigar_off, cigar, pos, rc_flag, scale, shift, var, events_per_base, flags))) return rc;
+        // the record of the unflagged reads (the flags are on the device; the count pass is queued behind the calibration)
+        int64_t n_rec = 0;
+        if ((rc = record_to_host(who, L, n, cal.cigar_off, cal.cigar, cal.pos, cal.rc, a.d_seq_off, a.d_seq_len, cal.map, cal.flags, a.seq_bytes, rec_off.data(), 0,
+                                 nullptr, &n_rec, &rec)))
+            return rc;
+        if ((rc = cal.finish(nullptr))) return rc;
+        // the site planner and the plan, on the host as they are
+        int64_t ns = 0, nb = 0;
+        rc = gbx_abea_meth_sites_host(n, ref_off, ref_len, ref_arena, pos, rc_flag, rec_off.data(), rec.data(), 0, nullptr, nullptr, &ns, 0, nullptr, &nb);
+        if (rc && !(rc == GBX_ERR_ARG && (ns > 0 || nb > 0))) return rc;
+        *n_sites = ns;
+        if (ns > site_cap) { set_error("%s: %lld sites, room for %lld", who, (long long)ns, (long long)site_cap); return GBX_ERR_ARG; }
+        if (ns == 0) { GBX_HIP(hipStreamSynchronize(cs)); return GBX_OK; }
+        const int64_t n_jobs = 2 * ns;
+        jobs.resize((size_t)n_jobs);
+        arena.resize((size_t)nb);
+        if ((rc = gbx_abea_meth_sites_host(n, ref_off, ref_len, ref_arena, pos, rc_flag, rec_off.data(), rec.data(), ns, sites, jobs.data(), &ns, nb,
+                                           arena.data(), &nb)))
+            return rc;
+        if ((rc = plan.build(n_jobs, jobs.data(), nb, n, a.event_off, events_per_base))) return rc;
+        DevBuf djb(L), dsq(L), dor(L), dout(L);
+        Carve tables(L);
+        const size_t job_bytes = (size_t)n_jobs * sizeof(gbx_abea_meth_job), model_bytes = GBX_ABEA_NMODEL_CPG * sizeof(gbx_abea_model);
+        const size_t flank_bytes = (size_t)plan.flank_len * 4;
+        for (size_t b : {model_bytes, (size_t)GBX_ABEA_FLOGSUM_TBL * 4, plan.trans.size() * 4, flank_bytes, flank_bytes}) tables.want(b);
+        if ((rc = djb.alloc(job_bytes)) || (rc = dsq.alloc((size_t)nb + 16)) || (rc = tables.alloc()) || (rc = dor.alloc((size_t)n_jobs * 4)) ||
+            (rc = dout.alloc((size_t)n_jobs * 4)))
+            return rc;
+        gbx_abea_model *dmo = tables.take<gbx_abea_model>(model_bytes);
+        float *dflg = tables.take<float>(GBX_ABEA_FLOGSUM_TBL * 4), *dtr = tables.take<float>(plan.trans.size() * 4);
+        float *dpr = tables.take<float>(flank_bytes), *dpo = tables.take<float>(flank_bytes);
+        GBX_HIP(hipMemcpyAsync(djb.p, jobs.data(), job_bytes, hipMemcpyHostToDevice, cs));
+        GBX_HIP(hipMemcpyAsync(dsq.p, arena.data(), (size_t)nb, hipMemcpyHostToDevice, cs));
+        GBX_HIP(hipMemcpyAsync(dmo, cpg_model, model_bytes, hipMemcpyHostToDevice, cs));
+        GBX_HIP(hipMemcpyAsync(dflg, plan.flogsum.data(), GBX_ABEA_FLOGSUM_TBL * 4, hipMemcpyHostToDevice, cs));
+        GBX_HIP(hipMemcpyAsync(dtr, plan.trans.data(), plan.trans.size() * 4, hipMemcpyHostToDevice, cs));
+        GBX_HIP(hipMemcpyAsync(dpr, plan.pre.data(), flank_bytes, hipMemcpyHostToDevice, cs));
+        GBX_HIP(hipMemcpyAsync(dpo, plan.post.data(), flank_bytes, hipMemcpyHostToDevice, cs));
+        GBX_HIP(hipMemcpyAsync(dor.p, plan.order.data(), (size_t)n_jobs * 4, hipMemcpyHostToDevice, cs));
+        if ((rc = abea_meth_launch(n_jobs, djb.as<gbx_abea_meth_job>(), dsq.as<char>(), a.d_event_off, a.d_event_mean, a.d_scale, a.d_shift, cal.var, cal.log_var,
+                                   dmo, dflg, dtr, dpr, dpo, dor.as<int32_t>(), plan.class_off, dout.as<float>(), cs)))
+            return rc;
+        GBX_HIP(hipMemcpyAsync(scores, dout.p, (size_t)n_jobs * 4, hipMemcpyDeviceToHost, cs));
+        GBX_HIP(hipStreamSynchronize(cs));
+        return GBX_OK;
+    };
     return abea_signal_align_tail(who, n_reads, raw, raw_off, range, digitisation, offset, seq_off, seq_len, seq_arena, seq_bytes, models, status, scale,
-                                  shift, call_meth_tail, &c);
+                                  shift, call_meth_tail);
 }
 
 }  // extern "C"

@@ -6,8 +6,6 @@ using namespace gbx;
 
 namespace {
 
-#define EA_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_fail(e_, #call); } while (0)
-
 // toupper and disambiguate (eventalign.c:1054-1109, 1294): the lowest base of an IUPAC code; -1 where the reference asserts
 int ea_host_rank(char c)
 {
@@ -49,7 +47,7 @@ struct EaOnDevice {
     const int64_t *d_cigar_off; const uint32_t *d_cigar; const int32_t *d_pos; const uint8_t *d_rc;
 };
 
-int eventalign_on_lane(const char *who, Lane *L, int64_t n, int64_t seq_bytes, const EaOnDevice &d, const int64_t *event_off, const double *events_per_base,
+int eventalign_on_lane(Lane *L, int64_t n, int64_t seq_bytes, const EaOnDevice &d, const int64_t *event_off, const double *events_per_base,
                        int64_t n_cig, const int64_t *ref_off, const int32_t *ref_len, const char *ref_arena, int32_t region_start, int32_t region_end,
                        gbx_abea_eventalign_rec *rec, int32_t *n_rec, int32_t *status)
 {
@@ -79,31 +77,25 @@ int eventalign_on_lane(const char *who, Lane *L, int64_t n, int64_t seq_bytes, c
     int64_t *droff = small.take<int64_t>(n * 8);
     int32_t *drl = small.take<int32_t>(n * 4), *dnr = small.take<int32_t>(n * 4), *dst = small.take<int32_t>(n * 4);
     int64_t *drecoff = small.take<int64_t>((n + 1) * 8);
-    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{cs};       // the host vectors above outlive the queued copies
-    EA_HIP(hipMemcpyAsync(dtr, trans.data(), trans.size() * 4, hipMemcpyHostToDevice, cs));
-    EA_HIP(hipMemcpyAsync(dord, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, cs));
-    EA_HIP(hipMemcpyAsync(droff, roff.data(), (size_t)n * 8, hipMemcpyHostToDevice, cs));
-    EA_HIP(hipMemcpyAsync(drl, ref_len, (size_t)n * 4, hipMemcpyHostToDevice, cs));
-    if (!refs.empty()) EA_HIP(hipMemcpyAsync(dref.p, refs.data(), refs.size(), hipMemcpyHostToDevice, cs));
+    StreamDrain drain{cs};                                                      // the host vectors above outlive the queued copies
+    GBX_HIP(hipMemcpyAsync(dtr, trans.data(), trans.size() * 4, hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(dord, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(droff, roff.data(), (size_t)n * 8, hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(drl, ref_len, (size_t)n * 4, hipMemcpyHostToDevice, cs));
+    if (!refs.empty()) GBX_HIP(hipMemcpyAsync(dref.p, refs.data(), refs.size(), hipMemcpyHostToDevice, cs));
     if ((rc = abea_record_launch(GBX_ABEA_RECORD_COUNT, n, d.d_cigar_off, d.d_cigar, d.d_pos, d.d_rc, d.d_seq_off, d.d_seq_len, d.d_map, d.d_flags,
                                  dnear.as<int32_t>(), drecoff, nullptr, 0, cs)))
         return rc;
-    AbeaEventalignArgs a{};
-    a.n_reads = n; a.seq_off = d.d_seq_off; a.seq_len = d.d_seq_len; a.event_off = d.d_event_off; a.event_mean = d.d_event_mean; a.models = d.d_models;
-    a.scale = d.d_scale; a.shift = d.d_shift; a.var = d.d_var; a.log_var = d.d_log_var; a.trans = dtr;
-    a.map = d.d_map; a.near = dnear.as<int32_t>(); a.flags = d.d_flags;
-    a.cigar_off = d.d_cigar_off; a.cigar = d.d_cigar; a.pos = d.d_pos; a.rc = d.d_rc;
-    a.ref_off = droff; a.ref_len = drl; a.ref = dref.as<char>();
-    a.region_start = region_start; a.region_end = region_end; a.order = dord;
-    a.rec = drec.as<gbx_abea_eventalign_rec>() - e0;                           // the kernel indexes records as it indexes events: absolutely
-    a.n_rec = dnr; a.status = dst; a.counts = nullptr;
-    a.n_cigar_total = n_cig; a.rows_cap = GBX_ABEA_EVENTALIGN_ROWS; a.work = dw.p;
+    // the kernel indexes records as it indexes events: absolutely
+    const AbeaEventalignArgs a = abea_eventalign_args(n, d.d_seq_off, d.d_seq_len, d.d_event_off, d.d_event_mean, d.d_models, d.d_scale, d.d_shift, d.d_var,
+                                                      d.d_log_var, dtr, d.d_map, dnear.as<int32_t>(), d.d_flags, d.d_cigar_off, d.d_cigar, d.d_pos, d.d_rc, droff,
+                                                      drl, dref.as<char>(), region_start, region_end, dord, drec.as<gbx_abea_eventalign_rec>() - e0, dnr, dst,
+                                                      nullptr, n_cig, GBX_ABEA_EVENTALIGN_ROWS, dw.p);
     if ((rc = abea_eventalign_launch(a, wb, cs))) return rc;
-    EA_HIP(hipMemcpyAsync(n_rec, dnr, (size_t)n * 4, hipMemcpyDeviceToHost, cs));
-    EA_HIP(hipMemcpyAsync(status, dst, (size_t)n * 4, hipMemcpyDeviceToHost, cs));
-    if (n_ev) EA_HIP(hipMemcpyAsync(rec, drec.p, (size_t)n_ev * sizeof(gbx_abea_eventalign_rec), hipMemcpyDeviceToHost, cs));
-    EA_HIP(hipStreamSynchronize(cs));
-    (void)who;
+    GBX_HIP(hipMemcpyAsync(n_rec, dnr, (size_t)n * 4, hipMemcpyDeviceToHost, cs));
+    GBX_HIP(hipMemcpyAsync(status, dst, (size_t)n * 4, hipMemcpyDeviceToHost, cs));
+    if (n_ev) GBX_HIP(hipMemcpyAsync(rec, drec.p, (size_t)n_ev * sizeof(gbx_abea_eventalign_rec), hipMemcpyDeviceToHost, cs));
+    GBX_HIP(hipStreamSynchronize(cs));
     return GBX_OK;
 }
 
@@ -115,7 +107,7 @@ int check_refs(const char *who, int64_t n_reads, const int64_t *ref_off, const i
         return GBX_ERR_ARG;
     }
     for (int64_t r = 0; r < n_reads; ++r) {
-        if (ref_off[r] < 0 || ref_len[r] < 0) { set_error("%s: bad reference segment at read %lld", who, (long long)r); return GBX_ERR_ARG; }
+        if (int rc = ref_segment_check(ref_off, ref_len, r, who)) return rc;
         for (int32_t i = 0; i < ref_len[r]; ++i)
             if (ea_host_rank(ref_arena[ref_off[r] + i]) < 0) {
                 set_error("%s: read %lld: reference base %d is outside the IUPAC alphabet", who, (long long)r, i);
@@ -123,69 +115,6 @@ int check_refs(const char *who, int64_t n_reads, const int64_t *ref_off, const i
             }
     }
     return GBX_OK;
-}
-
-struct EaCall {                                              // the caller's side of gbx_abea_eventalign_from_signal_host
-    const int64_t *cigar_off; const uint32_t *cigar; const int32_t *pos; const uint8_t *rc;
-    const int64_t *ref_off; const int32_t *ref_len; const char *ref_arena; int32_t region_start, region_end;
-    int32_t *flags; float *scale, *shift, *var, *log_var; double *events_per_base;
-    int64_t *event_off; gbx_abea_event *events; int64_t event_cap; int64_t *n_events_total;
-    gbx_abea_eventalign_rec *rec; int32_t *n_rec; int32_t *ea_status;
-};
-
-// behind align(), on the buffers it left: calibration, the logarithm on the host, eventalign, the event records down
-int eventalign_tail(void *ctx, const AbeaAligned &a)
-{
-    const char *who = "gbx_abea_eventalign_from_signal_host";
-    const EaCall &c = *(const EaCall *)ctx;
-    Lane *L = a.L;
-    const hipStream_t cs = L->compute;
-    const int64_t n = a.n_reads, total = a.event_off[n];
-    int rc;
-    for (int64_t r = 0; r <= n; ++r) c.event_off[r] = a.event_off[r];
-    *c.n_events_total = total;
-    if (total > c.event_cap) { set_error("%s: %lld events, room for %lld", who, (long long)total, (long long)c.event_cap); return GBX_ERR_ARG; }
-    DevBuf dmap(L), dcg(L);
-    Carve per_read(L);
-    const int64_t n_cig = c.cigar_off[n] - c.cigar_off[0];
-    for (size_t b : {n * 4, n * 4, n * 8, n * 8, n * 4, n * 4, n * 4, n * 4, (n + 1) * 8, n * 4, n}) per_read.want(b);
-    if ((rc = per_read.alloc()) || (rc = dmap.alloc((size_t)a.seq_bytes * 8 + 16)) || (rc = dcg.alloc((size_t)n_cig * 4 + 16))) return rc;
-    int32_t *dnp = per_read.take<int32_t>(n * 4);
-    float *dvar = per_read.take<float>(n * 4);
-    double *dv64 = per_read.take<double>(n * 8), *depb = per_read.take<double>(n * 8);
-    int32_t *dnea = per_read.take<int32_t>(n * 4), *dnm = per_read.take<int32_t>(n * 4), *dfl = per_read.take<int32_t>(n * 4);
-    float *dlv = per_read.take<float>(n * 4);
-    int64_t *dco = per_read.take<int64_t>((n + 1) * 8);
-    int32_t *dpos = per_read.take<int32_t>(n * 4);
-    uint8_t *drc = per_read.take<uint8_t>(n);
-    std::vector<int64_t> coff((size_t)n + 1);
-    std::vector<double> v64((size_t)n);
-    std::vector<int32_t> nm((size_t)n);
-    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{cs};
-    for (int64_t r = 0; r <= n; ++r) coff[(size_t)r] = c.cigar_off[r] - c.cigar_off[0];
-    EA_HIP(hipMemcpyAsync(dnp, a.n_pairs, (size_t)n * 4, hipMemcpyHostToDevice, cs));
-    EA_HIP(hipMemcpyAsync(dco, coff.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, cs));
-    if (n_cig) EA_HIP(hipMemcpyAsync(dcg.p, c.cigar + c.cigar_off[0], (size_t)n_cig * 4, hipMemcpyHostToDevice, cs));
-    EA_HIP(hipMemcpyAsync(dpos, c.pos, (size_t)n * 4, hipMemcpyHostToDevice, cs));
-    EA_HIP(hipMemcpyAsync(drc, c.rc, (size_t)n, hipMemcpyHostToDevice, cs));
-    if ((rc = abea_calib_launch(n, a.d_seq_off, a.d_seq_len, a.d_seq, a.d_event_off, a.d_event_mean, a.d_models, a.d_pairs, dnp, a.d_scale, a.d_shift, dvar,
-                                dv64, dmap.as<int32_t>(), depb, dnea, dnm, dfl, cs)))
-        return rc;
-    EA_HIP(hipMemcpyAsync(c.scale, a.d_scale, (size_t)n * 4, hipMemcpyDeviceToHost, cs));
-    EA_HIP(hipMemcpyAsync(c.shift, a.d_shift, (size_t)n * 4, hipMemcpyDeviceToHost, cs));
-    EA_HIP(hipMemcpyAsync(c.var, dvar, (size_t)n * 4, hipMemcpyDeviceToHost, cs));
-    EA_HIP(hipMemcpyAsync(v64.data(), dv64, (size_t)n * 8, hipMemcpyDeviceToHost, cs));
-    EA_HIP(hipMemcpyAsync(c.events_per_base, depb, (size_t)n * 8, hipMemcpyDeviceToHost, cs));
-    EA_HIP(hipMemcpyAsync(nm.data(), dnm, (size_t)n * 4, hipMemcpyDeviceToHost, cs));
-    EA_HIP(hipMemcpyAsync(c.flags, dfl, (size_t)n * 4, hipMemcpyDeviceToHost, cs));
-    if (total) EA_HIP(hipMemcpyAsync(c.events, a.d_events, (size_t)total * sizeof(gbx_abea_event), hipMemcpyDeviceToHost, cs));
-    EA_HIP(hipStreamSynchronize(cs));
-    if ((rc = gbx_abea_calib_logvar_host(n, v64.data(), nm.data(), c.log_var))) return rc;
-    EA_HIP(hipMemcpyAsync(dlv, c.log_var, (size_t)n * 4, hipMemcpyHostToDevice, cs));
-    const EaOnDevice d{a.d_seq_off, a.d_seq_len, a.d_event_off, a.d_event_mean, a.d_models, a.d_scale, a.d_shift, dvar, dlv, dmap.as<int32_t>(), dfl,
-                       dco, dcg.as<uint32_t>(), dpos, drc};
-    return eventalign_on_lane(who, L, n, a.seq_bytes, d, a.event_off, c.events_per_base, n_cig, c.ref_off, c.ref_len, c.ref_arena, c.region_start,
-                              c.region_end, c.rec, c.n_rec, c.ea_status);
 }
 
 }  // namespace
@@ -222,12 +151,9 @@ int gbx_abea_eventalign_device(int64_t n_reads, const int64_t *d_seq_off, const 
     }
     int rc = require_device();
     if (rc) return rc;
-    AbeaEventalignArgs a{};
-    a.n_reads = n_reads; a.seq_off = d_seq_off; a.seq_len = d_seq_len; a.event_off = d_event_off; a.event_mean = d_event_mean; a.models = d_models;
-    a.scale = d_scale; a.shift = d_shift; a.var = d_var; a.log_var = d_log_var; a.trans = d_trans; a.map = d_map; a.near = d_near; a.flags = d_flags;
-    a.cigar_off = d_cigar_off; a.cigar = d_cigar; a.pos = d_pos; a.rc = d_rc; a.ref_off = d_ref_off; a.ref_len = d_ref_len; a.ref = d_ref_arena;
-    a.region_start = region_start; a.region_end = region_end; a.order = d_order; a.rec = d_rec; a.n_rec = d_n_rec; a.status = d_status; a.counts = d_counts;
-    a.n_cigar_total = n_cigar_total; a.rows_cap = rows_cap; a.work = d_work;
+    const AbeaEventalignArgs a = abea_eventalign_args(n_reads, d_seq_off, d_seq_len, d_event_off, d_event_mean, d_models, d_scale, d_shift, d_var, d_log_var,
+                                                      d_trans, d_map, d_near, d_flags, d_cigar_off, d_cigar, d_pos, d_rc, d_ref_off, d_ref_len, d_ref_arena,
+                                                      region_start, region_end, d_order, d_rec, d_n_rec, d_status, d_counts, n_cigar_total, rows_cap, d_work);
     return abea_eventalign_launch(a, work_bytes, (hipStream_t)stream);
 }
 
@@ -247,21 +173,17 @@ int gbx_abea_eventalign_host(int64_t n_reads, const int64_t *seq_off, const int3
         return GBX_ERR_ARG;
     }
     if (event_off[0] < 0) { set_error("%s: event_off below 0", who); return GBX_ERR_ARG; }
-    for (int64_t r = 0; r < n_reads; ++r) {
-        if (seq_off[r] < 0 || seq_len[r] < 0 || seq_off[r] + seq_len[r] > seq_bytes) { set_error("%s: read %lld lies outside the arena", who, (long long)r); return GBX_ERR_ARG; }
-        if (event_off[r + 1] < event_off[r]) { set_error("%s: event_off not monotone at read %lld", who, (long long)r); return GBX_ERR_ARG; }
-        if (event_off[r + 1] - event_off[r] > 0x3fffffffLL) { set_error("%s: read %lld has too many events", who, (long long)r); return GBX_ERR_UNSUPPORTED; }
-    }
+    int rc;
+    for (int64_t r = 0; r < n_reads; ++r)
+        if ((rc = read_check(seq_off, seq_len, seq_bytes, r, who)) || (rc = event_off_check(event_off, r, who)) || (rc = event_count_check(event_off, r, who)))
+            return rc;
     if (event_off[n_reads] > event_off[0] && (!events || !rec)) { set_error("%s: null pointer", who); return GBX_ERR_ARG; }
-    int rc = check_cigars(who, n_reads, cigar_off, cigar, seq_len);
-    if (rc) return rc;
+    if ((rc = check_cigars(who, n_reads, cigar_off, cigar, seq_len))) return rc;
     if ((rc = check_refs(who, n_reads, ref_off, ref_len, ref_arena, region_start, region_end))) return rc;
     if ((rc = require_device())) return rc;
     const int64_t e0 = event_off[0], n_ev = event_off[n_reads] - e0, c0 = cigar_off[0], n_cig = cigar_off[n_reads] - c0;
-    std::vector<int64_t> eoff((size_t)n_reads + 1), coff((size_t)n_reads + 1);
-    for (int64_t r = 0; r <= n_reads; ++r) { eoff[(size_t)r] = event_off[r] - e0; coff[(size_t)r] = cigar_off[r] - c0; }
-    std::vector<float> means((size_t)n_ev + 1);
-    for (int64_t i = 0; i < n_ev; ++i) means[(size_t)i] = events[e0 + i].mean;                                 // only the mean is read (eventalign.c:314)
+    const std::vector<int64_t> eoff = rebased0(event_off, n_reads), coff = rebased0(cigar_off, n_reads);
+    const std::vector<float> means = event_means(events, e0, n_ev);                                            // only the mean is read (eventalign.c:314)
     HostLane lane;
     if ((rc = lane.acquire())) return rc;
     Lane *L = lane.l;
@@ -281,25 +203,25 @@ int gbx_abea_eventalign_host(int64_t n_reads, const int64_t *seq_off, const int3
     int64_t *dco = small.take<int64_t>(n8 + 8);
     int32_t *dpos = small.take<int32_t>(n4);
     uint8_t *drc = small.take<uint8_t>((size_t)n_reads);
-    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{cs};
-    EA_HIP(hipMemcpyAsync(dso, seq_off, n8, hipMemcpyHostToDevice, cs));
-    EA_HIP(hipMemcpyAsync(dsl, seq_len, n4, hipMemcpyHostToDevice, cs));
-    EA_HIP(hipMemcpyAsync(deo, eoff.data(), n8 + 8, hipMemcpyHostToDevice, cs));
-    EA_HIP(hipMemcpyAsync(dsc, scale, n4, hipMemcpyHostToDevice, cs));
-    EA_HIP(hipMemcpyAsync(dsh, shift, n4, hipMemcpyHostToDevice, cs));
-    EA_HIP(hipMemcpyAsync(dvar, var, n4, hipMemcpyHostToDevice, cs));
-    EA_HIP(hipMemcpyAsync(dlv, log_var, n4, hipMemcpyHostToDevice, cs));
-    if (flags) EA_HIP(hipMemcpyAsync(dfl, flags, n4, hipMemcpyHostToDevice, cs));
-    EA_HIP(hipMemcpyAsync(dco, coff.data(), n8 + 8, hipMemcpyHostToDevice, cs));
-    EA_HIP(hipMemcpyAsync(dpos, pos, n4, hipMemcpyHostToDevice, cs));
-    EA_HIP(hipMemcpyAsync(drc, rc_flag, (size_t)n_reads, hipMemcpyHostToDevice, cs));
-    if (n_ev) EA_HIP(hipMemcpyAsync(dem.p, means.data(), (size_t)n_ev * 4, hipMemcpyHostToDevice, cs));
-    EA_HIP(hipMemcpyAsync(dmo.p, models, GBX_ABEA_NMODEL * sizeof(gbx_abea_model), hipMemcpyHostToDevice, cs));
-    if (seq_bytes) EA_HIP(hipMemcpyAsync(dmap.p, map, (size_t)seq_bytes * 8, hipMemcpyHostToDevice, cs));
-    if (n_cig) EA_HIP(hipMemcpyAsync(dcg.p, cigar + c0, (size_t)n_cig * 4, hipMemcpyHostToDevice, cs));
+    StreamDrain drain{cs};
+    GBX_HIP(hipMemcpyAsync(dso, seq_off, n8, hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(dsl, seq_len, n4, hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(deo, eoff.data(), n8 + 8, hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(dsc, scale, n4, hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(dsh, shift, n4, hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(dvar, var, n4, hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(dlv, log_var, n4, hipMemcpyHostToDevice, cs));
+    if (flags) GBX_HIP(hipMemcpyAsync(dfl, flags, n4, hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(dco, coff.data(), n8 + 8, hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(dpos, pos, n4, hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(drc, rc_flag, (size_t)n_reads, hipMemcpyHostToDevice, cs));
+    if (n_ev) GBX_HIP(hipMemcpyAsync(dem.p, means.data(), (size_t)n_ev * 4, hipMemcpyHostToDevice, cs));
+    GBX_HIP(hipMemcpyAsync(dmo.p, models, GBX_ABEA_NMODEL * sizeof(gbx_abea_model), hipMemcpyHostToDevice, cs));
+    if (seq_bytes) GBX_HIP(hipMemcpyAsync(dmap.p, map, (size_t)seq_bytes * 8, hipMemcpyHostToDevice, cs));
+    if (n_cig) GBX_HIP(hipMemcpyAsync(dcg.p, cigar + c0, (size_t)n_cig * 4, hipMemcpyHostToDevice, cs));
     const EaOnDevice d{dso, dsl, deo, dem.as<float>(), dmo.as<gbx_abea_model>(), dsc, dsh, dvar, dlv, dmap.as<int32_t>(), flags ? dfl : nullptr,
                        dco, dcg.as<uint32_t>(), dpos, drc};
-    return eventalign_on_lane(who, L, n_reads, seq_bytes, d, eoff.data(), events_per_base, n_cig, ref_off, ref_len, ref_arena, region_start, region_end, rec,
+    return eventalign_on_lane(L, n_reads, seq_bytes, d, eoff.data(), events_per_base, n_cig, ref_off, ref_len, ref_arena, region_start, region_end, rec,
                               n_rec, status);
 }
 
@@ -435,10 +357,25 @@ int gbx_abea_eventalign_from_signal_host(int64_t n_reads, const int16_t *raw, co
         flags[r] = GBX_ABEA_FAILED_ALIGNMENT; var[r] = 0.0f; log_var[r] = 0.0f; events_per_base[r] = 0.0; n_rec[r] = 0; ea_status[r] = 0; event_off[r] = 0;
     }
     event_off[n_reads] = 0;
-    EaCall c{cigar_off, cigar, pos, rc_flag, ref_off, ref_len, ref_arena, region_start, region_end, flags, scale, shift, var, log_var, events_per_base,
-             event_off, events, event_cap, n_events_total, rec, n_rec, ea_status};
+    // behind align(), on the buffers it left: calibration, the logarithm on the host, eventalign, the event records down
+    const abea_tail_fn eventalign_tail = [&](const AbeaAligned &a) -> int {
+        Lane *L = a.L;
+        const hipStream_t cs = L->compute;
+        const int64_t n = a.n_reads, total = a.event_off[n];
+        for (int64_t r = 0; r <= n; ++r) event_off[r] = a.event_off[r];
+        *n_events_total = total;
+        if (total > event_cap) { set_error("%s: %lld events, room for %lld", who, (long long)total, (long long)event_cap); return GBX_ERR_ARG; }
+        AbeaCalibrated cal(L);                                   // its guard drains the stream however this function is left
+        if ((rc = cal.queue(a, cigar_off, cigar, pos, rc_flag, scale, shift, var, events_per_base, flags))) return rc;
+        if (total) GBX_HIP(hipMemcpyAsync(events, a.d_events, (size_t)total * sizeof(gbx_abea_event), hipMemcpyDeviceToHost, cs));
+        if ((rc = cal.finish(log_var))) return rc;
+        const EaOnDevice d{a.d_seq_off, a.d_seq_len, a.d_event_off, a.d_event_mean, a.d_models, a.d_scale, a.d_shift, cal.var, cal.log_var, cal.map, cal.flags,
+                           cal.cigar_off, cal.cigar, cal.pos, cal.rc};
+        return eventalign_on_lane(L, n, a.seq_bytes, d, a.event_off, events_per_base, cal.n_cigar, ref_off, ref_len, ref_arena, region_start,
+                                  region_end, rec, n_rec, ea_status);
+    };
     return abea_signal_align_tail(who, n_reads, raw, raw_off, range, digitisation, offset, seq_off, seq_len, seq_arena, seq_bytes, models, status, scale,
-                                  shift, eventalign_tail, &c);
+                                  shift, eventalign_tail);
 }
 
 }  // extern "C"

@@ -8,7 +8,7 @@ static int abea_signal_host(const char *who, bool align, int64_t n_reads, const 
                             const float *digitisation, const float *offset, const int64_t *seq_off, const int32_t *seq_len, const char *seq_arena,
                             int64_t seq_bytes, const gbx_abea_model *models, int64_t *n_events, int64_t *event_off, gbx_abea_event *events,
                             int64_t event_cap, int64_t *n_events_total, float *scale, float *shift, int32_t *status, gbx_abea_pair *out,
-                            int32_t *n_pairs, abea_tail_fn tail = nullptr, void *tail_ctx = nullptr)
+                            int32_t *n_pairs, const abea_tail_fn &tail = nullptr)
 {
     RoctxRange range_(who);
     if (n_reads < 0 || event_cap < 0 || (align && seq_bytes < 0)) { set_error("%s: bad argument", who); return GBX_ERR_ARG; }
@@ -19,18 +19,17 @@ static int abea_signal_host(const char *who, bool align, int64_t n_reads, const 
         set_error("%s: null pointer", who);
         return GBX_ERR_ARG;
     }
+    int rc;
     for (int64_t r = 0; r < n_reads; ++r) {
         if (raw_off[r] < 0 || raw_off[r + 1] < raw_off[r]) { set_error("%s: raw_off not monotone at read %lld", who, (long long)r); return GBX_ERR_ARG; }
         if (raw_off[r + 1] - raw_off[r] > 0x3fffffff) { set_error("%s: read %lld is too long", who, (long long)r); return GBX_ERR_UNSUPPORTED; }
         if (!align) continue;
-        if (seq_off[r] < 0 || seq_len[r] < 0 || seq_off[r] + seq_len[r] > seq_bytes) { set_error("%s: read %lld lies outside the arena", who, (long long)r); return GBX_ERR_ARG; }
-        if (seq_len[r] < GBX_ABEA_KMER) { set_error("%s: read %lld needs at least %d bases", who, (long long)r, GBX_ABEA_KMER); return GBX_ERR_ARG; }
+        if ((rc = read_check(seq_off, seq_len, seq_bytes, r, who)) || (rc = kmer_check(seq_len, r, who))) return rc;
     }
-    int rc = require_device();
-    if (rc) return rc;
+    if ((rc = require_device())) return rc;
     const int64_t s0 = raw_off[0], n_samples = raw_off[n_reads] - s0;
-    std::vector<int64_t> roff((size_t)n_reads + 1), nev_own;
-    for (int64_t r = 0; r <= n_reads; ++r) roff[(size_t)r] = raw_off[r] - s0;
+    const std::vector<int64_t> roff = rebased0(raw_off, n_reads);
+    std::vector<int64_t> nev_own;
     if (!n_events) { nev_own.resize((size_t)n_reads); n_events = nev_own.data(); }
 
     HostLane lane;
@@ -133,7 +132,7 @@ static int abea_signal_host(const char *who, bool align, int64_t n_reads, const 
         for (int64_t k = 0; k < m; ++k) n_pairs[keep[(size_t)k]] = cnp[(size_t)k];
         const AbeaAligned a{L, n_reads, seq_bytes, event_off, n_pairs, dso.as<int64_t>(), dsl.as<int32_t>(), dsq.as<char>(), deo.as<int64_t>(),
                             dem.as<float>(), dmo.as<gbx_abea_model>(), dsc.as<float>(), dsh.as<float>(), dout.as<gbx_abea_pair>(), dev.as<gbx_abea_event>()};
-        return pipe.finish(tail(tail_ctx, a));
+        return pipe.finish(tail(a));
     }
     // half of the 2 x n_events slots are slack: the pairs are packed on the device, come back in one piece and go to
     // the reads' places from there
@@ -162,13 +161,13 @@ static int abea_signal_host(const char *who, bool align, int64_t n_reads, const 
 namespace gbx {
 int abea_signal_align_tail(const char *who, int64_t n_reads, const int16_t *raw, const int64_t *raw_off, const float *range, const float *digitisation,
                            const float *offset, const int64_t *seq_off, const int32_t *seq_len, const char *seq_arena, int64_t seq_bytes,
-                           const gbx_abea_model *models, int32_t *status, float *scale, float *shift, abea_tail_fn tail, void *ctx)
+                           const gbx_abea_model *models, int32_t *status, float *scale, float *shift, const abea_tail_fn &tail)
 {
     std::vector<int64_t> event_off((size_t)(n_reads > 0 ? n_reads : 0) + 1);
     std::vector<int32_t> n_pairs((size_t)(n_reads > 0 ? n_reads : 0) + 1);
     int64_t total = 0;
     return abea_signal_host(who, true, n_reads, raw, raw_off, range, digitisation, offset, seq_off, seq_len, seq_arena, seq_bytes, models, nullptr,
-                            event_off.data(), nullptr, 0, &total, scale, shift, status, nullptr, n_pairs.data(), tail, ctx);
+                            event_off.data(), nullptr, 0, &total, scale, shift, status, nullptr, n_pairs.data(), tail);
 }
 }  // namespace gbx
 

@@ -6,11 +6,6 @@ using namespace gbx;
 
 namespace {
 
-inline int64_t job_rows(const gbx_abea_meth_job &J)
-{
-    return J.event_stop > J.event_start ? (int64_t)J.event_stop - J.event_start + 1 : (int64_t)J.event_start - J.event_stop + 1;
-}
-
 inline int job_class(int64_t n_kmers) { return n_kmers <= 16 ? 0 : n_kmers <= 64 ? 1 : n_kmers <= 128 ? 2 : 3; }
 
 // ---- the string functions of meth.c
@@ -242,20 +237,13 @@ int gbx_abea_meth_score_host(int64_t n_jobs, const gbx_abea_meth_job *jobs, cons
         return GBX_ERR_ARG;
     }
     if (event_off[0] < 0) { set_error("gbx_abea_meth_score_host: event_off below 0"); return GBX_ERR_ARG; }
-    int64_t max_rows = 1;
-    for (int64_t j = 0; j < n_jobs; ++j) max_rows = std::max(max_rows, job_rows(jobs[j]));
-    const int64_t flank_len = max_rows + 1;
-    std::vector<float> flogsum(GBX_ABEA_FLOGSUM_TBL), trans((size_t)n_reads * GBX_ABEA_METH_NTRANS), pre((size_t)flank_len), post((size_t)flank_len);
-    std::vector<int32_t> order((size_t)n_jobs);
-    int64_t class_off[GBX_ABEA_METH_NCLASS + 1];
-    int rc = gbx_abea_meth_plan_host(n_jobs, jobs, seq_bytes, n_reads, event_off, events_per_base, flogsum.data(), trans.data(), flank_len,
-                                     pre.data(), post.data(), order.data(), class_off);
+    AbeaMethPlan plan;
+    int rc = plan.build(n_jobs, jobs, seq_bytes, n_reads, event_off, events_per_base);
     if (rc) return rc;
     if ((rc = require_device())) return rc;
     // only the means of the events are read (hmm.c:76): gathered from the 24-byte records on the way up, as in gbx_abea_align_host
     const int64_t e0 = event_off[0], n_ev = event_off[n_reads] - e0;
-    std::vector<int64_t> eoff((size_t)n_reads + 1);
-    for (int64_t r = 0; r <= n_reads; ++r) eoff[(size_t)r] = event_off[r] - e0;
+    const std::vector<int64_t> eoff = rebased0(event_off, n_reads);
     HostLane lane;
     if ((rc = lane.acquire())) return rc;
     Lane *L = lane.l;
@@ -263,8 +251,8 @@ int gbx_abea_meth_score_host(int64_t n_jobs, const gbx_abea_meth_job *jobs, cons
     const size_t job_bytes = (size_t)n_jobs * sizeof(gbx_abea_meth_job), model_bytes = GBX_ABEA_NMODEL_CPG * sizeof(gbx_abea_model);
     if ((rc = djb.alloc(job_bytes)) || (rc = dsq.alloc((size_t)seq_bytes + 16)) || (rc = deo.alloc((n_reads + 1) * 8)) || (rc = dem.alloc((size_t)n_ev * 4 + 16)) ||
         (rc = dsc.alloc(n_reads * 4)) || (rc = dsh.alloc(n_reads * 4)) || (rc = dvr.alloc(n_reads * 4)) || (rc = dlv.alloc(n_reads * 4)) ||
-        (rc = dmo.alloc(model_bytes)) || (rc = dfl.alloc(GBX_ABEA_FLOGSUM_TBL * 4)) || (rc = dtr.alloc(trans.size() * 4)) ||
-        (rc = dpr.alloc((size_t)flank_len * 4)) || (rc = dpo.alloc((size_t)flank_len * 4)) || (rc = dor.alloc((size_t)n_jobs * 4)) ||
+        (rc = dmo.alloc(model_bytes)) || (rc = dfl.alloc(GBX_ABEA_FLOGSUM_TBL * 4)) || (rc = dtr.alloc(plan.trans.size() * 4)) ||
+        (rc = dpr.alloc((size_t)plan.flank_len * 4)) || (rc = dpo.alloc((size_t)plan.flank_len * 4)) || (rc = dor.alloc((size_t)n_jobs * 4)) ||
         (rc = dout.alloc((size_t)n_jobs * 4)))
         return rc;
     HostPipe pipe(L, job_bytes + (size_t)seq_bytes + (size_t)n_ev * 4 + model_bytes + (size_t)n_jobs * 4 + (size_t)n_reads * 64, false);
@@ -276,14 +264,14 @@ int gbx_abea_meth_score_host(int64_t n_jobs, const gbx_abea_meth_job *jobs, cons
     pipe.stage(0, dsc.p, scale, n_reads * 4); pipe.stage(0, dsh.p, shift, n_reads * 4);
     pipe.stage(0, dvr.p, var, n_reads * 4); pipe.stage(0, dlv.p, log_var, n_reads * 4);
     pipe.stage(0, dmo.p, cpg_model, model_bytes);
-    pipe.stage(0, dfl.p, flogsum.data(), GBX_ABEA_FLOGSUM_TBL * 4); pipe.stage(0, dtr.p, trans.data(), trans.size() * 4);
-    pipe.stage(0, dpr.p, pre.data(), (size_t)flank_len * 4); pipe.stage(0, dpo.p, post.data(), (size_t)flank_len * 4);
-    pipe.stage(0, dor.p, order.data(), (size_t)n_jobs * 4);
+    pipe.stage(0, dfl.p, plan.flogsum.data(), GBX_ABEA_FLOGSUM_TBL * 4); pipe.stage(0, dtr.p, plan.trans.data(), plan.trans.size() * 4);
+    pipe.stage(0, dpr.p, plan.pre.data(), (size_t)plan.flank_len * 4); pipe.stage(0, dpo.p, plan.post.data(), (size_t)plan.flank_len * 4);
+    pipe.stage(0, dor.p, plan.order.data(), (size_t)n_jobs * 4);
     pipe.start();
     if ((rc = pipe.wait_stage(0))) return pipe.finish(rc);
     rc = abea_meth_launch(n_jobs, djb.as<gbx_abea_meth_job>(), dsq.as<char>(), deo.as<int64_t>(), dem.as<float>(), dsc.as<float>(), dsh.as<float>(),
                           dvr.as<float>(), dlv.as<float>(), dmo.as<gbx_abea_model>(), dfl.as<float>(), dtr.as<float>(), dpr.as<float>(),
-                          dpo.as<float>(), dor.as<int32_t>(), class_off, dout.as<float>(), L->compute);
+                          dpo.as<float>(), dor.as<int32_t>(), plan.class_off, dout.as<float>(), L->compute);
     if (rc) return pipe.finish(rc);
     pipe.fetch(0, scores, dout.p, (size_t)n_jobs * 4);
     if ((rc = pipe.chunk_launched(0))) return pipe.finish(rc);
