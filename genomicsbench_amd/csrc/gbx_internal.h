@@ -338,13 +338,14 @@ struct MmMapIo {                     // the device arguments of gbx_mm_map_devic
 };
 size_t mm_map_workspace_bytes(int64_t n_reads, int64_t anchor_cap, int64_t chain_cap);
 int mm_map_launch(const gbx_mm_map_params *p, const MmMapIo &io, void *d_work, size_t work_bytes, hipStream_t s);
-struct MmPafIo {                     // the device arguments of gbx_mm_paf_device
+struct MmPafIo {                     // the device arguments of gbx_mm_paf_device and gbx_mm_paf_cigar_device
     int64_t n_reads; const gbx_mm_reg *regs; const int64_t *reg_off; const int64_t *n_regs; int64_t reg_cap;
+    const gbx_mm_aln *alns; const uint32_t *cigar; int64_t cigar_cap;       // alns null: the plain text, no region prints cg:Z:
     const uint8_t *qnames; const int64_t *qname_off, *seq_off; const int32_t *rep_len;
     int64_t n_targets; const uint8_t *tnames; const int64_t *tname_off, *tseq_off;
     uint8_t *lines; int64_t text_cap; int64_t *line_off; int64_t *n_text;
 };
-size_t mm_paf_workspace_bytes(int64_t n_reads, int64_t reg_cap);
+size_t mm_paf_workspace_bytes(int64_t reg_cap);
 int mm_paf_launch(const MmPafIo &io, void *d_work, size_t work_bytes, hipStream_t s);
 
 // ---- base-level alignment of the regions (mm_align_kernels.hip; the rules: mm_align_rules.h)
@@ -356,9 +357,6 @@ struct MmAlignIo {                   // the device arguments of gbx_mm_align_dev
 };
 size_t mm_align_workspace_bytes(int64_t n_reads, int64_t reg_cap, int64_t anchor_cap);
 int mm_align_launch(const gbx_mm_align_params *p, const MmAlignIo &io, void *d_work, size_t work_bytes, hipStream_t s);
-struct MmPafCigarIo { MmPafIo paf; const gbx_mm_aln *alns; const uint32_t *cigar; int64_t cigar_cap; };
-size_t mm_paf_cigar_workspace_bytes(int64_t reg_cap);
-int mm_paf_cigar_launch(const MmPafCigarIo &io, void *d_work, size_t work_bytes, hipStream_t s);
 
 // ---- the aligner's gather behind the chain (mem_align_kernels.hip): every stage's count into one record
 struct MemAlignGather {              // a null pointer: the stage does not run, its count is 0

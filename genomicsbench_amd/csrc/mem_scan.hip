@@ -1,5 +1,6 @@
-// mem_scan.hip — the exclusive scan that turns per-unit counts into offsets (the bwa-mem stages, the index builder, the mm stages
-// and the radix sort of dev_sort.hip) and the tail fill of a CIGAR list (regs, pair).  The pieces of the scan are in dev_prims.h.
+// mem_scan.hip — the exclusive scan that turns per-unit counts into offsets (the bwa-mem stages, the index builder, mm seeding
+// and mm alignment, and the radix sort of dev_sort.hip) and the tail fill of a CIGAR list (regs, pair).  mm_map_kernels.hip keeps a
+// one-launch scan for its map and PAF stages, where three launches measured slower.  The pieces of the scan are in dev_prims.h.
 #include "dev_prims.h"
 
 namespace gbx {

@@ -21,9 +21,8 @@
 namespace gbx {
 namespace {
 
-constexpr int EL = 256, LDS_M = 512;
+constexpr int LDS_M = 512;
 constexpr long long GRID_MOST = 1 << 20;
-inline unsigned el_blocks(long long n) { const long long b = (n + EL - 1) / EL; return (unsigned)(b > 0 ? b : 1); }
 inline unsigned wave_blocks(long long n) { return (unsigned)(n < 1 ? 1 : n > GRID_MOST ? GRID_MOST : n); }
 
 struct MmAlnWave {
@@ -73,9 +72,9 @@ __device__ inline bool region_valid(const AlnArgs &A, const gbx_mm_reg &g, MmAln
     return region_view(A, g, S, x, y, &nc) && mm_aln_valid(g, A.io.n_targets, nc, *x, *y, S->tlen, S->qlen);
 }
 
-__global__ void __launch_bounds__(EL) mm_align_plan_kernel(AlnArgs A)
+__global__ void __launch_bounds__(MM_EL) mm_align_plan_kernel(AlnArgs A)
 {
-    const long long g = (long long)blockIdx.x * EL + threadIdx.x;
+    const long long g = (long long)blockIdx.x * MM_EL + threadIdx.x;
     if (g > A.io.reg_cap) return;
     long long nj = 0, zb = 0;
     if (g < clip_count(A.io.n_regs, A.io.reg_cap)) {
@@ -91,9 +90,9 @@ __global__ void __launch_bounds__(EL) mm_align_plan_kernel(AlnArgs A)
     A.njobs[g] = nj; A.zneed[g] = zb; A.words[g] = 0;
 }
 
-__global__ void __launch_bounds__(EL) mm_align_jobs_kernel(AlnArgs A)
+__global__ void __launch_bounds__(MM_EL) mm_align_jobs_kernel(AlnArgs A)
 {
-    const long long g = (long long)blockIdx.x * EL + threadIdx.x;
+    const long long g = (long long)blockIdx.x * MM_EL + threadIdx.x;
     if (g >= clip_count(A.io.n_regs, A.io.reg_cap)) return;
     const long long j0 = A.njobs[g], j1 = A.njobs[g + 1];
     if (j1 <= j0) return;
@@ -124,9 +123,9 @@ __global__ void __launch_bounds__(64) mm_align_dp_kernel(AlnArgs A)
     }
 }
 
-__global__ void __launch_bounds__(EL) mm_align_place_kernel(AlnArgs A)
+__global__ void __launch_bounds__(MM_EL) mm_align_place_kernel(AlnArgs A)
 {
-    const long long g = (long long)blockIdx.x * EL + threadIdx.x;
+    const long long g = (long long)blockIdx.x * MM_EL + threadIdx.x;
     if (g >= clip_count(A.io.n_regs, A.io.reg_cap)) return;
     const long long j0 = A.njobs[g], j1 = A.njobs[g + 1];
     if (j1 <= j0 || j1 > A.job_cap || A.jobs[j0].skip) return;
@@ -149,47 +148,6 @@ __global__ void __launch_bounds__(64) mm_align_pack_kernel(AlnArgs A)
     }
 }
 
-// ------------------------------------------------------------------------------------------------ PAF with CIGAR
-struct PafCigArgs { MmPafCigarIo io; long long *at; };
-
-__device__ inline long long paf_cig_line(const PafCigArgs &J, long long g, uint8_t *out, long long at)
-{
-    const MmPafIo &io = J.io.paf;
-    const gbx_mm_reg reg = io.regs[g];
-    const long long r = reg.read;
-    if (r < 0 || r >= io.n_reads) return 0;
-    const long long q0 = io.qname_off[r], q1 = io.qname_off[r + 1];
-    const bool tok = reg.rid >= 0 && reg.rid < io.n_targets;
-    const long long t0 = tok ? io.tname_off[reg.rid] : 0, t1 = tok ? io.tname_off[reg.rid + 1] : 0;
-    const int32_t tlen = tok ? (int32_t)(io.tseq_off[reg.rid + 1] - io.tseq_off[reg.rid]) : 0, qlen = (int32_t)(io.seq_off[r + 1] - io.seq_off[r]);
-    const gbx_mm_aln a = J.io.alns[g];
-    const bool aligned = (a.flags & GBX_MM_ALN_ALIGNED) && !(a.flags & (GBX_MM_ALN_NO_ROOM | GBX_MM_ALN_INVALID)) && a.n_cigar >= 0 && a.cigar_off >= 0 &&
-                         a.cigar_off + a.n_cigar <= J.io.cigar_cap;
-    if (aligned)
-        return mm_paf_cigar_line(out, at, io.text_cap, reg, a, J.io.cigar, io.qnames + q0, q1 > q0 ? q1 - q0 : 0, qlen, tok ? io.tnames + t0 : nullptr,
-                                 t1 > t0 ? t1 - t0 : 0, tlen, io.rep_len[r]);
-    return mm_paf_line(out, at, io.text_cap, reg, io.qnames + q0, q1 > q0 ? q1 - q0 : 0, qlen, tok ? io.tnames + t0 : nullptr, t1 > t0 ? t1 - t0 : 0, tlen,
-                       io.rep_len[r]);
-}
-
-__global__ void __launch_bounds__(EL) mm_paf_cig_measure_kernel(PafCigArgs J)
-{
-    const long long g = (long long)blockIdx.x * EL + threadIdx.x;
-    if (g > J.io.paf.reg_cap) return;
-    J.at[g] = g < clip_count(J.io.paf.n_regs, J.io.paf.reg_cap) ? paf_cig_line(J, g, nullptr, 0) : 0;
-}
-
-__global__ void __launch_bounds__(EL) mm_paf_cig_write_kernel(PafCigArgs J)
-{
-    const long long g = (long long)blockIdx.x * EL + threadIdx.x;
-    const MmPafIo &io = J.io.paf;
-    if (g < clip_count(io.n_regs, io.reg_cap)) paf_cig_line(J, g, io.lines, J.at[g]);
-    if (g <= io.n_reads) {
-        const long long ro = io.reg_off[g];
-        io.line_off[g] = J.at[ro < 0 ? 0 : ro > io.reg_cap ? io.reg_cap : ro];
-    }
-}
-
 }  // namespace
 
 size_t mm_align_workspace_bytes(int64_t n_reads, int64_t reg_cap, int64_t anchor_cap) { (void)n_reads; return aln_layout(reg_cap, anchor_cap).total; }
@@ -209,10 +167,10 @@ int mm_align_launch(const gbx_mm_align_params *p, const MmAlignIo &io, void *d_w
     const long long R = io.reg_cap;
     {
         Stage st("mm_align_plan", s);
-        hipLaunchKernelGGL(mm_align_plan_kernel, dim3(el_blocks(R + 1)), dim3(EL), 0, s, A);
+        hipLaunchKernelGGL(mm_align_plan_kernel, dim3(mm_el_blocks(R + 1)), dim3(MM_EL), 0, s, A);
         scan_launch1(A.njobs, R, bsum, io.counts, MemScanGuard{}, s);
         scan_launch1(A.zneed, R, bsum, io.counts + 2, MemScanGuard{}, s);
-        hipLaunchKernelGGL(mm_align_jobs_kernel, dim3(el_blocks(R)), dim3(EL), 0, s, A);
+        hipLaunchKernelGGL(mm_align_jobs_kernel, dim3(mm_el_blocks(R)), dim3(MM_EL), 0, s, A);
     }
     {
         Stage st("mm_align_dp", s);
@@ -220,32 +178,10 @@ int mm_align_launch(const gbx_mm_align_params *p, const MmAlignIo &io, void *d_w
     }
     {
         Stage st("mm_align_pack", s);
-        hipLaunchKernelGGL(mm_align_place_kernel, dim3(el_blocks(R)), dim3(EL), 0, s, A);
+        hipLaunchKernelGGL(mm_align_place_kernel, dim3(mm_el_blocks(R)), dim3(MM_EL), 0, s, A);
         scan_launch1(A.words, R, bsum, io.counts + 1, MemScanGuard{}, s);
         hipLaunchKernelGGL(mm_align_pack_kernel, dim3(wave_blocks(R)), dim3(64), 0, s, A);
     }
-    GBX_HIP(hipGetLastError());
-    return GBX_OK;
-}
-
-size_t mm_paf_cigar_workspace_bytes(int64_t reg_cap)
-{
-    const int64_t R = reg_cap > 0 ? reg_cap : 0;
-    return align256((size_t)(R + 1) * 8) + align256((size_t)mem_scan_blocks(R) * 8);
-}
-
-int mm_paf_cigar_launch(const MmPafCigarIo &io, void *d_work, size_t work_bytes, hipStream_t s)
-{
-    const size_t need = mm_paf_cigar_workspace_bytes(io.paf.reg_cap);
-    if (work_bytes < need) { set_error("mm paf cigar: workspace too small (%zu bytes, %zu needed)", work_bytes, need); return GBX_ERR_ARG; }
-    const long long R = io.paf.reg_cap > 0 ? io.paf.reg_cap : 0;
-    PafCigArgs J{io, (long long *)d_work};
-    long long *bsum = (long long *)((char *)d_work + align256((size_t)(R + 1) * 8));
-    Stage st("mm_paf_cigar", s);
-    hipLaunchKernelGGL(mm_paf_cig_measure_kernel, dim3(el_blocks(R + 1)), dim3(EL), 0, s, J);
-    scan_launch1(J.at, R, bsum, io.paf.n_text, MemScanGuard{}, s);
-    const long long span = R > io.paf.n_reads + 1 ? R : io.paf.n_reads + 1;
-    hipLaunchKernelGGL(mm_paf_cig_write_kernel, dim3(el_blocks(span)), dim3(EL), 0, s, J);
     GBX_HIP(hipGetLastError());
     return GBX_OK;
 }

@@ -23,11 +23,9 @@ using u32 = unsigned;
 using u64 = uint64_t;
 
 constexpr int LDS_W = 16;                                        // the widest ring kept in LDS
-constexpr int EL = 256;                                          // the element-wise kernels' block
 constexpr int READ_SHIFT = 43;                                   // the read's place in an anchor's sort word
 constexpr u64 Y_MASK = (1ull << READ_SHIFT) - 1;
 
-inline unsigned el_blocks(long long n) { const long long b = (n + EL - 1) / EL; return (unsigned)(b > 0 ? b : 1); }
 inline int bits_of(long long v) { int b = 0; while (v > 0) { ++b; v >>= 1; } return b; }
 
 // ------------------------------------------------------------------------------------------------ sketch
@@ -123,18 +121,18 @@ struct IndexJob {
     float frac; int mid_occ, k, w, hpc;
 };
 
-__global__ void __launch_bounds__(EL) mm_idx_head_kernel(IndexJob J)
+__global__ void __launch_bounds__(MM_EL) mm_idx_head_kernel(IndexJob J)
 {
-    const long long i = (long long)blockIdx.x * EL + threadIdx.x;
+    const long long i = (long long)blockIdx.x * MM_EL + threadIdx.x;
     if (i >= J.cap) return;
     const long long m = clip_count(J.v.hdr, J.cap);
     J.cnt[i] = i < m && (i == 0 || J.hi[i] >> 8 != J.hi[i - 1] >> 8) ? 1 : 0;
 }
 
 // cnt has become the ranks of the heads; cnt[cap] = hdr[1] = the number of keys
-__global__ void __launch_bounds__(EL) mm_idx_write_kernel(IndexJob J)
+__global__ void __launch_bounds__(MM_EL) mm_idx_write_kernel(IndexJob J)
 {
-    const long long i = (long long)blockIdx.x * EL + threadIdx.x;
+    const long long i = (long long)blockIdx.x * MM_EL + threadIdx.x;
     const long long m = clip_count(J.v.hdr, J.cap);
     if (i == 0) J.v.koff[J.cnt[J.cap]] = m;
     if (i >= m) return;
@@ -142,9 +140,9 @@ __global__ void __launch_bounds__(EL) mm_idx_write_kernel(IndexJob J)
     if (i == 0 || J.hi[i] >> 8 != J.hi[i - 1] >> 8) { const long long r = J.cnt[i]; J.v.keys[r] = J.hi[i] >> 8; J.v.koff[r] = i; }
 }
 
-__global__ void __launch_bounds__(EL) mm_idx_count_kernel(IndexJob J)
+__global__ void __launch_bounds__(MM_EL) mm_idx_count_kernel(IndexJob J)
 {
-    const long long j = (long long)blockIdx.x * EL + threadIdx.x;
+    const long long j = (long long)blockIdx.x * MM_EL + threadIdx.x;
     if (j < clip_count(J.v.hdr + 1, J.cap)) J.chi[j] = (u64)(J.v.koff[j + 1] - J.v.koff[j]);
 }
 
@@ -191,9 +189,9 @@ struct SeedJob {
     int max_gap, bw;
 };
 
-__global__ void __launch_bounds__(EL) mm_seed_lookup_kernel(SeedJob J)
+__global__ void __launch_bounds__(MM_EL) mm_seed_lookup_kernel(SeedJob J)
 {
-    const long long j = (long long)blockIdx.x * EL + threadIdx.x;
+    const long long j = (long long)blockIdx.x * MM_EL + threadIdx.x;
     if (j >= J.mini_cap) return;
     const long long n = clip_count(J.counts, J.mini_cap);
     if (j >= n) { J.acnt[j] = 0; return; }
@@ -258,9 +256,9 @@ __global__ void __launch_bounds__(64) mm_seed_read_kernel(SeedJob J)
     J.hdr[r] = h;
 }
 
-__global__ void __launch_bounds__(EL) mm_seed_fill_kernel(SeedJob J)
+__global__ void __launch_bounds__(MM_EL) mm_seed_fill_kernel(SeedJob J)
 {
-    const long long j = (long long)blockIdx.x * EL + threadIdx.x;
+    const long long j = (long long)blockIdx.x * MM_EL + threadIdx.x;
     if (j >= clip_count(J.counts, J.mini_cap)) return;
     const long long a0 = J.acnt[j], cnt = J.acnt[j + 1] - a0;
     if (cnt <= 0) return;
@@ -284,9 +282,9 @@ __global__ void __launch_bounds__(EL) mm_seed_fill_kernel(SeedJob J)
     }
 }
 
-__global__ void __launch_bounds__(EL) mm_seed_unpack_kernel(const u64 *hi, const u64 *lo, const int64_t *d_m, long long cap, u64 *ax, u64 *ay)
+__global__ void __launch_bounds__(MM_EL) mm_seed_unpack_kernel(const u64 *hi, const u64 *lo, const int64_t *d_m, long long cap, u64 *ax, u64 *ay)
 {
-    const long long i = (long long)blockIdx.x * EL + threadIdx.x;
+    const long long i = (long long)blockIdx.x * MM_EL + threadIdx.x;
     if (i >= clip_count(d_m, cap)) return;
     ax[i] = hi[i]; ay[i] = lo[i] & Y_MASK;
 }
@@ -396,10 +394,10 @@ int mm_index_launch(const gbx_mm_params *p, int64_t n_seqs, const uint8_t *d_seq
     J.hi = B.a[cur]; J.lo = B.b[cur]; J.chi = B.a[cur ^ 1];
     {
         Stage st("mm_index_group", s);
-        hipLaunchKernelGGL(mm_idx_head_kernel, dim3(el_blocks(J.cap)), dim3(EL), 0, s, J);
+        hipLaunchKernelGGL(mm_idx_head_kernel, dim3(mm_el_blocks(J.cap)), dim3(MM_EL), 0, s, J);
         scan_launch1(J.cnt, J.cap, (long long *)(wb + L.o_bsum), J.v.hdr + 1, MemScanGuard{}, s);
-        hipLaunchKernelGGL(mm_idx_write_kernel, dim3(el_blocks(J.cap)), dim3(EL), 0, s, J);
-        hipLaunchKernelGGL(mm_idx_count_kernel, dim3(el_blocks(J.cap)), dim3(EL), 0, s, J);
+        hipLaunchKernelGGL(mm_idx_write_kernel, dim3(mm_el_blocks(J.cap)), dim3(MM_EL), 0, s, J);
+        hipLaunchKernelGGL(mm_idx_count_kernel, dim3(mm_el_blocks(J.cap)), dim3(MM_EL), 0, s, J);
     }
     {
         Stage st("mm_index_mid_occ", s);
@@ -448,14 +446,14 @@ int mm_seed_launch(const gbx_mm_params *p, const MmSeedIo &io, void *d_work, siz
     J.ax = (u64 *)io.ax; J.ay = (u64 *)io.ay; J.max_gap = p->max_gap; J.bw = p->bw;
     {
         Stage st("mm_seed_lookup", s);
-        if (io.mini_cap > 0) hipLaunchKernelGGL(mm_seed_lookup_kernel, dim3(el_blocks(io.mini_cap)), dim3(EL), 0, s, J);
+        if (io.mini_cap > 0) hipLaunchKernelGGL(mm_seed_lookup_kernel, dim3(mm_el_blocks(io.mini_cap)), dim3(MM_EL), 0, s, J);
         else GBX_HIP(hipMemsetAsync(J.acnt, 0, 16, s));
         scan_launch1(J.acnt, io.mini_cap, (long long *)(wb + L.o_bsum), io.counts + 1, MemScanGuard{io.counts, 0, io.mini_cap}, s);
         hipLaunchKernelGGL(mm_seed_read_kernel, dim3((unsigned)io.n_reads), dim3(64), 0, s, J);
     }
     {
         Stage st("mm_seed_fill", s);
-        if (io.mini_cap > 0) hipLaunchKernelGGL(mm_seed_fill_kernel, dim3(el_blocks(io.mini_cap)), dim3(EL), 0, s, J);
+        if (io.mini_cap > 0) hipLaunchKernelGGL(mm_seed_fill_kernel, dim3(mm_el_blocks(io.mini_cap)), dim3(MM_EL), 0, s, J);
     }
     SortPass pass[24];
     int np = 0;
@@ -469,7 +467,7 @@ int mm_seed_launch(const gbx_mm_params *p, const MmSeedIo &io, void *d_work, siz
     {
         Stage st("mm_seed_sort", s);
         const int cur = radix_sort(B, SortCount{io.counts + 1, sort_cap}, pass, np, s);
-        hipLaunchKernelGGL(mm_seed_unpack_kernel, dim3(el_blocks(sort_cap)), dim3(EL), 0, s, B.a[cur], B.b[cur], io.counts + 1, (long long)io.anchor_cap,
+        hipLaunchKernelGGL(mm_seed_unpack_kernel, dim3(mm_el_blocks(sort_cap)), dim3(MM_EL), 0, s, B.a[cur], B.b[cur], io.counts + 1, (long long)io.anchor_cap,
                            J.ax, J.ay);
     }
     GBX_HIP(hipGetLastError());

@@ -1,23 +1,26 @@
-// mm_map_kernels.hip — minimap2 behind the chain scores: chains, regions, parents, selection, mapq and the PAF text.
-// The rules are in mm_map_rules.h, one text for these kernels and for the host build the CPU tests run; this file gives them a
-// team (one wavefront a read: a block of 64, __syncthreads() as the barrier) and the memory.
+// mm_map_kernels.hip — minimap2 behind the chain scores: chains, regions, parents, selection, mapq, and the PAF text
+// with or without the alignments of DESIGN 3.20.  The rules are in mm_map_rules.h and mm_paf_rules.h, one text for these kernels
+// and for the host build the CPU tests run; this file gives them a team (one wavefront a read: a block of 64, __syncthreads()
+// as the barrier) and the memory.
 //
 //   chains    a wavefront per read: ends and their peaks, the keys sorted in the read's workspace, every key's walk at once
 //             (atomicMin on the owner), chain order, the chained anchors -> per-read counts
 //   scan      chain_off in place, the total into counts[0]
 //   regions   a wavefront per read: u to its place, mm_gen_regs per lane, then lane 0 takes parents, selection and mapq into a
 //             staging record per chain -> per-read counts; scan; a copy to reg_off
-//   PAF       a lane per region measures its line, scan, a lane per region writes it
+//   PAF       a lane per region measures its line (plain, or with cg:Z: where alignments are given and the region has one), scan,
+//             a lane per region writes it
+// The scans are one launch of one block (mm_map_scan_kernel), not the three launches of the shared scan (mem_scan_launch): with
+// the shared scan 400 reads took 1.035 against 1.017 ms to map and 0.055 against 0.051 ms to print (profiles/mm_refactor_ab.json).
 // Counts live on the device, nothing is written past a capacity, no kernel waits for another block and no entry synchronises
 // with the host.
 #include "dev_prims.h"
-#include "mm_map_rules.h"
+#include "mm_paf_rules.h"
 
 namespace gbx {
 namespace {
 
-constexpr int EL = 256, SCAN_T = 1024;
-inline unsigned el_blocks(long long n) { const long long b = (n + EL - 1) / EL; return (unsigned)(b > 0 ? b : 1); }
+constexpr int SCAN_T = 1024;
 
 struct MmWave {
     __device__ int lane() const { return (int)threadIdx.x; }
@@ -80,11 +83,9 @@ __global__ void __launch_bounds__(64) mm_map_chain_kernel(MapJob J)
 }
 
 // exclusive scan of a[0 .. n) in place, a[n] = the total, also to *total (-1 where *guard > guard_cap); one block
-__global__ void __launch_bounds__(SCAN_T) mm_map_scan_kernel(int64_t *a, const int64_t *n_dev, long long n_cap, int64_t *total, const int64_t *guard,
-                                                             long long guard_cap)
+__global__ void __launch_bounds__(SCAN_T) mm_map_scan_kernel(int64_t *a, long long n, int64_t *total, const int64_t *guard, long long guard_cap)
 {
     __shared__ long long part[SCAN_T];
-    const long long n = n_dev ? clip_count(n_dev, n_cap) : n_cap;
     const long long chunk = (n + SCAN_T - 1) / SCAN_T, lo = (long long)threadIdx.x * chunk, hi = lo + chunk < n ? lo + chunk : n;
     long long sum = 0;
     for (long long i = lo; i < hi; ++i) sum += a[i];
@@ -100,9 +101,14 @@ __global__ void __launch_bounds__(SCAN_T) mm_map_scan_kernel(int64_t *a, const i
     for (long long i = lo; i < hi; ++i) { const long long c = a[i]; a[i] = run; run += c; }
     if (threadIdx.x == 0) {
         const long long tot = part[SCAN_T - 1];
-        for (long long i = n; i <= n_cap; ++i) a[i] = tot;            // n_cap - n entries at most: the tail of a clipped count
+        a[n] = tot;
         if (total) *total = guard && *guard > guard_cap ? -1 : tot;
     }
+}
+
+inline void map_scan(int64_t *a, long long n, int64_t *total, const int64_t *guard, long long guard_cap, hipStream_t s)
+{
+    hipLaunchKernelGGL(mm_map_scan_kernel, dim3(1), dim3(SCAN_T), 0, s, a, n, total, guard, guard_cap);
 }
 
 __global__ void __launch_bounds__(64) mm_map_reg_kernel(MapJob J)
@@ -134,35 +140,27 @@ __global__ void __launch_bounds__(64) mm_map_place_kernel(MapJob J)
 }
 
 // ------------------------------------------------------------------------------------------------ PAF
-struct PafJob { MmPafIo io; int64_t *at; };
+struct PafJob {
+    MmPafView v;
+    const int64_t *reg_off, *n_regs; int64_t reg_cap;
+    uint8_t *lines; int64_t text_cap; int64_t *line_off;
+    int64_t *at;                                    // [reg_cap + 1]: the lines' lengths, then their offsets
+};
 
-__device__ inline long long paf_line(const PafJob &J, long long g, uint8_t *out, long long at)
+__global__ void __launch_bounds__(MM_EL) mm_paf_measure_kernel(PafJob J)
 {
-    const gbx_mm_reg reg = J.io.regs[g];
-    const long long r = reg.read;
-    if (r < 0 || r >= J.io.n_reads) return 0;
-    const long long q0 = J.io.qname_off[r], q1 = J.io.qname_off[r + 1];
-    const bool tok = reg.rid >= 0 && reg.rid < J.io.n_targets;
-    const long long t0 = tok ? J.io.tname_off[reg.rid] : 0, t1 = tok ? J.io.tname_off[reg.rid + 1] : 0;
-    const int32_t tlen = tok ? (int32_t)(J.io.tseq_off[reg.rid + 1] - J.io.tseq_off[reg.rid]) : 0;
-    return mm_paf_line(out, at, J.io.text_cap, reg, J.io.qnames + q0, q1 > q0 ? q1 - q0 : 0, (int32_t)(J.io.seq_off[r + 1] - J.io.seq_off[r]),
-                       tok ? J.io.tnames + t0 : nullptr, t1 > t0 ? t1 - t0 : 0, tlen, J.io.rep_len[r]);
+    const long long g = (long long)blockIdx.x * MM_EL + threadIdx.x;
+    if (g >= J.reg_cap) return;                                       // at[reg_cap] is the scan's to write
+    J.at[g] = g < clip_count(J.n_regs, J.reg_cap) ? mm_paf_region_line(J.v, g, nullptr, 0, 0) : 0;
 }
 
-__global__ void __launch_bounds__(EL) mm_paf_measure_kernel(PafJob J)
+__global__ void __launch_bounds__(MM_EL) mm_paf_write_kernel(PafJob J)
 {
-    const long long g = (long long)blockIdx.x * EL + threadIdx.x;
-    if (g >= J.io.reg_cap) return;
-    J.at[g] = g < clip_count(J.io.n_regs, J.io.reg_cap) ? paf_line(J, g, nullptr, 0) : 0;
-}
-
-__global__ void __launch_bounds__(EL) mm_paf_write_kernel(PafJob J)
-{
-    const long long g = (long long)blockIdx.x * EL + threadIdx.x;
-    if (g < clip_count(J.io.n_regs, J.io.reg_cap)) paf_line(J, g, J.io.lines, J.at[g]);
-    if (g <= J.io.n_reads) {
-        const long long ro = J.io.reg_off[g];
-        J.io.line_off[g] = J.at[ro < 0 ? 0 : ro > J.io.reg_cap ? J.io.reg_cap : ro];
+    const long long g = (long long)blockIdx.x * MM_EL + threadIdx.x;
+    if (g < clip_count(J.n_regs, J.reg_cap)) mm_paf_region_line(J.v, g, J.lines, J.at[g], J.text_cap);
+    if (g <= J.v.n_reads) {
+        const long long ro = J.reg_off[g];
+        J.line_off[g] = J.at[ro < 0 ? 0 : ro > J.reg_cap ? J.reg_cap : ro];
     }
 }
 
@@ -191,33 +189,34 @@ int mm_map_launch(const gbx_mm_map_params *p, const MmMapIo &io, void *d_work, s
     {
         Stage st("mm_map_chains", s);
         hipLaunchKernelGGL(mm_map_chain_kernel, grid, dim3(64), 0, s, J);
-        hipLaunchKernelGGL(mm_map_scan_kernel, dim3(1), dim3(SCAN_T), 0, s, io.chain_off, (const int64_t *)nullptr, (long long)io.n_reads, io.counts,
-                           (const int64_t *)nullptr, 0ll);
+        map_scan(io.chain_off, io.n_reads, io.counts, nullptr, 0, s);
     }
     {
         Stage st("mm_map_regs", s);
         hipLaunchKernelGGL(mm_map_reg_kernel, grid, dim3(64), 0, s, J);
-        hipLaunchKernelGGL(mm_map_scan_kernel, dim3(1), dim3(SCAN_T), 0, s, io.reg_off, (const int64_t *)nullptr, (long long)io.n_reads, io.counts + 1,
-                           (const int64_t *)io.counts, (long long)io.chain_cap);
+        map_scan(io.reg_off, io.n_reads, io.counts + 1, io.counts, io.chain_cap, s);      // -1: the chains did not fit
         hipLaunchKernelGGL(mm_map_place_kernel, grid, dim3(64), 0, s, J);
     }
     GBX_HIP(hipGetLastError());
     return GBX_OK;
 }
 
-size_t mm_paf_workspace_bytes(int64_t n_reads, int64_t reg_cap) { (void)n_reads; return align256((size_t)((reg_cap > 0 ? reg_cap : 0) + 1) * 8); }
+size_t mm_paf_workspace_bytes(int64_t reg_cap) { return align256((size_t)((reg_cap > 0 ? reg_cap : 0) + 1) * 8); }
 
+// measure, scan, write; with io.alns the aligned regions print their cg:Z: lines
 int mm_paf_launch(const MmPafIo &io, void *d_work, size_t work_bytes, hipStream_t s)
 {
-    const size_t need = mm_paf_workspace_bytes(io.n_reads, io.reg_cap);
-    if (work_bytes < need) { set_error("mm paf: workspace too small (%zu bytes, %zu needed)", work_bytes, need); return GBX_ERR_ARG; }
-    PafJob J{io, (int64_t *)d_work};
-    Stage st("mm_paf", s);
-    if (io.reg_cap > 0) hipLaunchKernelGGL(mm_paf_measure_kernel, dim3(el_blocks(io.reg_cap)), dim3(EL), 0, s, J);
-    hipLaunchKernelGGL(mm_map_scan_kernel, dim3(1), dim3(SCAN_T), 0, s, J.at, (const int64_t *)nullptr, (long long)io.reg_cap, io.n_text,
-                       (const int64_t *)nullptr, 0ll);
-    const long long span = io.reg_cap > io.n_reads + 1 ? io.reg_cap : io.n_reads + 1;
-    hipLaunchKernelGGL(mm_paf_write_kernel, dim3(el_blocks(span)), dim3(EL), 0, s, J);
+    const char *who = io.alns ? "mm paf cigar" : "mm paf";
+    const size_t need = mm_paf_workspace_bytes(io.reg_cap);
+    if (work_bytes < need) { set_error("%s: workspace too small (%zu bytes, %zu needed)", who, work_bytes, need); return GBX_ERR_ARG; }
+    const long long R = io.reg_cap > 0 ? io.reg_cap : 0;
+    const PafJob J{MmPafView{io.n_reads, io.regs, io.alns, io.cigar, io.cigar_cap, io.qnames, io.qname_off, io.seq_off, io.rep_len, io.n_targets, io.tnames,
+                             io.tname_off, io.tseq_off}, io.reg_off, io.n_regs, io.reg_cap, io.lines, io.text_cap, io.line_off, (int64_t *)d_work};
+    Stage st(io.alns ? "mm_paf_cigar" : "mm_paf", s);
+    if (R > 0) hipLaunchKernelGGL(mm_paf_measure_kernel, dim3(mm_el_blocks(R)), dim3(MM_EL), 0, s, J);
+    map_scan(J.at, R, io.n_text, nullptr, 0, s);
+    const long long span = R > io.n_reads + 1 ? R : io.n_reads + 1;
+    hipLaunchKernelGGL(mm_paf_write_kernel, dim3(mm_el_blocks(span)), dim3(MM_EL), 0, s, J);
     GBX_HIP(hipGetLastError());
     return GBX_OK;
 }

@@ -2,7 +2,7 @@
 // one lane.  The CPU tests hold it against the plain-Python restatement tests/mm_align_ref.py, so the text the kernels run is
 // tested where there is no GPU.
 #include <vector>
-#include "../mm_align_rules.h"
+#include "../mm_paf_rules.h"
 
 extern "C" {
 
@@ -70,27 +70,8 @@ int64_t gbx_mm_paf_cigar_cpu(int64_t n_reads, const gbx_mm_reg *regs, const int6
                              const uint8_t *qnames, const int64_t *qname_off, const int64_t *seq_off, const int32_t *rep_len, int64_t n_targets,
                              const uint8_t *tnames, const int64_t *tname_off, const int64_t *tseq_off, uint8_t *lines, int64_t text_cap, int64_t *line_off)
 {
-    int64_t at = 0;
-    for (int64_t r = 0; r < n_reads; ++r) {
-        line_off[r] = at;
-        for (int64_t g = reg_off[r]; g < reg_off[r + 1]; ++g) {
-            const gbx_mm_reg &reg = regs[g];
-            const gbx_mm_aln &a = alns[g];
-            const bool tok = reg.rid >= 0 && reg.rid < n_targets;
-            const uint8_t *tn = tok ? tnames + tname_off[reg.rid] : nullptr;
-            const int64_t tnl = tok ? tname_off[reg.rid + 1] - tname_off[reg.rid] : 0;
-            const int32_t tlen = tok ? (int32_t)(tseq_off[reg.rid + 1] - tseq_off[reg.rid]) : 0, qlen = (int32_t)(seq_off[r + 1] - seq_off[r]);
-            const bool aligned = (a.flags & GBX_MM_ALN_ALIGNED) && !(a.flags & (GBX_MM_ALN_NO_ROOM | GBX_MM_ALN_INVALID)) && a.n_cigar >= 0 &&
-                                 a.cigar_off >= 0 && a.cigar_off + a.n_cigar <= n_cigar;
-            if (aligned)
-                at += gbx::mm_paf_cigar_line(lines, at, text_cap, reg, a, cigar, qnames + qname_off[r], qname_off[r + 1] - qname_off[r], qlen, tn, tnl, tlen,
-                                             rep_len[r]);
-            else
-                at += gbx::mm_paf_line(lines, at, text_cap, reg, qnames + qname_off[r], qname_off[r + 1] - qname_off[r], qlen, tn, tnl, tlen, rep_len[r]);
-        }
-    }
-    line_off[n_reads] = at;
-    return at;
+    const gbx::MmPafView V{n_reads, regs, alns, cigar, n_cigar, qnames, qname_off, seq_off, rep_len, n_targets, tnames, tname_off, tseq_off};
+    return gbx::mm_paf_text(V, reg_off, lines, text_cap, line_off);
 }
 
 }  // extern "C"

@@ -1,8 +1,8 @@
-// mm_map_cpu_twin.cpp — the device's rules behind the chain scores (mm_map_rules.h) compiled for the host into libgbx_mm_cpu.so:
-// a team of one lane.  The CPU tests hold it against the plain-Python restatement tests/mm_map_ref.py, so the text the kernels
-// run is tested where there is no GPU.
+// mm_map_cpu_twin.cpp — the device's rules behind the chain scores (mm_map_rules.h) and of a PAF line (mm_paf_rules.h) compiled
+// for the host into libgbx_mm_cpu.so: a team of one lane.  The CPU tests hold it against the plain-Python restatement
+// tests/mm_map_ref.py, so the text the kernels run is tested where there is no GPU.
 #include <vector>
-#include "../mm_map_rules.h"
+#include "../mm_paf_rules.h"
 
 extern "C" {
 
@@ -42,19 +42,8 @@ int64_t gbx_mm_paf_cpu(int64_t n_reads, const gbx_mm_reg *regs, const int64_t *r
                        const int64_t *seq_off, const int32_t *rep_len, int64_t n_targets, const uint8_t *tnames, const int64_t *tname_off,
                        const int64_t *tseq_off, uint8_t *lines, int64_t text_cap, int64_t *line_off)
 {
-    int64_t at = 0;
-    for (int64_t r = 0; r < n_reads; ++r) {
-        line_off[r] = at;
-        for (int64_t g = reg_off[r]; g < reg_off[r + 1]; ++g) {
-            const gbx_mm_reg &reg = regs[g];
-            const bool tok = reg.rid >= 0 && reg.rid < n_targets;
-            at += gbx::mm_paf_line(lines, at, text_cap, reg, qnames + qname_off[r], qname_off[r + 1] - qname_off[r], (int32_t)(seq_off[r + 1] - seq_off[r]),
-                                   tok ? tnames + tname_off[reg.rid] : nullptr, tok ? tname_off[reg.rid + 1] - tname_off[reg.rid] : 0,
-                                   tok ? (int32_t)(tseq_off[reg.rid + 1] - tseq_off[reg.rid]) : 0, rep_len[r]);
-        }
-    }
-    line_off[n_reads] = at;
-    return at;
+    const gbx::MmPafView V{n_reads, regs, nullptr, nullptr, 0, qnames, qname_off, seq_off, rep_len, n_targets, tnames, tname_off, tseq_off};
+    return gbx::mm_paf_text(V, reg_off, lines, text_cap, line_off);
 }
 
 uint32_t gbx_mm_map_cpu_read_hash(const uint8_t *name, int64_t len, int32_t qlen) { return gbx::mm_map_read_hash(name, len, qlen); }

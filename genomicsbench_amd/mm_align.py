@@ -5,19 +5,18 @@ text with ``cg:Z:``.
 itself.  All arithmetic in libgbx.so on the GPU.
 """
 import ctypes as C
-import os
 
 import numpy as np
 
 from . import _native as N
 from . import mm_map as MM
-from . import mm_seed as MS
+from . import mm_stage as ST
+from .mm_stage import TAG_ROOM, c as _c, pad as _pad, twin as _twin      # noqa: F401  (TAG_ROOM: part of this module's interface)
 
 ALN_DTYPE = np.dtype([(k, "<i4") for k in ("rs", "re", "qs", "qe", "mlen", "blen", "n_ambi", "nm", "dp_score", "dp_max", "n_cigar", "flags")] +
                      [("cigar_off", "<i8")])
 assert ALN_DTYPE.itemsize == 56                              # sizeof(gbx_mm_aln)
 ALIGNED, ZDROP_L, ZDROP_R, END_L, END_R, NO_ROOM, INVALID = 1, 2, 4, 8, 16, 32, 64
-TAG_ROOM = 96                                                # the bytes the tags NM ms AS nn and cg:Z: add to a line, at most
 
 
 class MmAlignParams(C.Structure):
@@ -51,17 +50,9 @@ def check_params(p):
     N.check(lib().gbx_mm_align_check_params(C.byref(p)))
 
 
-def _c(a, dt):
-    return np.ascontiguousarray(a, dtype=dt)
-
-
-def _pad(a):
-    return a if len(a) else np.zeros(1, a.dtype)
-
-
 def _inputs(regs, reg_off, off, cax, cay, n_chained, reads, refs):
-    seq, seq_off = MS.pack_seqs(reads)
-    tseq, tseq_off = MS.pack_seqs(refs)
+    seq, seq_off = ST.pack_seqs(reads)
+    tseq, tseq_off = ST.pack_seqs(refs)
     return (_c(regs, MM.REG_DTYPE), _c(reg_off, np.int64), _c(off, np.int64), _pad(_c(cax, np.uint64)), _pad(_c(cay, np.uint64)),
             _pad(_c(n_chained, np.int32)), _pad(seq), seq_off, _pad(tseq), tseq_off)
 
@@ -94,17 +85,6 @@ def align_host(p, regs, reg_off, off, cax, cay, n_chained, reads, refs, cigar_ca
     return _cut(alns[:nr], cig, cnt)
 
 
-def _twin():
-    T = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "libgbx_mm_cpu.so"))
-    vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int32
-    T.gbx_mm_align_cpu.argtypes = [C.POINTER(MmAlignParams), i64, i64] + [vp] * 6 + [vp, i64, vp, vp, vp, vp, i64, i64, vp]
-    T.gbx_mm_align_cpu_job.argtypes = [C.POINTER(MmAlignParams), vp, i32, vp, i32, i32, C.c_int, C.c_int, vp, vp, i64]
-    T.gbx_mm_align_cpu_job.restype = i64
-    T.gbx_mm_paf_cigar_cpu.argtypes = [i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]
-    T.gbx_mm_paf_cigar_cpu.restype = i64
-    return T
-
-
 def align_cpu(p, regs, reg_off, off, cax, cay, n_chained, reads, refs, cigar_cap=None, z_bytes=None):
     """The same rules compiled for the host (mm_align_rules.h in libgbx_mm_cpu.so), one thread -> the dict align_host gives.
     z_bytes None: room for everything."""
@@ -133,45 +113,26 @@ def job_cpu(p, target, query, w, mode, ext):
     return dict(score=int(out[0]), end_t=int(out[1]), end_q=int(out[2]), flags=int(out[3]), ct=int(out[4]), cq=int(out[5]), cigar=cig[:n])
 
 
-def _paf_inputs(regs, reg_off, alns, cigar, qnames, seq_off, rep_len, tnames, tseq_off):
-    qn, qo = MM.pack_names(qnames)
-    tn, to = MM.pack_names(tnames)
-    return (_c(regs, MM.REG_DTYPE), _c(reg_off, np.int64), _c(alns, ALN_DTYPE), _pad(_c(cigar, np.uint32)), _pad(qn), qo, _c(seq_off, np.int64),
-            _pad(_c(rep_len, np.int32)), _pad(tn), to, _c(tseq_off, np.int64))
-
-
-def _text_cap(alns, cigar, qnames, tnames):
-    return len(alns) * (MM.LINE_ROOM + TAG_ROOM + max([len(s) for s in qnames] + [0]) + max([len(s) for s in tnames] + [1])) + 11 * len(cigar)
-
-
 def paf_cigar_host(regs, reg_off, alns, cigar, qnames, seq_off, rep_len, tnames, tseq_off, text_cap=None):
     """gbx_mm_paf_cigar_host -> (text bytes, line_off)"""
-    g, ro, a, cg, qn, qo, so, rep, tn, to, ts = _paf_inputs(regs, reg_off, alns, cigar, qnames, seq_off, rep_len, tnames, tseq_off)
-    n = len(ro) - 1
-    if text_cap is None:
-        text_cap = _text_cap(a, cigar, qnames, tnames)
-    lines, line_off, nt = np.zeros(max(text_cap, 1), np.uint8), np.zeros(n + 1, np.int64), C.c_int64(0)
-    N.check(lib().gbx_mm_paf_cigar_host(n, N.ptr(g), N.ptr(ro), N.ptr(a), N.ptr(cg), len(cigar), N.ptr(qn), N.ptr(qo), N.ptr(so), N.ptr(rep), len(to) - 1,
-                                        N.ptr(tn), N.ptr(to), N.ptr(ts), N.ptr(lines), text_cap, N.ptr(line_off), C.byref(nt)))
-    return lines[:nt.value].tobytes(), line_off
+    return ST.paf_text(lib().gbx_mm_paf_cigar_host, _c(regs, MM.REG_DTYPE), reg_off, qnames, seq_off, rep_len, tnames, tseq_off, text_cap,
+                       _c(alns, ALN_DTYPE), cigar)
 
 
 def paf_cigar_cpu(regs, reg_off, alns, cigar, qnames, seq_off, rep_len, tnames, tseq_off):
     """the host build of the same line rules -> (text bytes, line_off)"""
-    g, ro, a, cg, qn, qo, so, rep, tn, to, ts = _paf_inputs(regs, reg_off, alns, cigar, qnames, seq_off, rep_len, tnames, tseq_off)
-    n, cap = len(ro) - 1, _text_cap(a, cigar, qnames, tnames)
-    lines, line_off = np.zeros(max(cap, 1), np.uint8), np.zeros(n + 1, np.int64)
-    nt = _twin().gbx_mm_paf_cigar_cpu(n, N.ptr(g), N.ptr(ro), N.ptr(a), N.ptr(cg), len(cigar), N.ptr(qn), N.ptr(qo), N.ptr(so), N.ptr(rep), len(to) - 1, N.ptr(tn),
-                                      N.ptr(to), N.ptr(ts), N.ptr(lines), cap, N.ptr(line_off))
-    return lines[:nt].tobytes(), line_off
+    return ST.paf_text(_twin().gbx_mm_paf_cigar_cpu, _c(regs, MM.REG_DTYPE), reg_off, qnames, seq_off, rep_len, tnames, tseq_off, None,
+                       _c(alns, ALN_DTYPE), cigar, host=False)
 
 
-class DeviceMmAligner:
+class DeviceMmAligner(ST.Fits):
     """The regions of a DeviceMmMapper -> records, CIGAR words and PAF text with cg:Z:, queued behind the mapper on its stream.
     cigar_cap / z_bytes / text_cap None: sized from what the mapper knows once its anchors are counted - a region's words from its
     reads' bases (cigar_cap = the bases of all reads / 2 + 8 a region), z from `z_per_base` bytes a read base (None: two diagonals of bw + 1 cells and the rows), the text from both.
     counts() reports the needs when a capacity was too small.  z is one allocation for the whole read set (about 1 000 bytes a read
     base at the default band): a read set that does not fit the device that way is aligned a batch of reads a mapper."""
+
+    FIT = (("CIGAR words", 1, "cigar_cap"), ("bytes of z", 2, "z_bytes"), ("bytes of text", 3, "text_cap"))      # the jobs (0) have no capacity
 
     def __init__(self, mapper, p=None, cigar_cap=None, z_bytes=None, text_cap=None, z_per_base=None):
         import torch
@@ -190,12 +151,12 @@ class DeviceMmAligner:
         key = (mp.reg_cap, sd.anchor_cap)
         if self.sized_for == key:
             return
-        e = lambda n, dt: torch.empty(max(n, 1), dtype=dt, device=self.device)
+        e = ST.allocator(self.device)
         cc, zb, tc = self.caps
         bases = int(sd.text.numel())
         self.cigar_cap = bases // 2 + 8 * mp.reg_cap if cc is None else int(cc)
         self.z_bytes = (bases * self.z_per_base + 15) & ~15 if zb is None else int(zb)
-        self.text_cap = mp.reg_cap * (MM.LINE_ROOM + TAG_ROOM + mp.name_room) + 11 * self.cigar_cap if tc is None else int(tc)
+        self.text_cap = ST.text_cap(mp.reg_cap, mp.name_room, True, self.cigar_cap) if tc is None else int(tc)
         self.alns = e(mp.reg_cap * ALN_DTYPE.itemsize, torch.uint8)
         self.cigar = e(self.cigar_cap, torch.int32)
         self.z = e(self.z_bytes, torch.uint8)
@@ -231,17 +192,6 @@ class DeviceMmAligner:
     def counts(self):
         """(jobs, CIGAR words, bytes of z, bytes of text) of the last run().  Synchronises."""
         return tuple(int(v) for v in self.cnt.cpu().numpy())
-
-    def fits(self):
-        _, w, z, t = self.counts()
-        return 0 <= w <= self.cigar_cap and 0 <= z <= self.z_bytes and 0 <= t <= self.text_cap
-
-    def _need_fit(self):
-        j, w, z, t = self.counts()
-        if not (0 <= w <= self.cigar_cap and 0 <= z <= self.z_bytes and 0 <= t <= self.text_cap):
-            raise N.GbxError(N.GBX_ERR_ARG, "%d CIGAR words, %d bytes of z and %d bytes of text do not fit cigar_cap = %d, z_bytes = %d, text_cap = %d"
-                             % (w, z, t, self.cigar_cap, self.z_bytes, self.text_cap))
-        return j, w, z, t
 
     def results(self):
         """dict(alns, cigar, line_off) as numpy arrays, cut to the counts"""

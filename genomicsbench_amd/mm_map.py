@@ -8,12 +8,12 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
-from . import mm_seed as MS
+from . import mm_stage as ST
+from .mm_stage import LINE_ROOM, c as _c, pack_seqs as pack_names      # noqa: F401  (LINE_ROOM, pack_names: part of this module's interface)
 
 REG_DTYPE = np.dtype([(k, "<i4") for k in ("id", "parent", "score", "subsc", "cnt", "as", "rid", "rev", "rs", "re", "qs", "qe", "mlen", "blen",
                                            "n_sub", "mapq")] + [("hash", "<u4"), ("read", "<i4")])
 assert REG_DTYPE.itemsize == 72                              # sizeof(gbx_mm_reg)
-LINE_ROOM = 192                                              # the bytes of a PAF line besides its two names, at most
 
 
 class MmMapParams(C.Structure):
@@ -72,10 +72,6 @@ def read_hash(name, qlen):
     return x31(name) ^ ((wang(qlen & 0xffffffff) + wang(11)) & 0xffffffff)
 
 
-def _c(a, dt):
-    return np.ascontiguousarray(a, dtype=dt)
-
-
 def map_host(p, off, ax, ay, score, parent, peak, seq_off, rep_len, hashes, chain_cap=None, reg_cap=None):
     """gbx_mm_map_host -> dict(chain_off, u, cax, cay, n_chained, reg_off, regs, counts).  Capacities None: one per anchor (always enough)."""
     off, seq_off = _c(off, np.int64), _c(seq_off, np.int64)
@@ -99,47 +95,31 @@ def map_host(p, off, ax, ay, score, parent, peak, seq_off, rep_len, hashes, chai
 def map_cpu(p, off, ax, ay, score, parent, peak, seq_off, rep_len, hashes):
     """The same rules compiled for the host (mm_map_rules.h in libgbx_mm_cpu.so), one thread -> the dict map_host gives.  What the
     device is held against where no restatement is at hand (smoke(), scripts/time_mm_map.py)."""
-    import os
-    T = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "libgbx_mm_cpu.so"))
-    T.gbx_mm_map_cpu.argtypes = [C.POINTER(MmMapParams), C.c_int64] + [C.c_void_p] * 17
     off, seq_off = _c(off, np.int64), _c(seq_off, np.int64)
     n, m = len(off) - 1, max(int(off[-1]), 1)
     ins = [_c(ax, np.uint64), _c(ay, np.uint64), _c(score, np.int32), _c(parent, np.int32), _c(peak, np.int32), seq_off, _c(rep_len, np.int32),
            _c(hashes, np.uint32)]
     chain_off, reg_off, cnt = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64), np.zeros(2, np.int64)
     u, cax, cay, nc, regs = np.zeros(m, np.uint64), np.zeros(m, np.uint64), np.zeros(m, np.uint64), np.zeros(max(n, 1), np.int32), np.zeros(m, REG_DTYPE)
-    T.gbx_mm_map_cpu(C.byref(p), n, N.ptr(off), *[N.ptr(a) for a in ins], N.ptr(chain_off), N.ptr(u), N.ptr(cax), N.ptr(cay), N.ptr(nc), N.ptr(reg_off),
-                     N.ptr(regs), N.ptr(cnt))
+    ST.twin().gbx_mm_map_cpu(C.byref(p), n, N.ptr(off), *[N.ptr(a) for a in ins], N.ptr(chain_off), N.ptr(u), N.ptr(cax), N.ptr(cay), N.ptr(nc),
+                             N.ptr(reg_off), N.ptr(regs), N.ptr(cnt))
     return dict(chain_off=chain_off, u=u[:cnt[0]], cax=cax[:int(off[-1])], cay=cay[:int(off[-1])], n_chained=nc[:n], reg_off=reg_off, regs=regs[:cnt[1]],
                 counts=(int(cnt[0]), int(cnt[1])))
 
 
-def pack_names(names):
-    """[str or bytes] -> (uint8 arena, int64 offsets)"""
-    return MS.pack_seqs(names)
-
-
 def paf_host(regs, reg_off, qnames, seq_off, rep_len, tnames, tseq_off, text_cap=None):
     """gbx_mm_paf_host -> (text bytes, line_off)"""
-    regs, reg_off = _c(regs, REG_DTYPE), _c(reg_off, np.int64)
-    n = len(reg_off) - 1
-    qn, qo = pack_names(qnames)
-    tn, to = pack_names(tnames)
-    seq_off, tseq_off, rep = _c(seq_off, np.int64), _c(tseq_off, np.int64), _c(rep_len, np.int32)
-    if text_cap is None:
-        text_cap = len(regs) * (LINE_ROOM + max([len(s) for s in qnames] + [0]) + max([len(s) for s in tnames] + [1]))
-    lines, line_off, nt = np.zeros(max(text_cap, 1), np.uint8), np.zeros(n + 1, np.int64), C.c_int64(0)
-    N.check(lib().gbx_mm_paf_host(n, N.ptr(regs), N.ptr(reg_off), N.ptr(qn), N.ptr(qo), N.ptr(seq_off), N.ptr(rep), len(to) - 1, N.ptr(tn), N.ptr(to),
-                                  N.ptr(tseq_off), N.ptr(lines), text_cap, N.ptr(line_off), C.byref(nt)))
-    return lines[:nt.value].tobytes(), line_off
+    return ST.paf_text(lib().gbx_mm_paf_host, _c(regs, REG_DTYPE), reg_off, qnames, seq_off, rep_len, tnames, tseq_off, text_cap)
 
 
-class DeviceMmMapper:
+class DeviceMmMapper(ST.Fits):
     """Reads -> PAF on one stream.  seeder: a DeviceMmSeeder (its index names the targets); read_names / ref_names default to
     read<i> / ref<i>.  chain_cap / reg_cap / text_cap None: sized from the anchor count (a kept chain has min_cnt anchors of its
     own), which run() reads for gbx_chain_device anyway; counts() reports the need when a given capacity was too small.
     align: True or a gbx_mm_align_params (mm_align.make_params) - run() then queues seed -> chain -> map -> align -> PAF with
     CIGAR (`minimap2 -c`), results() also gives alns and cigar, and self.aligner is the DeviceMmAligner with its own counts()."""
+
+    FIT = (("chains", 0, "chain_cap"), ("regions", 1, "reg_cap"), ("bytes of text", 2, "text_cap"))
 
     def __init__(self, seeder, p=None, read_names=None, ref_names=None, chain_cap=None, reg_cap=None, text_cap=None, align=None):
         import torch
@@ -153,11 +133,11 @@ class DeviceMmMapper:
         t = lambda a: torch.from_numpy(a).to(self.device)
         qn, qo = pack_names(self.read_names)
         tn, to = pack_names(self.ref_names)
-        pad = lambda a: a if len(a) else np.zeros(1, a.dtype)
+        pad = ST.pad
         self.qnames, self.qname_off, self.tnames, self.tname_off = t(pad(qn)), t(qo), t(pad(tn)), t(to)
         qlen = np.diff(sd.seq_off.cpu().numpy())
         self.hash = t(pad(np.array([read_hash(nm, int(ln)) for nm, ln in zip(self.read_names, qlen)], np.uint32).view(np.int32)))
-        self.name_room = max([len(s) for s in self.read_names] + [0]) + max([len(s) for s in self.ref_names] + [1])
+        self.name_room = ST.name_room(self.read_names, self.ref_names)
         self.caps = (chain_cap, reg_cap, text_cap)
         self.chain_off = torch.zeros(sd.n_reads + 1, dtype=torch.int64, device=self.device)
         self.reg_off = torch.zeros(sd.n_reads + 1, dtype=torch.int64, device=self.device)
@@ -176,11 +156,11 @@ class DeviceMmMapper:
         if self.sized_for == n_anchors:
             return
         sd, L = self.seeder, lib()
-        e = lambda n, dt: torch.empty(max(n, 1), dtype=dt, device=self.device)
+        e = ST.allocator(self.device)
         cc, rc, tc = self.caps
         self.chain_cap = max(n_anchors // self.p.min_cnt, 1) if cc is None else int(cc)
         self.reg_cap = self.chain_cap if rc is None else int(rc)
-        self.text_cap = self.reg_cap * (LINE_ROOM + self.name_room) if tc is None else int(tc)
+        self.text_cap = ST.text_cap(self.reg_cap, self.name_room) if tc is None else int(tc)
         self.u = e(self.chain_cap, torch.int64)
         self.cax, self.cay = e(sd.anchor_cap, torch.int64), e(sd.anchor_cap, torch.int64)
         self.regs = e(self.reg_cap * REG_DTYPE.itemsize, torch.uint8)
@@ -225,17 +205,6 @@ class DeviceMmMapper:
     def counts(self):
         """(chains, regions, bytes of text) of the last run(); regions -1 when the chains did not fit.  Synchronises."""
         return tuple(int(v) for v in self.cnt.cpu().numpy())
-
-    def fits(self):
-        c, r, t = self.counts()
-        return 0 <= c <= self.chain_cap and 0 <= r <= self.reg_cap and 0 <= t <= self.text_cap
-
-    def _need_fit(self):
-        c, r, t = self.counts()
-        if not (0 <= c <= self.chain_cap and 0 <= r <= self.reg_cap and 0 <= t <= self.text_cap):
-            raise N.GbxError(N.GBX_ERR_ARG, "%d chains, %d regions and %d bytes of text do not fit chain_cap = %d, reg_cap = %d, text_cap = %d"
-                             % (c, r, t, self.chain_cap, self.reg_cap, self.text_cap))
-        return c, r, t
 
     def results(self):
         """dict of numpy arrays, cut to the counts"""

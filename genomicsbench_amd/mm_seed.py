@@ -9,6 +9,8 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
+from . import mm_stage as ST
+from .mm_stage import pack_seqs                             # noqa: F401  (part of this module's interface)
 
 SKETCH_CHUNK = 256                       # GBX_MM_SKETCH_CHUNK
 SEED_TANDEM = 1 << 42
@@ -57,14 +59,6 @@ def make_params(**kw):
 
 def check_params(p):
     N.check(lib().gbx_mm_check_params(C.byref(p)))
-
-
-def pack_seqs(seqs):
-    """[bytes or str] -> (uint8 text, int64 offsets)"""
-    bs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
-    off = np.zeros(len(bs) + 1, dtype=np.int64)
-    np.cumsum([len(b) for b in bs], out=off[1:])
-    return np.frombuffer(b"".join(bs), dtype=np.uint8).copy(), off
 
 
 def sketch_host(p, seqs, rid_ordinal=True, mini_cap=None):
@@ -130,9 +124,11 @@ class DeviceMmIndex:
                 b[o_vals:o_vals + nv * 8].view(np.uint64).copy())
 
 
-class DeviceMmSeeder:
+class DeviceMmSeeder(ST.Fits):
     """Reads resident in HBM and everything a seeding call leaves there.  mini_cap / anchor_cap None: a minimizer per base, and
     anchors sized by `anchors_per_mini` of them; counts() reports the need when a capacity was too small."""
+
+    FIT = (("minimizers", 0, "mini_cap"), ("anchors", 1, "anchor_cap"))
 
     def __init__(self, index, reads, device=None, mini_cap=None, anchor_cap=None, anchors_per_mini=4):
         import torch
@@ -145,7 +141,7 @@ class DeviceMmSeeder:
         self.mini_cap = max(self.total_len, 1) if mini_cap is None else int(mini_cap)
         self.anchor_cap = max(self.mini_cap * anchors_per_mini, 1) if anchor_cap is None else int(anchor_cap)
         self.text, self.seq_off = torch.from_numpy(text).to(device), torch.from_numpy(off).to(device)
-        e = lambda n, dt: torch.empty(max(n, 1), dtype=dt, device=device)
+        e = ST.allocator(device)
         self.mini_x, self.mini_y = e(self.mini_cap, torch.int64), e(self.mini_cap, torch.int64)
         self.mini_off = torch.zeros(self.n_reads + 1, dtype=torch.int64, device=device)
         self.ax, self.ay = e(self.anchor_cap, torch.int64), e(self.anchor_cap, torch.int64)
@@ -169,16 +165,10 @@ class DeviceMmSeeder:
         c = self.cnt.cpu().numpy()
         return int(c[0]), int(c[1])
 
-    def fits(self):
-        m, a = self.counts()
-        return 0 <= m <= self.mini_cap and 0 <= a <= self.anchor_cap
-
     def chain_batch(self):
         """The calls of the last run() as a DeviceChainBatch over the same tensors (no copy).  Reads the anchor count."""
         from .chain import DeviceChainBatch
-        m, a = self.counts()
-        if not (0 <= m <= self.mini_cap and 0 <= a <= self.anchor_cap):
-            raise N.GbxError(N.GBX_ERR_ARG, "%d minimizers and %d anchors do not fit mini_cap = %d, anchor_cap = %d" % (m, a, self.mini_cap, self.anchor_cap))
+        self._need_fit()
         return DeviceChainBatch.from_tensors(dict(off=self.off, ax=self.ax, ay=self.ay, hdr=self.hdr), self.device)
 
     def results(self):

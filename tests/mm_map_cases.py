@@ -146,3 +146,48 @@ def map_case():
     assert (g["subsc"][pri] > 0).any() and len(set(g["mapq"][pri].tolist())) >= 2
     text = MR.paf(g, ro, qnames, qlen, tnames, [len(r) for r in refs], seeds["rep_len"])
     return dict(refs=refs, reads=reads, qnames=qnames, tnames=tnames, seeds=seeds, batch=batch, exp=exp, paf=text)
+
+
+def device_paf(regs, reg_off, qnames, seq_off, rep_len, tnames, tseq_off, reg_cap, text_cap, alns=None, cigar=None):
+    """gbx_mm_paf_device - with alns gbx_mm_paf_cigar_device - on host arrays: room for reg_cap regions (and records), what lies behind
+    the count filled with 0x5a, the text in front of guard bytes -> dict(text: the bytes below text_cap, n_text, line_off, intact:
+    nothing behind text_cap was touched)"""
+    import ctypes as C
+    import torch
+    from genomicsbench_amd import _native as N
+    from genomicsbench_amd import mm_align as MA
+    from genomicsbench_amd import mm_map as MM
+    d = torch.device("cuda:0")
+    n, nr = len(reg_off) - 1, len(regs)
+    assert nr <= reg_cap
+
+    def t(a, dt, room=0):
+        buf = np.full(max(room * np.dtype(dt).itemsize, np.dtype(dt).itemsize, len(a) * np.dtype(dt).itemsize), 0x5a, np.uint8)
+        raw = np.ascontiguousarray(a, dtype=dt).view(np.uint8)
+        buf[:len(raw)] = raw
+        return torch.from_numpy(buf).to(d)
+    qn, qo = MM.pack_names(qnames)
+    tn, to = MM.pack_names(tnames)
+    keep = [t(regs, MM.REG_DTYPE, reg_cap), t(reg_off, np.int64), t([nr], np.int64), t(qn, np.uint8), t(qo, np.int64), t(seq_off, np.int64),
+            t(rep_len, np.int32), t(tn, np.uint8), t(to, np.int64), t(tseq_off, np.int64)]
+    g, ro, n_regs, qn, qo, so, rep, tn, to_, tso = [x.data_ptr() for x in keep]
+    room = 64
+    out = torch.full((text_cap + room,), 0x5a, dtype=torch.uint8, device=d)
+    lo, nt = torch.full((n + 1,), -7, dtype=torch.int64, device=d), torch.full((1,), -7, dtype=torch.int64, device=d)
+    s = torch.cuda.current_stream().cuda_stream
+    if alns is None:
+        L = MM.lib()
+        wb = L.gbx_mm_paf_workspace_bytes(n, reg_cap)
+        work = torch.empty(max(wb, 1), dtype=torch.uint8, device=d)
+        N.check(L.gbx_mm_paf_device(n, g, ro, n_regs, reg_cap, qn, qo, so, rep, len(tnames), tn, to_, tso, out.data_ptr(), text_cap, lo.data_ptr(),
+                                    nt.data_ptr(), work.data_ptr(), wb, s))
+    else:
+        L = MA.lib()
+        wb = L.gbx_mm_paf_cigar_workspace_bytes(n, reg_cap)
+        work = torch.empty(max(wb, 1), dtype=torch.uint8, device=d)
+        ta, tc = t(alns, MA.ALN_DTYPE, reg_cap), t(cigar, np.uint32)
+        N.check(L.gbx_mm_paf_cigar_device(n, g, ro, n_regs, reg_cap, ta.data_ptr(), tc.data_ptr(), len(cigar), qn, qo, so, rep, len(tnames), tn, to_, tso,
+                                          out.data_ptr(), text_cap, lo.data_ptr(), nt.data_ptr(), work.data_ptr(), wb, s))
+    torch.cuda.synchronize()
+    o = out.cpu().numpy()
+    return dict(text=o[:text_cap].tobytes(), n_text=int(nt.item()), line_off=lo.cpu().numpy(), intact=bool((o[text_cap:] == 0x5a).all()))

@@ -212,6 +212,19 @@ def test_paf_with_cigar_text():
     assert one[12].startswith("NM:i:") and one[13].startswith("ms:i:") and one[14].startswith("AS:i:") and one[15].startswith("nn:i:") and one[16] == "tp:A:P"
 
 
+def test_paf_cigar_text_without_alignments_is_the_plain_text():
+    """one line rule behind both entries of the host build: gbx_mm_paf_cigar_cpu on records with their flags cleared gives what
+    gbx_mm_paf_cpu gives, which is the restatement's plain text"""
+    from genomicsbench_amd import mm_stage as ST
+    g, ro, alns, cig, qn, so, rep, tn, to, _ = AK.paf_case()
+    cleared = alns.copy()
+    cleared["flags"] = 0
+    got, line_off = MA.paf_cigar_cpu(g, ro, cleared, cig, qn, so, rep, tn, to)
+    plain, plain_off = ST.paf_text(ST.twin().gbx_mm_paf_cpu, g, ro, qn, so, rep, tn, to, host=False)
+    want = AR.paf_cigar([{k: int(r[k]) for k in AK.REG_KEYS} for r in g], ro, cleared, cig, qn, np.diff(so), tn, np.diff(to), rep)      # rule 9: not aligned
+    assert got == plain and plain.decode() == want and np.array_equal(line_off, plain_off) and want.count("\n") == len(g)
+
+
 def test_golden_example():
     """The frozen worked example: a forward and a reverse region, each with a left extension, two fills and a right extension; one
     fill holds a 25-base deletion, which the second gap piece pays for (24 + 25 = 49 against 4 + 50)."""

@@ -177,6 +177,46 @@ def test_paf_with_cigar_host():
     assert e.value.code == N.GBX_ERR_ARG and str(len(text)) in str(e.value)
 
 
+def _paf_device(alns=None, cigar=None, n_reads=None, **kw):
+    """both device entries on the composed regions of paf_case(): alns None is gbx_mm_paf_device"""
+    g, ro, _, _, qn, so, rep, tn, to, text = AK.paf_case()
+    return MK.device_paf(g, ro, qn, so, rep, tn, to, kw.get("reg_cap", len(g)), kw.get("text_cap", len(text) + 64), alns, cigar)
+
+
+def test_paf_one_stage_two_modes():
+    """The cigar entry on records with their flags cleared prints the plain entry's text; with every second record marked NO_ROOM those
+    regions print plain lines and the rest cg:Z: lines, as the host build of the rule and the restatement do"""
+    g, ro, alns, cig, qn, so, rep, tn, to, text = AK.paf_case()
+    qlen, tlen = np.diff(so), np.diff(to)
+    cleared = alns.copy()
+    cleared["flags"] = 0
+    plain = AR.paf_cigar([{k: int(r[k]) for k in AK.REG_KEYS} for r in g], ro, cleared, cig, qn, qlen, tn, tlen, rep)
+    assert "cg:Z:" not in plain and plain.count("\n") == len(g)
+    a, b = _paf_device(), _paf_device(cleared, cig)
+    assert a["intact"] and b["intact"] and a["n_text"] == b["n_text"] == len(plain)
+    assert a["text"][:len(plain)].decode() == plain and b["text"] == a["text"] and np.array_equal(a["line_off"], b["line_off"])
+    mixed = alns.copy()
+    mixed["flags"][1::2] |= MA.NO_ROOM
+    want = AR.paf_cigar([{k: int(r[k]) for k in AK.REG_KEYS} for r in g], ro, mixed, cig, qn, qlen, tn, tlen, rep)
+    n_cg = sum(1 for i, r in enumerate(alns) if i % 2 == 0 and r["flags"] & MA.ALIGNED and not r["flags"] & (MA.NO_ROOM | MA.INVALID))
+    assert 0 < n_cg == want.count("cg:Z:") < text.count("cg:Z:")
+    got = _paf_device(mixed, cig)
+    cpu, cpu_off = MA.paf_cigar_cpu(g, ro, mixed, cig, qn, so, rep, tn, to)
+    assert got["intact"] and got["n_text"] == len(want) and got["text"][:len(want)].decode() == want == cpu.decode()
+    assert np.array_equal(got["line_off"], cpu_off)
+
+
+@pytest.mark.parametrize("with_alns", [False, True], ids=["plain", "cigar"])
+def test_paf_device_without_reads_or_room(with_alns):
+    """no reads, and reads with room for no region: GBX_OK, no text, line_off all 0 - through both device entries"""
+    g, ro, alns, cig, qn, so, rep, tn, to, _ = AK.paf_case()
+    al = dict(alns=alns[:0], cigar=cig[:0]) if with_alns else {}
+    got = MK.device_paf(g[:0], [0], [], [0], rep[:0], tn, to, 0, 0, **al)
+    assert got["n_text"] == 0 and got["line_off"].tolist() == [0] and got["intact"]
+    got = MK.device_paf(g[:0], np.zeros(len(ro), np.int64), qn, so, rep, tn, to, 0, 0, **al)
+    assert got["n_text"] == 0 and not got["line_off"].any() and got["intact"]
+
+
 @pytest.fixture(scope="module")
 def mapper():
     c = MK.map_case()

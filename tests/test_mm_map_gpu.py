@@ -2,6 +2,7 @@
 included, every order and count - with the restatement tests/mm_map_ref.py; the capacities; then reads -> PAF on one stream
 (DeviceMmMapper) against the restatement of everything, and the mmpaf driver."""
 import ctypes as C
+import functools
 import os
 import subprocess
 
@@ -243,3 +244,63 @@ def test_mmpaf_driver(tmp_path):
     assert open(out).read() == c["paf"]
     r = subprocess.run([os.path.join(BIN, "mmpaf"), "--mid-occ", "20", "-N", "0", str(fa), str(fq)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "tp:A:S" not in r.stdout and r.stdout.count("\n") == int((c["exp"]["regs"]["parent"] == c["exp"]["regs"]["id"]).sum())
+
+
+# ------------------------------------------------------------------------------------------------ the scans' block edges
+SCAN_BLOCK = 1024                                            # the entries a block of the scan takes (the threads of the one-block scan)
+
+
+@functools.lru_cache(maxsize=None)
+def padded_forests(n_reads):
+    """The forest batch among empty reads (no anchors), n_reads in all: four real reads in front, eight up to the last but one - across
+    entry 1024 of the offsets where n_reads reaches it - and one last.  -> (batch, the restatement's answer on it)"""
+    b = MK.forest_batch()
+    k = len(b["off"]) - 1
+    pos = np.array(list(range(4)) + list(range(n_reads - 1 - (k - 5), n_reads - 1)) + [n_reads - 1])
+    assert len(pos) == k and (np.diff(pos) > 0).all() and pos[-1] == n_reads - 1
+
+    def spread(per_read, fill, dt):
+        out = np.full(n_reads, fill, dt)
+        out[pos] = per_read
+        return out
+    offs = lambda per_read: np.concatenate([[0], np.cumsum(per_read)]).astype(np.int64)
+    pb = dict(b, off=offs(spread(np.diff(b["off"]), 0, np.int64)), qlen=spread(b["qlen"], 100, np.int64), rep_len=spread(b["rep_len"], 0, np.int32),
+              hash=spread(b["hash"], 0, np.uint32))
+    pb["seq_off"] = offs(pb["qlen"])
+    want = MK.expected(pb, min_chain_score=40, min_cnt=3)
+    flat = MK.forest_expected(40, 3)                              # the padding shifts the offsets and the regions' reads, nothing else
+    assert np.array_equal(want["u"], flat["u"]) and np.array_equal(want["regs"]["read"], pos[flat["regs"]["read"]])
+    assert np.array_equal(np.diff(want["reg_off"])[pos], np.diff(flat["reg_off"])) and want["reg_off"][-1] == flat["reg_off"][-1]
+    return pb, want
+
+
+@pytest.mark.parametrize("n_reads", [SCAN_BLOCK - 1, SCAN_BLOCK, SCAN_BLOCK + 1])
+def test_map_scans_at_the_block_edge(n_reads):
+    """chain_off and reg_off of n_reads + 1 entries fill a scan block exactly, pass it by one and by two: both scans, u, the regions and
+    both counts equal the restatement's shifted by the padding; at 1 025 reads a chain_cap one short still means no regions"""
+    b, want = padded_forests(n_reads)
+    got = device_map(b, MM.make_params())
+    assert got["intact"] and got["counts"] == (len(want["u"]), len(want["regs"]["id"]))
+    same(got, want, b)
+    if n_reads == SCAN_BLOCK + 1:
+        short = device_map(b, MM.make_params(), chain_cap=len(want["u"]) - 1)
+        assert short["intact"] and short["counts"] == (len(want["u"]), -1) and np.array_equal(short["chain_off"], want["chain_off"])
+        assert not short["reg_off"].any() and short["reg_off"].shape == (n_reads + 1,)
+
+
+@pytest.mark.parametrize("reg_cap", [None, SCAN_BLOCK, SCAN_BLOCK + 1], ids=["need", "1024", "1025"])
+def test_paf_device_scan_at_the_block_edge(reg_cap):
+    """gbx_mm_paf_device with room for more regions than there are, up to and past a scan block: the recorded text byte for byte,
+    n_text and line_off true, nothing behind text_cap"""
+    c = MK.map_case()
+    e = c["exp"]
+    regs = np.zeros(len(e["regs"]["id"]), MM.REG_DTYPE)
+    for k in MR.REG_FIELDS:
+        regs[k] = e["regs"][k]
+    assert 0 < len(regs) < SCAN_BLOCK
+    text = c["paf"].encode()
+    ends = np.concatenate([[0], np.cumsum([len(ln) + 1 for ln in c["paf"].split("\n")[:-1]])])
+    got = MK.device_paf(regs, e["reg_off"], c["qnames"], c["batch"]["seq_off"], c["batch"]["rep_len"], c["tnames"], _tseq_off(c["refs"]),
+                        len(regs) if reg_cap is None else reg_cap, len(text))
+    assert got["n_text"] == len(text) and got["text"] == text and got["intact"]
+    assert np.array_equal(got["line_off"], ends[e["reg_off"]])
