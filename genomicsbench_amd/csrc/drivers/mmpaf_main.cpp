@@ -1,5 +1,6 @@
-// mmpaf — long reads to PAF, as `minimap2 -x map-ont` prints it: without -c approximate mappings, with -c the base-level alignment
-// of every mapping (CIGAR in cg:Z:, NM, ms, AS, nn).  A reference FASTA and reads (FASTA / FASTQ) in, one PAF line per mapping out.
+// mmpaf — long reads to PAF or SAM, as `minimap2 -x map-ont` prints it: without -c approximate mappings, with -c the base-level
+// alignment of every mapping (CIGAR in cg:Z:, NM, ms, AS, nn), with -a SAM records.  A reference FASTA and reads (FASTA / FASTQ)
+// in, one PAF line per mapping or one SAM record per alignment out.
 //   mmpaf [options] <ref.fa> <reads.fa|fq> > out.paf
 //     -k INT  k-mer size (15)            -w INT  window (10)               -H  homopolymer-compressed k-mers
 //     -f FLOAT  mid_occ_frac (2e-4)      --mid-occ INT  the threshold itself (0: from -f)
@@ -10,9 +11,12 @@
 //         extension (2,1)  -z INT z-drop (400)  --end-bonus INT (0)  --min-ksw-len INT (200)  --max-ext INT (5000); -r is its band too
 //         all reads are aligned in one call, which takes about 2 (r + 1) bytes of device memory a read base: split a read file
 //         that does not fit
+//     -a  SAM output (implies -c): a header (@HD, one @SQ a contig, @PG) and one record per aligned mapping, unmapped reads with
+//         flag 4, the FASTQ qualities handed through;  -Y  soft clips on supplementary and secondary records
+//     --cs[=short|long]  the cs:Z: tag    --MD  the MD:Z: tag    --eqx  = / X in place of M  (each needs -c or -a)
 // Index, seeds, chain scores, chains, regions, mapq, alignments and the text are all made on the device (gbx_mm_index_build_host,
-// gbx_mm_seed_host, gbx_chain_host, gbx_mm_map_host, gbx_mm_align_host, gbx_mm_paf_host / gbx_mm_paf_cigar_host); this file
-// parses, hashes the read names and prints.
+// gbx_mm_seed_host, gbx_chain_host, gbx_mm_map_host, gbx_mm_align_host, gbx_mm_paf_host / gbx_mm_paf_cigar_host / gbx_mm_sam_host);
+// this file parses, hashes the read names and prints.
 #include "driver_common.h"
 #include <algorithm>
 #include "seq_reader.h"
@@ -23,12 +27,13 @@ int usage(FILE *f, int rc)
 {
     fprintf(f, "usage: mmpaf [-k INT] [-w INT] [-H] [-f FLOAT] [--mid-occ INT] [-g INT] [-r INT] [-n INT] [-m INT] [-M FLOAT] [-p FLOAT] [-N INT]\n"
                "             [-c [-A INT] [-B INT] [-O INT,INT] [-E INT,INT] [-z INT] [--end-bonus INT] [--min-ksw-len INT] [--max-ext INT]]\n"
+               "             [-a [-Y]] [--cs[=short|long]] [--MD] [--eqx]\n"
                "             [-o out.paf] <ref.fa> <reads.fa|fq>\n");
     return rc;
 }
 
 struct Seqs {
-    std::vector<uint8_t> text, names;
+    std::vector<uint8_t> text, names, qual;            // qual: on the offsets of text, when every record brought qualities
     std::vector<int64_t> off, name_off;
     int64_t n() const { return (int64_t)off.size() - 1; }
 };
@@ -44,6 +49,7 @@ bool read_seqs(const char *path, Seqs &s)
     int rc;
     while ((rc = rd.next(r)) == 1) {
         for (size_t k = r.seq0; k < r.seq1; ++k) s.text.insert(s.text.end(), rd.line[k], rd.line[k] + rd.llen[k]);
+        if (r.qual) s.qual.insert(s.qual.end(), r.qual, r.qual + r.len);
         s.off.push_back((int64_t)s.text.size());
         int len = 0;
         while (len < r.head_len && r.head[len] != ' ' && r.head[len] != '\t') ++len;
@@ -51,6 +57,7 @@ bool read_seqs(const char *path, Seqs &s)
         s.name_off.push_back((int64_t)s.names.size());
     }
     if (rc < 0) { fprintf(stderr, "%s: malformed record %zu\n", path, s.off.size()); return false; }
+    if (s.qual.size() != s.text.size()) s.qual.clear();
     return true;
 }
 
@@ -98,8 +105,11 @@ int main(int argc, char **argv)
     gbx_mm_map_default_params(&mp);
     gbx_mm_align_params ap;
     gbx_mm_align_default_params(&ap);
+    gbx_mm_sam_params sp;
+    gbx_mm_sam_default_params(&sp);
     bool cigar = false;
     const char *align_opt = nullptr;                                   // the first option that only means something with -c
+    const char *tag_opt = nullptr;                                     // the first option that needs -c or -a
     const char *out_path = nullptr;
     std::vector<const char *> files;
     for (int i = 1; i < argc; ++i) {
@@ -121,6 +131,13 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "-M")) fp = &mp.mask_level;
         else if (!strcmp(a, "-p")) fp = &mp.pri_ratio;
         else if (!strcmp(a, "-c")) cigar = true;
+        else if (!strcmp(a, "-a")) { sp.format = 1; cigar = true; }
+        else if (!strcmp(a, "-Y")) sp.softclip = 1;
+        else if (!strcmp(a, "--cs") || !strcmp(a, "--cs=short")) { sp.cs = 1; if (!tag_opt) tag_opt = a; }
+        else if (!strcmp(a, "--cs=long")) { sp.cs = 2; if (!tag_opt) tag_opt = a; }
+        else if (!strncmp(a, "--cs=", 5)) { fprintf(stderr, "mmpaf: --cs takes short or long\n"); return usage(stderr, 1); }
+        else if (!strcmp(a, "--MD")) { sp.md = 1; if (!tag_opt) tag_opt = a; }
+        else if (!strcmp(a, "--eqx")) { sp.eqx = 1; if (!tag_opt) tag_opt = a; }
         else if (!strcmp(a, "-A")) ip = &ap.a;
         else if (!strcmp(a, "-B")) ip = &ap.b;
         else if (!strcmp(a, "-z")) ip = &ap.zdrop;
@@ -149,6 +166,9 @@ int main(int argc, char **argv)
     }
     if (files.size() != 2) { fprintf(stderr, "mmpaf: a reference and a read file\n"); return usage(stderr, 1); }
     if (align_opt && !cigar) { fprintf(stderr, "mmpaf: %s needs -c\n", align_opt); return usage(stderr, 1); }
+    if (tag_opt && !cigar) { fprintf(stderr, "mmpaf: %s needs -c or -a\n", tag_opt); return usage(stderr, 1); }
+    if (sp.softclip && !sp.format) { fprintf(stderr, "mmpaf: -Y needs -a\n"); return usage(stderr, 1); }
+    const bool sam_stage = sp.format || sp.cs || sp.md || sp.eqx;      // without a new option the text comes from the entries it came from before
     ap.bw = p.bw;
     if (gbx_mm_check_params(&p) || gbx_mm_map_check_params(&mp) || (cigar && gbx_mm_align_check_params(&ap))) return fail();
     mp.min_diff = 2 * p.k;
@@ -222,7 +242,12 @@ int main(int argc, char **argv)
         if (rc) return fail();
     }
     const double t4a = now_s();
+    int64_t sc[2] = {0, 0};
     auto paf = [&](uint8_t *lines, int64_t cap) {
+        if (sam_stage)
+            return gbx_mm_sam_host(&sp, n_reads, regs.data(), reg_off.data(), alns.data(), cig.data(), ac[1], rd.names.data(), rd.name_off.data(), rd.text.data(),
+                                   rd.qual.empty() ? nullptr : rd.qual.data(), rd.off.data(), rep.data(), n_ref, ref.names.data(), ref.name_off.data(),
+                                   ref.text.data(), ref.off.data(), lines, cap, line_off.data(), &n_text, sc);
         return cigar ? gbx_mm_paf_cigar_host(n_reads, regs.data(), reg_off.data(), alns.data(), cig.data(), ac[1], rd.names.data(), rd.name_off.data(),
                                              rd.off.data(), rep.data(), n_ref, ref.names.data(), ref.name_off.data(), ref.off.data(), lines, cap,
                                              line_off.data(), &n_text)
@@ -243,6 +268,15 @@ int main(int argc, char **argv)
 
     FILE *fo = out_path ? fopen(out_path, "w") : stdout;
     if (!fo) { fprintf(stderr, "mmpaf: cannot write %s\n", out_path); return 1; }
+    if (sp.format) {
+        fprintf(fo, "@HD\tVN:1.6\tSO:unsorted\tGO:query\n");
+        for (int64_t s = 0; s < n_ref; ++s)
+            fprintf(fo, "@SQ\tSN:%.*s\tLN:%lld\n", (int)(ref.name_off[(size_t)s + 1] - ref.name_off[(size_t)s]), (const char *)ref.names.data() + ref.name_off[(size_t)s],
+                    (long long)(ref.off[(size_t)s + 1] - ref.off[(size_t)s]));
+        fprintf(fo, "@PG\tID:mmpaf\tPN:mmpaf\tCL:mmpaf");
+        for (int i = 1; i < argc; ++i) fprintf(fo, " %s", argv[i]);
+        fprintf(fo, "\n");
+    }
     if (n_text && fwrite(text.data(), 1, (size_t)n_text, fo) != (size_t)n_text) { fprintf(stderr, "mmpaf: cannot write the output\n"); return 1; }
     if (fo != stdout && fclose(fo)) { fprintf(stderr, "mmpaf: cannot write %s\n", out_path); return 1; }
     return 0;

@@ -358,6 +358,15 @@ struct MmAlignIo {                   // the device arguments of gbx_mm_align_dev
 size_t mm_align_workspace_bytes(int64_t n_reads, int64_t reg_cap, int64_t anchor_cap);
 int mm_align_launch(const gbx_mm_align_params *p, const MmAlignIo &io, void *d_work, size_t work_bytes, hipStream_t s);
 
+// ---- SAM records, cs / MD and = / X of the aligned regions (mm_sam_kernels.hip; the rules: mm_sam_rules.h)
+struct MmSamIo {                     // the device arguments of gbx_mm_sam_device: gbx_mm_paf_cigar_device's and the texts
+    MmPafIo paf;
+    const uint8_t *seq, *qual, *tseq;
+    int64_t *counts;
+};
+size_t mm_sam_workspace_bytes(int64_t n_reads, int64_t reg_cap);
+int mm_sam_launch(const gbx_mm_sam_params *p, const MmSamIo &io, void *d_work, size_t work_bytes, hipStream_t s);
+
 // ---- the aligner's gather behind the chain (mem_align_kernels.hip): every stage's count into one record
 struct MemAlignGather {              // a null pointer: the stage does not run, its count is 0
     const unsigned long long *fmi_counters;         // the fmi workspace: [2] is the slot overflow word fmi_read_overflow reads

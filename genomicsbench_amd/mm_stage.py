@@ -1,4 +1,4 @@
-"""What the long-read stage modules (mm_seed, mm_map, mm_align) share: array marshalling, the device allocator, the sizing of a
+"""What the long-read stage modules (mm_seed, mm_map, mm_align, mm_sam) share: array marshalling, the device allocator, the sizing of a
 PAF text, the host build of the rules (libgbx_mm_cpu.so) and the fits() / _need_fit() pair of the stage classes."""
 import ctypes as C
 import functools
@@ -58,6 +58,10 @@ def twin():
     T.gbx_mm_align_cpu_job.restype = i64
     T.gbx_mm_paf_cigar_cpu.argtypes = [i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]
     T.gbx_mm_paf_cigar_cpu.restype = i64
+    T.gbx_mm_sam_cpu.argtypes = [vp, i64] + [vp] * 4 + [i64] + [vp] * 6 + [i64] + [vp] * 5 + [i64, vp, vp]
+    T.gbx_mm_sam_cpu.restype = i64
+    T.gbx_mm_sam_cpu_lanes.argtypes = [vp, C.c_int] + T.gbx_mm_sam_cpu.argtypes[1:]
+    T.gbx_mm_sam_cpu_lanes.restype = i64
     return T
 
 

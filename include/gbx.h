@@ -2099,6 +2099,63 @@ int gbx_mm_paf_cigar_host(int64_t n_reads, const gbx_mm_reg *regs, const int64_t
                           int64_t n_targets, const uint8_t *tnames, const int64_t *tname_off, const int64_t *tseq_off,
                           uint8_t *lines, int64_t text_cap, int64_t *line_off, int64_t *n_text);
 
+/* ------------------------------------------------------------------- mm sam: SAM records, cs / MD tags and = / X operations
+ * The text of the aligned regions behind gbx_mm_align_*, beside gbx_mm_paf_cigar_*.  UNPINNED by a compiled reference; the rules
+ * are DESIGN 3.21, restated in tests/mm_sam_ref.py, after minimap2's mm_write_sam3, write_cs_core, write_MD_core and
+ * mm_update_cigar_eqx.  In short:
+ *   columns   codes as mm align's; two columns are equal iff their codes are (4 against 4 is equal).  The alignment lies between
+ *             the contig forward and the read as the anchors see it: reversed and complemented (ACGTUMRWSYKVHDBN ->
+ *             TGCAAKYWSRMBDHVN, case kept, other bytes as they are) on the reverse strand.
+ *   prints    a region prints its alignment iff gbx_mm_paf_cigar_* prints its cg:Z: line.  Any other region prints the plain PAF
+ *             line (format 0) or nothing (format 1, counted in counts[1]).
+ *   eqx       every M word is cut into maximal runs of equal (=, op 7) and unequal (X, op 8) columns; letters MIDNSHP=X.
+ *   cs        short: `:n` a maximal equal run within an M word, `*` contig letter read letter (acgtn) an unequal column, `+` and the
+ *             read letters an I, `-` and the contig letters a D.  Long: `=` and the letters (ACGTN) in place of `:n`.
+ *   MD        a counter over equal M columns, printed with the contig letter (ACGTN) at an unequal column and with `^` and the
+ *             contig letters at a D, each of which resets it; an I leaves it alone; at the end it prints only when above 0.
+ *   SAM       QNAME FLAG RNAME rs+1 mapq CIGAR * 0 0 SEQ QUAL, the tags NM ms AS nn tp cm s1 s2 rl of the PAF line, SA:Z:, cs:Z:,
+ *             MD:Z:.  Among a read's printing regions the first with parent == id is the primary, the others with parent == id are
+ *             supplementary (0x800), the rest secondary (0x100); 0x10 on the reverse strand.  Clips S, or H on supplementary and
+ *             secondary records unless softclip; SEQ and QUAL `*` on secondary records, the oriented read between H clips, else
+ *             the whole oriented read; QUAL mirrored, `*` without qual.  SA on every parent == id record of a read with two or
+ *             more, the others as tname,rs+1,+|-,[c5 S]lM[dI|dD][c3 S],mapq,NM; with l = min(qe - qs, re - rs).  A read none of
+ *             whose regions prints gives QNAME 4 * 0 0 * * 0 0 SEQ QUAL as stored.
+ *   PAF       the line of gbx_mm_paf_cigar_*, with the = / X letters, cs:Z: and MD:Z: behind it as asked; with every field 0 the
+ *             text is gbx_mm_paf_cigar_*'s byte for byte.
+ * Malformed input is cut, never read past: a word counts at most to the end of the read (M, I) or the contig (M, D), an op above
+ * 2 counts no columns, a word that counts none prints nothing in cs and MD, a region whose `read` is not the read reg_off puts it
+ * in prints nothing. */
+typedef struct gbx_mm_sam_params {
+    int32_t format;            /* 0 PAF, 1 SAM */
+    int32_t cs;                /* 0 none, 1 short, 2 long */
+    int32_t md;                /* 0, 1 */
+    int32_t eqx;               /* 0, 1 */
+    int32_t softclip;          /* 0, 1: S clips on supplementary and secondary records */
+} gbx_mm_sam_params;
+
+void gbx_mm_sam_default_params(gbx_mm_sam_params *p);          /* every field 0 */
+/* GBX_ERR_ARG naming the field: a value outside the ones listed above. */
+int gbx_mm_sam_check_params(const gbx_mm_sam_params *p);
+
+/* The arguments of gbx_mm_paf_cigar_device, the parameters, the reads' bytes (seq on seq_off), their qualities on the same
+ * offsets (qual, may be NULL) and the contigs' text (tseq on tseq_off).  Output: lines, line_off[n_reads + 1], *n_text as
+ * gbx_mm_paf_*'s, counts[2] = lines written (as if text_cap held them all), regions that print nothing.  Nothing is written at or
+ * past text_cap, *n_text reports the true need.  No host synchronisation. */
+size_t gbx_mm_sam_workspace_bytes(int64_t n_reads, int64_t reg_cap);
+int gbx_mm_sam_device(const gbx_mm_sam_params *p, int64_t n_reads, const gbx_mm_reg *d_regs, const int64_t *d_reg_off, const int64_t *d_n_regs,
+                      int64_t reg_cap, const gbx_mm_aln *d_alns, const uint32_t *d_cigar, int64_t cigar_cap,
+                      const uint8_t *d_qnames, const int64_t *d_qname_off, const uint8_t *d_seq, const uint8_t *d_qual, const int64_t *d_seq_off,
+                      const int32_t *d_rep_len, int64_t n_targets, const uint8_t *d_tnames, const int64_t *d_tname_off, const uint8_t *d_tseq,
+                      const int64_t *d_tseq_off, uint8_t *d_lines, int64_t text_cap, int64_t *d_line_off, int64_t *d_n_text, int64_t *d_counts,
+                      void *d_work, size_t work_bytes, void *stream);
+/* The checks of gbx_mm_paf_cigar_host.  More text than text_cap: GBX_ERR_ARG with the need in *n_text (line_off and counts are
+ * written; call with 0 / NULL to size). */
+int gbx_mm_sam_host(const gbx_mm_sam_params *p, int64_t n_reads, const gbx_mm_reg *regs, const int64_t *reg_off, const gbx_mm_aln *alns,
+                    const uint32_t *cigar, int64_t n_cigar, const uint8_t *qnames, const int64_t *qname_off, const uint8_t *seq, const uint8_t *qual,
+                    const int64_t *seq_off, const int32_t *rep_len, int64_t n_targets, const uint8_t *tnames, const int64_t *tname_off,
+                    const uint8_t *tseq, const int64_t *tseq_off, uint8_t *lines, int64_t text_cap, int64_t *line_off, int64_t *n_text,
+                    int64_t *counts);
+
 #ifdef __cplusplus
 }
 #endif
