@@ -22,8 +22,11 @@
 // Everything is integer sums, minima and ORs, so the graph does not depend on the schedule.  Every loop is bounded: probes
 // by the table size, the list walk by the edge table size, the binary searches by log2 of their range; in the
 // GBX_LOOP_GUARD build the probe and list loops count down from those bounds as well (kernel 9).
+// The hash (FNV-1a fold, mix64, tag / home split, edge key) and the table sizing are in dbg_hash.h, which the plain host compiler
+// takes as well: tests/hostcheck/dbg_hash_check.cpp holds the tests' colliding k-mers (tests/dbg_cases.py) against it.
 #include <algorithm>
 #include "gbx_internal.h"
+#include "dbg_hash.h"
 
 namespace gbx {
 namespace {
@@ -31,14 +34,8 @@ namespace {
 constexpr int FIN_THREADS = 256;
 constexpr int INS_THREADS = 256;
 constexpr int REC_MAX = GBX_DBG_MAX_K + 1 + 4 + 8 + 1 + 4 * 12;   // one node's digest record at most
-constexpr uint64_t FNV_BASIS = 0xcbf29ce484222325ull, FNV_PRIME = 0x100000001b3ull;
-constexpr uint64_t ADDR_MASK = (1ull << 41) - 1;
-
-__device__ inline uint64_t mix64(uint64_t h)
-{
-    h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull; h ^= h >> 33;
-    return h;
-}
+constexpr uint64_t FNV_BASIS = DBG_FNV_BASIS, FNV_PRIME = DBG_FNV_PRIME;   // (the digest is FNV-1a too)
+constexpr uint64_t ADDR_MASK = (1ull << DBG_TAG_SHIFT) - 1;
 
 struct Tables {                      // one window's tables inside the batch region (dbg_window_bytes)
     uint64_t *key, *first, *weight;  // node slots
@@ -91,8 +88,8 @@ __device__ inline const uint8_t *text_at(const DbgDev &a, uint64_t addr)
 __device__ inline int64_t node_slot(const DbgDev &a, const Tables &t, int64_t nc, uint64_t h, uint64_t addr, const uint8_t *mine,
                                     int k, int64_t unit)
 {
-    const uint64_t tag = h >> 41, want = tag << 41 | (addr + 1), mask = (uint64_t)nc - 1;
-    uint64_t i = h & mask;
+    const uint64_t tag = dbg_node_tag(h), want = tag << DBG_TAG_SHIFT | (addr + 1), mask = (uint64_t)nc - 1;
+    uint64_t i = dbg_node_home(h, nc);
     GBX_GUARD(gd, nc);
     for (int64_t probe = 0; probe < nc; ++probe, i = (i + 1) & mask) {
         if (GBX_GUARD_TRIP(gd, GBX_GK_DBG, 1, unit)) break;
@@ -101,7 +98,7 @@ __device__ inline int64_t node_slot(const DbgDev &a, const Tables &t, int64_t nc
             cur = atomicCAS((unsigned long long *)&t.key[i], 0ull, (unsigned long long)want);
             if (cur == 0) return (int64_t)i;
         }
-        if ((cur >> 41) == tag) {
+        if (dbg_node_tag(cur) == tag) {
             const uint8_t *o = text_at(a, (cur & ADDR_MASK) - 1);
             bool eq = true;
             for (int j = 0; j < k; ++j)
@@ -135,8 +132,8 @@ __global__ void __launch_bounds__(INS_THREADS) dbg_insert_kernel(DbgDev a, const
         wgt = 1; colour = GBX_DBG_REF;
         for (int j = 0; j <= k; ++j) {
             const uint64_t b = s[j];
-            if (j < k) h1 = (h1 ^ b) * FNV_PRIME;
-            if (j > 0) h2 = (h2 ^ b) * FNV_PRIME;
+            if (j < k) h1 = dbg_fnv_step(h1, b);
+            if (j > 0) h2 = dbg_fnv_step(h2, b);
         }
     } else {
         const int64_t g = a.rcp[W.read_lo] + (c - W.nref_c);
@@ -155,14 +152,14 @@ __global__ void __launch_bounds__(INS_THREADS) dbg_insert_kernel(DbgDev a, const
             const uint64_t b = s[j];
             mq = min(mq, (uint32_t)q[j]);
             has_n |= b == 'N';
-            if (j < k) h1 = (h1 ^ b) * FNV_PRIME;
-            if (j > 0) h2 = (h2 ^ b) * FNV_PRIME;
+            if (j < k) h1 = dbg_fnv_step(h1, b);
+            if (j > 0) h2 = dbg_fnv_step(h2, b);
         }
         if (has_n || (int)mq < a.min_qual) return;
         addr = (uint64_t)a.ref_bytes + (uint64_t)off;
         wgt = mq; colour = GBX_DBG_READ;
     }
-    h1 = mix64(h1); h2 = mix64(h2);
+    h1 = dbg_mix64(h1); h2 = dbg_mix64(h2);
     const Tables tb = tables_of(region, W);
     const int64_t sa = node_slot(a, tb, W.nc, h1, addr, s, k, t);
     const int64_t sb = sa < 0 ? -1 : node_slot(a, tb, W.nc, h2, addr + 1, s + 1, k, t);
@@ -174,8 +171,8 @@ __global__ void __launch_bounds__(INS_THREADS) dbg_insert_kernel(DbgDev a, const
     atomicAdd((unsigned long long *)&tb.weight[sb], (unsigned long long)wgt);
     atomicOr(&tb.col[sb], colour);
     // the edge (start slot, next byte)
-    const uint64_t ek = (uint64_t)(sa + 1) << 8 | s[k], emask = (uint64_t)W.ec - 1;
-    uint64_t i = mix64(ek) & emask;
+    const uint64_t ek = dbg_edge_key(sa, s[k]), emask = (uint64_t)W.ec - 1;
+    uint64_t i = dbg_edge_home(ek, W.ec);
     int64_t j = -1;
     GBX_GUARD(gd, W.ec);
     for (int64_t probe = 0; probe < W.ec; ++probe, i = (i + 1) & emask) {
@@ -369,10 +366,7 @@ __global__ void __launch_bounds__(FIN_THREADS) dbg_finish_kernel(DbgDev a, const
 
 size_t dbg_window_bytes(int64_t C)
 {
-    int64_t nc = 2, ec = 2;
-    while (nc < 2 * C + 1) nc <<= 1;
-    while (ec < C + 1) ec <<= 1;
-    return (size_t)(nc * 36 + ec * 36 + 8 * C);
+    return (size_t)(dbg_node_slots(C) * 36 + dbg_edge_slots(C) * 36 + 8 * C);
 }
 
 int dbg_plan(int64_t k, int64_t w0, int64_t w1, const int64_t *ref_off, const int64_t *ref_pos, const int64_t *read_lo, const int64_t *read_hi,
@@ -392,9 +386,8 @@ int dbg_plan(int64_t k, int64_t w0, int64_t w1, const int64_t *ref_off, const in
         P.ref_off = ref_off[w];
         P.ref_pos = ref_pos[w];
         P.win = w - w0;
-        P.nc = 2; P.ec = 2;
-        while (P.nc < 2 * P.C + 1) P.nc <<= 1;
-        while (P.ec < P.C + 1) P.ec <<= 1;
+        P.nc = dbg_node_slots(P.C);
+        P.ec = dbg_edge_slots(P.C);
         const size_t b = dbg_window_bytes(P.C);
         if (b > table_bytes) {
             set_error("dbg: window %lld needs %zu bytes of tables, the workspace has %zu (gbx_dbg_workspace_bytes: max_window_occ)", (long long)w, b,
