@@ -17,6 +17,21 @@ SITE_DTYPE = np.dtype([("read", "<i4"), ("start_position", "<i4"), ("end_positio
 assert JOB_DTYPE.itemsize == 40 and SITE_DTYPE.itemsize == 32
 PRE_CLIP, POST_CLIP = 1, 2                               # HAF_ALLOW_PRE_CLIP, HAF_ALLOW_POST_CLIP (f5cmisc.h:13-17)
 NMODEL_CPG, FLOGSUM_TBL, NTRANS, NCLASS, MAX_KMERS = 15625, 16000, 10, 4, 256
+SITES_COUNT, SITES_FILL = 1, 2                           # GBX_ABEA_METH_SITES_COUNT / _FILL
+NO_BAD_JOB = 2 ** 63 - 1                                 # *d_first_bad when every job passes the checks
+
+
+def _declare(L):
+    vp, i64, i32 = N.C.c_void_p, N.C.c_int64, N.C.c_int
+    L.gbx_abea_meth_sites_work.argtypes, L.gbx_abea_meth_sites_work.restype = [i64, i64], i64
+    L.gbx_abea_meth_sites_device.argtypes = [i32, i64] + [vp] * 11 + [i64, vp, vp, i64, vp, vp]
+    L.gbx_abea_meth_tables_host.argtypes = [i64, vp, vp, vp, i64, vp, vp]
+    L.gbx_abea_meth_order_work.argtypes, L.gbx_abea_meth_order_work.restype = [i64], i64
+    L.gbx_abea_meth_order_device.argtypes = [i64, vp, i64, i64, vp, i64, i32, vp, vp, vp, vp, vp]
+    L.gbx_abea_meth_tsv_host.argtypes = [i64, vp, vp, i64] + [vp] * 6 + [i32, i32, i32, i32, i64, vp, vp]
+
+
+_lib = N.declare_once(_declare)
 
 
 def make_cpg_model(level_mean, level_stdv):
@@ -72,6 +87,39 @@ class AbeaMethJobSet:
                                                 N.ptr(self.events_per_base), N.ptr(p["flogsum"]), N.ptr(p["trans"]), flank_len,
                                                 N.ptr(p["pre_flank"]), N.ptr(p["post_flank"]), N.ptr(p["order"]), N.ptr(p["class_off"])))
         return p
+
+
+def tables_host(events_per_base, flank_len):
+    """gbx_abea_meth_tables_host -> dict(flogsum, trans, pre_flank, post_flank): the half of the plan that needs the host C library"""
+    epb = np.ascontiguousarray(events_per_base, np.float64)
+    n = len(epb)
+    p = dict(flogsum=np.zeros(FLOGSUM_TBL, np.float32), trans=np.zeros((max(n, 1), NTRANS), np.float32),
+             pre_flank=np.zeros(max(flank_len, 0), np.float32), post_flank=np.zeros(max(flank_len, 0), np.float32))
+    N.check(_lib().gbx_abea_meth_tables_host(n, N.ptr(epb), N.ptr(p["flogsum"]), N.ptr(p["trans"]), flank_len, N.ptr(p["pre_flank"]),
+                                             N.ptr(p["post_flank"])))
+    return p
+
+
+def tsv_host(sites, scores, read_names, contig_names, rc, ref_off, ref_len, ref_arena, version=1, clip_start=-1, clip_end=-1, with_header=False,
+             cap=None):
+    """gbx_abea_meth_tsv_host -> bytes: the lines f5c call-methylation prints for the sites (scores[s] = unmethylated, methylated).
+    cap=None sizes first and then calls with exactly that room."""
+    sites = np.ascontiguousarray(sites, SITE_DTYPE)
+    scores = np.ascontiguousarray(np.asarray(scores, np.float32).reshape(-1))
+    n, nr = len(sites), len(read_names)
+    assert scores.size == 2 * n and len(contig_names) == nr
+    names = (N.C.c_char_p * max(nr, 1))(*[s.encode() if isinstance(s, str) else s for s in read_names])
+    contigs = (N.C.c_char_p * max(nr, 1))(*[s.encode() if isinstance(s, str) else s for s in contig_names])
+    rc, ref_off = np.ascontiguousarray(rc, np.uint8), np.ascontiguousarray(ref_off, np.int64)
+    ref_len, ref_arena = np.ascontiguousarray(ref_len, np.int32), np.ascontiguousarray(ref_arena, np.uint8)
+    need = np.zeros(1, np.int64)
+
+    def call(room):
+        out = np.zeros(max(room, 1), np.uint8)
+        return _lib().gbx_abea_meth_tsv_host(n, N.ptr(sites), N.ptr(scores), nr, names, contigs, N.ptr(rc), N.ptr(ref_off), N.ptr(ref_len), N.ptr(ref_arena),
+                                             version, clip_start, clip_end, 1 if with_header else 0, room, N.ptr(out) if room else None, N.ptr(need)), out
+    out = N.call_with_room(call, 0 if cap is None else int(cap), need, fixed=cap is not None)
+    return out[:int(need[0])].tobytes()
 
 
 def score_host(js):
@@ -166,3 +214,108 @@ class DeviceAbeaMethJobSet:
 
     def cells(self):
         return self.js.cells()
+
+
+    @classmethod
+    def from_device(cls, jobs, seq_arena, order, class_off, reads, model, tables, n_jobs):
+        """A job set whose jobs, strings and order never were on the host: `jobs` (uint8, 40 n_jobs bytes), `seq_arena` and
+        `order` as DeviceAbeaMethSites leaves them, class_off on the host, `reads` as DeviceAbeaCalib.reads(), the CpG model
+        (host) and tables_host's dictionary."""
+        import torch
+        device = jobs.device
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+        self = cls.__new__(cls)
+        self.js, self.n_jobs = None, int(n_jobs)
+        self.class_off = np.ascontiguousarray(class_off, np.int64)
+        model = np.ascontiguousarray(model, MODEL_DTYPE)
+        assert model.size == NMODEL_CPG and self.class_off.size == NCLASS + 1 and int(self.class_off[NCLASS]) == self.n_jobs
+        d = dict(jobs=jobs, seq_arena=seq_arena, order=order, model=t(model.view(np.uint8)))
+        d.update({k: t(tables[k]) for k in ("flogsum", "trans", "pre_flank", "post_flank")})
+        d.update({k: reads[k] for k in ("event_off", "event_mean", "scale", "shift", "var", "log_var")})
+        self.d = d
+        self.scores = torch.zeros(max(self.n_jobs, 1), dtype=torch.float32, device=device)
+        return self
+
+
+class DeviceAbeaMethSites:
+    """The site planner and the job order on the device, behind DeviceAbeaCalib.record(): takes that object's tensors (pos, rc,
+    rec_off, rec, event_off) and the reference segments.  count(): the per-read offsets and the strand flags; size(): synchronises,
+    brings the two totals and the flags over, raises GBX_ERR_ARG naming the lowest read whose record runs against its strand, and
+    allocates; fill(): sites, jobs and strings; order(): the jobs' order, class_off and the per-job checks (synchronises for the
+    48 bytes; raises what gbx_abea_meth_plan_host would, naming the lowest bad job).  Nothing else comes to the host."""
+
+    def __init__(self, cal, ref_off, ref_len, ref_arena):
+        import torch
+        self.torch, self.cal = torch, cal
+        dev = self.device = cal.device
+        n = self.n_reads = cal.n_reads
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        ref_arena = np.ascontiguousarray(ref_arena, np.uint8)
+        self.ref_off, self.ref_len = t(np.ascontiguousarray(ref_off, np.int64)), t(np.ascontiguousarray(ref_len, np.int32))
+        self.ref_arena = t(np.concatenate([ref_arena, np.zeros(16, np.uint8)]))
+        assert len(ref_len) == n
+        z = lambda dt, k: torch.zeros(max(k, 1), dtype=dt, device=dev)
+        self.site_off, self.byte_off, self.bad = z(torch.int64, n + 1), z(torch.int64, n + 1), z(torch.uint8, n)
+        self.work = z(torch.uint8, int(_lib().gbx_abea_meth_sites_work(n, ref_arena.size)))
+        self.n_sites = self.n_bytes = self.n_jobs = 0
+        self.sites = self.jobs = self.seq_arena = self.order_ = None
+        self.site_cap = self.seq_cap = 0
+        self.class_off, self.first_bad = np.zeros(NCLASS + 1, np.int64), NO_BAD_JOB
+
+    def _sites(self, pass_, stream):
+        c, p = self.cal, lambda a: a.data_ptr() if a is not None else None
+        rec = c.rec if c.rec is not None else self.torch.zeros((1, 2), dtype=self.torch.int32, device=self.device)
+        N.check(_lib().gbx_abea_meth_sites_device(pass_, self.n_reads, p(self.ref_off), p(self.ref_len), p(self.ref_arena), p(c.pos), p(c.rc), p(c.rec_off),
+                                                  p(rec), p(self.work), p(self.site_off), p(self.byte_off), p(self.bad), self.site_cap, p(self.sites),
+                                                  p(self.jobs), self.seq_cap, p(self.seq_arena), stream))
+
+    def count(self, stream=None):
+        self._sites(SITES_COUNT, stream)
+
+    def size(self, site_cap=None, seq_cap=None):
+        n, torch = self.n_reads, self.torch
+        bad = self.bad[:n].cpu().numpy() if n else np.zeros(0, np.uint8)
+        if bad.any():
+            raise N.GbxError(N.GBX_ERR_ARG, "gbx_abea_meth_sites_device: the record of read %d runs against its strand" % int(np.flatnonzero(bad)[0]))
+        self.n_sites, self.n_bytes = (int(self.site_off[n].item()), int(self.byte_off[n].item())) if n else (0, 0)
+        self.n_jobs = 2 * self.n_sites
+        self.site_cap = self.n_sites if site_cap is None else int(site_cap)
+        self.seq_cap = self.n_bytes if seq_cap is None else int(seq_cap)
+        self.sites = torch.zeros(max(self.site_cap, 1) * SITE_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+        self.jobs = torch.zeros(max(2 * self.site_cap, 1) * JOB_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+        self.seq_arena = torch.zeros(max(self.seq_cap, 1) + 16, dtype=torch.uint8, device=self.device)
+
+    def fill(self, stream=None):
+        if self.n_reads:
+            self._sites(SITES_FILL, stream)
+
+    def order(self, flank_len, stream=None):
+        """flank_len: as tables_host's (above the largest row count; the largest event count of a read, and one, serves)"""
+        torch = self.torch
+        nj = self.n_jobs
+        bits = max(1, int(flank_len - 1).bit_length())
+        self.order_ = torch.zeros(max(nj, 1), dtype=torch.int32, device=self.device)
+        work = torch.zeros(max(int(_lib().gbx_abea_meth_order_work(nj)), 1), dtype=torch.uint8, device=self.device)
+        tail = torch.zeros(NCLASS + 2, dtype=torch.int64, device=self.device)
+        N.check(_lib().gbx_abea_meth_order_device(nj, self.jobs.data_ptr(), self.n_bytes, self.n_reads, self.cal.dss.event_off.data_ptr(), flank_len, bits,
+                                                  work.data_ptr(), self.order_.data_ptr(), tail.data_ptr(), tail[NCLASS + 1:].data_ptr(), stream))
+        h = tail.cpu().numpy()                                    # synchronises
+        self.class_off, self.first_bad = h[:NCLASS + 1].copy(), int(h[NCLASS + 1])
+        if self.first_bad != NO_BAD_JOB:
+            self.refuse_bad_job()
+
+    def refuse_bad_job(self):
+        """raises what gbx_abea_meth_plan_host says of the lowest bad job (that one job comes to the host for the text)"""
+        j = self.first_bad
+        job = self.jobs[j * JOB_DTYPE.itemsize:(j + 1) * JOB_DTYPE.itemsize].cpu().numpy().view(JOB_DTYPE)
+        raise N.GbxError(N.GBX_ERR_UNSUPPORTED if int(job["seq_len"][0]) - KMER + 1 > MAX_KMERS else N.GBX_ERR_ARG,
+                         "gbx_abea_meth_order_device: job %d fails the checks of gbx_abea_meth_plan_host: %s" % (j, job[0]))
+
+    def results(self):
+        """(sites, jobs, seq_arena) on the host, as sites_host returns them"""
+        ns = min(self.n_sites, self.site_cap)
+        return (self.sites.cpu().numpy().view(SITE_DTYPE)[:ns], self.jobs.cpu().numpy().view(JOB_DTYPE)[:2 * ns],
+                self.seq_arena[:min(self.n_bytes, self.seq_cap)].cpu().numpy())
+
+    def job_set(self, model, tables):
+        return DeviceAbeaMethJobSet.from_device(self.jobs, self.seq_arena, self.order_, self.class_off, self.cal.reads(), model, tables, self.n_jobs)

@@ -6,31 +6,46 @@ using namespace gbx;
 
 namespace {
 
-// COUNT, the total to the host, FILL, the record to the host.  Everything else is on the device already.
-int record_to_host(const char *who, Lane *L, int64_t n_reads, const int64_t *d_cigar_off, const uint32_t *d_cigar, const int32_t *d_pos,
-                   const uint8_t *d_rc, const int64_t *d_seq_off, const int32_t *d_seq_len, const int32_t *d_map, const int32_t *d_flags,
-                   int64_t seq_bytes, int64_t *rec_off, int64_t rec_cap, gbx_abea_pair *rec, int64_t *n_rec, std::vector<gbx_abea_pair> *own)
+// COUNT, the total (rec_off != nullptr: all the offsets) to the host, FILL.  The record stays on the device, in drec at droff.
+// rec_cap < 0: whatever the count says.
+int record_on_device(const char *who, Lane *L, int64_t n_reads, const int64_t *d_cigar_off, const uint32_t *d_cigar, const int32_t *d_pos,
+                     const uint8_t *d_rc, const int64_t *d_seq_off, const int32_t *d_seq_len, const int32_t *d_map, const int32_t *d_flags,
+                     int64_t seq_bytes, int64_t *rec_off, int64_t rec_cap, DevBuf &droff, DevBuf &drec, int64_t *n_rec)
 {
     const hipStream_t cs = L->compute;
-    DevBuf dnear(L), droff(L), drec(L);
+    DevBuf dnear(L);
     int rc;
     if ((rc = dnear.alloc((size_t)seq_bytes * 8 + 16)) || (rc = droff.alloc((size_t)(n_reads + 1) * 8))) return rc;
     if ((rc = abea_record_launch(GBX_ABEA_RECORD_COUNT, n_reads, d_cigar_off, d_cigar, d_pos, d_rc, d_seq_off, d_seq_len, d_map, d_flags,
                                  dnear.as<int32_t>(), droff.as<int64_t>(), nullptr, 0, cs)))
         return rc;
-    GBX_HIP(hipMemcpyAsync(rec_off, droff.p, (size_t)(n_reads + 1) * 8, hipMemcpyDeviceToHost, cs));
+    int64_t total = 0;
+    if (rec_off) GBX_HIP(hipMemcpyAsync(rec_off, droff.p, (size_t)(n_reads + 1) * 8, hipMemcpyDeviceToHost, cs));
+    else GBX_HIP(hipMemcpyAsync(&total, droff.as<int64_t>() + n_reads, 8, hipMemcpyDeviceToHost, cs));
     GBX_HIP(hipStreamSynchronize(cs));
-    const int64_t total = rec_off[n_reads];
+    if (rec_off) total = rec_off[n_reads];
     *n_rec = total;
-    if (own) { own->resize((size_t)std::max<int64_t>(total, 1)); rec = own->data(); rec_cap = total; }
-    if (total > rec_cap) { set_error("%s: %lld record pairs, room for %lld", who, (long long)total, (long long)rec_cap); return GBX_ERR_ARG; }
+    if (rec_cap >= 0 && total > rec_cap) { set_error("%s: %lld record pairs, room for %lld", who, (long long)total, (long long)rec_cap); return GBX_ERR_ARG; }
+    if ((rc = drec.alloc((size_t)std::max<int64_t>(total, 1) * sizeof(gbx_abea_pair)))) return rc;
     if (total == 0) return GBX_OK;
-    if ((rc = drec.alloc((size_t)total * sizeof(gbx_abea_pair)))) return rc;
-    if ((rc = abea_record_launch(GBX_ABEA_RECORD_FILL, n_reads, d_cigar_off, d_cigar, d_pos, d_rc, d_seq_off, d_seq_len, d_map, d_flags,
-                                 dnear.as<int32_t>(), droff.as<int64_t>(), drec.as<gbx_abea_pair>(), total, cs)))
-        return rc;
-    GBX_HIP(hipMemcpyAsync(rec, drec.p, (size_t)total * sizeof(gbx_abea_pair), hipMemcpyDeviceToHost, cs));
-    GBX_HIP(hipStreamSynchronize(cs));
+    rc = abea_record_launch(GBX_ABEA_RECORD_FILL, n_reads, d_cigar_off, d_cigar, d_pos, d_rc, d_seq_off, d_seq_len, d_map, d_flags, dnear.as<int32_t>(),
+                            droff.as<int64_t>(), drec.as<gbx_abea_pair>(), total, cs);
+    if (rc) return rc;
+    GBX_HIP(hipStreamSynchronize(cs));                          // dnear dies with this scope
+    return GBX_OK;
+}
+
+// the same, and the record to the host
+int record_to_host(const char *who, Lane *L, int64_t n_reads, const int64_t *d_cigar_off, const uint32_t *d_cigar, const int32_t *d_pos,
+                   const uint8_t *d_rc, const int64_t *d_seq_off, const int32_t *d_seq_len, const int32_t *d_map, const int32_t *d_flags,
+                   int64_t seq_bytes, int64_t *rec_off, int64_t rec_cap, gbx_abea_pair *rec, int64_t *n_rec)
+{
+    DevBuf droff(L), drec(L);
+    int rc = record_on_device(who, L, n_reads, d_cigar_off, d_cigar, d_pos, d_rc, d_seq_off, d_seq_len, d_map, d_flags, seq_bytes, rec_off, rec_cap, droff,
+                              drec, n_rec);
+    if (rc || *n_rec == 0) return rc;
+    GBX_HIP(hipMemcpyAsync(rec, drec.p, (size_t)*n_rec * sizeof(gbx_abea_pair), hipMemcpyDeviceToHost, L->compute));
+    GBX_HIP(hipStreamSynchronize(L->compute));
     return GBX_OK;
 }
 
@@ -198,7 +213,7 @@ int gbx_abea_event_record_host(int64_t n_reads, const int64_t *cigar_off, const 
     if (seq_bytes) GBX_HIP(hipMemcpyAsync(dmap.p, map, (size_t)seq_bytes * 8, hipMemcpyHostToDevice, cs));
     if (flags) GBX_HIP(hipMemcpyAsync(dfl.p, flags, (size_t)n_reads * 4, hipMemcpyHostToDevice, cs));
     return record_to_host(who, L, n_reads, dco.as<int64_t>(), dcg.as<uint32_t>(), dpos.as<int32_t>(), drc.as<uint8_t>(), dso.as<int64_t>(),
-                          dsl.as<int32_t>(), dmap.as<int32_t>(), flags ? dfl.as<int32_t>() : nullptr, seq_bytes, rec_off, rec_cap, rec, n_rec, nullptr);
+                          dsl.as<int32_t>(), dmap.as<int32_t>(), flags ? dfl.as<int32_t>() : nullptr, seq_bytes, rec_off, rec_cap, rec, n_rec);
 }
 
 int gbx_abea_call_methylation_host(int64_t n_reads, const int16_t *raw, const int64_t *raw_off, const float *range, const float *digitisation,
@@ -224,60 +239,103 @@ int gbx_abea_call_methylation_host(int64_t n_reads, const int16_t *raw, const in
     if ((rc = check_cigars(who, n_reads, cigar_off, cigar, seq_len))) return rc;
     // a batch in which no read has events never reaches the tail
     for (int64_t r = 0; r < n_reads; ++r) { flags[r] = GBX_ABEA_FAILED_ALIGNMENT; var[r] = 0.0f; events_per_base[r] = 0.0; }
-    // behind align(), on the buffers it left: calibration, record, the host planner and plan, the score
+    // behind align(), on the buffers it left: calibration, record, the site planner, the order and the score.  The record, the jobs
+    // and the strings never leave the device; the site table and the scores come down.
     const abea_tail_fn call_meth_tail = [&](const AbeaAligned &a) -> int {
         Lane *L = a.L;
         const hipStream_t cs = L->compute;
         const int64_t n = a.n_reads;
-        std::vector<int64_t> rec_off((size_t)n + 1);
-        std::vector<gbx_abea_pair> rec;
-        std::vector<gbx_abea_meth_job> jobs;
-        std::vector<char> arena;
-        AbeaMethPlan plan;
+        std::vector<uint8_t> bad((size_t)n);
+        std::vector<float> flogsum(GBX_ABEA_FLOGSUM_TBL), trans((size_t)n * GBX_ABEA_METH_NTRANS), pre, post;
+        int64_t totals[2] = {0, 0}, tail[GBX_ABEA_METH_NCLASS + 2];
+        gbx_abea_meth_job bad_job;
         AbeaCalibrated cal(L);                                   // behind every host array a queued copy uses: it drains the stream before they die
         if ((rc = cal.queue(a, cigar_off, cigar, pos, rc_flag, scale, shift, var, events_per_base, flags))) return rc;
         // the record of the unflagged reads (the flags are on the device; the count pass is queued behind the calibration)
         int64_t n_rec = 0;
-        if ((rc = record_to_host(who, L, n, cal.cigar_off, cal.cigar, cal.pos, cal.rc, a.d_seq_off, a.d_seq_len, cal.map, cal.flags, a.seq_bytes, rec_off.data(), 0,
-                                 nullptr, &n_rec, &rec)))
+        DevBuf droff(L), drec(L);
+        if ((rc = record_on_device(who, L, n, cal.cigar_off, cal.cigar, cal.pos, cal.rc, a.d_seq_off, a.d_seq_len, cal.map, cal.flags, a.seq_bytes, nullptr, -1,
+                                   droff, drec, &n_rec)))
             return rc;
         if ((rc = cal.finish(nullptr))) return rc;
-        // the site planner and the plan, on the host as they are
-        int64_t ns = 0, nb = 0;
-        rc = gbx_abea_meth_sites_host(n, ref_off, ref_len, ref_arena, pos, rc_flag, rec_off.data(), rec.data(), 0, nullptr, nullptr, &ns, 0, nullptr, &nb);
-        if (rc && !(rc == GBX_ERR_ARG && (ns > 0 || nb > 0))) return rc;
+        // the reference segments go up; planner COUNT; the two totals and the strand flags come down
+        int64_t ref_bytes = 0, flank_len = 2;
+        for (int64_t r = 0; r < n; ++r) {
+            ref_bytes = std::max<int64_t>(ref_bytes, ref_off[r] + ref_len[r]);
+            flank_len = std::max<int64_t>(flank_len, a.event_off[r + 1] - a.event_off[r] + 1);      // a job's rows are events of one read
+        }
+        int bits = 1;
+        while (bits < 30 && (1ll << bits) < flank_len) bits++;
+        Carve per_read(L);
+        DevBuf dref(L);
+        const size_t sites_work = abea_meth_sites_work_bytes(n);
+        for (size_t b : {(size_t)n * 8, (size_t)n * 4, (size_t)(n + 1) * 8, (size_t)(n + 1) * 8, (size_t)n, sites_work, sizeof tail}) per_read.want(b);
+        if ((rc = per_read.alloc()) || (rc = dref.alloc((size_t)ref_bytes + 16))) return rc;
+        int64_t *d_ref_off = per_read.take<int64_t>((size_t)n * 8);
+        int32_t *d_ref_len = per_read.take<int32_t>((size_t)n * 4);
+        int64_t *d_site_off = per_read.take<int64_t>((size_t)(n + 1) * 8), *d_byte_off = per_read.take<int64_t>((size_t)(n + 1) * 8);
+        uint8_t *d_bad = per_read.take<uint8_t>((size_t)n);
+        void *d_swork = per_read.take<char>(sites_work);
+        int64_t *d_tail = per_read.take<int64_t>(sizeof tail);                                       // class_off, then first_bad
+        GBX_HIP(hipMemcpyAsync(d_ref_off, ref_off, (size_t)n * 8, hipMemcpyHostToDevice, cs));
+        GBX_HIP(hipMemcpyAsync(d_ref_len, ref_len, (size_t)n * 4, hipMemcpyHostToDevice, cs));
+        if (ref_bytes) GBX_HIP(hipMemcpyAsync(dref.p, ref_arena, (size_t)ref_bytes, hipMemcpyHostToDevice, cs));
+        if ((rc = abea_meth_sites_launch(GBX_ABEA_METH_SITES_COUNT, n, d_ref_off, d_ref_len, dref.as<char>(), cal.pos, cal.rc, droff.as<int64_t>(),
+                                         drec.as<gbx_abea_pair>(), d_swork, d_site_off, d_byte_off, d_bad, 0, nullptr, nullptr, 0, nullptr, cs)))
+            return rc;
+        GBX_HIP(hipMemcpyAsync(&totals[0], d_site_off + n, 8, hipMemcpyDeviceToHost, cs));
+        GBX_HIP(hipMemcpyAsync(&totals[1], d_byte_off + n, 8, hipMemcpyDeviceToHost, cs));
+        GBX_HIP(hipMemcpyAsync(bad.data(), d_bad, (size_t)n, hipMemcpyDeviceToHost, cs));
+        GBX_HIP(hipStreamSynchronize(cs));
+        for (int64_t r = 0; r < n; ++r)
+            if (bad[(size_t)r]) { set_error("gbx_abea_meth_sites_host: the record of read %lld runs against its strand", (long long)r); return GBX_ERR_ARG; }
+        const int64_t ns = totals[0], nb = totals[1];
         *n_sites = ns;
         if (ns > site_cap) { set_error("%s: %lld sites, room for %lld", who, (long long)ns, (long long)site_cap); return GBX_ERR_ARG; }
-        if (ns == 0) { GBX_HIP(hipStreamSynchronize(cs)); return GBX_OK; }
+        if (ns == 0) return GBX_OK;
         const int64_t n_jobs = 2 * ns;
-        jobs.resize((size_t)n_jobs);
-        arena.resize((size_t)nb);
-        if ((rc = gbx_abea_meth_sites_host(n, ref_off, ref_len, ref_arena, pos, rc_flag, rec_off.data(), rec.data(), ns, sites, jobs.data(), &ns, nb,
-                                           arena.data(), &nb)))
-            return rc;
-        if ((rc = plan.build(n_jobs, jobs.data(), nb, n, a.event_off, events_per_base))) return rc;
-        DevBuf djb(L), dsq(L), dor(L), dout(L);
+        if (n_jobs > 0x7fffffffLL - 1024) { set_error("gbx_abea_meth_plan_host: more than 2^31 jobs in one call"); return GBX_ERR_UNSUPPORTED; }
+        // the tables that need the host C library, planner FILL, the order and its checks
+        pre.resize((size_t)flank_len); post.resize((size_t)flank_len);
+        if ((rc = gbx_abea_meth_tables_host(n, events_per_base, flogsum.data(), trans.data(), flank_len, pre.data(), post.data()))) return rc;
+        DevBuf dst(L), djb(L), dsq(L), dor(L), dout(L), dow(L);
         Carve tables(L);
         const size_t job_bytes = (size_t)n_jobs * sizeof(gbx_abea_meth_job), model_bytes = GBX_ABEA_NMODEL_CPG * sizeof(gbx_abea_model);
-        const size_t flank_bytes = (size_t)plan.flank_len * 4;
-        for (size_t b : {model_bytes, (size_t)GBX_ABEA_FLOGSUM_TBL * 4, plan.trans.size() * 4, flank_bytes, flank_bytes}) tables.want(b);
-        if ((rc = djb.alloc(job_bytes)) || (rc = dsq.alloc((size_t)nb + 16)) || (rc = tables.alloc()) || (rc = dor.alloc((size_t)n_jobs * 4)) ||
-            (rc = dout.alloc((size_t)n_jobs * 4)))
+        const size_t flank_bytes = (size_t)flank_len * 4, site_bytes = (size_t)ns * sizeof(gbx_abea_meth_site);
+        for (size_t b : {model_bytes, (size_t)GBX_ABEA_FLOGSUM_TBL * 4, trans.size() * 4, flank_bytes, flank_bytes}) tables.want(b);
+        if ((rc = dst.alloc(site_bytes)) || (rc = djb.alloc(job_bytes)) || (rc = dsq.alloc((size_t)nb + 16)) || (rc = tables.alloc()) ||
+            (rc = dor.alloc((size_t)n_jobs * 4)) || (rc = dout.alloc((size_t)n_jobs * 4)) || (rc = dow.alloc(abea_meth_order_work_bytes(n_jobs))))
             return rc;
         gbx_abea_model *dmo = tables.take<gbx_abea_model>(model_bytes);
-        float *dflg = tables.take<float>(GBX_ABEA_FLOGSUM_TBL * 4), *dtr = tables.take<float>(plan.trans.size() * 4);
+        float *dflg = tables.take<float>(GBX_ABEA_FLOGSUM_TBL * 4), *dtr = tables.take<float>(trans.size() * 4);
         float *dpr = tables.take<float>(flank_bytes), *dpo = tables.take<float>(flank_bytes);
-        GBX_HIP(hipMemcpyAsync(djb.p, jobs.data(), job_bytes, hipMemcpyHostToDevice, cs));
-        GBX_HIP(hipMemcpyAsync(dsq.p, arena.data(), (size_t)nb, hipMemcpyHostToDevice, cs));
         GBX_HIP(hipMemcpyAsync(dmo, cpg_model, model_bytes, hipMemcpyHostToDevice, cs));
-        GBX_HIP(hipMemcpyAsync(dflg, plan.flogsum.data(), GBX_ABEA_FLOGSUM_TBL * 4, hipMemcpyHostToDevice, cs));
-        GBX_HIP(hipMemcpyAsync(dtr, plan.trans.data(), plan.trans.size() * 4, hipMemcpyHostToDevice, cs));
-        GBX_HIP(hipMemcpyAsync(dpr, plan.pre.data(), flank_bytes, hipMemcpyHostToDevice, cs));
-        GBX_HIP(hipMemcpyAsync(dpo, plan.post.data(), flank_bytes, hipMemcpyHostToDevice, cs));
-        GBX_HIP(hipMemcpyAsync(dor.p, plan.order.data(), (size_t)n_jobs * 4, hipMemcpyHostToDevice, cs));
-        if ((rc = abea_meth_launch(n_jobs, djb.as<gbx_abea_meth_job>(), dsq.as<char>(), a.d_event_off, a.d_event_mean, a.d_scale, a.d_shift, cal.var, cal.log_var,
-                                   dmo, dflg, dtr, dpr, dpo, dor.as<int32_t>(), plan.class_off, dout.as<float>(), cs)))
+        GBX_HIP(hipMemcpyAsync(dflg, flogsum.data(), GBX_ABEA_FLOGSUM_TBL * 4, hipMemcpyHostToDevice, cs));
+        GBX_HIP(hipMemcpyAsync(dtr, trans.data(), trans.size() * 4, hipMemcpyHostToDevice, cs));
+        GBX_HIP(hipMemcpyAsync(dpr, pre.data(), flank_bytes, hipMemcpyHostToDevice, cs));
+        GBX_HIP(hipMemcpyAsync(dpo, post.data(), flank_bytes, hipMemcpyHostToDevice, cs));
+        if ((rc = abea_meth_sites_launch(GBX_ABEA_METH_SITES_FILL, n, d_ref_off, d_ref_len, dref.as<char>(), cal.pos, cal.rc, droff.as<int64_t>(),
+                                         drec.as<gbx_abea_pair>(), d_swork, d_site_off, d_byte_off, d_bad, ns, dst.as<gbx_abea_meth_site>(),
+                                         djb.as<gbx_abea_meth_job>(), nb, dsq.as<char>(), cs)))
             return rc;
+        if ((rc = abea_meth_order_launch(n_jobs, djb.as<gbx_abea_meth_job>(), nb, n, a.d_event_off, flank_len, bits, dow.p, dor.as<int32_t>(), d_tail,
+                                         d_tail + GBX_ABEA_METH_NCLASS + 1, cs)))
+            return rc;
+        GBX_HIP(hipMemcpyAsync(tail, d_tail, sizeof tail, hipMemcpyDeviceToHost, cs));
+        GBX_HIP(hipStreamSynchronize(cs));
+        const int64_t first_bad = tail[GBX_ABEA_METH_NCLASS + 1];
+        if (first_bad != INT64_MAX) {                            // the score indexes events with what the jobs say: it is not launched
+            if (first_bad < 0 || first_bad >= n_jobs) { set_error("%s: the order stage names job %lld of %lld", who, (long long)first_bad, (long long)n_jobs); return GBX_ERR_HIP; }
+            GBX_HIP(hipMemcpyAsync(&bad_job, djb.as<gbx_abea_meth_job>() + first_bad, sizeof bad_job, hipMemcpyDeviceToHost, cs));
+            GBX_HIP(hipStreamSynchronize(cs));
+            if ((rc = abea_meth_job_refuse(first_bad, bad_job, nb, n, a.event_off, flank_len))) return rc;
+            set_error("%s: the order stage refuses job %lld, the host check does not", who, (long long)first_bad);
+            return GBX_ERR_HIP;
+        }
+        if ((rc = abea_meth_launch(n_jobs, djb.as<gbx_abea_meth_job>(), dsq.as<char>(), a.d_event_off, a.d_event_mean, a.d_scale, a.d_shift, cal.var, cal.log_var,
+                                   dmo, dflg, dtr, dpr, dpo, dor.as<int32_t>(), tail, dout.as<float>(), cs)))
+            return rc;
+        GBX_HIP(hipMemcpyAsync(sites, dst.p, site_bytes, hipMemcpyDeviceToHost, cs));
         GBX_HIP(hipMemcpyAsync(scores, dout.p, (size_t)n_jobs * 4, hipMemcpyDeviceToHost, cs));
         GBX_HIP(hipStreamSynchronize(cs));
         return GBX_OK;

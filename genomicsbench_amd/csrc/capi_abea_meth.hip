@@ -1,4 +1,5 @@
-// capi_abea_meth.hip — abea methylation scoring: the plan, the site planner and the score entries of the C-ABI (include/gbx.h).
+// capi_abea_meth.hip — abea methylation scoring: the plan (tables, order), the site planner on the host and the entries of the one on the
+// device, the score entries and the call-methylation TSV writer of the C-ABI (include/gbx.h).
 #include "capi_common.h"
 #include <cctype>
 
@@ -6,7 +7,7 @@ using namespace gbx;
 
 namespace {
 
-inline int job_class(int64_t n_kmers) { return n_kmers <= 16 ? 0 : n_kmers <= 64 ? 1 : n_kmers <= 128 ? 2 : 3; }
+using abea_meth_rules::job_class;
 
 // ---- the string functions of meth.c
 char possible0(char c)                                       // getPossibleSymbols(c)[0], meth.c:221-256
@@ -145,6 +146,26 @@ bool sites_of_read(int32_t read, const char *ref, int64_t ref_len, int32_t ref_s
 
 extern "C" {
 
+int gbx_abea_meth_tables_host(int64_t n_reads, const double *events_per_base, float *flogsum, float *trans, int64_t flank_len, float *pre_flank,
+                              float *post_flank)
+{
+    if (n_reads < 0 || flank_len < 2 || !flogsum || !pre_flank || !post_flank || (n_reads > 0 && (!events_per_base || !trans))) {
+        set_error("gbx_abea_meth_tables_host: bad argument");
+        return GBX_ERR_ARG;
+    }
+    for (int i = 0; i < GBX_ABEA_FLOGSUM_TBL; i++) flogsum[i] = log(1. + exp((double)-i / 1000.f));           /* logsum.h:44-46 */
+    for (int64_t r = 0; r < n_reads; ++r) abea_transitions(events_per_base[r], trans + r * GBX_ABEA_METH_NTRANS);      /* hmm.c:247-295 */
+    /* pre_flank[i] depends on i alone (hmm.c:172-205), post_flank on the distance to the last event (hmm.c:132-168); the sums
+       are double, stored to float */
+    pre_flank[0] = log(1 - 0.5);
+    pre_flank[1] = log(0.5) + -3.0f + log(1 - 0.9);
+    for (int64_t i = 2; i < flank_len; ++i) pre_flank[i] = log(0.9) + -3.0f + pre_flank[i - 1];
+    post_flank[0] = log(1 - 0.5);
+    post_flank[1] = log(0.5) + -3.0f + log(1 - 0.9);
+    for (int64_t j = 2; j < flank_len; ++j) post_flank[j] = log(0.9) + -3.0f + post_flank[j - 1];
+    return GBX_OK;
+}
+
 int gbx_abea_meth_plan_host(int64_t n_jobs, const gbx_abea_meth_job *jobs, int64_t seq_bytes, int64_t n_reads, const int64_t *event_off,
                             const double *events_per_base, float *flogsum, float *trans, int64_t flank_len, float *pre_flank,
                             float *post_flank, int32_t *order, int64_t *class_off)
@@ -155,36 +176,15 @@ int gbx_abea_meth_plan_host(int64_t n_jobs, const gbx_abea_meth_job *jobs, int64
         return GBX_ERR_ARG;
     }
     if (n_jobs > 0x7fffffffLL - 1024) { set_error("gbx_abea_meth_plan_host: more than 2^31 jobs in one call"); return GBX_ERR_UNSUPPORTED; }
-    for (int i = 0; i < GBX_ABEA_FLOGSUM_TBL; i++) flogsum[i] = log(1. + exp((double)-i / 1000.f));           /* logsum.h:44-46 */
-    for (int64_t r = 0; r < n_reads; ++r) {                                                  /* hmm.c:247-295 */
+    for (int64_t r = 0; r < n_reads; ++r)
         if (event_off[r + 1] < event_off[r]) { set_error("gbx_abea_meth_plan_host: event_off not monotone at read %lld", (long long)r); return GBX_ERR_ARG; }
-        abea_transitions(events_per_base[r], trans + r * GBX_ABEA_METH_NTRANS);
-    }
-    /* pre_flank[i] depends on i alone (hmm.c:172-205), post_flank on the distance to the last event (hmm.c:132-168); the sums
-       are double, stored to float */
-    pre_flank[0] = log(1 - 0.5);
-    pre_flank[1] = log(0.5) + -3.0f + log(1 - 0.9);
-    for (int64_t i = 2; i < flank_len; ++i) pre_flank[i] = log(0.9) + -3.0f + pre_flank[i - 1];
-    post_flank[0] = log(1 - 0.5);
-    post_flank[1] = log(0.5) + -3.0f + log(1 - 0.9);
-    for (int64_t j = 2; j < flank_len; ++j) post_flank[j] = log(0.9) + -3.0f + post_flank[j - 1];
+    if (int e = gbx_abea_meth_tables_host(n_reads, events_per_base, flogsum, trans, flank_len, pre_flank, post_flank)) return e;
     std::vector<std::pair<int64_t, int32_t>> key((size_t)n_jobs);
     int64_t count[GBX_ABEA_METH_NCLASS] = {0, 0, 0, 0};
     for (int64_t j = 0; j < n_jobs; ++j) {
         const gbx_abea_meth_job &J = jobs[j];
         const int64_t nk = (int64_t)J.seq_len - GBX_ABEA_KMER + 1, rows = job_rows(J);
-        if (nk < 1 || J.seq_off < 0 || J.rc_off < 0 || J.seq_off + J.seq_len > seq_bytes || J.rc_off + J.seq_len > seq_bytes) {
-            set_error("gbx_abea_meth_plan_host: job %lld: its strings need %d bases inside the arena", (long long)j, GBX_ABEA_KMER);
-            return GBX_ERR_ARG;
-        }
-        if (nk > GBX_ABEA_METH_MAX_KMERS) { set_error("gbx_abea_meth_plan_host: job %lld has %lld k-mers (at most %d)", (long long)j, (long long)nk, GBX_ABEA_METH_MAX_KMERS); return GBX_ERR_UNSUPPORTED; }
-        if (J.read < 0 || J.read >= n_reads) { set_error("gbx_abea_meth_plan_host: job %lld names read %d", (long long)j, J.read); return GBX_ERR_ARG; }
-        const int64_t ne = event_off[J.read + 1] - event_off[J.read];
-        if (J.event_start < 0 || J.event_stop < 0 || J.event_start >= ne || J.event_stop >= ne || (J.rc ? J.event_stop > J.event_start : J.event_stop < J.event_start)) {
-            set_error("gbx_abea_meth_plan_host: job %lld: events %d..%d (rc %d) of a read with %lld", (long long)j, J.event_start, J.event_stop, J.rc, (long long)ne);
-            return GBX_ERR_ARG;
-        }
-        if (rows + 1 > flank_len) { set_error("gbx_abea_meth_plan_host: job %lld has %lld rows, the flank tables %lld entries", (long long)j, (long long)rows, (long long)flank_len); return GBX_ERR_ARG; }
+        if (int e = abea_meth_job_refuse(j, J, seq_bytes, n_reads, event_off, flank_len)) return e;
         const int c = job_class(nk);
         count[c]++;
         key[(size_t)j] = std::make_pair(((int64_t)c << 40) - rows, (int32_t)j);              /* class, then longest first; ties in input order */
@@ -326,6 +326,98 @@ int gbx_abea_meth_sites_host(int64_t n_reads, const int64_t *ref_off, const int3
         return GBX_ERR_ARG;
     }
     pass(true);
+    return GBX_OK;
+}
+
+int64_t gbx_abea_meth_sites_work(int64_t n_reads, int64_t ref_bytes)
+{
+    if (n_reads < 0 || ref_bytes < 0) return 0;
+    return (int64_t)abea_meth_sites_work_bytes(n_reads);
+}
+
+int gbx_abea_meth_sites_device(int pass, int64_t n_reads, const int64_t *d_ref_off, const int32_t *d_ref_len, const char *d_ref_arena,
+                               const int32_t *d_ref_start_pos, const uint8_t *d_rc, const int64_t *d_rec_off, const gbx_abea_pair *d_rec, void *d_work,
+                               int64_t *d_site_off, int64_t *d_byte_off, uint8_t *d_bad, int64_t site_cap, gbx_abea_meth_site *d_sites,
+                               gbx_abea_meth_job *d_jobs, int64_t seq_cap, char *d_seq_arena, void *stream)
+{
+    const char *who = "gbx_abea_meth_sites_device";
+    if (n_reads < 0 || site_cap < 0 || seq_cap < 0 || pass < 1 || pass > (GBX_ABEA_METH_SITES_COUNT | GBX_ABEA_METH_SITES_FILL)) {
+        set_error("%s: bad argument", who);
+        return GBX_ERR_ARG;
+    }
+    if (n_reads == 0) return GBX_OK;
+    if (!d_ref_off || !d_ref_len || !d_ref_arena || !d_ref_start_pos || !d_rc || !d_rec_off || !d_rec || !d_work || !d_site_off || !d_byte_off || !d_bad ||
+        ((pass & GBX_ABEA_METH_SITES_FILL) && ((site_cap > 0 && (!d_sites || !d_jobs)) || (seq_cap > 0 && !d_seq_arena)))) {
+        set_error("%s: null pointer", who);
+        return GBX_ERR_ARG;
+    }
+    int rc = require_device();
+    if (rc) return rc;
+    return abea_meth_sites_launch(pass, n_reads, d_ref_off, d_ref_len, d_ref_arena, d_ref_start_pos, d_rc, d_rec_off, d_rec, d_work, d_site_off, d_byte_off,
+                                  d_bad, site_cap, d_sites, d_jobs, seq_cap, d_seq_arena, (hipStream_t)stream);
+}
+
+int64_t gbx_abea_meth_order_work(int64_t n_jobs) { return n_jobs < 0 ? 0 : (int64_t)abea_meth_order_work_bytes(n_jobs); }
+
+int gbx_abea_meth_order_device(int64_t n_jobs, const gbx_abea_meth_job *d_jobs, int64_t seq_bytes, int64_t n_reads, const int64_t *d_event_off,
+                               int64_t flank_len, int max_rows_bits, void *d_work, int32_t *d_order, int64_t *d_class_off, int64_t *d_first_bad,
+                               void *stream)
+{
+    const char *who = "gbx_abea_meth_order_device";
+    if (n_jobs < 0 || n_reads < 0 || seq_bytes < 0 || flank_len < 2 || max_rows_bits < 1 || max_rows_bits > 30 || flank_len > (1ll << max_rows_bits)) {
+        set_error("%s: bad argument", who);
+        return GBX_ERR_ARG;
+    }
+    if (!d_class_off || !d_first_bad || (n_jobs > 0 && (!d_jobs || !d_work || !d_order)) || (n_jobs > 0 && n_reads > 0 && !d_event_off)) {
+        set_error("%s: null pointer", who);
+        return GBX_ERR_ARG;
+    }
+    int rc = require_device();
+    if (rc) return rc;
+    return abea_meth_order_launch(n_jobs, d_jobs, seq_bytes, n_reads, d_event_off, flank_len, max_rows_bits, d_work, d_order, d_class_off, d_first_bad,
+                                  (hipStream_t)stream);
+}
+
+int gbx_abea_meth_tsv_host(int64_t n_sites, const gbx_abea_meth_site *sites, const float *scores, int64_t n_reads, const char *const *read_names,
+                           const char *const *contig_names, const uint8_t *rc, const int64_t *ref_off, const int32_t *ref_len, const char *ref_arena,
+                           int version, int32_t clip_start, int32_t clip_end, int with_header, int64_t cap, char *out, int64_t *n_bytes)
+{
+    const char *who = "gbx_abea_meth_tsv_host";
+    if (!n_bytes || n_sites < 0 || n_reads < 0 || cap < 0 || (version != 1 && version != 2)) { set_error("%s: bad argument", who); return GBX_ERR_ARG; }
+    *n_bytes = 0;
+    if (n_sites > 0 && (!sites || !scores || !read_names || !contig_names || !rc || !ref_off || !ref_len || !ref_arena)) {
+        set_error("%s: null pointer", who);
+        return GBX_ERR_ARG;
+    }
+    std::string text;
+    char line[256];
+    if (with_header)                                                                         /* meth_main.c:449-457 */
+        text += version == 1 ? "chromosome\tstart\tend\tread_name\tlog_lik_ratio\tlog_lik_methylated\tlog_lik_unmethylated\tnum_calling_strands\tnum_cpgs\tsequence\n"
+                             : "chromosome\tstrand\tstart\tend\tread_name\tlog_lik_ratio\tlog_lik_methylated\tlog_lik_unmethylated\tnum_calling_strands\tnum_motifs\tsequence\n";
+    for (int64_t s = 0; s < n_sites; ++s) {                                                  /* f5c.c:1629-1653 */
+        const gbx_abea_meth_site &S = sites[s];
+        if (S.read < 0 || S.read >= n_reads || !read_names[S.read] || !contig_names[S.read]) { set_error("%s: site %lld names read %d", who, (long long)s, S.read); return GBX_ERR_ARG; }
+        const int64_t len = ref_len[S.read];
+        if (ref_off[S.read] < 0 || S.ctx_len < 0 || S.ctx_off < 0 || S.ctx_off + S.ctx_len > len) {
+            set_error("%s: the context of site %lld lies outside its reference segment", who, (long long)s);
+            return GBX_ERR_ARG;
+        }
+        if ((clip_start != -1 && S.start_position < clip_start) || (clip_end != -1 && S.end_position >= clip_end)) continue;
+        const double sum_ll_m = scores[2 * s + 1], sum_ll_u = scores[2 * s], diff = sum_ll_m - sum_ll_u;
+        text += contig_names[S.read];
+        if (version == 1) snprintf(line, sizeof line, "\t%d\t%d\t", S.start_position, S.end_position);
+        else snprintf(line, sizeof line, "\t%c\t%d\t%d\t", rc[S.read] ? '-' : '+', S.start_position, S.end_position);
+        text += line;
+        text += read_names[S.read];
+        snprintf(line, sizeof line, "\t%.2lf\t%.2lf\t%.2lf\t%d\t%d\t", diff, sum_ll_m, sum_ll_u, 1, S.n_cpg);
+        text += line;
+        const char *seg = ref_arena + ref_off[S.read] + S.ctx_off;
+        for (int32_t i = 0; i < S.ctx_len; ++i) text += possible0((char)toupper((unsigned char)seg[i]));      /* ss.sequence: of ref_seq, meth.c:288-306 */
+        text += "\n";
+    }
+    *n_bytes = (int64_t)text.size();
+    if ((int64_t)text.size() > cap) { set_error("%s: %lld bytes of text, room for %lld", who, (long long)text.size(), (long long)cap); return GBX_ERR_ARG; }
+    if (!text.empty()) { if (!out) { set_error("%s: null pointer", who); return GBX_ERR_ARG; } memcpy(out, text.data(), text.size()); }
     return GBX_OK;
 }
 

@@ -38,4 +38,5 @@ struct Carve {
 };
 }
 
+#include "abea_meth_rules.h"
 #include "host_abea.h"

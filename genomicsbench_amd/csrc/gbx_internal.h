@@ -457,6 +457,16 @@ int abea_meth_launch(int64_t n_jobs, const gbx_abea_meth_job *d_jobs, const char
                      const float *d_flogsum, const float *d_trans, const float *d_pre, const float *d_post, const int32_t *d_order,
                      const int64_t *class_off, float *d_scores, hipStream_t s);
 
+// ---- abea call-methylation site planner and job order (abea_meth_plan_kernels.hip; the rules: abea_meth_rules.h)
+size_t abea_meth_sites_work_bytes(int64_t n_reads);
+int abea_meth_sites_launch(int pass, int64_t n_reads, const int64_t *d_ref_off, const int32_t *d_ref_len, const char *d_ref, const int32_t *d_ref_start_pos,
+                           const uint8_t *d_rc, const int64_t *d_rec_off, const gbx_abea_pair *d_rec, void *d_work, int64_t *d_site_off, int64_t *d_byte_off,
+                           uint8_t *d_bad, int64_t site_cap, gbx_abea_meth_site *d_sites, gbx_abea_meth_job *d_jobs, int64_t seq_cap, char *d_seq_arena,
+                           hipStream_t s);
+size_t abea_meth_order_work_bytes(int64_t n_jobs);
+int abea_meth_order_launch(int64_t n_jobs, const gbx_abea_meth_job *d_jobs, int64_t seq_bytes, int64_t n_reads, const int64_t *d_event_off, int64_t flank_len,
+                           int max_rows_bits, void *d_work, int32_t *d_order, int64_t *d_class_off, int64_t *d_first_bad, hipStream_t s);
+
 // ---- abea eventalign (abea_eventalign_kernels.hip)
 struct AbeaEventalignArgs {                   // the device entry's arguments, by value to the kernel
     long long n_reads;

@@ -190,9 +190,29 @@ private:
     StreamDrain drain;
 };
 
-inline int64_t job_rows(const gbx_abea_meth_job &J)
+using abea_meth_rules::job_rows;
+
+// The per-job checks of the score plan (abea_meth_rules.h: job_check, what the device order stage runs too) with the error texts
+// of gbx_abea_meth_plan_host, which both it and the one call give for job j.
+inline int abea_meth_job_refuse(int64_t j, const gbx_abea_meth_job &J, int64_t seq_bytes, int64_t n_reads, const int64_t *event_off, int64_t flank_len)
 {
-    return J.event_stop > J.event_start ? (int64_t)J.event_stop - J.event_start + 1 : (int64_t)J.event_start - J.event_stop + 1;
+    const char *who = "gbx_abea_meth_plan_host";
+    const int64_t nk = (int64_t)J.seq_len - GBX_ABEA_KMER + 1;
+    switch (abea_meth_rules::job_check(J, seq_bytes, n_reads, event_off, flank_len)) {
+        case abea_meth_rules::JOB_OK: return GBX_OK;
+        case abea_meth_rules::JOB_STRINGS: set_error("%s: job %lld: its strings need %d bases inside the arena", who, (long long)j, GBX_ABEA_KMER); return GBX_ERR_ARG;
+        case abea_meth_rules::JOB_TOO_LONG:
+            set_error("%s: job %lld has %lld k-mers (at most %d)", who, (long long)j, (long long)nk, GBX_ABEA_METH_MAX_KMERS);
+            return GBX_ERR_UNSUPPORTED;
+        case abea_meth_rules::JOB_READ: set_error("%s: job %lld names read %d", who, (long long)j, J.read); return GBX_ERR_ARG;
+        case abea_meth_rules::JOB_EVENTS:
+            set_error("%s: job %lld: events %d..%d (rc %d) of a read with %lld", who, (long long)j, J.event_start, J.event_stop, J.rc,
+                      (long long)(event_off[J.read + 1] - event_off[J.read]));
+            return GBX_ERR_ARG;
+        default:
+            set_error("%s: job %lld has %lld rows, the flank tables %lld entries", who, (long long)j, (long long)job_rows(J), (long long)flank_len);
+            return GBX_ERR_ARG;
+    }
 }
 
 // What the score kernel needs beside the jobs: the flank tables sized by the longest job, the flogsum and transition tables, the

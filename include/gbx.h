@@ -539,6 +539,46 @@ int gbx_abea_meth_sites_host(int64_t n_reads, const int64_t *ref_off, const int3
                              const int32_t *ref_start_pos, const uint8_t *rc, const int64_t *rec_off, const gbx_abea_pair *rec,
                              int64_t site_cap, gbx_abea_meth_site *sites, gbx_abea_meth_job *jobs, int64_t *n_sites,
                              int64_t seq_cap, char *seq_arena, int64_t *seq_bytes);
+/* The site planner on the device, behind gbx_abea_event_record_device: the inputs of gbx_abea_meth_sites_host resident in
+ * device memory, the output byte for byte the host planner's.  pass COUNT writes d_site_off[n_reads + 1] and
+ * d_byte_off[n_reads + 1] (exclusive scans, the totals in entry n_reads) and d_bad[r] = 1 for a read whose record runs
+ * against rc[r] (the host planner refuses the batch; what such a read counts means nothing).  pass FILL writes, at the offsets of a count pass,
+ * the sites, 2 * n_sites jobs and the strings; a read whose sites would end past site_cap or whose strings would end past
+ * seq_cap is left unwritten.  d_work: gbx_abea_meth_sites_work bytes (ref_bytes, the bytes of the reference arena, does not
+ * enter it today: a closed group is decided in registers).  A record longer than 2^31 - 1 pairs is read that far.  Nothing
+ * is synchronised. */
+#define GBX_ABEA_METH_SITES_COUNT 1
+#define GBX_ABEA_METH_SITES_FILL  2
+int64_t gbx_abea_meth_sites_work(int64_t n_reads, int64_t ref_bytes);
+int gbx_abea_meth_sites_device(int pass, int64_t n_reads, const int64_t *d_ref_off, const int32_t *d_ref_len,
+                               const char *d_ref_arena, const int32_t *d_ref_start_pos, const uint8_t *d_rc,
+                               const int64_t *d_rec_off, const gbx_abea_pair *d_rec, void *d_work, int64_t *d_site_off,
+                               int64_t *d_byte_off, uint8_t *d_bad, int64_t site_cap, gbx_abea_meth_site *d_sites,
+                               gbx_abea_meth_job *d_jobs, int64_t seq_cap, char *d_seq_arena, void *stream);
+/* The half of gbx_abea_meth_plan_host that needs the host C library: the p7_FLogsum table, trans[n_reads][NTRANS] and the
+ * two flank tables, in its bits.  gbx_abea_meth_plan_host calls it. */
+int gbx_abea_meth_tables_host(int64_t n_reads, const double *events_per_base, float *flogsum, float *trans, int64_t flank_len,
+                              float *pre_flank, float *post_flank);
+/* The other half on the device: d_order[n_jobs] and d_class_off[GBX_ABEA_METH_NCLASS + 1] as gbx_abea_meth_plan_host gives
+ * them (class by k-mer count, longest first, ties in input order), and its per-job checks: *d_first_bad (device int64) is
+ * the lowest job that gbx_abea_meth_plan_host would refuse, INT64_MAX when there is none.  The score kernel indexes events
+ * with what the jobs say: read d_class_off and d_first_bad back, and do not launch the score when a job is bad.
+ * max_rows_bits (1 .. 30): the sort key's bits for the row count; flank_len <= 2^max_rows_bits.  d_work:
+ * gbx_abea_meth_order_work bytes.  Nothing is synchronised. */
+int64_t gbx_abea_meth_order_work(int64_t n_jobs);
+int gbx_abea_meth_order_device(int64_t n_jobs, const gbx_abea_meth_job *d_jobs, int64_t seq_bytes, int64_t n_reads,
+                               const int64_t *d_event_off, int64_t flank_len, int max_rows_bits, void *d_work,
+                               int32_t *d_order, int64_t *d_class_off, int64_t *d_first_bad, void *stream);
+/* The TSV f5c call-methylation prints (f5c.c:1629-1653; with_header: the header of meth_main.c:449-457 first).  Site s
+ * with scores[2 s] unmethylated and scores[2 s + 1] methylated: contig, (version 2: strand,) start, end, read name, the
+ * difference of the two scores as doubles, both scores ("%.2lf"), strands_scored 1, n_cpg and the context, ctx_len bytes at
+ * ctx_off of the read's disambiguated reference segment.  A site is printed unless (clip_start != -1 && start_position <
+ * clip_start) || (clip_end != -1 && end_position >= clip_end).  *n_bytes: the bytes of text; more than cap: GBX_ERR_ARG
+ * with the need in *n_bytes (call with 0 / NULL to size). */
+int gbx_abea_meth_tsv_host(int64_t n_sites, const gbx_abea_meth_site *sites, const float *scores, int64_t n_reads,
+                           const char *const *read_names, const char *const *contig_names, const uint8_t *rc,
+                           const int64_t *ref_off, const int32_t *ref_len, const char *ref_arena, int version, int32_t clip_start,
+                           int32_t clip_end, int with_header, int64_t cap, char *out, int64_t *n_bytes);
 
 /* abea, calibration and the event-alignment record: what f5c runs per read between align() and the methylation score.
  * Replaces  int32_t postalign(alignment, base_to_event_map, events_per_base, sequence, n_kmers, event_alignment, n_events)
