@@ -19,18 +19,17 @@
 //
 // Every loop is counted: the unit loop by the unit total, the base loop by (KC_CHUNK + k - 1) / 16 + 2 words, the sweeps
 // by the slice size.  Base codes are masked with & 3, so a table index never leaves the slice whatever the input bytes.
+//
+// The unit size, the sweeps' split and the slice rule are in kmer_split.h, which the plain host compiler takes as well:
+// tests/hostcheck/kmer_split_check.cpp holds the tests' boundary cases (tests/kmer_cases.py) against it.
 #include <algorithm>
 #include "dev_prims.h"
+#include "kmer_split.h"
 
 namespace gbx {
 namespace {
 
-constexpr int KC_CHUNK = 256;                      // positions per unit of the count pass
-constexpr int KC_THREADS = 256;
 constexpr int KC_COUNT_BLOCKS = 256 * 8;           // count pass grid: eight workgroups of four wavefronts per CU
-constexpr int KC_SWEEP = KC_THREADS * 4;           // counters a workgroup of the sweeps covers per round (one uint4 a lane)
-constexpr int KC_MAX_BLOCKS = 2048;                // workgroups of the sweeps
-constexpr long long KC_SLICE = 1ll << 30;          // counters per slice
 constexpr long long KC_TOO_MANY = 1ll << 32;       // n_positions from which nothing is counted (32-bit counters)
 
 struct KmerLayout {
@@ -41,23 +40,13 @@ struct KmerLayout {
 KmerLayout kmer_layout(int k, long long n_reads)
 {
     KmerLayout L;
-    const long long space = 1ll << (2 * k);
-    L.slice_n = std::min(space, KC_SLICE);
-    L.n_slices = space / L.slice_n;
+    L.slice_n = kmer_slice_n(k);
+    L.n_slices = kmer_n_slices(k);
     L.o_blk = align256((size_t)(n_reads + 1) * 8);                     // unit prefix sum: n_reads + 1 int64
     L.o_base = L.o_blk + align256((size_t)KC_MAX_BLOCKS * 2 * 8);      // per-workgroup selected count and first slot
     L.o_table = L.o_base + 256;                                        // the selection's running total
     L.total = L.o_table + (size_t)L.slice_n * 4 + 64;
     return L;
-}
-
-// The sweeps' split of a slice: nb workgroups of `per` counters each (a multiple of KC_SWEEP), the last one shorter.
-void sweep_split(long long n, int *nb, long long *per)
-{
-    const long long rounds = (n + KC_SWEEP - 1) / KC_SWEEP;
-    const long long rpb = (rounds + KC_MAX_BLOCKS - 1) / KC_MAX_BLOCKS;
-    *per = rpb * KC_SWEEP;
-    *nb = (int)((n + *per - 1) / *per);
 }
 
 // One workgroup: unit_off[r] = units of reads 0 .. r-1 (KC_CHUNK positions each, max(0, len - k) positions per read),
@@ -70,9 +59,8 @@ __global__ void __launch_bounds__(1024) kmer_units_kernel(const int32_t *read_le
     const long long per = (n_reads + 1023) / 1024, r0 = std::min(n_reads, t * per), r1 = std::min(n_reads, r0 + per);
     long long u = 0, p = 0;
     for (long long r = r0; r < r1; ++r) {
-        const long long np = std::max(0ll, (long long)read_len[r] - k);
-        u += (np + KC_CHUNK - 1) / KC_CHUNK;
-        p += np;
+        u += kmer_read_units(read_len[r], k);
+        p += std::max(0ll, (long long)read_len[r] - k);
     }
     sh_u[t] = u; sh_p[t] = p;
     __syncthreads();
@@ -85,8 +73,7 @@ __global__ void __launch_bounds__(1024) kmer_units_kernel(const int32_t *read_le
     long long run = sh_u[t] - u;
     for (long long r = r0; r < r1; ++r) {
         unit_off[r] = run;
-        const long long np = std::max(0ll, (long long)read_len[r] - k);
-        run += (np + KC_CHUNK - 1) / KC_CHUNK;
+        run += kmer_read_units(read_len[r], k);
     }
     if (t == 1023) {
         unit_off[n_reads] = sh_u[1023];

@@ -10,7 +10,7 @@ def canonical_codes(reads, k):
         npos = n - k
         if npos <= 0:
             continue
-        b = reads.enc[o:o + n].astype(np.uint64)
+        b = (reads.enc[o:o + n] & 3).astype(np.uint64)               # gbx.h: of a byte above 3 the kernels use the low two bits
         fwd = np.zeros(npos, dtype=np.uint64)
         rev = np.zeros(npos, dtype=np.uint64)
         for j in range(k):
