@@ -65,10 +65,16 @@ struct BswPairs {
 constexpr int WS_HDR = 4 * HDR;
 struct BswWork {
     int32_t *counts, *cursors, *base, *bad, *order, *wband;
-    // lane path (bsw_lane_kernel): pairs sorted by (query length, seed score): lbase[] = exclusive prefix of the key
-    // histogram (LANE_BINS + 1 entries), lrank[] = a pair's rank in its bin, lorder[] = sorted pair indices, lchunk[] = per-launch
-    // chunk cursors.  Keys, and with them lorder[], hold the sort's group L first and group S behind it (lane_row).
-    int32_t *lbase, *lrank, *lorder, *lchunk;
+    // lane path (bsw_lane_kernel): pairs sorted by (query length, seed score): lbase[r << 8] = first position of key row r in
+    // lorder[] (LANE_ROWS + 1 entries in use), lorder[] = sorted pair indices, lchunk[] = per-launch chunk cursors.  Keys, and
+    // with them lorder[], hold the sort's group L first and group S behind it (lane_row).  lidx[] is the sort's temporary.
+    int32_t *lbase, *lidx, *lorder, *lchunk;
+    // the lane sort's other temporaries (bsw_lsort_*): lh0[] = clamped seed scores beside lidx[]; lm1[row][tile] and lrowtot[row]
+    // = level 1's counts; lrowbase[row] and lslabfirst[row] = the rows' first positions and first slabs (bsw_lsort_rows_kernel);
+    // lm2[] = level 2's counts by (row, seed score, slab); ltiles = tiles of LSORT_TILE pairs
+    uint8_t *lh0 = nullptr;
+    int32_t *lm1 = nullptr, *lrowtot = nullptr, *lrowbase = nullptr, *lslabfirst = nullptr, *lm2 = nullptr;
+    int ltiles = 0;
 };
 
 __host__ __device__ inline int cls_of(int qlen, int bound)
@@ -98,8 +104,9 @@ __host__ __device__ inline bool lane_ok(int lane_on, int qlen, int tlen, int h0,
 // The sort can run in two groups (queue_prepare, GBX_BSW_SORT_SPLIT=1): group L, the queries from LANE_SPLIT_Q on in both formats - the launches that
 // hold the most LDS and run longest - and group S, the rest.  The key rows of L come first, so that L's stretch of lbase[] and
 // lorder[] is complete once L alone is counted, scanned and placed: rows [0, LANE_L_ROWS) = L compact, L wide; the rows
-// behind them = S compact, S wide.  lbase[LANE_L_BINS] is both L's total and the base of S's lists: L's scan writes it, S's
-// only reads it.  The cut is a class bound of both formats, so a launch's rows lie in one group.
+// behind them = S compact, S wide.  lbase[LANE_L_BINS] is both L's total and the base of S's lists: L's sort writes it
+// (bsw_lsort_rows_kernel with grp 0 or -1), S's only reads it.  The cut is a class bound of both formats, so a launch's rows
+// lie in one group.
 constexpr int LANE_SPLIT_Q = 80;
 constexpr int LANE_L_QROWS = LANE_QMAX + 1 - LANE_SPLIT_Q;   // key rows of group L per format
 constexpr int LANE_L_ROWS = 2 * LANE_L_QROWS;
@@ -243,7 +250,7 @@ __global__ void __launch_bounds__(CLS_THREADS) bsw_classify_kernel(BswDev prm, B
                 P.out[k] = r;
             }
         } else if (lane_ok(prm.lane_on, qlen, tlen, h0, prm.max_mat)) {
-            // bsw_lane_kernel's pair (sorted by bsw_lane_sort_kernel)
+            // bsw_lane_kernel's pair (sorted by the bsw_lsort_* kernels)
         } else {
             const int bound = max(h0, 0) + qlen * max(prm.max_mat, 0);
             bin = bin_of(prm.remap[cls_of(qlen, bound)], tlen);
@@ -595,45 +602,237 @@ __global__ void __launch_bounds__(64) bsw_lds_kernel(BswDev prm, BswPairs P, Bsw
 // pairs of a wavefront lives in LDS, one 32-bit word per cell (h:14 | e:13 | query code x 6 : 5), column-major
 // ([column][lane]: every access is bank-conflict free whatever column each lane is at).  The wavefront runs the rows
 // in lock-step (a row lasts as long as its widest window), which costs nothing when the lanes' windows agree: the
-// pairs are sorted by (query length, seed score) first (bsw_lane_sort_kernel).
-// grp: 0 = the pairs of group L only, 1 = of group S only (every pass reads every pair's lengths: 24 MB on 'large'), -1 = all
-__global__ void __launch_bounds__(256) bsw_lane_sort_kernel(BswDev prm, BswPairs P, int64_t n, BswWork W, int pass, int grp)
+// pairs are sorted by (query length, seed score) first (bsw_lsort_*).
+//
+// The lane sort: a counting sort in two levels, most significant first, whose histograms live in LDS.  (One global atomic a
+// pair into the 81 920 bins ran at the chip's rate for scattered atomics, 16 G/s: 0.13 ms for 'large', and the one-block scan
+// of the bins 0.035 ms more - profiles/bsw_step_ends.)  Level 1 orders by key row: a block takes a tile of LSORT_TILE pairs,
+// counts them by row (hist1), a block per row turns lm1[row][tile] into the tile's first position within the row and the
+// row's total (scan1), one wavefront turns the totals into the rows' first positions and first slabs (rows: tables that every
+// later block reads, and lbase[] for the lane kernels), and the tiles write (pair, clamped seed score) to lidx[] / lh0[] in
+// row order (place1).  Level 2 orders a row by seed score: the row is cut into slabs of at most LSORT_TILE consecutive
+// positions - a job whose queries all have one length is one row, and a block per row would be serial - a block counts a
+// slab's 256 scores (hist2), a block per row scans lm2[] in (score, slab) order (scan2) and the slabs write lorder[]
+// (place2).  Every wavefront counts on a histogram of its own and takes its ranks from returning LDS atomics of that
+// histogram: no other wavefront's timing enters a rank, so two runs over the same pairs give the same order and the same
+// chunks.  Every table is written whole: nothing has to be zeroed in front of the sort, and the rows kernel zeroes the
+// chunk cursors.
+// grp: 0 = the pairs of group L only, 1 = of group S only (both read every pair's lengths: 24 MB on 'large'), -1 = all.  Group S
+// counts from lbase[LANE_L_BINS], L's total, and writes neither L's stretch of lbase[] and lorder[] nor lchunk[]: L's
+// kernels are running by then.
+constexpr int LSORT_TILE = 4096, LSORT_THREADS = 256, LSORT_WAVES = LSORT_THREADS / 64, LSORT_PER = LSORT_TILE / LSORT_THREADS;
+static_assert(LSORT_TILE / LSORT_WAVES <= 1024, "a rank within a wavefront's share of a tile has ten bits");
+
+// the sort key of pair k, or -1 for a pair this sort leaves out
+__device__ inline int lsort_key(const BswDev &prm, const BswPairs &P, int64_t k, int grp)
 {
-    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= n) return;
     const int qlen = P.len2[k], tlen = P.len1[k], h0 = P.h0[k];
-    if (!lane_ok(prm.lane_on, qlen, tlen, h0, prm.max_mat) || tlen > GBX_BSW_MAX_TLEN) return;
+    if (!lane_ok(prm.lane_on, qlen, tlen, h0, prm.max_mat) || tlen > GBX_BSW_MAX_TLEN) return -1;
     const int key = lane_key(qlen, h0, prm.max_mat);
-    if (grp >= 0 && (key >= LANE_L_BINS ? 1 : 0) != grp) return;
-    // one pass of atomics: the count's old value is the pair's rank in its bin, kept for the placement (2 M scattered atomics
-    // cost 0.13 ms whether they return a value or not: the second pass used to pay that again for its cursors)
-    if (pass == 0) W.lrank[k] = atomicAdd(&W.lbase[key + 1], 1);
-    else W.lorder[W.lbase[key] + W.lrank[k]] = (int)k;
+    return grp >= 0 && (key >= LANE_L_BINS ? 1 : 0) != grp ? -1 : key;
 }
-// exclusive prefix of the key histogram over the bins [LO, LO + NB) in place: lbase[k + 1] holds count(k) on entry, lbase[k] =
-// pairs with a key below k on exit (one block).  lbase[LO] is read, never written: group L's total is the base of group S's lists.
-// (The range at compile time: with it as kernel arguments the scan of half the bins took 80 us, of all bins 67 us, against 34 us.)
-template <int LO, int NB>
-__global__ void __launch_bounds__(1024) bsw_lane_scan_kernel(BswWork W)
+// inclusive prefix sum over the wavefront
+__device__ inline int wave_incl_scan(int v)
 {
-    constexpr int PER = (NB + 1023) / 1024, HI = LO + NB;
-    __shared__ int part[1024];
-    const int tid = threadIdx.x;
-    int sum = 0;
-    for (int k = 0; k < PER; ++k) { const int b = LO + tid * PER + k; if (b < HI) sum += W.lbase[b + 1]; }
-    part[tid] = sum;
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(v, d, 64); if (lane >= d) v += o; }
+    return v;
+}
+// inclusive prefix sum over a block of LSORT_THREADS; total = the block's sum.  wsum: LSORT_WAVES ints of LDS; two barriers
+__device__ inline int lsort_block_scan(int v, int *wsum, int &total)
+{
+    const int incl = wave_incl_scan(v), wave = threadIdx.x >> 6;
+    __syncthreads();                                            // (the previous round's readers of wsum[] are done)
+    if ((threadIdx.x & 63) == 63) wsum[wave] = incl;
     __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const int add = tid >= d ? part[tid - d] : 0;
-        __syncthreads();
-        part[tid] += add;
-        __syncthreads();
+    int before = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < LSORT_WAVES; ++w) { const int s = wsum[w]; total += s; if (w < wave) before += s; }
+    return incl + before;
+}
+// level 1, counts: lm1[row][tile] = pairs of the tile in the row
+__global__ void __launch_bounds__(LSORT_THREADS) bsw_lsort_hist1_kernel(BswDev prm, BswPairs P, int64_t n, BswWork W, int grp)
+{
+    __shared__ int hist[LSORT_WAVES][LANE_ROWS];
+    const int tid = threadIdx.x, wave = tid >> 6, tile = blockIdx.x;
+    for (int r = tid; r < LSORT_WAVES * LANE_ROWS; r += LSORT_THREADS) (&hist[0][0])[r] = 0;
+    __syncthreads();
+    const int64_t first = (int64_t)tile * LSORT_TILE + wave * (LSORT_TILE / LSORT_WAVES) + (tid & 63);
+#pragma unroll
+    for (int j = 0; j < LSORT_PER; ++j) {
+        const int64_t k = first + j * 64;
+        const int key = k < n ? lsort_key(prm, P, k, grp) : -1;
+        if (key >= 0) atomicAdd(&hist[wave][key >> 8], 1);
     }
-    int run = (LO ? W.lbase[LO] : 0) + part[tid] - sum;
-    for (int k = 0; k < PER; ++k) {
-        const int b = LO + tid * PER + k;
-        if (b < HI) { const int c = W.lbase[b + 1]; run += c; W.lbase[b + 1] = run; }
+    __syncthreads();
+    for (int r = tid; r < LANE_ROWS; r += LSORT_THREADS) {
+        int c = 0;
+#pragma unroll
+        for (int w = 0; w < LSORT_WAVES; ++w) c += hist[w][r];
+        W.lm1[(int64_t)r * W.ltiles + tile] = c;
     }
+}
+// level 1, scan: a block per row; lm1[row][tile] = pairs of the row in the tiles in front, lrowtot[row] = pairs of the row
+__global__ void __launch_bounds__(LSORT_THREADS) bsw_lsort_scan1_kernel(BswWork W)
+{
+    __shared__ int wsum[LSORT_WAVES];
+    int32_t *m = W.lm1 + (int64_t)blockIdx.x * W.ltiles;
+    int carry = 0;
+    for (int t0 = 0; t0 < W.ltiles; t0 += LSORT_THREADS) {
+        const int t = t0 + (int)threadIdx.x, c = t < W.ltiles ? m[t] : 0;
+        int total;
+        const int incl = lsort_block_scan(c, wsum, total);
+        if (t < W.ltiles) m[t] = carry + incl - c;
+        carry += total;
+    }
+    if (threadIdx.x == 0) W.lrowtot[blockIdx.x] = carry;
+}
+// level 1, the rows' tables, written once by one wavefront: lrowbase[r] = first position of row r in lorder[], lslabfirst[r] =
+// slabs of the rows in front of r (LANE_ROWS + 1 entries each).  It also writes the group's rows' first positions to lbase[] for
+// the lane kernels and zeroes their chunk cursors.
+__global__ void __launch_bounds__(64) bsw_lsort_rows_kernel(BswWork W, int grp)
+{
+    const int rlo = grp == 1 ? LANE_L_ROWS + 1 : 0, rhi = grp == 0 ? LANE_L_ROWS : LANE_ROWS;
+    int pos = grp == 1 ? W.lbase[LANE_L_BINS] : 0, slabs = 0;
+    for (int r0 = 0; r0 < LANE_ROWS; r0 += 64) {
+        const int r = r0 + (int)threadIdx.x;
+        const int c = r < LANE_ROWS ? W.lrowtot[r] : 0, sl = (c + LSORT_TILE - 1) / LSORT_TILE;
+        const int ci = wave_incl_scan(c), si = wave_incl_scan(sl);
+        if (r < LANE_ROWS) {
+            W.lrowbase[r] = pos + ci - c;
+            W.lslabfirst[r] = slabs + si - sl;
+            if (r >= rlo && r <= rhi) W.lbase[r << 8] = pos + ci - c;
+        }
+        pos += __shfl(ci, 63, 64);
+        slabs += __shfl(si, 63, 64);
+    }
+    if (threadIdx.x == 0) {
+        W.lrowbase[LANE_ROWS] = pos;
+        W.lslabfirst[LANE_ROWS] = slabs;
+        if (rhi == LANE_ROWS) W.lbase[LANE_ROWS << 8] = pos;
+    }
+    if (grp != 1) W.lchunk[threadIdx.x] = 0;
+}
+// level 1, placement: lidx[] / lh0[] = the pairs and their clamped seed scores in row order (tile after tile within a row)
+__global__ void __launch_bounds__(LSORT_THREADS) bsw_lsort_place1_kernel(BswDev prm, BswPairs P, int64_t n, BswWork W, int grp)
+{
+    __shared__ int cur[LSORT_WAVES][LANE_ROWS];
+    const int tid = threadIdx.x, wave = tid >> 6, tile = blockIdx.x;
+    for (int r = tid; r < LSORT_WAVES * LANE_ROWS; r += LSORT_THREADS) (&cur[0][0])[r] = 0;
+    __syncthreads();
+    const int64_t first = (int64_t)tile * LSORT_TILE + wave * (LSORT_TILE / LSORT_WAVES) + (tid & 63);
+    int kr[LSORT_PER];                                          // key << 10 | rank among the wavefront's pairs of the row
+#pragma unroll
+    for (int j = 0; j < LSORT_PER; ++j) {
+        const int64_t k = first + j * 64;
+        const int key = k < n ? lsort_key(prm, P, k, grp) : -1;
+        kr[j] = key >= 0 ? key << 10 | atomicAdd(&cur[wave][key >> 8], 1) : -1;
+    }
+    __syncthreads();
+    // counts -> the first position of each wavefront's pairs of the row
+    for (int r = tid; r < LANE_ROWS; r += LSORT_THREADS) {
+        int run = W.lrowbase[r] + W.lm1[(int64_t)r * W.ltiles + tile];
+#pragma unroll
+        for (int w = 0; w < LSORT_WAVES; ++w) { const int c = cur[w][r]; cur[w][r] = run; run += c; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < LSORT_PER; ++j) {
+        if (kr[j] < 0) continue;
+        const int pos = cur[wave][kr[j] >> 18] + (kr[j] & 1023);
+        W.lidx[pos] = (int)(first + j * 64);
+        W.lh0[pos] = (uint8_t)(kr[j] >> 10);
+    }
+}
+// The slab of this block: row, ordinal in the row, slabs of the row, first position and pairs.  False for a block behind the last slab.
+// shrow: one int of LDS; a barrier for the blocks that stay.
+struct LsortSlab { int row, s, nsl, p0, cnt, m2; };
+__device__ inline bool lsort_slab(const BswWork &W, int *shrow, LsortSlab &sl)
+{
+    const int32_t *rowbase = W.lrowbase, *slabfirst = W.lslabfirst;
+    const int b = blockIdx.x;
+    if (b >= slabfirst[LANE_ROWS]) return false;                // (uniform over the block)
+    for (int r = threadIdx.x; r < LANE_ROWS; r += LSORT_THREADS) if (slabfirst[r] <= b && b < slabfirst[r + 1]) *shrow = r;
+    __syncthreads();
+    sl.row = *shrow;
+    sl.s = b - slabfirst[sl.row];
+    sl.nsl = slabfirst[sl.row + 1] - slabfirst[sl.row];
+    const int c = rowbase[sl.row + 1] - rowbase[sl.row], left = c - sl.s * LSORT_TILE;
+    sl.p0 = rowbase[sl.row] + sl.s * LSORT_TILE;
+    sl.cnt = left < LSORT_TILE ? left : LSORT_TILE;
+    sl.m2 = slabfirst[sl.row] * 256;                            // the row's stretch of lm2[]: [score][slab]
+    return true;
+}
+// level 2, counts: lm2[row's stretch][score][slab] = pairs of the slab with the score
+__global__ void __launch_bounds__(LSORT_THREADS) bsw_lsort_hist2_kernel(BswWork W)
+{
+    __shared__ int hist[LSORT_WAVES][256];
+    __shared__ int shrow;
+    const int tid = threadIdx.x, wave = tid >> 6;
+    for (int r = tid; r < LSORT_WAVES * 256; r += LSORT_THREADS) (&hist[0][0])[r] = 0;
+    LsortSlab sl;
+    if (!lsort_slab(W, &shrow, sl)) return;
+    const int first = wave * (LSORT_TILE / LSORT_WAVES) + (tid & 63);
+#pragma unroll
+    for (int j = 0; j < LSORT_PER; ++j) {
+        const int i = first + j * 64;
+        if (i < sl.cnt) atomicAdd(&hist[wave][W.lh0[sl.p0 + i]], 1);
+    }
+    __syncthreads();
+    static_assert(LSORT_THREADS == 256, "a thread per score");
+    int c = 0;
+#pragma unroll
+    for (int w = 0; w < LSORT_WAVES; ++w) c += hist[w][tid];
+    W.lm2[sl.m2 + tid * sl.nsl + sl.s] = c;
+}
+// level 2, scan: a block per row; lm2[] of the row = first position in lorder[] of each (score, slab)
+__global__ void __launch_bounds__(LSORT_THREADS) bsw_lsort_scan2_kernel(BswWork W)
+{
+    __shared__ int wsum[LSORT_WAVES];
+    const int row = blockIdx.x, sf = W.lslabfirst[row], cells = (W.lslabfirst[row + 1] - sf) * 256;
+    int32_t *m = W.lm2 + sf * 256;
+    int carry = W.lrowbase[row];
+    for (int t0 = 0; t0 < cells; t0 += 4 * LSORT_THREADS) {     // (cells is a multiple of 256: uniform trip count)
+        const int t = t0 + 4 * (int)threadIdx.x;
+        int c[4], sum = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { c[k] = t + k < cells ? m[t + k] : 0; sum += c[k]; }
+        int total;
+        int run = carry + lsort_block_scan(sum, wsum, total) - sum;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { if (t + k < cells) m[t + k] = run; run += c[k]; }
+        carry += total;
+    }
+}
+// level 2, placement: lorder[] = the pairs of the slab by seed score
+__global__ void __launch_bounds__(LSORT_THREADS) bsw_lsort_place2_kernel(BswWork W)
+{
+    __shared__ int cur[LSORT_WAVES][256];
+    __shared__ int shrow;
+    const int tid = threadIdx.x, wave = tid >> 6;
+    for (int r = tid; r < LSORT_WAVES * 256; r += LSORT_THREADS) (&cur[0][0])[r] = 0;
+    LsortSlab sl;
+    if (!lsort_slab(W, &shrow, sl)) return;
+    const int first = wave * (LSORT_TILE / LSORT_WAVES) + (tid & 63);
+    int hr[LSORT_PER];                                          // score << 10 | rank among the wavefront's pairs of the score
+#pragma unroll
+    for (int j = 0; j < LSORT_PER; ++j) {
+        const int i = first + j * 64;
+        hr[j] = -1;
+        if (i < sl.cnt) { const int h = W.lh0[sl.p0 + i]; hr[j] = h << 10 | atomicAdd(&cur[wave][h], 1); }
+    }
+    __syncthreads();
+    {
+        int run = W.lm2[sl.m2 + tid * sl.nsl + sl.s];
+#pragma unroll
+        for (int w = 0; w < LSORT_WAVES; ++w) { const int c = cur[w][tid]; cur[w][tid] = run; run += c; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < LSORT_PER; ++j)
+        if (hr[j] >= 0) W.lorder[cur[wave][hr[j] >> 10] + (hr[j] & 1023)] = W.lidx[sl.p0 + first + j * 64];
 }
 
 // Two columns of the compact lane kernel, scheduled by hand (28 VALU instructions; the compiler's version of the same
@@ -1542,12 +1741,32 @@ int make_dev_params(const gbx_bsw_params *p, BswDev *d)
 
 }  // namespace
 
-// ints: header | order[n] | wband[n] | lorder[n] | lrank[n] | lbase[LANE_BINS + 1] (+pad) | lchunk[64]
+// ints: header | order[n] | wband[n] | lorder[n] | lidx[n] | lbase[LANE_BINS + 1] (+pad) | lchunk[64] | the lane sort's
+// temporaries: lh0[n] (bytes, padded to ints) | lm1[LANE_ROWS][tiles] | lrowtot, lrowbase, lslabfirst (WS_LROWS ints each) |
+// lm2[tiles + LANE_ROWS][256]
+// (tiles + LANE_ROWS bounds the slabs: a row of c pairs has ceil(c / LSORT_TILE) <= c / LSORT_TILE + 1 of them)
 constexpr int64_t WS_LANE = (int64_t)(LANE_BINS + 64) + 64;
+constexpr int64_t WS_LROWS = LANE_ROWS + 64;                    // LANE_ROWS + 1 entries in use
+static int64_t lsort_tiles(int64_t n) { return (n + LSORT_TILE - 1) / LSORT_TILE; }
+static int64_t lsort_h0_ints(int64_t n) { return ((n + 3) / 4 + 63) & ~(int64_t)63; }
 size_t bsw_workspace_bytes(int64_t n)
 {
-    return (size_t)(WS_HDR + 4 * (n > 0 ? n : 0) + WS_LANE) * sizeof(int32_t);
+    n = n > 0 ? n : 0;
+    const int64_t tiles = lsort_tiles(n);
+    return (size_t)(WS_HDR + 4 * n + WS_LANE + lsort_h0_ints(n) + LANE_ROWS * tiles + 3 * WS_LROWS + (tiles + LANE_ROWS) * 256) * sizeof(int32_t);
 }
+
+// lorder[] and the key rows' first positions (LANE_ROWS + 1 values) of the last lane sort on a workspace of n pairs, for the tests
+int bsw_debug_lane_lists(const void *d_work, int64_t n, int32_t *h_order, int32_t *h_row_first)
+{
+    if (n <= 0) return GBX_ERR_ARG;
+    const int32_t *wi = (const int32_t *)d_work, *lbase = wi + WS_HDR + 4 * n;
+    GBX_HIP(hipDeviceSynchronize());
+    GBX_HIP(hipMemcpy(h_order, wi + WS_HDR + 2 * n, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    GBX_HIP(hipMemcpy2D(h_row_first, sizeof(int32_t), lbase, 256 * sizeof(int32_t), sizeof(int32_t), LANE_ROWS + 1, hipMemcpyDeviceToHost));
+    return GBX_OK;
+}
+int bsw_lane_sort_tile() { return LSORT_TILE; }
 
 // Expands the packed image of a byte arena (two base codes per byte, host_pipeline.h: pack4) over [lo, hi) of the
 // arena, lo even: 4 x 8 packed bytes -> 4 x 16 codes per thread, a block's four rounds each one contiguous 4 KB (in a
@@ -1671,6 +1890,7 @@ struct BswCall {
     bool packed_lanes;                          // ... and they read the packed bases as they were uploaded
     int phase;                                  // BswChunkPrep::phase
     hipStream_t s_cls;                          // classify's stream
+    hipStream_t s_rows, s_last;                 // the row-kernel classes' stream (with the lane launches behind them); the lane sort's when not `ahead`
     hipEvent_t ev_pre, ev_aux;                  // behind classify (recorded when `ahead`), behind the lane sort
     bool split;                                 // the lane sort in two groups: group L's launches wait for ev_aux_first only
     hipEvent_t ev_aux_first;                    // behind the sort of group L (recorded when `split`)
@@ -1686,7 +1906,15 @@ static int plan_call(BswCall &c)
     // 1.9 ms for a third of the job; GBX_BSW_PREP=0 keeps that order).
     static const bool prep_off = switched_off("GBX_BSW_PREP");
     c.ahead = prep && prep->uploaded && c.join_events && !prep_off;
-    c.s_cls = c.ahead ? c.ss->pre[0] : c.s;
+    // The lane sort is what the lane launches wait for, classify and the row-kernel classes are not: with the lane path on, the
+    // sort goes to the caller's stream, where its first kernel is the call's first dispatch, and classify, the row-kernel classes
+    // and the lane launches that used to follow them on the caller's stream go to the last side stream, behind the fork.  The
+    // two streams swap their parts, nothing else moves: the unpacking pass of a staged chunk stays on the caller's stream, ahead
+    // of the fork (queue_prepare).  (A pipelined chunk's passes are on the urgent streams: as before.)
+    const bool swap = c.dev.lane_on && !c.ahead;
+    c.s_rows = swap ? c.ss->side[SideStreams::N - 1] : c.s;
+    c.s_last = swap ? c.s : c.ss->side[SideStreams::N - 1];
+    c.s_cls = c.ahead ? c.ss->pre[0] : c.s_rows;
     // A chunk whose pairs all go to the lane kernels (the host entry has counted: rows_pairs == 0) leaves out the row-kernel
     // classes, twenty-one near-empty launches that each wait for LDS behind the lane kernels, and its bases stay packed: the
     // lane kernels read the nibbles (PACKED).  Beside the previous chunk's lane kernels the unpacking took 0.5-1.0 ms
@@ -1726,38 +1954,37 @@ static int queue_prepare(BswCall &c)
         GBX_HIP(hipStreamWaitEvent(ss->pre[1], prep->uploaded, 0));
     }
     if (!c.packed_lanes && prep && prep->ref_packed) {
-        // from the call's watermark (everything below it is expanded; chunks that ran PACKED expanded nothing) - s_cls waits
-        // for this chunk's uploads, and the host entry queues the chunks' uploads in order, so all of [from, hi) is up
+        // from the call's watermark (everything below it is expanded; chunks that ran PACKED expanded nothing) - `su` waits
+        // for this chunk's uploads, and the host entry queues the chunks' uploads in order, so all of [from, hi) is up.
+        // Every kernel that reads the expanded bases is ordered behind the unpacking: `ahead`, it is on classify's urgent stream
+        // in front of classify, and the kernel streams wait for ev_pre, recorded behind classify; otherwise it is on the
+        // caller's stream - the stream of a staged chunk's uploads, or the one that waits for them - in front of the fork that
+        // the side streams start from (below, or in bsw_launch with the lane path off) and of all that follows on the stream.
+        hipStream_t su = c.ahead ? c.s_cls : c.s;
         const int64_t from_r = prep->unp_r ? *prep->unp_r : prep->lo_r, from_q = prep->unp_q ? *prep->unp_q : prep->lo_q;
-        if ((rc = bsw_unpack4(prep->ref_packed, prep->ref_bytes, from_r, prep->hi_r, c.s_cls)) ||
-            (rc = bsw_unpack4(prep->qer_packed, prep->qer_bytes, from_q, prep->hi_q, c.s_cls)))
+        if ((rc = bsw_unpack4(prep->ref_packed, prep->ref_bytes, from_r, prep->hi_r, su)) ||
+            (rc = bsw_unpack4(prep->qer_packed, prep->qer_bytes, from_q, prep->hi_q, su)))
             return rc;
         if (prep->unp_r && prep->hi_r > *prep->unp_r) *prep->unp_r = prep->hi_r;
         if (prep->unp_q && prep->hi_q > *prep->unp_q) *prep->unp_q = prep->hi_q;
     }
-    GBX_HIP(hipMemsetAsync(c.W.counts, 0, WS_HDR * sizeof(int32_t), c.s_cls));        // the workspace's header arrays
-    // The lane sort (0.2 ms on 'large': a pass of scattered atomics, a scan, a placement pass) runs on a side stream of its
-    // own, beside classify and the row-kernel classes on the caller's stream, which do not need it; the lane launches wait
-    // for it.  lbase[] and lchunk[] are zeroed once, also when the sort runs in two groups.
+    // The lane sort (bsw_lsort_*: two levels of count, scan, place, and the rows' tables between level 1's scan and place)
+    // runs beside classify and the row-kernel classes, which do not need it; the lane launches wait for it.  It needs nothing zeroed in front of it and zeroes lchunk[] itself, once,
+    // also when it runs in two groups.  The side streams are forked first: classify's starts beside the sort.
+    if (c.dev.lane_on && !c.ahead && (rc = ss->fork(c.s))) return rc;
     if (c.dev.lane_on) {
-        hipStream_t so;
-        if (c.ahead) {
-            so = ss->pre[1];
-            GBX_HIP(hipMemsetAsync(c.W.lbase, 0, (size_t)WS_LANE * sizeof(int32_t), so));
-        } else {
-            GBX_HIP(hipMemsetAsync(c.W.lbase, 0, (size_t)WS_LANE * sizeof(int32_t), c.s));
-            if ((rc = ss->fork(c.s))) return rc;
-            so = ss->side[SideStreams::N - 1];
-        }
-        const int sblocks = (int)((n + 255) / 256);
-        // count, scan, place: the pairs of one group over its bins of the key space, or of both (grp = -1) over all bins
+        hipStream_t so = c.ahead ? ss->pre[1] : c.s_last;
+        const dim3 tiles((unsigned)c.W.ltiles), slabs((unsigned)(c.W.ltiles + LANE_ROWS)), rows(LANE_ROWS), th(LSORT_THREADS);
+        // the pairs of one group, or of both (grp = -1): the other group's rows count nothing and have no slab
         auto sort_group = [&](int grp) {
             Stage st("bsw_lane_sort", so);                  // (the profile adds up the stages of one name)
-            hipLaunchKernelGGL(bsw_lane_sort_kernel, dim3(sblocks), dim3(256), 0, so, c.dev, c.P, n, c.W, 0, grp);
-            if (grp < 0) hipLaunchKernelGGL((bsw_lane_scan_kernel<0, LANE_BINS>), dim3(1), dim3(1024), 0, so, c.W);
-            else if (grp == 0) hipLaunchKernelGGL((bsw_lane_scan_kernel<0, LANE_L_BINS>), dim3(1), dim3(1024), 0, so, c.W);
-            else hipLaunchKernelGGL((bsw_lane_scan_kernel<LANE_L_BINS, LANE_BINS - LANE_L_BINS>), dim3(1), dim3(1024), 0, so, c.W);
-            hipLaunchKernelGGL(bsw_lane_sort_kernel, dim3(sblocks), dim3(256), 0, so, c.dev, c.P, n, c.W, 1, grp);
+            hipLaunchKernelGGL(bsw_lsort_hist1_kernel, tiles, th, 0, so, c.dev, c.P, n, c.W, grp);
+            hipLaunchKernelGGL(bsw_lsort_scan1_kernel, rows, th, 0, so, c.W);
+            hipLaunchKernelGGL(bsw_lsort_rows_kernel, dim3(1), dim3(64), 0, so, c.W, grp);
+            hipLaunchKernelGGL(bsw_lsort_place1_kernel, tiles, th, 0, so, c.dev, c.P, n, c.W, grp);
+            hipLaunchKernelGGL(bsw_lsort_hist2_kernel, slabs, th, 0, so, c.W);
+            hipLaunchKernelGGL(bsw_lsort_scan2_kernel, rows, th, 0, so, c.W);
+            hipLaunchKernelGGL(bsw_lsort_place2_kernel, slabs, th, 0, so, c.W);
         };
         if (c.split) {
             // Group L first, with an event of its own: its launches (bsw_launch) start while group S is still being sorted here.
@@ -1770,6 +1997,7 @@ static int queue_prepare(BswCall &c)
         }
         GBX_HIP(hipEventRecord(c.ev_aux, so));
     }
+    GBX_HIP(hipMemsetAsync(c.W.counts, 0, WS_HDR * sizeof(int32_t), c.s_cls));        // the workspace's header arrays
     const int cblocks = (int)((n + CLS_THREADS - 1) / CLS_THREADS);
     {
         Stage st("bsw_classify", c.s_cls);
@@ -1791,7 +2019,7 @@ static int kernel_streams_wait(const BswCall &c, hipEvent_t ev, int n_side = Sid
 }
 
 // The row-kernel classes.  With the lane path on they hold next to nothing (what the lane kernels cannot take): twenty
-// near-empty launches, all on the caller's stream, in the shadow of the lane sort.
+// near-empty launches, all on one stream (BswCall::s_rows) behind classify, beside the lane sort.
 static void launch_row_classes(BswCall &c)
 {
     // Four kernel streams when the inputs are resident.  The host pipeline (join_events) uses three: the
@@ -1802,7 +2030,7 @@ static void launch_row_classes(BswCall &c)
     for (int cls = 0; cls < NCLS - 1; ++cls) {
         if (CLASS_REMAP[c.mode][cls] != cls) continue;        // this class's pairs run on a wider class's kernel
         const int sk = (c.mode ? launched++ : cls) % nk;
-        hipStream_t sc = c.dev.lane_on || sk == 0 ? c.s : c.ss->side[sk - 1];
+        hipStream_t sc = c.dev.lane_on || sk == 0 ? c.s_rows : c.ss->side[sk - 1];
         RowKernel &k = row_kernels[cls];
         // persistent groups: the grid is the number of blocks that are resident at once (occupancy query), so that the static
         // round-robin over the longest-first list starts every group on the longest pairs together; never more groups than pairs
@@ -1862,7 +2090,9 @@ static void launch_lanes(const BswCall &c, int grp)
     const int64_t want = (c.n + 63) / 64;
     // The wide launches go first, while the chip is empty: a launch has to be given its LDS before its wavefronts can
     // see that their list is empty (the usual case for short reads), and behind a working compact launch that wait
-    // held up the stream for up to a millisecond (6.36 -> 6.03 ms on 'large').
+    // held up the stream for up to a millisecond (6.36 -> 6.03 ms on 'large').  (The empty wide launches take 25-40 us
+    // each in front of the compact ones.  The compact ones first, with nothing but the join behind a wide one, started
+    // the DP 45 us earlier and measured slower, on every stream or on the three that follow the sort: DESIGN.md §8.)
     for (int fmt = 1; fmt >= 0; --fmt) {
         for (int r = LANE_NRANGE - 1; r >= 0; --r) {
             const int qlo = r ? LANE_RANGE_HI[fmt][r - 1] + 1 : 1, qhi = LANE_RANGE_HI[fmt][r];
@@ -1872,10 +2102,11 @@ static void launch_lanes(const BswCall &c, int grp)
             const int kind = fmt ? LANE_WIDE : qhi > 99 ? LANE_COMPACT4 : LANE_COMPACT;
             const size_t lds = (size_t)lane_lds_bytes(!fmt, kind == LANE_COMPACT4, cols);
             const int fit = (int)((size_t)160 * 1024 / lds), per_cu = fit > 16 ? 16 : fit;
-            // the launch's ordinal in its format, longest first.  (The shortest class behind the second shortest on the last side
-            // stream, so that it need not wait for the row-kernel launches on the caller's stream: 5.54-5.63 against 5.17-5.26 ms.)
+            // the launch's ordinal in its format, longest first: s_rows, side[0], side[1], s_last, and the shortest class on s_rows
+            // again, behind the row-kernel launches.  (The shortest class behind the second shortest on s_last instead, so that it
+            // need not wait for the row-kernel launches on s_rows, measured slower: 5.54-5.63 against 5.17-5.26 ms.)
             const int sk = (LANE_NRANGE - 1 - r) & 3;
-            hipStream_t sc = sk == 0 ? c.s : c.ss->side[sk - 1];
+            hipStream_t sc = sk == 0 ? c.s_rows : sk == SideStreams::N ? c.s_last : c.ss->side[sk - 1];
             const int64_t cap = (int64_t)c.cus * per_cu;
             const int rlo = lane_row(fmt, qlo), rhi = lane_row(fmt, qhi), slot = fmt * LANE_NRANGE + r;
             Stage st(names[fmt][r], sc);
@@ -1887,8 +2118,8 @@ static void launch_lanes(const BswCall &c, int grp)
     }
 }
 
-// The one-pair-per-wavefront kernel for what no register class holds (CLS_LDS), on the caller's stream
-static int launch_lds(const BswCall &c)
+// The one-pair-per-wavefront kernel for what no register class holds (CLS_LDS)
+static int launch_lds(const BswCall &c, hipStream_t s)
 {
     const size_t lds_bytes = (size_t)(GBX_BSW_MAX_QLEN + 1) * 2 * sizeof(int);
     // per device (a process may drive several GPUs through gbx_set_device), set at most once each
@@ -1901,8 +2132,8 @@ static int launch_lds(const BswCall &c)
         if (cur < 128) attr_set[cur >> 6].fetch_or(bit, std::memory_order_release);
     }
     const int blocks = (int)(c.n < (int64_t)c.cus * 2 ? c.n : (int64_t)c.cus * 2);
-    Stage st("bsw_lds", c.s);
-    hipLaunchKernelGGL(bsw_lds_kernel, dim3(blocks), dim3(64), lds_bytes, c.s, c.dev, c.P, c.W, CLS_LDS);
+    Stage st("bsw_lds", s);
+    hipLaunchKernelGGL(bsw_lds_kernel, dim3(blocks), dim3(64), lds_bytes, s, c.dev, c.P, c.W, CLS_LDS);
     return GBX_OK;
 }
 
@@ -1924,6 +2155,13 @@ int bsw_launch(const gbx_bsw_params *p, int64_t n,
     c.P = {d_ref, d_qer, d_idr, d_idq, d_len1, d_len2, d_h0, d_out};
     int32_t *wi = (int32_t *)d_work, *wl = wi + WS_HDR + 4 * n;
     c.W = {wi, wi + HDR, wi + 2 * HDR, wi + 3 * HDR, wi + WS_HDR, wi + WS_HDR + n, wl, wi + WS_HDR + 3 * n, wi + WS_HDR + 2 * n, wl + LANE_BINS + 64};
+    c.W.ltiles = (int)lsort_tiles(n);
+    c.W.lh0 = (uint8_t *)(wl + WS_LANE);
+    c.W.lm1 = wl + WS_LANE + lsort_h0_ints(n);
+    c.W.lrowtot = c.W.lm1 + (int64_t)LANE_ROWS * c.W.ltiles;
+    c.W.lrowbase = c.W.lrowtot + WS_LROWS;
+    c.W.lslabfirst = c.W.lrowbase + WS_LROWS;
+    c.W.lm2 = c.W.lslabfirst + WS_LROWS;
     c.dev.lane_on = c.dev.lane_on && lane_wanted(n) ? 1 : 0;
     c.dev.lane_prio = switched_off("GBX_BSW_LANE_PRIO") ? 0 : 1;         // read per call: the tests vary it
     c.sym = c.dev.oe_ins == c.dev.oe_del;
@@ -1943,20 +2181,19 @@ int bsw_launch(const gbx_bsw_params *p, int64_t n,
     int dev_id = 0;
     (void)hipGetDevice(&dev_id);
     (void)hipDeviceGetAttribute(&c.cus, hipDeviceAttributeMultiprocessorCount, dev_id);
-    // (with the lane path on, the lane sort has forked the side streams already)
+    // (with the lane path on, queue_prepare has forked the side streams already)
     if (!c.dev.lane_on && !c.ahead && (rc = c.ss->fork(s))) return rc;
     if (!c.no_rows) launch_row_classes(c);
     if (c.dev.lane_on) {
-        // the lane launches need the sorted lists (the sort's own stream, the last side stream unless `ahead`, has them in order)
-        const int n_side = c.ahead ? SideStreams::N : SideStreams::N - 1;
+        // the lane launches need the sorted lists (the sort's own stream, the caller's unless `ahead`, has them in order anyway)
         if (c.split) {
             // group L's launches behind L's sort alone, then group S's behind the whole sort; within a group the order is as before
-            if ((rc = kernel_streams_wait(c, c.ev_aux_first, n_side))) return rc;
+            if ((rc = kernel_streams_wait(c, c.ev_aux_first))) return rc;
             launch_lanes(c, 0);
-            if ((rc = kernel_streams_wait(c, c.ev_aux, n_side))) return rc;
+            if ((rc = kernel_streams_wait(c, c.ev_aux))) return rc;
             launch_lanes(c, 1);
         } else {
-            if ((rc = kernel_streams_wait(c, c.ev_aux, n_side))) return rc;
+            if ((rc = kernel_streams_wait(c, c.ev_aux))) return rc;
             launch_lanes(c, -1);
         }
     }
@@ -1967,7 +2204,8 @@ int bsw_launch(const gbx_bsw_params *p, int64_t n,
     // overlap the next chunk's kernels, and its downloader waits for the events.
     if (!join_events && (rc = c.ss->join(s))) return rc;
     // (bsw_lds queued with the row classes instead, ahead of the lane launches, measured no faster: DESIGN.md §8)
-    if (!c.no_rows && (rc = launch_lds(c))) return rc;
+    // behind classify: on the joined caller's stream, or where nothing joins on the row classes' stream
+    if (!c.no_rows && (rc = launch_lds(c, join_events ? c.s_rows : s))) return rc;
     if (join_events) {
         GBX_HIP(hipEventRecord(join_events[0], s));
         for (int k = 0; k < SideStreams::N; ++k) GBX_HIP(hipEventRecord(join_events[1 + k], c.ss->side[k]));

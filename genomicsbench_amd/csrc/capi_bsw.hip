@@ -28,6 +28,15 @@ void gbx_bsw_default_params(gbx_bsw_params *p)
 
 size_t gbx_bsw_workspace_bytes(int64_t n) { return bsw_workspace_bytes(n); }
 
+// Debug read-back of the lane sort (the tests): the sorted pair indices (n ints, the lists' total of them valid) and the
+// first position of every key row (LANE_ROWS + 1 ints, the last = the total) of the last call on a workspace of n pairs.
+int gbx_debug_bsw_lane_lists(const void *d_work, int64_t n, int32_t *h_order, int32_t *h_row_first)
+{
+    if (!d_work || !h_order || !h_row_first) { set_error("gbx_debug_bsw_lane_lists: null pointer"); return GBX_ERR_ARG; }
+    return bsw_debug_lane_lists(d_work, n, h_order, h_row_first);
+}
+int gbx_debug_bsw_lane_sort_tile(void) { return bsw_lane_sort_tile(); }
+
 int gbx_bsw_extend_device(const gbx_bsw_params *p, int64_t n,
                           const uint8_t *d_ref, const uint8_t *d_qer,
                           const int64_t *d_idr, const int64_t *d_idq,

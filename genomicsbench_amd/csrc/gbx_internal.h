@@ -128,6 +128,9 @@ static inline bool bsw_lane_takes(const BswLaneRule &r, int qlen, int tlen, int 
     return r.on && qlen >= 1 && qlen <= r.qmax && tlen >= 1 && h0 >= 0 && h0 + qlen * r.max_mat < r.limit;
 }
 size_t bsw_workspace_bytes(int64_t n);
+// for the tests: the sorted lists of the last lane sort on a workspace (synchronises the device); the sort's tile in pairs
+int bsw_debug_lane_lists(const void *d_work, int64_t n, int32_t *h_order, int32_t *h_row_first);
+int bsw_lane_sort_tile();
 int bsw_launch(const gbx_bsw_params *p, int64_t n,
                const uint8_t *d_ref, const uint8_t *d_qer,
                const int64_t *d_idr, const int64_t *d_idq,

@@ -1,5 +1,5 @@
 """CPU costing of column lock-step for bsw's compact lane classes: replays the windows of every row of bsw 'large' (seed 1002)
-with the oracle's row loop, the pairs in the device's sorted order (bsw_lane_sort_kernel: query length, then min(h0, 255)),
+with the oracle's row loop, the pairs in the device's sorted order (the bsw_lsort_* kernels: query length, then min(h0, 255)),
 in chunks of 64 taken from the end of each class's list as bsw_lane_kernel takes them.  Per class it prints the cells the
 lanes compute, 64 x the widest window of every row (what the LDS lane kernel pays), 64 x the hull of the lanes' windows per
 row in column pairs and in 8-column blocks (what a column-lock-step kernel pays), and the share of those blocks that some
