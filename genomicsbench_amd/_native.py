@@ -188,6 +188,13 @@ def _declare(L):
         L.gbx_dbg_graph_host.argtypes = [vp, vp, vp, i64, i64, vp, vp, vp, vp]
         L.gbx_dbg_build_device.argtypes = [vp, vp, vp, vp, vp, sz, vp]
         L.gbx_dbg_graph_device.argtypes = [vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, sz, vp]
+    if hasattr(L, "gbx_dbg_assemble_host"):
+        L.gbx_dbg_asm_default_params.argtypes = [vp]
+        L.gbx_dbg_asm_default_params.restype = None
+        L.gbx_dbg_assemble_workspace_bytes.argtypes = [vp, i64, i64, i64]
+        L.gbx_dbg_assemble_workspace_bytes.restype = sz
+        L.gbx_dbg_assemble_host.argtypes = [vp, vp, vp, vp, vp]
+        L.gbx_dbg_assemble_device.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp]
     if hasattr(L, "gbx_chain_host"):
         L.gbx_chain_job_stats.argtypes = [vp, i64, i64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]
         L.gbx_chain_workspace_bytes.argtypes = [i64, i64]

@@ -7,7 +7,10 @@
 // its message and status 1, as does the window rule's lo > hi.  Printed as the reference (stderr): "Found N batches. Running
 // with threads: T" and "Kernel runtime: X s", which brackets graph building only, after BAM and FASTA ingest.
 // Not reference flags: --print (one line per window: assem start and end, ref start, read range, the stats, the digest in
-// hex), --parse-only (reads, longest and a CRC-32 of the reads; no GPU), --gpus N.
+// hex), --parse-only (reads, longest and a CRC-32 of the reads; no GPU), --gpus N, and --assemble: gbx_dbg_assemble_host instead
+// of the build (cycle check, retry at a larger k, variant paths; default gbx_dbg_asm_params), which prints one line per window:
+// the final k, the builds, the cyclic flag, starts, paths and give-ups, and with --print behind it one line per path: P, the
+// positions of its first and last node, its weight and its sequence.
 // Deviations: the FASTA is read whole with no .fai (the reference's fai_load would write one); a bare contig name runs to
 // the contig's length, not to INT_MAX.
 #include <zlib.h>
@@ -49,15 +52,16 @@ bool fasta_contig(const char *path, const std::string &name, std::string &out)
 int main(int argc, char **argv)
 {
     const int gpus = take_gpus_flag(argc, argv);
-    bool print = false, parse_only = false;
+    bool print = false, parse_only = false, assemble = false;
     std::vector<char *> pos_args;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--print")) print = true;
         else if (!strcmp(argv[i], "--parse-only")) parse_only = true;
+        else if (!strcmp(argv[i], "--assemble")) assemble = true;
         else pos_args.push_back(argv[i]);
     }
     if (pos_args.size() != 4) {
-        fprintf(stderr, "Usage %s file.bam chr:start-stop ref.fa n_threads [--print] [--parse-only] [--gpus n]\n", argv[0]);
+        fprintf(stderr, "Usage %s file.bam chr:start-stop ref.fa n_threads [--print] [--parse-only] [--assemble] [--gpus n]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const char *bam_file = pos_args[0], *fa_file = pos_args[2];
@@ -143,6 +147,52 @@ int main(int argc, char **argv)
     fprintf(stderr, "Found %lld batches. Running with threads: %d\n", (long long)nw, threads);
     print_device_banner(gpus);
     std::vector<gbx_dbg_stats> st((size_t)std::max<int64_t>(nw, 1));
+    if (assemble) {
+        gbx_dbg_asm_params ap;
+        gbx_dbg_asm_default_params(&ap);
+        std::vector<gbx_dbg_asm_win> aw((size_t)std::max<int64_t>(nw, 1));
+        std::vector<gbx_dbg_asm_start> starts(1024);
+        std::vector<gbx_dbg_asm_path> paths(1024);
+        std::vector<int32_t> pnodes(1 << 16);
+        std::vector<uint8_t> pseq(1 << 16);
+        int64_t totals[3] = {0, 0, 0};
+        const double t0 = now_s();
+        for (int attempt = 0;; ++attempt) {          // a short capacity: the totals say what to allocate (the starts first)
+            gbx_dbg_asm_out o;
+            o.stats = st.data(); o.wins = aw.data(); o.starts = starts.data(); o.paths = paths.data(); o.path_nodes = pnodes.data(); o.path_seq = pseq.data();
+            o.cap_starts = (int64_t)starts.size(); o.cap_paths = (int64_t)paths.size(); o.cap_path_nodes = (int64_t)pnodes.size(); o.totals = totals;
+            const int arc = gbx_dbg_assemble_host(&p, &ap, &rd, &wn, &o);
+            const bool is_short = totals[0] > o.cap_starts || totals[1] > o.cap_paths || totals[2] > o.cap_path_nodes;
+            if (arc == GBX_ERR_UNSUPPORTED && is_short && attempt < 3) {
+                starts.resize((size_t)std::max(totals[0], o.cap_starts));
+                paths.resize((size_t)std::max(totals[1], o.cap_paths));
+                pnodes.resize((size_t)std::max(totals[2], o.cap_path_nodes));
+                pseq.resize(pnodes.size());
+                continue;
+            }
+            die_on(arc, "gbx_dbg_assemble_host");
+            break;
+        }
+        const double runtime = now_s() - t0;
+        std::string out;
+        char line[160];
+        for (int64_t w = 0; w < nw; ++w) {
+            const gbx_dbg_asm_win &a = aw[(size_t)w];
+            out.append(line, (size_t)snprintf(line, sizeof line, "%d\t%d\t%d\t%lld\t%lld\t%lld\n", a.k, a.n_builds, a.cyclic, (long long)a.n_starts,
+                                              (long long)a.n_paths, (long long)a.n_gave_up));
+            for (int64_t s = a.first_start; print && s < a.first_start + a.n_starts; ++s)
+                for (int64_t x = starts[(size_t)s].first_path; x < starts[(size_t)s].first_path + starts[(size_t)s].n_paths; ++x) {
+                    const gbx_dbg_asm_path &pa = paths[(size_t)x];
+                    out.append(line, (size_t)snprintf(line, sizeof line, "P\t%d\t%d\t%lld\t", pa.pos_first, pa.pos_last, (long long)pa.weight));
+                    out.append((const char *)pseq.data() + pa.first_node, (size_t)pa.n_nodes);
+                    out.push_back('\n');
+                }
+        }
+        fwrite(out.data(), 1, out.size(), stdout);
+        fflush(stdout);
+        fprintf(stderr, "Kernel runtime: %.2f s\n", runtime);
+        return 0;
+    }
     const double t0 = now_s();
     die_on(gbx_dbg_build_host(&p, &rd, &wn, st.data()), "gbx_dbg_build_host");
     const double runtime = now_s() - t0;

@@ -424,6 +424,30 @@ int dbg_plan(int64_t k, int64_t w0, int64_t w1, const int64_t *ref_off, const in
 int dbg_launch(const DbgDev &a, const std::vector<DbgWinPlan> &plan, const std::vector<int64_t> &batches, DbgWinPlan *d_plan, int *d_err,
                char *d_region, gbx_dbg_stats *d_stats, const DbgGraphOut &g, hipStream_t s);
 
+// ---- dbg_asm (dbg_asm_kernels.hip): cycle check, start list and path search on one range of windows whose graphs lie in
+// nodes / edges at the capacities node_off / edge_off[nw + 1] (window j of the range: plan[j], plan[j].win its index in the call).
+struct DbgAsmDev {
+    int32_t nw, k, n_builds, last_round;          // last_round: k > k_last, a cyclic window is final as well
+    gbx_dbg_asm_params ap;
+    const DbgWinPlan *plan;
+    const int64_t *node_off, *edge_off;
+    const gbx_dbg_node *nodes;
+    const gbx_dbg_edge *edges;
+    const uint8_t *ref, *seq;
+    int32_t *cyc;                                 // the call's windows: cyclic flag of the latest build
+    int32_t *win_slot;                            // the call's windows: index in the range
+    int32_t *deg, *list, *nxt;                    // node capacity of the range each (windows above DBG_ASM_LDS_NODES)
+    int32_t *fin;                                 // nw: the window's graph is final
+    int64_t *wstart;                              // nw
+    int64_t *counters;                            // 0..2 the call's starts, paths, path nodes; 3 the range's first start
+    int32_t *pathbuf;                             // path_blocks slices of path_slice ints
+    int64_t path_slice;
+    int32_t path_blocks;
+    gbx_dbg_asm_out out;
+};
+constexpr int DBG_ASM_LDS_NODES = 4096;
+int dbg_asm_launch(const DbgAsmDev &a, hipStream_t s);
+
 // ---- phmm (phmm_kernels.hip)
 size_t phmm_workspace_bytes(int64_t n_pairs, int64_t n_reads, int max_hap_len, int64_t stream_syms = -1);
 int phmm_init_tables();

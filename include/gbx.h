@@ -1873,6 +1873,103 @@ int gbx_dbg_graph_device(const gbx_dbg_params *p, const gbx_dbg_reads *reads, co
                          const int64_t *d_node_off, const int64_t *d_edge_off, gbx_dbg_node *d_nodes, gbx_dbg_edge *d_edges,
                          void *d_work, size_t work_bytes, void *stream);
 
+/* ------------------------------------------------------------- dbg_asm: cycle check, k-mer retry, variant paths
+ * What Platypus's assembler does with each window's graph behind the build: the cycle check
+ * (R/benchmarks/dbg/debruijn.cpp:923-998, dfsVisit / detectCyclesInGraph_Recursive), the rebuild at a larger k while the
+ * graph is cyclic (1408-1428, commented out in the benchmark) and the variant paths (1094-1239, checkPathForCycles,
+ * getVariantPathsThroughGraphFromNode, createSequenceFromPath).  All of it reads the graph of the dbg section (nodes in
+ * first-touch order, at most 4 kept edges per node in order of first appearance) and changes nothing there.  Pinned by
+ * the restatement tests/dbg_asm_ref.py; the start rule is UPSTREAM (Platypus's findBubbles, not in the reference tree).
+ * Weights are whole numbers, every comparison is on integers.
+ * Cycle check: the window is cyclic iff the directed graph of its counted edges has a cycle (a self-loop is one).  An
+ *   edge is not counted when its end node's colours are READ only and its weight is below min_weight; an edge into a REF
+ *   or REF|READ node counts whatever its weight.  This is detectCyclesInGraph_Recursive's return value; it does not depend
+ *   on the visiting order.
+ * Retry: a window starts at the dbg params' k; while its graph is cyclic and k <= k_last it is rebuilt at k + k_step
+ *   (15, 20, .., 55 by default; a window still cyclic at 55 stays at 55 with cyclic = 1).  Every k reached must lie in
+ *   GBX_DBG_MIN_K..GBX_DBG_MAX_K (checked up front for the largest k any window can reach).  A window's graph at a k is
+ *   exactly gbx_dbg_build_*'s at that k: a reference shorter than k + 2 contributes nothing, and without reads the graph
+ *   is empty and acyclic.
+ * Variant paths, on the final graph of every window (cyclic ones too):
+ *   starts (UPSTREAM)   nodes in first-touch order, then their edges in edge order: a node of colours REF|READ with a kept
+ *                       edge of weight >= min_weight whose end node is READ only.  The start path is the two nodes, its
+ *                       weight that edge's weight.
+ *   search              a LIFO stack of paths holding the start path, and a list of finished paths.  While the stack is
+ *                       not empty, pop P, then in this order: count a step, more than max_steps: status STEPS, no paths;
+ *                       more than max_pending paths left on the stack or more than max_finished finished: status GAVE_UP,
+ *                       no paths; P's last node occurs earlier in P: drop P; its last node is REF|READ: P is finished;
+ *                       REF only: drop P; else for each kept edge of the last node in edge order, when its weight is
+ *                       >= min_weight or its end node has REF among its colours, push P + that end node, weight P's plus
+ *                       the edge's.  max_steps is this library's own bound (none in the reference).
+ *   a path              its node indices (first-touch order of its window), its weight, the positions of its first and
+ *                       last node, and its sequence: one byte per node, the first byte of the node's k-mer.
+ * Output (gbx_dbg_asm_out), against the caller's capacities: per window a gbx_dbg_asm_win and the final graph's
+ * gbx_dbg_stats; starts[], paths[], path_nodes[] / path_seq[].  A window's starts are starts[first_start ..+ n_starts] in
+ * the order above; a start's paths are paths[first_path ..+ n_paths] in finishing order; a path's nodes are
+ * path_nodes[first_node ..+ n_nodes] and its bytes path_seq at the same place.  The windows' blocks of starts lie in the
+ * order the windows became final: by round, then by window index (so the layout is a function of the input alone).
+ * totals[0..2] receive the starts, paths and path nodes of the whole call; where one exceeds its capacity the arrays hold
+ * what fitted (every index below the capacity is as it would be with room), totals says what to allocate, and the entry
+ * returns GBX_ERR_UNSUPPORTED with the sizes in the error text.  k, n_builds, cyclic, stats and n_starts are complete
+ * either way; a start that did not fit is not searched, so with cap_starts short the paths' totals and the windows' path
+ * counts cover the starts that fitted (n_starts <= n_edges of the final graphs bounds the starts beforehand). */
+#define GBX_DBG_ASM_OK        0
+#define GBX_DBG_ASM_GAVE_UP   1
+#define GBX_DBG_ASM_STEPS     2
+#define GBX_DBG_ASM_MAX_PENDING 59    /* the stack of one search holds max_pending + 4 paths at most: 63 */
+typedef struct gbx_dbg_asm_params {
+    int32_t min_weight;      /* >= 0; 40 (the reference's minReads * minQual) */
+    int32_t k_step;          /* >= 1; 5 */
+    int32_t k_last;          /* rebuild while k <= k_last; 50.  Below the dbg params' k: no retry */
+    int32_t max_pending;     /* 0..GBX_DBG_ASM_MAX_PENDING; 20 */
+    int32_t max_finished;    /* >= 0; 20 */
+    int32_t pad_;
+    int64_t max_steps;       /* >= 0; 2^20 */
+} gbx_dbg_asm_params;
+void gbx_dbg_asm_default_params(gbx_dbg_asm_params *p);
+typedef struct gbx_dbg_asm_win {
+    int32_t k;               /* of the final graph */
+    int32_t n_builds;
+    int32_t cyclic;          /* of the final graph */
+    int32_t pad_;
+    int64_t first_start, n_starts;
+    int64_t n_paths, n_path_nodes;    /* over its starts of status OK */
+    int64_t n_gave_up, n_steps;       /* starts of status GAVE_UP / STEPS */
+} gbx_dbg_asm_win;
+typedef struct gbx_dbg_asm_start {
+    int64_t first_path, n_paths;      /* n_paths = 0 unless status is OK */
+    int64_t first_node, n_nodes;      /* its paths' nodes are contiguous: path_nodes[first_node ..+ n_nodes] */
+    int32_t win, node, edge, status;  /* edge: the number of the start edge among the node's kept edges */
+} gbx_dbg_asm_start;
+typedef struct gbx_dbg_asm_path {
+    int64_t weight;
+    int64_t first_node;
+    int32_t n_nodes;
+    int32_t pos_first, pos_last;      /* gbx_dbg_node.position of the first and last node (-1: a READ-only node) */
+    int32_t pad_;
+} gbx_dbg_asm_path;
+typedef struct gbx_dbg_asm_out {
+    gbx_dbg_stats *stats;             /* n_win */
+    gbx_dbg_asm_win *wins;            /* n_win */
+    gbx_dbg_asm_start *starts;
+    gbx_dbg_asm_path *paths;
+    int32_t *path_nodes;
+    uint8_t *path_seq;
+    int64_t cap_starts, cap_paths, cap_path_nodes;
+    int64_t *totals;                  /* 3 */
+} gbx_dbg_asm_out;
+/* Reads and windows as gbx_dbg_build_host; one device (no spreading over devices). */
+int gbx_dbg_assemble_host(const gbx_dbg_params *p, const gbx_dbg_asm_params *ap, const gbx_dbg_reads *reads, const gbx_dbg_wins *wins,
+                          const gbx_dbg_asm_out *out);
+/* Device path, the contract of gbx_dbg_build_device: every pointer inside reads, wins and out is device memory.  The call
+ * reads the offsets and ranges back once, and after every round the windows' cyclic flags, to plan the next round (it
+ * synchronises `stream` there); totals are read back at the end for the return value.  The graphs are taken in ranges of
+ * windows that fit the workspace (tables, nodes at 2 * occ and edges at occ per window), at least one window.
+ * max_window_occ as in gbx_dbg_workspace_bytes, at the dbg params' k (larger k have fewer slots). */
+size_t gbx_dbg_assemble_workspace_bytes(const gbx_dbg_params *p, int64_t n_win, int64_t n_reads, int64_t max_window_occ);
+int gbx_dbg_assemble_device(const gbx_dbg_params *p, const gbx_dbg_asm_params *ap, const gbx_dbg_reads *reads, const gbx_dbg_wins *wins,
+                            const gbx_dbg_asm_out *out, void *d_work, size_t work_bytes, void *stream);
+
 /* ------------------------------------------------------------------- mm: minimizer seeding in front of chain
  * minimap2's seeding stage: the minimizer sketch (mm_sketch), the minimizer index (mm_idx_*) and seed collection with the
  * occurrence filter (collect_matches + collect_seed_hits): what fmi + fmi_sal are for bsw, this is for chain.  UNPINNED by a
