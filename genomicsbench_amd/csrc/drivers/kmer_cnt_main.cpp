@@ -2,13 +2,18 @@
 //
 // CLI as the reference: --reads a,b,... --config path [--kmer k] [--min-read n] [--min-ovlp n] [--threads n] [--debug]
 // [--log file].  k is --kmer, else kmer_size of the config file (Flye's key=value lines, '#' comments, %include relative to
-// the file, config.h:36-72); only the count path (use_minimizers = 0) is built.  Reads longer than max(--min-read,
+// the file, config.h:36-72).  use_minimizers = 0 (or absent) times the count path (countKmers), anything else the minimizer
+// index (buildIndexMinimizers(1, minimizer_window) with repeat_kmer_rate, over gbx_kmer_index_host; k = 1..31 there); a key
+// the chosen path needs and the config lacks ends the run with "No such parameter: <key>".  Reads longer than max(--min-read,
 // --min-ovlp) are kept (kmer_cnt.cpp:189, sequence_container.cpp:102), duplicated IDs among them are refused
 // (sequence_container.cpp:62-69), and a character outside ACGTacgt turns itself and the rest of its 32-base chunk into T, as
 // the reference's DnaSequence packing does on LP64 (see genomicsbench_amd/kmer.py: encode).
-// Printed as the reference: "Hash size: H" and "Total k-mers N" (with --debug) and "Kernel time: X sec" (stderr).
+// Printed as the reference: "Hash size: H" and "Total k-mers N", or the index's seven lines from "Mean k-mer frequency" to
+// "Minimizer rate" (with --debug), and "Kernel time: X sec" (stderr).  On the minimizer path "Kernel time" is one build of the
+// index: the output buffers are sized from the read lengths, and a build that found them short is repeated and reported apart.
 // Not reference flags: --hist FILE (f<TAB>n lines, 1 <= f < 255, the last bin "count >= 255"), --solid MIN FILE (k-mers with
-// count >= MIN as ACGT...<TAB>count, ascending code), --parse-only (reads, bases and a checksum; no GPU), --gpus N.
+// count >= MIN as ACGT...<TAB>count, ascending code), --index FILE (the minimizer index: a line per kept k-mer, ACGT... and then
+// its global positions, tab-separated, ascending code), --parse-only (reads, bases and a checksum; no GPU), --gpus N.
 // Unlike the reference, gzip-compressed inputs are refused (no zlib).
 #include <omp.h>
 #include <map>
@@ -19,7 +24,7 @@ namespace {
 
 struct Options {
     std::vector<std::string> reads;
-    std::string config, log, hist, solid;
+    std::string config, log, hist, solid, index;
     int kmer = -1, min_read = 0, min_ovlp = 5000, threads = 1;
     long solid_min = 0;
     bool debug = false, parse_only = false;
@@ -28,7 +33,7 @@ struct Options {
 void usage()
 {
     fprintf(stderr, "Usage: kmer-cnt --reads path1[,path2,...] --config path [--kmer size] [--min-read length] [--min-ovlp size]\n"
-                    "\t\t[--threads num] [--debug] [--log path] [--hist path] [--solid min path] [--parse-only] [--gpus n]\n");
+                    "\t\t[--threads num] [--debug] [--log path] [--hist path] [--solid min path] [--index path] [--parse-only] [--gpus n]\n");
 }
 
 std::string trim(const std::string &s)
@@ -149,6 +154,61 @@ bool parse_file(const std::vector<char> &text, bool fastq, int threads, std::vec
     return true;
 }
 
+// the minimizer path: buildIndexMinimizers between the reference's two gettimeofday calls
+int run_index(const Options &o, const gbx_kmer_index_params &ip, int64_t n_reads, const std::vector<uint8_t> &enc, const std::vector<int64_t> &off,
+              const std::vector<int32_t> &len)
+{
+    gbx_kmer_index_stats st{};
+    // room for the expected two minimizers a window and a quarter more (every position for a window of 1): one build, as the
+    // reference times one.  Where that is too little the needed counts come back and the build is repeated with them; "Kernel
+    // time" is then the second build's alone and the first is reported on a line of its own.
+    int64_t positions = 0;
+    for (int64_t r = 0; r < n_reads; ++r) positions += std::max<int64_t>(0, (int64_t)len[(size_t)r] - ip.k);
+    const int64_t room = ip.window == 1 ? positions : std::min<int64_t>(positions, positions / (ip.window + 1) * 5 / 2 + n_reads + 1024);
+    std::vector<uint64_t> kmer((size_t)room), pos((size_t)room);
+    std::vector<int64_t> koff((size_t)room + 1);
+    double t1 = now_s();
+    int rc = gbx_kmer_index_host(&ip, n_reads, enc.data(), (int64_t)enc.size(), off.data(), len.data(), &st, kmer.data(), koff.data(), room,
+                                 pos.data(), room);
+    if (rc == GBX_ERR_ARG && (st.n_selected > room || st.n_entries > room)) {
+        fprintf(stderr, "index sized by a first build: %.3f sec\n", now_s() - t1);
+        kmer.resize((size_t)st.n_selected);
+        koff.resize((size_t)st.n_selected + 1);
+        pos.resize((size_t)st.n_entries);
+        t1 = now_s();
+        rc = gbx_kmer_index_host(&ip, n_reads, enc.data(), (int64_t)enc.size(), off.data(), len.data(), &st, kmer.data(), koff.data(),
+                                 (int64_t)kmer.size(), pos.data(), (int64_t)pos.size());
+    }
+    die_on(rc, "gbx_kmer_index_host");
+    const double dt = now_s() - t1;
+    kmer.resize((size_t)st.n_selected);
+    if (o.debug) {
+        // as the reference's ostream prints its floats (%g); the ratios in fp32 as it computes them
+        fprintf(stderr, "Mean k-mer frequency: %g\n", (double)st.mean_frequency);
+        fprintf(stderr, "Repetitive k-mer frequency: %lld\n", (long long)st.repetitive_frequency);
+        fprintf(stderr, "Filtered %lld repetitive k-mers (%g)\n", (long long)st.n_repetitive_entries,
+                (double)((float)(uint64_t)st.n_repetitive_entries / (float)(uint64_t)st.n_chosen));
+        fprintf(stderr, "Selected k-mers: %lld\n", (long long)st.n_selected);
+        fprintf(stderr, "K-mer index size: %lld\n", (long long)st.n_entries);
+        fprintf(stderr, "Mean k-mer frequency: %g\n", (double)((float)(uint64_t)st.n_entries / (float)(uint64_t)st.n_selected));
+        fprintf(stderr, "Minimizer rate: %g\n", (double)((float)(uint64_t)st.total_len / (float)(uint64_t)st.n_entries));
+    }
+    fprintf(stderr, "Kernel time: %.3f sec\n", dt);
+    if (!o.index.empty()) {
+        FILE *f = fopen(o.index.c_str(), "w");
+        if (!f) { fprintf(stderr, "Can't open %s\n", o.index.c_str()); return EXIT_FAILURE; }
+        std::string s((size_t)ip.k, 'A');
+        for (size_t j = 0; j < kmer.size(); ++j) {
+            for (int b = 0; b < ip.k; ++b) s[(size_t)b] = "ACGT"[(kmer[j] >> (2 * (ip.k - 1 - b))) & 3];
+            fputs(s.c_str(), f);
+            for (int64_t e = koff[j]; e < koff[j + 1]; ++e) fprintf(f, "\t%llu", (unsigned long long)pos[(size_t)e]);
+            fputc('\n', f);
+        }
+        fclose(f);
+    }
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
@@ -168,6 +228,7 @@ int main(int argc, char **argv)
         else if (a == "--debug") o.debug = true;
         else if (a == "--hist") { need(1); o.hist = argv[++i]; }
         else if (a == "--solid") { need(2); o.solid_min = atol(argv[++i]); o.solid = argv[++i]; }
+        else if (a == "--index") { need(1); o.index = argv[++i]; }
         else if (a == "--parse-only") o.parse_only = true;
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else { fprintf(stderr, "unknown option %s\n", argv[i]); usage(); return EXIT_FAILURE; }
@@ -180,12 +241,22 @@ int main(int argc, char **argv)
         if (!cfg.count("kmer_size")) { fprintf(stderr, "No such parameter: kmer_size (and no --kmer)\n"); return EXIT_FAILURE; }
         o.kmer = (int)cfg["kmer_size"];
     }
-    if (cfg.count("use_minimizers") && cfg["use_minimizers"] != 0) {
-        fprintf(stderr, "use_minimizers = %g: the minimizer index (buildIndexMinimizers) is not built; only the k-mer count path (use_minimizers=0) is\n",
-                cfg["use_minimizers"]);
+    // the minimizer path's keys, as Config::get asks for them (config.h:24-34); checked here, before --parse-only acts
+    const bool minimizers = cfg.count("use_minimizers") && cfg["use_minimizers"] != 0;
+    gbx_kmer_index_params ip{};
+    if (minimizers) {
+        for (const char *key : {"minimizer_window", "repeat_kmer_rate"})
+            if (!cfg.count(key)) { fprintf(stderr, "No such parameter: %s\n", key); return EXIT_FAILURE; }
+        ip.k = o.kmer;
+        ip.window = (int)cfg["minimizer_window"];
+        ip.repeat_rate = (float)cfg["repeat_kmer_rate"];
+        if (o.kmer < 1 || o.kmer > GBX_KMER_INDEX_MAX_K) { fprintf(stderr, "Can't build the minimizer index for k-mer size %d (1..%d)\n", o.kmer, GBX_KMER_INDEX_MAX_K); return EXIT_FAILURE; }
+        if (ip.window < 1 || ip.window > GBX_KMER_INDEX_MAX_WINDOW) { fprintf(stderr, "minimizer_window = %d outside 1..%d\n", ip.window, GBX_KMER_INDEX_MAX_WINDOW); return EXIT_FAILURE; }
+    } else if (!o.index.empty()) {
+        fprintf(stderr, "--index needs the minimizer path (use_minimizers=1 in the config)\n");
         return EXIT_FAILURE;
     }
-    if (o.kmer < 1 || o.kmer > GBX_KMER_MAX_K) { fprintf(stderr, "Can't use flat counter for k-mer size %d (1..%d)\n", o.kmer, GBX_KMER_MAX_K); return EXIT_FAILURE; }
+    if (!minimizers && (o.kmer < 1 || o.kmer > GBX_KMER_MAX_K)) { fprintf(stderr, "Can't use flat counter for k-mer size %d (1..%d)\n", o.kmer, GBX_KMER_MAX_K); return EXIT_FAILURE; }
     if (o.debug) fprintf(stderr, "Running with k-mer size: %d\n", o.kmer);
 
     // ---- ingest: every file whole, lines split with threads, records in file order, then the kept reads encoded in parallel
@@ -254,6 +325,7 @@ int main(int argc, char **argv)
     }
 
     print_device_banner(gpus);
+    if (minimizers) return run_index(o, ip, n_reads, enc, off, len);
     gbx_kmer_params p{o.kmer, 256, o.solid.empty() ? 0u : (uint32_t)std::max(1l, o.solid_min), 0u};
     gbx_kmer_stats st{};
     std::vector<int64_t> hist(256);

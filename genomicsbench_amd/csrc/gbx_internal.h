@@ -51,7 +51,7 @@ struct Stage {
 //   GBX_GUARD_TRIP(var, kernel, loop, unit) true when the bound is exhausted (constant false in the product build)
 //   GBX_GUARD_CHECK(what)                   in a launch function, after its launches: hipDeviceSynchronize() (the whole device, other
 //                                           callers' streams included: the guard build is diagnostic only and its timings mean nothing), then a record becomes an error
-enum { GBX_GK_BSW = 1, GBX_GK_CHAIN = 2, GBX_GK_PHMM = 3, GBX_GK_POA = 4, GBX_GK_ABEA = 5, GBX_GK_FMI = 6, GBX_GK_PILEUP = 8, GBX_GK_DBG = 9, GBX_GK_MEM = 10 };
+enum { GBX_GK_BSW = 1, GBX_GK_CHAIN = 2, GBX_GK_PHMM = 3, GBX_GK_POA = 4, GBX_GK_ABEA = 5, GBX_GK_FMI = 6, GBX_GK_PILEUP = 8, GBX_GK_DBG = 9, GBX_GK_MEM = 10, GBX_GK_KMER_INDEX = 11 };
 #ifdef GBX_LOOP_GUARD
 namespace { __device__ unsigned long long gbx_guard_word; }      // one per translation unit
 __device__ inline bool gbx_guard_report(int kernel, int loop, long long unit)
@@ -385,6 +385,14 @@ size_t kmer_workspace_bytes(int32_t k, int64_t n_reads);
 int kmer_launch(const gbx_kmer_params *p, int64_t n_reads, const uint8_t *d_enc, const int64_t *d_read_off, const int32_t *d_read_len,
                 gbx_kmer_stats *d_stats, int64_t *d_hist, uint64_t *d_sel_kmer, uint32_t *d_sel_count, int64_t sel_cap, void *d_work,
                 size_t work_bytes, hipStream_t s);
+
+// ---- kmer index (kmer_index_kernels.hip; the rules are in kmer_index_rules.h)
+struct KmerIndexReads { const uint8_t *enc; const int64_t *read_off; const int32_t *read_len; int64_t n_reads, total_len; };
+size_t kmer_index_workspace_bytes(int64_t n_reads, int64_t total_len, bool index);
+int kmer_minimizers_launch(const gbx_kmer_index_params *p, const KmerIndexReads &rd, int64_t *d_mini_off, int32_t *d_mini_pos,
+                           uint8_t *d_mini_rev, int64_t mini_cap, int64_t *d_n_mini, void *d_work, size_t work_bytes, hipStream_t s);
+int kmer_index_launch(const gbx_kmer_index_params *p, const KmerIndexReads &rd, gbx_kmer_index_stats *d_stats, uint64_t *d_kmer,
+                      int64_t *d_off, int64_t kmer_cap, uint64_t *d_pos, int64_t pos_cap, void *d_work, size_t work_bytes, hipStream_t s);
 
 // ---- pileup (pileup_kernels.hip)
 size_t pileup_workspace_bytes(int64_t n_reads, int64_t n_cigar, int64_t n_pos);

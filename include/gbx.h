@@ -1685,6 +1685,70 @@ int gbx_kmer_count_device(const gbx_kmer_params *p, int64_t n_reads, const uint8
                           const int32_t *d_read_len, gbx_kmer_stats *d_stats, int64_t *d_hist, uint64_t *d_sel_kmer,
                           uint32_t *d_sel_count, int64_t sel_cap, void *d_work, size_t work_bytes, void *stream);
 
+/* -------------------------------------------------------------- kmer index
+ * Flye's minimizer index of long reads: VertexIndex::buildIndexMinimizers(1, window) as the kmer-cnt benchmark times it with
+ * use_minimizers = 1 (R/benchmarks/kmer-cnt/kmer_cnt.cpp:228-233, vertex_index.cpp:389-497, kmer.h:206-262).  DESIGN 3.7.1.
+ * Reads as the count entries take them (codes 0..3 a byte, larger values use their low two bits); k-mers at positions
+ * 0 .. len - k - 1, canonical = min(code, revcomp), "reversed" only when revcomp < code; hash = splitmix64 of the canonical
+ * code.  Per read the minimizers are the front positions of the reference's monotone deque over windows of `window`
+ * positions, ties as it breaks them (the earlier of two equal hashes stays until it expires, then the last of the equal
+ * run takes over); window = 1 chooses every position.
+ * The index: a canonical k-mer's capacity is its number of chosen positions; mean_frequency = (float)chosen /
+ * (float)(distinct + 1) and repetitive_frequency = (uint64)(repeat_rate * mean_frequency), both in fp32 as the reference
+ * rounds them; a k-mer with capacity > repetitive_frequency is repetitive and left out.  Every other chosen position is
+ * stored as the global position of the canonical strand's copy: read r of L bases starts at G_r = 2 * (the lengths of the
+ * reads before it), a forward k-mer at p has G_r + p, a reversed one G_r + L + (L - p - k).
+ * Results (exact, independent of the scheduling): kmer[] the kept k-mers in ascending canonical code, k-mer j's positions
+ * pos[off[j] .. off[j + 1]) ascending.  The reference's min_coverage is always 1 and no capacity is below 1: left out. */
+#define GBX_KMER_INDEX_MAX_K       31   /* the reference's own mask, 1 << 2k, is undefined at 32 */
+#define GBX_KMER_INDEX_MAX_WINDOW  64
+typedef struct gbx_kmer_index_params {
+    int32_t k;           /* 1..31 */
+    int32_t window;      /* 1..64 */
+    float repeat_rate;   /* Flye's repeat_kmer_rate, 0 .. 2^20 */
+    int32_t reserved_;   /* 0 */
+} gbx_kmer_index_params;
+typedef struct gbx_kmer_index_stats {
+    int64_t n_chosen;               /* minimizer positions of all reads */
+    int64_t n_distinct;             /* canonical k-mers among them */
+    int64_t repetitive_frequency;   /* "Repetitive k-mer frequency" */
+    int64_t n_repetitive_kmers;     /* k-mers left out ... */
+    int64_t n_repetitive_entries;   /* ... and the sum of their capacities: "Filtered N repetitive k-mers" */
+    int64_t n_selected;             /* "Selected k-mers": may exceed kmer_cap, then the output did not fit */
+    int64_t n_entries;              /* "K-mer index size": may exceed pos_cap */
+    int64_t total_len;              /* sum of the read lengths */
+    float mean_frequency;           /* the filter's "Mean k-mer frequency" */
+    int32_t reserved_;
+} gbx_kmer_index_stats;
+
+/* The selection alone.  Read r's chosen positions are mini_pos[mini_off[r] .. mini_off[r + 1]) ascending, mini_rev[] 1 where
+ * the k-mer there is reversed; mini_off has n_reads + 1 entries.  *n_mini = mini_off[n_reads] is the needed count; nothing is
+ * written past mini_cap, and the host entry returns GBX_ERR_ARG when it is larger.  Limits, checked on the host before any
+ * device work: every read inside enc_bytes; 2 * total_len < 2^40, else GBX_ERR_UNSUPPORTED. */
+int gbx_kmer_minimizers_host(const gbx_kmer_index_params *p, int64_t n_reads, const uint8_t *enc, int64_t enc_bytes,
+                             const int64_t *read_off, const int32_t *read_len, int64_t *mini_off, int32_t *mini_pos,
+                             uint8_t *mini_rev, int64_t mini_cap, int64_t *n_mini);
+/* Host-buffer entry of the index.  kmer[kmer_cap], off[kmer_cap + 1], pos[pos_cap]; a result that does not fit gives
+ * GBX_ERR_ARG with the needed counts in st->n_selected / st->n_entries and in gbx_last_error(); st is filled then too.  The
+ * limits of gbx_kmer_minimizers_host.  Calls are serialised; it runs on the calling thread's current device. */
+int gbx_kmer_index_host(const gbx_kmer_index_params *p, int64_t n_reads, const uint8_t *enc, int64_t enc_bytes,
+                        const int64_t *read_off, const int32_t *read_len, gbx_kmer_index_stats *st, uint64_t *kmer,
+                        int64_t *off, int64_t kmer_cap, uint64_t *pos, int64_t pos_cap);
+/* Device path: every pointer is device memory, the work is queued on `stream` and nothing is synchronised.  total_len is the
+ * sum of the read lengths (negative lengths count as 0); the device checks it, and with another sum nothing is selected and
+ * every count is -1.  The workspace holds two bytes a base, the tiles' counts and, for the index, the sort's buffers: 48
+ * bytes a base (any position can be a minimizer).  index = 0 sizes it for gbx_kmer_minimizers_device alone; 0 for arguments
+ * outside the limits. */
+size_t gbx_kmer_index_workspace_bytes(int32_t k, int64_t n_reads, int64_t total_len, int32_t index);
+int gbx_kmer_minimizers_device(const gbx_kmer_index_params *p, int64_t n_reads, const uint8_t *d_enc,
+                               const int64_t *d_read_off, const int32_t *d_read_len, int64_t total_len, int64_t *d_mini_off,
+                               int32_t *d_mini_pos, uint8_t *d_mini_rev, int64_t mini_cap, int64_t *d_n_mini, void *d_work,
+                               size_t work_bytes, void *stream);
+int gbx_kmer_index_device(const gbx_kmer_index_params *p, int64_t n_reads, const uint8_t *d_enc, const int64_t *d_read_off,
+                          const int32_t *d_read_len, int64_t total_len, gbx_kmer_index_stats *d_stats, uint64_t *d_kmer,
+                          int64_t *d_off, int64_t kmer_cap, uint64_t *d_pos, int64_t pos_cap, void *d_work,
+                          size_t work_bytes, void *stream);
+
 /* ------------------------------------------------------------------ pileup
  * medaka's pileup feature counts over a region of aligned long reads: calculate_pileup as the pileup benchmark times it
  * (R/benchmarks/pileup/medaka_counts.c:298-478).  Points marked UPSTREAM rest on htslib's pileup engine.
