@@ -502,6 +502,22 @@ size_t abea_meth_order_work_bytes(int64_t n_jobs);
 int abea_meth_order_launch(int64_t n_jobs, const gbx_abea_meth_job *d_jobs, int64_t seq_bytes, int64_t n_reads, const int64_t *d_event_off, int64_t flank_len,
                            int max_rows_bits, void *d_work, int32_t *d_order, int64_t *d_class_off, int64_t *d_first_bad, hipStream_t s);
 
+// ---- abea methylation frequency, f5c meth-freq (abea_freq_kernels.hip; the rules: abea_freq_rules.h).  The arguments of the device entries
+size_t abea_freq_work_bytes(int64_t n_in, int64_t n_items);
+int abea_freq_launch(int pass, int64_t n_records, const gbx_abea_freq_record *d_records, const char *d_rec_arena, double threshold, int split_groups,
+                     int pos_bits, int contig_bits, int64_t n_items, void *d_work, int64_t *d_item_off, int64_t *d_counts, int64_t site_cap,
+                     gbx_abea_freq_site *d_sites, int64_t seq_cap, char *d_seq_arena, hipStream_t s);
+int abea_freq_merge_launch(int pass, int64_t n_a, const gbx_abea_freq_site *d_sites_a, const char *d_arena_a, int64_t n_b, const gbx_abea_freq_site *d_sites_b,
+                           const char *d_arena_b, int pos_bits, int contig_bits, void *d_work, int64_t *d_counts, int64_t site_cap,
+                           gbx_abea_freq_site *d_sites, int64_t seq_cap, char *d_seq_arena, hipStream_t s);
+size_t abea_freq_records_work_bytes(int64_t n_sites);
+int abea_freq_records_launch(int pass, int64_t n_sites, const gbx_abea_meth_site *d_sites, const float *d_scores, int64_t n_reads, const int32_t *d_contig,
+                             const int64_t *d_ref_off, const int32_t *d_ref_len, const char *d_ref, int32_t clip_start, int32_t clip_end, void *d_work,
+                             int64_t *d_off, int64_t rec_cap, gbx_abea_freq_record *d_records, int64_t seq_cap, char *d_seq_arena, hipStream_t s);
+size_t abea_freq_tsv_work_bytes(int64_t n_sites);
+int abea_freq_tsv_launch(int pass, int64_t n_sites, const gbx_abea_freq_site *d_sites, const char *d_seq_arena, int64_t n_contigs, const int64_t *d_name_off,
+                         const char *d_names, int header_kind, int with_header, void *d_work, int64_t *d_line_off, int64_t cap, char *d_out, hipStream_t s);
+
 // ---- abea eventalign (abea_eventalign_kernels.hip)
 struct AbeaEventalignArgs {                   // the device entry's arguments, by value to the kernel
     long long n_reads;

@@ -580,6 +580,117 @@ int gbx_abea_meth_tsv_host(int64_t n_sites, const gbx_abea_meth_site *sites, con
                            const int64_t *ref_off, const int32_t *ref_len, const char *ref_arena, int version, int32_t clip_start,
                            int32_t clip_end, int with_header, int64_t cap, char *out, int64_t *n_bytes);
 
+/* abea, methylation frequency: f5c meth-freq (freq.c), the stage behind call-methylation that folds the per-read calls into one
+ * line per genomic site.  Replaces  int freq_main(int argc, char **argv)   freq.c:253-430.
+ * A record is one line of the call-methylation TSV: contig (the rank of its name among the run's names under strcmp), start,
+ * end, n_cpg, llr (log_lik_ratio as meth-freq reads it: strtod of the printed text) and the sequence, seq_len bytes at seq_off
+ * of an arena.  A record with fabs(llr) < threshold is dropped (so NaN is kept); it is methylated iff llr > 0.  Without
+ * split_groups, or when n_cpg <= 1, it is one item of weight n_cpg under the key (contig, start, end); otherwise one item of
+ * weight 1 per occurrence of "CG" in its sequence, at start + pos - first_pos for both start and end, with the sequence
+ * "split-group".  Per key: called_sites and called_sites_methylated are the sums of the weights; group_size and the sequence
+ * are those of the first item in input order.  Keys with called_sites == 0 are not in the table.  The table is sorted by
+ * contig, start, end; a site's sequence is seq_len bytes at seq_off of the arena the table owns, seq_len == -1 is "split-group".
+ * Limits: a sum above INT32_MAX (the reference's int overflows) and a split position above INT32_MAX are GBX_ERR_UNSUPPORTED. */
+typedef struct gbx_abea_freq_record {
+    int32_t contig, start, end, n_cpg;
+    double  llr;
+    int64_t seq_off;
+    int32_t seq_len, pad_;
+} gbx_abea_freq_record;
+typedef struct gbx_abea_freq_site {
+    int32_t contig, start, end, group_size, called_sites, called_sites_methylated;
+    int64_t seq_off;
+    int32_t seq_len, pad_;             /* seq_len == -1: "split-group" (seq_off 0) */
+} gbx_abea_freq_site;
+#define GBX_ABEA_FREQ_COUNT   1        /* pass: the per-record item counts and their offsets */
+#define GBX_ABEA_FREQ_REDUCE  2        /* pass: items, sort, segments, sums; the table's sizes */
+#define GBX_ABEA_FREQ_FILL    4        /* pass: the table and its arena */
+#define GBX_ABEA_FREQ_NCOUNTS 8        /* d_counts: int64 [0] items [1] keys [2] sites [3] arena bytes [4] flags */
+#define GBX_ABEA_FREQ_SUM_OVERFLOW 1   /* flags: a site's sum is above INT32_MAX */
+#define GBX_ABEA_FREQ_POS_OVERFLOW 2   /*        a split position is above INT32_MAX */
+#define GBX_ABEA_FREQ_KEY_BITS     4   /*        a key does not fit pos_bits / contig_bits */
+#define GBX_ABEA_FREQ_ITEMS        8   /*        n_items is not what the count pass found */
+#define GBX_ABEA_FREQ_CPGS   1         /* header kind: num_cpgs / num_cpgs_in_group */
+#define GBX_ABEA_FREQ_MOTIFS 2         /*              num_motifs / num_motifs_in_group */
+/* Records -> table on the device, on the caller's stream; nothing is synchronised.  pass COUNT writes d_item_off[n_records + 1]
+ * (exclusive scan, the total in entry n_records and in d_counts[0]); the caller reads the total and passes it as n_items to
+ * the later passes.  pass REDUCE makes the items, sorts them stably by key with as many 8-bit passes as pos_bits (1..31, for
+ * start and end) and contig_bits (1..31) need, and writes d_counts[1..4]; pass FILL writes the sites and the arena, nothing
+ * past site_cap sites and nothing of a sequence that would end past seq_cap.  d_work: gbx_abea_freq_work(n_records, n_items)
+ * bytes, the same buffer in REDUCE and FILL (COUNT needs gbx_abea_freq_work(n_records, 0)).  d_counts: GBX_ABEA_FREQ_NCOUNTS
+ * int64.  An n_items other than the count pass's total sets GBX_ABEA_FREQ_ITEMS: a record whose items would end past it
+ * writes none, and the table means nothing then. */
+int64_t gbx_abea_freq_work(int64_t n_records, int64_t n_items);
+int gbx_abea_freq_device(int pass, int64_t n_records, const gbx_abea_freq_record *d_records, const char *d_rec_arena,
+                         double threshold, int split_groups, int pos_bits, int contig_bits, int64_t n_items, void *d_work,
+                         int64_t *d_item_off, int64_t *d_counts, int64_t site_cap, gbx_abea_freq_site *d_sites, int64_t seq_cap,
+                         char *d_seq_arena, void *stream);
+/* Pageable host buffers (one device).  Checked before the device is touched, GBX_ERR_ARG naming the lowest offender:
+ * negative contig, start, end or n_cpg, a sequence outside the arena.  *n_sites and *seq_bytes: the table's sizes; one above
+ * its capacity gives GBX_ERR_ARG with the needs there (call with 0 / NULL to size). */
+int gbx_abea_freq_host(int64_t n_records, const gbx_abea_freq_record *records, const char *rec_arena, int64_t rec_arena_bytes,
+                       double threshold, int split_groups, int64_t site_cap, gbx_abea_freq_site *sites, int64_t *n_sites,
+                       int64_t seq_cap, char *seq_arena, int64_t *seq_bytes);
+/* call-methylation's sites and scores -> records, without the text: site s of read r becomes the record (contig_of_read[r],
+ * start_position, end_position, n_cpg, llr, context) unless (clip_start != -1 && start_position < clip_start) ||
+ * (clip_end != -1 && end_position >= clip_end), the filter of gbx_abea_meth_tsv_host.  llr is what meth-freq reads from the
+ * text: the double scores[2 s + 1] - scores[2 s] rounded to two decimals as "%.2lf" prints it (the exact binary value, ties to
+ * even) and divided by 100.0; from 2^46 in magnitude, and for inf / NaN, the value itself.  The context is ctx_len bytes at
+ * ctx_off of the read's reference segment, each mapped as the TSV writer maps it.  pass COUNT writes d_off[2 (n_sites + 1)]:
+ * the record offsets, then the byte offsets (totals in the last entry of each); pass FILL writes the records and the arena,
+ * nothing past rec_cap / seq_cap.  d_work: gbx_abea_freq_records_work(n_sites) bytes.  Nothing is synchronised. */
+int64_t gbx_abea_freq_records_work(int64_t n_sites);
+int gbx_abea_freq_records_device(int pass, int64_t n_sites, const gbx_abea_meth_site *d_sites, const float *d_scores,
+                                 int64_t n_reads, const int32_t *d_contig_of_read, const int64_t *d_ref_off,
+                                 const int32_t *d_ref_len, const char *d_ref_arena, int32_t clip_start, int32_t clip_end,
+                                 void *d_work, int64_t *d_off, int64_t rec_cap, gbx_abea_freq_record *d_records, int64_t seq_cap,
+                                 char *d_seq_arena, void *stream);
+/* The arrays gbx_abea_call_methylation_host returns.  Checked first, GBX_ERR_ARG naming the lowest offender: a site's read, a
+ * context outside the read's segment, a negative contig.  Capacities as gbx_abea_freq_host. */
+int gbx_abea_freq_records_host(int64_t n_sites, const gbx_abea_meth_site *sites, const float *scores, int64_t n_reads,
+                               const int32_t *contig_of_read, const int64_t *ref_off, const int32_t *ref_len,
+                               const char *ref_arena, int32_t clip_start, int32_t clip_end, int64_t rec_cap,
+                               gbx_abea_freq_record *records, int64_t *n_records, int64_t seq_cap, char *seq_arena,
+                               int64_t *seq_bytes);
+/* Two tables -> the table of the concatenated input, A's records first: both become items (weights called_sites and
+ * called_sites_methylated, group_size and sequence as they stand), then the same sort and reduce, so a key in both keeps A's
+ * group size and sequence.  (A table holds no site whose records all had weight 0, so such records of A no longer fix a
+ * group size of 0 for B's calls: the one difference from the concatenated input, at threshold 0 only.)  pass REDUCE and / or FILL; d_work: gbx_abea_freq_work(n_a + n_b, n_a + n_b) bytes. */
+int gbx_abea_freq_merge_device(int pass, int64_t n_a, const gbx_abea_freq_site *d_sites_a, const char *d_arena_a, int64_t n_b,
+                               const gbx_abea_freq_site *d_sites_b, const char *d_arena_b, int pos_bits, int contig_bits,
+                               void *d_work, int64_t *d_counts, int64_t site_cap, gbx_abea_freq_site *d_sites, int64_t seq_cap,
+                               char *d_seq_arena, void *stream);
+int gbx_abea_freq_merge_host(int64_t n_a, const gbx_abea_freq_site *sites_a, const char *arena_a, int64_t arena_a_bytes,
+                             int64_t n_b, const gbx_abea_freq_site *sites_b, const char *arena_b, int64_t arena_b_bytes,
+                             int64_t site_cap, gbx_abea_freq_site *sites, int64_t *n_sites, int64_t seq_cap, char *seq_arena,
+                             int64_t *seq_bytes);
+/* Table -> the text meth-freq prints (freq.c:381-416): with_header the header of `header_kind` first, then per site
+ * "%s\t%d\t%d\t%d\t%d\t%d\t%.3lf\t%s\n" with the frequency (double)called_sites_methylated / called_sites rounded as printf
+ * rounds it.  Contig c's name is d_names[d_name_off[c] .. d_name_off[c + 1]); a contig outside 0 .. n_contigs - 1 prints
+ * an empty name.  pass COUNT (GBX_ABEA_FREQ_COUNT) writes d_line_off[n_sites + 2]: entry 0 the header's place (0), entry s + 1 site s's
+ * line, the last entry the bytes of the whole text; pass FILL writes the lines that end inside cap.  d_work:
+ * gbx_abea_freq_tsv_work(n_sites) bytes.  Nothing is synchronised. */
+int64_t gbx_abea_freq_tsv_work(int64_t n_sites);
+int gbx_abea_freq_tsv_device(int pass, int64_t n_sites, const gbx_abea_freq_site *d_sites, const char *d_seq_arena,
+                             int64_t n_contigs, const int64_t *d_name_off, const char *d_names, int header_kind, int with_header,
+                             void *d_work, int64_t *d_line_off, int64_t cap, char *d_out, void *stream);
+/* Host buffers.  Checked first: contigs inside contig_names, sequences inside the arena, called_sites > 0.  *n_bytes: the
+ * bytes of text; more than cap: GBX_ERR_ARG with the need there (call with 0 / NULL to size). */
+int gbx_abea_freq_tsv_host(int64_t n_sites, const gbx_abea_freq_site *sites, const char *seq_arena, int64_t seq_bytes,
+                           int64_t n_contigs, const char *const *contig_names, int header_kind, int with_header, int64_t cap,
+                           char *out, int64_t *n_bytes);
+/* Host only: the call-methylation TSV -> records, as get_tsv_line reads it (freq.c:175-251): one of the four headers (with /
+ * without strand, num_cpgs / num_motifs -> *header_kind), fields cut as strtok cuts them, atoi and strtod of the C library.
+ * The contig names come back sorted by strcmp, NUL-terminated one after the other in `names`; a record's contig is its
+ * name's rank.  Where the reference exits (no header, a bad header, a missing column, an extra column, a negative coordinate
+ * or count) the return is GBX_ERR_ARG, gbx_last_error() is the reference's message and *bad_line its line number (0 for the
+ * header); a contig name holding ':' (the reference's own key breaks on it) is GBX_ERR_UNSUPPORTED.  counts[4]: records,
+ * sequence bytes, contigs, name bytes; one above its capacity gives GBX_ERR_ARG with *bad_line = -1 and the needs in counts
+ * (call with 0 / NULL to size). */
+int gbx_abea_freq_parse_host(const char *text, int64_t n_bytes, int64_t rec_cap, gbx_abea_freq_record *records, int64_t seq_cap,
+                             char *seq_arena, int64_t name_cap, char *names, int64_t *counts, int *header_kind,
+                             int64_t *bad_line);
+
 /* abea, calibration and the event-alignment record: what f5c runs per read between align() and the methylation score.
  * Replaces  int32_t postalign(alignment, base_to_event_map, events_per_base, sequence, n_kmers, event_alignment, n_events)
  *                                                                                              align.c:550-650
