@@ -1,6 +1,6 @@
 // capi_common.h — what every capi_<kernel>.hip includes: the internal declarations, the host entries' transfer pipeline
 // (host_pipeline.h), the bwa-mem entries' shared checks (host_mem.h), the multi-device layer on top of it (host_multi.h), the call combiner (host_combine.h), the device
-// allocations kept between calls (host_cache.h), Carve, and behind it what the abea entries share (host_abea.h).
+// allocations kept between calls (host_cache.h), Carve, upload and StreamDrain, and behind them what the abea entries share (host_abea.h).
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -36,6 +36,18 @@ struct Carve {
     int alloc() { return buf.alloc(need); }
     template <class T> T *take(size_t bytes) { T *p = (T *)((char *)buf.p + used); used += (bytes + 255) & ~(size_t)255; return p; }
 };
+
+// room for `bytes` in b and the copy of src into it on s (none at zero bytes)
+inline int upload(DevBuf &b, const void *src, size_t bytes, hipStream_t s)
+{
+    const int rc = b.alloc(bytes);
+    if (rc) return rc;
+    if (bytes) GBX_HIP(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s));
+    return GBX_OK;
+}
+
+// Declared after every host array that a queued copy uses: however the scope is left, the stream is drained before they die.
+struct StreamDrain { hipStream_t s; ~StreamDrain() { (void)hipStreamSynchronize(s); } };
 }
 
 #include "abea_meth_rules.h"

@@ -364,51 +364,7 @@ __global__ void __launch_bounds__(FIN_THREADS) dbg_finish_kernel(DbgDev a, const
 
 }  // namespace
 
-size_t dbg_window_bytes(int64_t C)
-{
-    return (size_t)(dbg_node_slots(C) * 36 + dbg_edge_slots(C) * 36 + 8 * C);
-}
-
-int dbg_plan(int64_t k, int64_t w0, int64_t w1, const int64_t *ref_off, const int64_t *ref_pos, const int64_t *read_lo, const int64_t *read_hi,
-             const int64_t *rcp, size_t table_bytes, std::vector<DbgWinPlan> &plan, std::vector<int64_t> &batches)
-{
-    plan.clear();
-    batches.assign(1, 0);
-    int64_t cand = 0;
-    size_t used = 0;
-    for (int64_t w = w0; w < w1; ++w) {
-        DbgWinPlan P;
-        const int64_t rl = ref_off[w + 1] - ref_off[w];
-        P.nref_c = std::max<int64_t>(0, rl - k - 1);
-        P.read_lo = read_lo[w];
-        P.read_hi = std::max(read_lo[w], read_hi[w]);
-        P.C = P.nref_c + (rcp[P.read_hi] - rcp[P.read_lo]);
-        P.ref_off = ref_off[w];
-        P.ref_pos = ref_pos[w];
-        P.win = w - w0;
-        P.nc = dbg_node_slots(P.C);
-        P.ec = dbg_edge_slots(P.C);
-        const size_t b = dbg_window_bytes(P.C);
-        if (b > table_bytes) {
-            set_error("dbg: window %lld needs %zu bytes of tables, the workspace has %zu (gbx_dbg_workspace_bytes: max_window_occ)", (long long)w, b,
-                      table_bytes);
-            return GBX_ERR_ARG;
-        }
-        if (used + b > table_bytes || (int64_t)plan.size() - batches.back() >= (1 << 20)) {
-            batches.push_back((int64_t)plan.size());
-            used = 0; cand = 0;
-        }
-        P.base = (int64_t)used;
-        P.cand0 = cand;
-        used += b;
-        cand += P.C;
-        plan.push_back(P);
-    }
-    if (batches.back() != (int64_t)plan.size()) batches.push_back((int64_t)plan.size());
-    return GBX_OK;
-}
-
-// Batches of plan (cut by dbg_plan) on stream s.  d_plan: room for the plan in the workspace; d_err: an int there.
+// Batches of plan (cut by dbg_cut_batches, dbg_plan.h) on stream s.  d_plan: room for the plan in the workspace; d_err: an int there.
 int dbg_launch(const DbgDev &a, const std::vector<DbgWinPlan> &plan, const std::vector<int64_t> &batches, DbgWinPlan *d_plan, int *d_err,
                char *d_region, gbx_dbg_stats *d_stats, const DbgGraphOut &g, hipStream_t s)
 {

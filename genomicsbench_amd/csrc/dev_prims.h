@@ -4,22 +4,16 @@
 // them is dev_sort.hip.  What only the bwa-mem stages share is in mem_common.h.
 #pragma once
 #include "gbx_internal.h"
+#include "carver.h"           // align256, Carver
 
 namespace gbx {
 
 constexpr int MEM_SCAN = 1024;                      // entries a block of the scan takes
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline int mem_scan_blocks(int64_t n) { return (int)((n + 1 + MEM_SCAN - 1) / MEM_SCAN); }     // n counts make n + 1 offsets
 
 // the block of the mm stages' element-wise kernels (mm_kernels.hip, mm_map_kernels.hip, mm_align_kernels.hip) and the grid over n
 constexpr int MM_EL = 256;
 inline unsigned mm_el_blocks(long long n) { const long long b = (n + MM_EL - 1) / MM_EL; return (unsigned)(b > 0 ? b : 1); }
-
-// carves a workspace: carve(bytes) -> the offset of the next piece, 256-aligned; at: the bytes taken so far
-struct Carver {
-    size_t at = 0;
-    size_t operator()(size_t bytes) { const size_t o = at; at += align256(bytes); return o; }
-};
 
 // a count that lives on the device, as far as its capacity holds it
 __device__ inline long long clip_count(const int64_t *n, long long cap)

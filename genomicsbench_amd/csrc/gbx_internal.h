@@ -7,6 +7,7 @@
 #include <mutex>
 #include <vector>
 #include "../../include/gbx.h"
+#include "dbg_plan.h"
 
 namespace gbx {
 
@@ -413,11 +414,6 @@ struct DbgDev {
     const int64_t *seq_off, *rcp;
     const uint16_t *flag;
 };
-// One window of a batch (dbg_plan): C occurrence slots from cand0 in the batch, nref_c of them the reference's; its tables at
-// base in the batch region, nc node slots and ec edge slots (powers of two); win its index in the call's outputs.
-struct DbgWinPlan {
-    int64_t cand0, C, nref_c, base, nc, ec, read_lo, read_hi, ref_off, ref_pos, win;
-};
 // gbx_dbg_graph_*: where the nodes and edges of the call's windows go (nodes == nullptr: stats only); src values are moved
 // by ref_shift / seq_shift (a shard's rebased arrays back to the caller's).
 struct DbgGraphOut {
@@ -426,9 +422,7 @@ struct DbgGraphOut {
     const int64_t *node_off = nullptr, *edge_off = nullptr;
     int64_t ref_shift = 0, seq_shift = 0;
 };
-size_t dbg_window_bytes(int64_t C);
-int dbg_plan(int64_t k, int64_t w0, int64_t w1, const int64_t *ref_off, const int64_t *ref_pos, const int64_t *read_lo, const int64_t *read_hi,
-             const int64_t *rcp, size_t table_bytes, std::vector<DbgWinPlan> &plan, std::vector<int64_t> &batches);
+// batches of plan as dbg_cut_batches cuts them (dbg_plan.h, DbgWinPlan)
 int dbg_launch(const DbgDev &a, const std::vector<DbgWinPlan> &plan, const std::vector<int64_t> &batches, DbgWinPlan *d_plan, int *d_err,
                char *d_region, gbx_dbg_stats *d_stats, const DbgGraphOut &g, hipStream_t s);
 

@@ -1,13 +1,10 @@
 // host_abea.h — what the abea entries (capi_abea / _events / _calib / _meth / _eventalign .hip) share on the host: the argument checks
-// with their error texts, the stream-draining guard (HIP calls go through GBX_HIP), the rebased offsets and the compact event means, the
+// with their error texts, the rebased offsets and the compact event means, the
 // transition logarithms, the eventalign kernel's arguments, the calibration behind align() and the score plan.  Every check sets the
 // error text and returns GBX_ERR_ARG (event_count_check, a CIGAR past 2^30: GBX_ERR_UNSUPPORTED), or returns GBX_OK.
 #pragma once
 
 namespace gbx {
-
-// Declared after every host array that a queued copy uses: however the scope is left, the stream is drained before they die.
-struct StreamDrain { hipStream_t s; ~StreamDrain() { (void)hipStreamSynchronize(s); } };
 
 // ---- the checks of read r; `base` = index of read 0 in the caller's job (error texts only)
 inline int read_check(const int64_t *seq_off, const int32_t *seq_len, int64_t seq_bytes, int64_t r, const char *who, int64_t base = 0)

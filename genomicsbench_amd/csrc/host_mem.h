@@ -67,13 +67,4 @@ inline void sel_tail_fill(gbx_bsw_seed *seeds, gbx_bsw_seed_result *res, int64_t
     memset(res + from, 0xff, (size_t)(cap - from) * sizeof(gbx_bsw_seed_result));
 }
 
-// room for `bytes` in b and the copy of src into it on s (none at zero bytes)
-inline int upload(DevBuf &b, const void *src, size_t bytes, hipStream_t s)
-{
-    const int rc = b.alloc(bytes);
-    if (rc) return rc;
-    if (bytes) GBX_HIP(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s));
-    return GBX_OK;
-}
-
 }  // namespace gbx

@@ -3,8 +3,9 @@
 the build, the cycle check, the start list and the path search.  The rounds' times come from the library's per-kernel
 profile of calls cut short at each round (k_last = the round's k - 1): a round is the difference of two such calls.  A
 seeded sample of windows is held against the restatement (tests/dbg_asm_ref.py).  Prints one JSON line and writes it to
-profiles/dbg_asm_time_<preset>.json.
-    python scripts/time_dbg_asm.py --preset large [--reps 3] [--sample 6]"""
+profiles/dbg_asm_time_<preset>.json, or, with the preset's contig length overridden, to
+profiles/dbg_asm_time_<preset>_len<N>.json (the record says so too).
+    python scripts/time_dbg_asm.py --preset large [--contig-len N] [--reps 3] [--sample 6]"""
 import argparse
 import json
 import os
@@ -21,6 +22,7 @@ STAGES = {"build": ("dbg_init", "dbg_insert", "dbg_finish"), "cycle": ("dbg_asm_
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--preset", default="large")
+    ap.add_argument("--contig-len", type=int, default=0, help="override the preset's contig length")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sample", type=int, default=6)
     ap.add_argument("--out", default=None)
@@ -30,7 +32,9 @@ def main():
     import dbg_asm_ref as AR
     from genomicsbench_amd import _native as N, dbg as D, dbg_asm as A, pileup as P
     from genomicsbench_amd.datagen import DBG_PRESETS, gen_dbg_reads
-    pr = DBG_PRESETS[a.preset]
+    pr = dict(DBG_PRESETS[a.preset])
+    if a.contig_len:
+        pr["contig_len"] = a.contig_len
     c, recs, fa = gen_dbg_reads(pr["contig_len"], pr["coverage"], pr["seed"])
     d = tempfile.mkdtemp()
     bam, fasta = os.path.join(d, "d.bam"), os.path.join(d, "d.fa")
@@ -61,7 +65,7 @@ def main():
     da = A.DeviceAsm(rs, wins, "cuda:0", caps=caps)
     asm_ms, asm_all = timed(lambda: N.check(da.assemble(s.cuda_stream)), a.reps)
     res = da.results()
-    out = dict(preset=a.preset, contig_len=pr["contig_len"], reads=rs.n_reads, windows=wins.n_win, build_ms=round(build_ms, 3), build_ms_all=build_all,
+    out = dict(preset=a.preset, contig_len=pr["contig_len"], contig_len_overridden=bool(a.contig_len), reads=rs.n_reads, windows=wins.n_win, build_ms=round(build_ms, 3), build_ms_all=build_all,
                assemble_ms=round(asm_ms, 3), assemble_ms_all=asm_all, assemble_over_build=round(asm_ms / build_ms, 3),
                workspace_bytes=int(da.work_bytes), starts=len(res.starts), paths=len(res.paths), path_nodes=len(res.path_nodes),
                gave_up=int(res.wins["n_gave_up"].sum()), step_capped=int(res.wins["n_steps"].sum()), cyclic_at_the_end=int(res.wins["cyclic"].sum()))
@@ -97,7 +101,8 @@ def main():
     out["sample_verified"] = "%d/%d" % (ok, len(sample))
     line = json.dumps(out)
     print(line)
-    with open(a.out or os.path.join(ROOT, "profiles", "dbg_asm_time_%s.json" % a.preset), "w") as f:
+    name = "dbg_asm_time_%s.json" % a.preset if not a.contig_len else "dbg_asm_time_%s_len%d.json" % (a.preset, a.contig_len)
+    with open(a.out or os.path.join(ROOT, "profiles", name), "w") as f:
         f.write(line + "\n")
     return 0 if ok == len(sample) else 1
 
